@@ -16,7 +16,13 @@ value = N * K / max-over-ranks time.
 With --gpus N > 1 and no WORLD_SIZE in the environment the script launches itself under
 torch.distributed.run (one rank per GPU); under a launcher it checks WORLD_SIZE == --gpus.
 
-The JSON line also carries
+A plain run sets up, warms up, times --steps iterations and prints the headline: `value`, `ms_per_step` (wall time of the
+timed steps / --steps), `rmse` and `roofline` from the launches of the timed steps.  `--dump-outputs DIR` then also writes
+what the timed fit hands its caller after the last timed step (see dump_outputs).  Everything else below -- `sustained`,
+`parity_full_size`, `engines`, `workloads`, `strong`, `cpu_baseline` and the rocprofv3 counter children behind
+`roofline.traffic` / `roofline.mfma_pmc` -- runs with --full only.
+
+With --full the JSON line also carries
   roofline     : the dominant kernel = the relation contractions P = R G_j, Q = R^T G_i, timed with hipEvents on the
                  launch stream inside the timed region.  SURVEY.md 8(d): the algorithmic work of an iteration is ONE read of
                  every relation (22 GB in bf16) and sum 2 n_i n_j (c_i + c_j) flops = 9.472e12 -- 430 flop/B, above the
@@ -27,6 +33,8 @@ The JSON line also carries
                  HBM bytes per launch from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE children of THIS run (`traffic_kind`:
                  "PMC, this run ..."; the committed pass of profiles/pmc_traffic.json stands in where the box has no
                  rocprofv3, labelled so; `pmc_errors` says why a pass did not deliver), `traffic_scheduled`, `whole_iteration`.
+  roofline.traffic, roofline.mfma_pmc : the rocprofv3 counter children of this run (without --full the committed pass
+                 of profiles/pmc_traffic.json stands in, labelled so).
   sustained    : a second timed region of 1000 steps on the same plan.
   parity_full_size : per engine, its first FIVE iterations against the oracle's at FULL size on the same inputs (checkpoints
                  after iterations 2 and 5: backbones, 64 rows of every factor; relation errors after 5), and `S_gate`: the
@@ -67,6 +75,8 @@ Options beyond the driver's contract (defaults = the metric's configuration):
   --workload c3|c5          c5 = BASELINE configs[4]: Dfmc, MovieLens-style 6-relation graph
   --data uniform|planted    planted: rank-structured relations + 1 % noise (RMSE discriminates)
   --scale x                 linear scale of the object counts (smoke runs)
+  --full                    the sub-records and baselines above (off: the headline only)
+  --dump-outputs DIR        after the timed steps: DIR/G_<type>.npy and DIR/S_<row>_<col>.npy (dump_outputs)
 """
 import argparse
 import json
@@ -804,12 +814,37 @@ def bench_dicty(iters=100):
     return out
 
 
+DUMP_ROWS = 8192               # rows of every factor that --dump-outputs writes (all of them for a type with fewer objects)
+
+
+def dump_rows(n_t):
+    """The row indices of a factor of n_t rows that --dump-outputs writes: all rows up to DUMP_ROWS, otherwise a fixed
+    seeded sample of DUMP_ROWS of them (sorted) -- the same rows in every run and every build."""
+    if n_t <= DUMP_ROWS:
+        return np.arange(n_t)
+    return np.sort(np.random.RandomState(0).choice(n_t, DUMP_ROWS, replace=False))
+
+
+def dump_outputs(path, plan, types, spec, local_index, n, dtype):
+    """`--dump-outputs DIR`: what a caller of the timed fit receives after its last timed step -- the factor of every object
+    type (DIR/G_<type>.npy, the rows of dump_rows) and the backbone of every relation (DIR/S_<row>_<col>.npy), in the
+    engine's master precision (float32 for bf16 / f32, float64 for f64): under 44 MB at full size."""
+    os.makedirs(path, exist_ok=True)
+    out_dt = np.float64 if dtype == 'f64' else np.float32
+    for t in types:
+        np.save(os.path.join(path, 'G_%s.npy' % t), plan.get_factor(t)[dump_rows(n[t])].astype(out_dt))
+    for q, k in enumerate(local_index):
+        i, j, _ = spec[k]
+        np.save(os.path.join(path, 'S_%s_%s.npy' % (i, j)), plan.get_backbone(q).astype(out_dt))
+
+
 def run_workload(workload, dtype, steps, warmup, scale=1.0, data='uniform', mode='restarts', rank=0, world=1, dist=None,
-                 backend='nccl', emulate=None, parity=False, sustained=0):
+                 backend='nccl', emulate=None, parity=False, sustained=0, dump=None):
     """One engine on one workload.  Returns dict(elapsed, k_ms, k_launches, k_flops, k_bytes, rmse, n, spec, ranks, types).
     emulate = (k, W): this process computes what rank k of W would in mode 'owned', exchanges skipped (timing only).
     parity: the first PARITY_ITERS iterations are run apart and their backbones, PARITY_ROWS factor rows and relation errors
-    kept (`parity` of the result; config 3, one GPU) -- the engine's side of `parity_full_size`; the timed steps follow on."""
+    kept (`parity` of the result; config 3, one GPU) -- the engine's side of `parity_full_size`; the timed steps follow on.
+    dump (a directory): the factors and backbones after the last timed step go there (dump_outputs; not sharded, rank 0)."""
     import torch
     import skfusion_amd._native as nat
     from skfusion_amd._engine import DevicePlan, fill_uniform
@@ -944,6 +979,8 @@ def run_workload(workload, dtype, steps, warmup, scale=1.0, data='uniform', mode
     elapsed = time.perf_counter() - t0
     k_ms, k_launches, k_flops, k_bytes = plan.get_profile()
     plan.set_profiling(False)
+    if dump and rank == 0 and not emulate and not sharded:
+        dump_outputs(dump, plan, types, spec, local_index, n, dtype)
     sus = None
     if sustained and not emulate:              # a second, long timed region on the same plan: the rate the part sustains
         sync()                                 # (the chip clocks down under real operands: 1.67 GHz vs 2.41 GHz on zeros)
@@ -1232,8 +1269,16 @@ def main():
     ap.add_argument('--no-strong', action='store_true', help='N > 1, mode restarts: skip the `strong` sub-record (one fit sharded '
                                                              'by ownership over the same process group, configs 3 and 5)')
     ap.add_argument('--sustained-steps', type=int, default=1000,
-                    help='default run: a second timed region of this many steps (>= 10 s), reported as `sustained`; 0 = off')
+                    help='--full run: a second timed region of this many steps (>= 10 s), reported as `sustained`; 0 = off')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: sustained, parity, engines, workloads, strong, cpu_baseline and the '
+                         'rocprofv3 counter children (a plain run sets up, warms up, times --steps steps and prints the line)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write the factors (G_<type>.npy, a fixed seeded sample of %d rows where a '
+                         'type has more) and the backbones (S_<row>_<col>.npy) of the timed fit to DIR' % DUMP_ROWS)
     args = ap.parse_args()
+    if args.dump_outputs and (args.emulate_rank or (args.gpus > 1 and args.mode != 'restarts')):
+        ap.error('--dump-outputs: the fit of one GPU (rank 0 of --mode restarts), not a sharded or emulated one')
     if args.cpu_full_child:
         _full_size_child(args.parity_out)
         return
@@ -1277,13 +1322,15 @@ def main():
     if args.emulate_rank:
         print(json.dumps(emulated_ranks(args)))
         return
-    default_run = world == 1 and not c5 and args.scale == 1.0 and args.data == 'uniform'
-    want_parity = default_run and not args.no_cpu_baseline
+    # the sub-records of the metric's configuration (one GPU, config 3, full size, uniform data): --full only
+    full_run = args.full and world == 1 and not c5 and args.scale == 1.0 and args.data == 'uniform'
+    want_parity = full_run and not args.no_cpu_baseline
     parity_kept = {}
-    # Order of a default run: the headline (quiet host) -> the full-size oracle child starts in the background -> the GPU-only
+    # Order of a --full run: the headline (quiet host) -> the full-size oracle child starts in the background -> the GPU-only
     # sub-records (engines, workloads) beside it -> the child is collected -> the other host timings -> the PMC children.
     w = run_workload(args.workload, args.dtype, args.steps, args.warmup, args.scale, args.data, args.mode, rank, world,
-                     dist, backend, parity=want_parity, sustained=args.sustained_steps if default_run else 0)
+                     dist, backend, parity=want_parity, sustained=args.sustained_steps if full_run else 0,
+                     dump=args.dump_outputs)
     parity_kept[args.dtype] = w['parity']
     elapsed, rmse, n, spec, ranks_, types = w['elapsed'], w['rmse'], w['n'], w['spec'], w['ranks'], w['types']
     sharded = w['sharded']
@@ -1296,15 +1343,15 @@ def main():
                'rows': 'one fit, balanced row blocks of the relations over the GPUs',
                'owned': 'one fit, every GPU owns the same share of the rows of every object type'}[args.mode]
         cpu_child = pfile = dicty = None
-        if default_run and not args.no_workloads:
+        if full_run and not args.no_workloads:
             dicty = dicty_record()             # (bound by the host's launch rate: measured before the oracle child loads the host)
-        if world == 1 and not args.no_cpu_baseline and not c5:
+        if full_run and not args.no_cpu_baseline:
             import tempfile
             pfile = os.path.join(tempfile.gettempdir(), 'skf_parity_%d.npz' % os.getpid()) if want_parity else None
-            if default_run and not (args.no_engines and args.no_workloads):
+            if not (args.no_engines and args.no_workloads):
                 cpu_child = cpu_baseline_start({'auto': 'auto', 'full': True, 'sample': False}[args.cpu_baseline], pfile)
         pmc = mfma_pmc = None
-        if default_run and not args.no_pmc and cpu_child is None:
+        if full_run and not args.no_pmc and cpu_child is None:
             pmc = pmc_traffic_in_run(args.dtype)              # counters of THIS run when the box has rocprofv3
             mfma_pmc = None if c5 else pmc_mfma_in_run(args.dtype)
         roof = roofline_record(args.dtype, n, ranks_, spec, w['k_ms'], w['k_launches'], w['k_flops'], args.steps, elapsed,
@@ -1354,14 +1401,14 @@ def main():
             print(json.dumps(out, default=str), flush=True)
             os._exit(0)
         signal.signal(signal.SIGTERM, _line_and_leave)
-        if default_run and not (args.no_cpu_baseline and args.no_engines and args.no_workloads and args.no_pmc):
+        if full_run and not (args.no_cpu_baseline and args.no_engines and args.no_workloads and args.no_pmc):
             # ... and a process that does not survive a sub-record (a GPU fault aborts it) still leaves the headline behind
             # (not in the counter children of this file, which run no sub-record -- and run under a profiler)
             watchdog = LineWatchdog(json.dumps(dict(out, interrupted='the process died during the sub-records; the headline '
                                                                  'fields are complete'), default=str))
             if os.environ.get('SKF_BENCH_DIE_IN_SUBRECORDS'):        # rehearsal (tools/gpu_round2.sh)
                 os.kill(os.getpid(), signal.SIGKILL)
-    if default_run and not args.no_engines:
+    if full_run and not args.no_engines:
         # the reference computes in f64: short runs of the f32 and f64 engines on the same graph
         engines = {}
         for dt in ('f32', 'f64'):
@@ -1377,10 +1424,10 @@ def main():
             except Exception as exc:
                 engines[dt] = {'error': str(exc)[:300]}
         out['engines'] = engines
-    if default_run and not args.no_workloads:
+    if full_run and not args.no_workloads:
         out['workloads'] = other_workloads(args.dtype, dicty)
     hung = False
-    if world > 1 and args.mode == 'restarts' and not args.no_strong and not c5 and args.data == 'uniform':
+    if args.full and world > 1 and args.mode == 'restarts' and not args.no_strong and not c5 and args.data == 'uniform':
         # collective: every rank runs it; bounded, so that the restarts line above survives a collective that never returns,
         # and watched, so that it survives a rank 0 that does not come back at all
         if rank == 0:
@@ -1391,7 +1438,7 @@ def main():
             watchdog.disarm()
             out['strong'] = strong
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if c5:
                 full = cpu_baseline_c5_full(args.scale) if args.cpu_baseline == 'full' else None
                 out['cpu_baseline'] = full or cpu_baseline_c5(0.25 * args.scale, args.scale)
@@ -1411,9 +1458,9 @@ def main():
                     os.remove(pfile)
                 elif want_parity:
                     out['parity_full_size'] = {'error': 'no full-size oracle run on this host (cpu_baseline.projection)'}
-        if default_run and 'workloads' in out:
+        if full_run and 'workloads' in out:
             other_workloads_host(out['workloads'], args.dtype, cpu=not args.no_cpu_baseline, pmc=not args.no_pmc)
-        if default_run and not args.no_pmc and cpu_child is not None:
+        if full_run and not args.no_pmc and cpu_child is not None:
             # the counters of THIS run, once the host is quiet again: two rocprofv3 children; the roofline record is rebuilt
             pmc = pmc_traffic_in_run(args.dtype)
             if pmc:

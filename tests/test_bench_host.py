@@ -104,6 +104,70 @@ def test_relation_partition_is_deterministic_and_complete():
     assert a == b and sorted(set(a[0])) == [0, 1] and len(a[0]) == 3
 
 
+def test_dump_outputs_sample_is_fixed_and_small():
+    """`--dump-outputs`: every row of a small factor, a fixed sorted sample of DUMP_ROWS rows of a larger one, the same in
+    every run; the files of a full-size run of either workload, f64 engine included, stay under 64 MB."""
+    assert list(bench.dump_rows(100)) == list(range(100))
+    rows = bench.dump_rows(bench.FULL['t2'])
+    assert len(rows) == bench.DUMP_ROWS == len(np.unique(rows)) and np.all(np.diff(rows) > 0)
+    assert rows[-1] < bench.FULL['t2'] and np.array_equal(rows, bench.dump_rows(bench.FULL['t2']))
+    for full, ranks, pairs in ((bench.FULL, bench.RANKS, bench.PAIRS), (bench.C5_FULL, bench.C5_RANKS, bench.C5_PAIRS)):
+        n = bench.sizes(1.0, full)
+        nbytes = 8 * (sum(len(bench.dump_rows(n[t])) * ranks[t] for t in n) + sum(ranks[p[0]] * ranks[p[1]] for p in pairs))
+        assert nbytes < 64e6
+
+
+@pytest.mark.parametrize('full', [False, True])
+def test_plain_bench_run_times_the_headline_only(full, monkeypatch, capsys):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` runs ONE workload (no parity iterations, no sustained region) and
+    prints the headline; the sub-records, the baselines and the counter children run with --full only.  The GPU side is
+    stubbed: what is checked is which legs main() enters and the fields of the line."""
+    import json
+    import signal
+    import types
+    import torch
+    import __graft_entry__
+    calls, legs = [], []
+
+    def run(workload, dtype, steps, warmup, scale=1.0, data='uniform', mode='restarts', rank=0, world=1, dist=None,
+            backend='nccl', emulate=None, parity=False, sustained=0, dump=None):
+        calls.append(dict(workload=workload, dtype=dtype, steps=steps, warmup=warmup, parity=parity, sustained=sustained,
+                          dump=dump))
+        spec = [(i, j, False) for i, j, _ in bench.PAIRS]
+        return {'elapsed': 0.01 * steps, 'k_ms': 6.0 * steps, 'k_launches': 6 * steps, 'k_flops': 0.0, 'k_bytes': 0.0,
+                'rmse': {'t1-t2': 0.2887}, 'n': dict(bench.FULL), 'spec': spec, 'ranks': dict(bench.RANKS),
+                'types': list(bench.TYPES), 'sharded': False, 'exchange_bytes': None, 'parity': None,
+                'sustained': None, 'enqueue_ms_per_step': 0.1, 'launches_per_step': 60.0, 'comm': None}
+
+    def leg(name, result=None):
+        return lambda *a, **k: legs.append(name) or result
+    monkeypatch.setattr(bench, 'run_workload', run)
+    monkeypatch.setattr(torch.cuda, 'set_device', lambda d: None)
+    monkeypatch.setattr(__graft_entry__, 'build', lambda: None)
+    for name, result in (('dicty_record', {}), ('cpu_baseline_start', None), ('pmc_traffic_in_run', None),
+                         ('pmc_mfma_in_run', None), ('other_workloads', {}), ('other_workloads_host', None),
+                         ('cpu_baseline', {'projection': True})):
+        monkeypatch.setattr(bench, name, leg(name, result))
+    monkeypatch.setattr(bench, 'LineWatchdog', lambda line: types.SimpleNamespace(disarm=lambda: None))
+    monkeypatch.setattr(signal, 'signal', lambda *a: None)                 # (main() installs a TERM handler of its own)
+    monkeypatch.delenv('WORLD_SIZE', raising=False)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'] + (['--full'] if full else []))
+    bench.main()
+    line = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith('{')][-1])
+    assert line['steps'] == 7 and line['ms_per_step'] == pytest.approx(10.0) and line['value'] == pytest.approx(100.0)
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'rmse', 'roofline'):
+        assert key in line
+    assert calls[0] == dict(workload='c3', dtype='bf16', steps=7, warmup=2, parity=full, sustained=1000 if full else 0, dump=None)
+    if full:
+        assert len(calls) == 3 and {c['dtype'] for c in calls[1:]} == {'f32', 'f64'}        # the engines
+        assert {'dicty_record', 'cpu_baseline_start', 'other_workloads', 'cpu_baseline', 'pmc_traffic_in_run'} <= set(legs)
+        assert 'engines' in line and 'cpu_baseline' in line and 'parity_full_size' in line
+    else:
+        assert len(calls) == 1 and legs == []
+        for key in ('engines', 'workloads', 'cpu_baseline', 'parity_full_size', 'strong'):
+            assert key not in line
+
+
 def test_bench_gpus_n_launches_itself_and_checks_the_world_size(monkeypatch):
     """`python bench.py --gpus 2` without a launcher re-executes itself under torch.distributed.run with one
     rank per GPU; under a launcher WORLD_SIZE must equal --gpus (round-1 finding: --gpus was never read)."""

@@ -11,6 +11,8 @@ ranks 128/256/256), with checks a wrong kernel cannot pass:
   0.01 / sqrt(12) = 0.0029 -- on iid-uniform data every fit, right or wrong, sits at sqrt(1/12) -- and the
   RMSE the device reports must agree with a host evaluation on rows copied back from HBM.
 """
+import os
+
 import numpy as np
 import pytest
 import scipy.linalg
@@ -276,6 +278,36 @@ def test_config5_full_size_completion_and_contractions_against_host_rows(form):
     within(relerr(Q[cols], Rc_cols.T @ Gub), 2.5e-6, 'config 5 full size: Q rows of the completed ratings relation vs host')
     # and the known entries weigh in: the same products with the unknown entries alone are far off
     assert relerr(P[rows], np.where(U_rows, bf16(Hb[rows] @ Gmb.T), 0.0) @ Gmb) > 1e-2
+
+
+def test_bench_dump_outputs_are_the_factors_of_the_timed_fit(tmp_path):
+    """`bench.py --dump-outputs DIR` at 1/10 linear scale: after warm-up + timed steps the files hold exactly what a plain fit
+    of the same inputs and the same number of iterations hands back -- the sampled factor rows and every backbone, bit for
+    bit, in the engine's master precision -- and a second run writes the same bytes."""
+    import torch
+    n = bench.sizes(0.1)
+    for rep in ('a', 'b'):
+        bench.run_workload('c3', 'bf16', 2, 1, scale=0.1, dump=str(tmp_path / rep))
+    names = sorted(['G_%s.npy' % t for t in TYPES] + ['S_%s_%s.npy' % (i, j) for i, j, _ in bench.PAIRS])
+    assert sorted(os.listdir(str(tmp_path / 'a'))) == names
+    for name in names:
+        a, b = np.load(str(tmp_path / 'a' / name)), np.load(str(tmp_path / 'b' / name))
+        assert a.dtype == np.float32 and np.isfinite(a).all()
+        assert a.tobytes() == b.tobytes(), name
+    rels = [(i, j, bench.c3_relation(k, n, 'bf16'), None) for k, (i, j, _) in enumerate(bench.PAIRS)]
+    plan = DevicePlan(TYPES, n, RANK, rels, [], nat.SKF_DFMF, dtype='bf16')
+    for k, t in enumerate(TYPES):
+        plan.set_factor(t, fill_uniform((n[t], RANK[t]), 100 + k, 'f32'))
+    plan.iterate(3)
+    for t in TYPES:
+        rows = bench.dump_rows(n[t])
+        assert len(rows) == min(n[t], bench.DUMP_ROWS)
+        np.testing.assert_array_equal(np.load(str(tmp_path / 'a' / ('G_%s.npy' % t))), plan.get_factor(t)[rows].astype(np.float32))
+    for q, (i, j, _) in enumerate(bench.PAIRS):
+        np.testing.assert_array_equal(np.load(str(tmp_path / 'a' / ('S_%s_%s.npy' % (i, j)))), plan.get_backbone(q).astype(np.float32))
+    plan.close()
+    del rels, plan
+    torch.cuda.empty_cache()
 
 
 def test_bench_parity_record_at_a_tenth_of_the_size(tmp_path):

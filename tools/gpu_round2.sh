@@ -19,13 +19,13 @@ case "$step" in
     for a in "" "--tn"; do python tools/bench_gemm_bf16.py --shapes Q12,Q13,Q23 --tiles 256 --reps 10 $a 2>&1 | grep -v -e Warning -e amdgpu.ids | tee -a "$OUT/tnbench.txt"; done ;;
   bench_*)
     dt=${step#bench_}
-    ( time timeout 900 python bench.py --dtype $dt --steps 20 --warmup 3 --no-cpu-baseline ) > "$OUT/bench_$dt.log" 2>&1
+    ( time timeout 900 python bench.py --full --dtype $dt --steps 20 --warmup 3 --no-cpu-baseline ) > "$OUT/bench_$dt.log" 2>&1
     echo "bench $dt exit $?" | tee -a "$OUT/summary.txt"; grep '^{' "$OUT/bench_$dt.log" | cut -c1-600 | tee -a "$OUT/summary.txt" ;;
   dist_smoke)
     # `bench.py --gpus 2` launches itself (torch.distributed.run, one rank per GPU); on this one-GPU box the two
     # ranks share GPU 0 over a gloo group: all three multi-GPU modes end to end
     for mode in restarts relations rows owned; do
-      ( SKF_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 3 --warmup 1 --scale 0.2 --mode $mode --no-cpu-baseline --no-engines ) > "$OUT/dist_$mode.log" 2>&1
+      ( SKF_BENCH_BACKEND=gloo timeout 600 python bench.py --full --gpus 2 --steps 3 --warmup 1 --scale 0.2 --mode $mode --no-cpu-baseline --no-engines ) > "$OUT/dist_$mode.log" 2>&1
       echo "dist $mode exit $?" | tee -a "$OUT/summary.txt"; grep '^{' "$OUT/dist_$mode.log" | cut -c1-260 | tee -a "$OUT/summary.txt"
     done
     # (round 5) the default mode also carries the `strong` sub-record: one fit sharded by ownership over the same two ranks
@@ -33,7 +33,7 @@ case "$step" in
     # (round 6) a rank lost INSIDE the strong leg: the measured restarts line must still come out, exactly once -- rank 1 killed:
     # the launcher's TERM reaches rank 0's handler; rank 0 killed: the forked watchdog prints what rank 0 held
     for dead in 1 0; do
-      ( SKF_BENCH_DIE_IN_STRONG=$dead SKF_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 3 --warmup 1 --scale 0.2 --no-cpu-baseline --no-engines ) > "$OUT/dist_dead$dead.log" 2>&1
+      ( SKF_BENCH_DIE_IN_STRONG=$dead SKF_BENCH_BACKEND=gloo timeout 600 python bench.py --full --gpus 2 --steps 3 --warmup 1 --scale 0.2 --no-cpu-baseline --no-engines ) > "$OUT/dist_dead$dead.log" 2>&1
       echo "dist restarts, rank $dead killed in the strong leg: exit $?, JSON lines $(grep -c '^{' "$OUT/dist_dead$dead.log")" | tee -a "$OUT/summary.txt"
       grep '^{' "$OUT/dist_dead$dead.log" | python -c "import json,sys; d=json.loads(sys.stdin.readline()); print('  value', round(d['value'],1), 'n_gpus', d['n_gpus'], 'strong', d.get('strong'), 'interrupted', d.get('interrupted'))" | tee -a "$OUT/summary.txt"
     done
@@ -53,11 +53,11 @@ case "$step" in
     ( timeout 600 python tools/bench_transform.py ) > "$OUT/foldin_scale.txt" 2>&1
     echo "foldin exit $?" | tee -a "$OUT/summary.txt"; grep fold-in "$OUT/foldin_scale.txt" | cut -c1-200 | tee -a "$OUT/summary.txt" ;;
   fullbench)
-    ( time timeout 1200 python bench.py ) > "$OUT/bench_full.log" 2>&1
+    ( time timeout 1200 python bench.py --full ) > "$OUT/bench_full.log" 2>&1
     echo "bench exit $?" | tee -a "$OUT/summary.txt"; grep '^{' "$OUT/bench_full.log" | tee -a "$OUT/summary.txt" ;;
   die_sub)
     # (round 6) the default run killed right after its headline is measured: the forked watchdog prints the line, once
-    ( SKF_BENCH_DIE_IN_SUBRECORDS=1 timeout 600 python bench.py ) > "$OUT/die_sub.log" 2>&1
+    ( SKF_BENCH_DIE_IN_SUBRECORDS=1 timeout 600 python bench.py --full ) > "$OUT/die_sub.log" 2>&1
     echo "bench killed during the sub-records: exit $?, JSON lines $(grep -c '^{' "$OUT/die_sub.log")" | tee -a "$OUT/summary.txt"
     grep '^{' "$OUT/die_sub.log" | python -c "import json,sys; d=json.loads(sys.stdin.readline()); print('  value', round(d['value'],2), 'frac', round(d['roofline']['frac'],3), '|', d.get('interrupted'))" | tee -a "$OUT/summary.txt" ;;
   c5_*)

@@ -21,12 +21,12 @@ case "$step" in
   bench_*)
     dt=${step#bench_}
     echo "== bench $dt" | tee -a "$OUT/summary.txt"
-    ( time timeout 900 python bench.py --dtype $dt --steps 10 --warmup 3 ) > "$OUT/bench_$dt.log" 2>&1
+    ( time timeout 900 python bench.py --full --dtype $dt --steps 10 --warmup 3 ) > "$OUT/bench_$dt.log" 2>&1
     echo "bench exit $?" | tee -a "$OUT/summary.txt"; tail -4 "$OUT/bench_$dt.log" | tee -a "$OUT/summary.txt" ;;
   c5_*)
     dt=${step#c5_}
     echo "== bench c5 (Dfmc, MovieLens-style) $dt" | tee -a "$OUT/summary.txt"
-    ( time timeout 900 python bench.py --workload c5 --dtype $dt --steps 5 --warmup 2 ) > "$OUT/c5_$dt.log" 2>&1
+    ( time timeout 900 python bench.py --full --workload c5 --dtype $dt --steps 5 --warmup 2 ) > "$OUT/c5_$dt.log" 2>&1
     echo "c5 exit $?" | tee -a "$OUT/summary.txt"; tail -3 "$OUT/c5_$dt.log" | cut -c1-1500 | tee -a "$OUT/summary.txt" ;;
   c5prof_*)
     dt=${step#c5prof_}
@@ -44,7 +44,7 @@ case "$step" in
     # the torchrun paths of bench.py with 2 ranks sharing the one GPU of this box (gloo group)
     echo "== torchrun x2 (gloo, shared GPU) restarts / relations / rows" | tee -a "$OUT/summary.txt"
     for mode in restarts relations rows; do
-      ( SKF_BENCH_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 --scale 0.2 --mode $mode --no-cpu-baseline ) > "$OUT/dist_$mode.log" 2>&1
+      ( SKF_BENCH_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 3 --warmup 1 --scale 0.2 --mode $mode --no-cpu-baseline ) > "$OUT/dist_$mode.log" 2>&1
       echo "dist $mode exit $?" | tee -a "$OUT/summary.txt"; tail -1 "$OUT/dist_$mode.log" | cut -c1-700 | tee -a "$OUT/summary.txt"
     done ;;
   prof_*)
