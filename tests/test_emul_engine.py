@@ -1012,3 +1012,33 @@ def test_known_entries_dfmc_c5_golden_and_bound_too_small(monkeypatch):
     pm.known = pm.known - 5
     with pytest.raises(nat.SkfNativeError, match='known entries'):
         DevicePlan(types, n, rank, [(rel[0][0], rel[0][1], rel[0][2], pm)] + rel[1:], flatten_thetas(Theta), nat.SKF_DFMC)
+
+
+# one case per list-kernel family (launch_srp, csrc/skf_stages.inc; the SRP_ERR pass of skf_relation_sqerr on each), every
+# mask pattern and part count at least once; the full variant x pattern x parts matrix runs on the GPU
+# (tests/test_gpu_known_lists.py)
+@pytest.mark.parametrize('dtype,rank_a,parts,pattern', [
+    ('bf16', 128, 2, 'edges'),      # srp_bf16_v6_kernel<1> (residual + apply), srp_bf16_kernel<16> (error pass)
+    ('bf16', 256, 4, 'edges'),      # srp_bf16_kernel<32> (residual, error), srp_bf16_v6_kernel<2> (apply)
+    ('bf16', 64, 8, 'full'),        # srp_bf16_kernel<8>
+    ('bf16', 20, 1, 'heavy'),       # srp_any_kernel<uint16_t, float>
+    ('f32', 64, 1, 'edges'),        # srp_vec_kernel<float, float, 16>
+    ('f32', 24, 2, 'full'),         # srp_any_kernel<float, float>
+    ('f64', 64, 4, 'heavy'),        # srp_vec_kernel<double, double, 32>
+    ('f64', 20, 8, 'edges'),        # srp_any_kernel<double, double>
+])
+def test_known_entry_lists_against_host_model(dtype, rank_a, parts, pattern, monkeypatch):
+    """The known-entry list passes held to the host model of one DFMC iteration (tests/known_cases.py: error model and mask
+    patterns) -- the sparse terms E T and E^T G_i on their own and the list sum of the squared error."""
+    import known_cases as K
+    K.list_case(203, 197, rank_a, 8, dtype, parts, pattern, 'emulator %s rank %d parts %d %s' % (dtype, rank_a, parts, pattern),
+                monkeypatch)
+
+
+@pytest.mark.parametrize('rank_a,rank_b,parts,pattern', [(64, 128, 2, 'edges'), (256, 64, 4, 'full'), (128, 256, 8, 'heavy')])
+def test_known_ones_lists_against_host_model(rank_a, rank_b, parts, pattern, monkeypatch):
+    """A sparse 0 / 1 relation as lists over bf16 factor rows (srp_bf16_v6_kernel<.., SRP_ONES, 2 | 4>, gathered ranks
+    64 / 128 / 256; parted_ptr_kernel for the parts) against f64 sums of the bf16 rows."""
+    import known_cases as K
+    K.ones_case(331, 333, rank_a, rank_b, parts, pattern, 'emulator ones %d x %d parts %d %s' % (rank_a, rank_b, parts, pattern),
+                monkeypatch)
