@@ -1042,3 +1042,15 @@ def test_known_ones_lists_against_host_model(rank_a, rank_b, parts, pattern, mon
     import known_cases as K
     K.ones_case(331, 333, rank_a, rank_b, parts, pattern, 'emulator ones %d x %d parts %d %s' % (rank_a, rank_b, parts, pattern),
                 monkeypatch)
+
+
+# ---- one dense iteration held to the host model, stage by stage (tests/dense_cases.py: error model and cases; the full
+# matrix of engines, schedules and sizes runs on the GPU in tests/test_gpu_dense_model.py)
+@pytest.mark.parametrize('case', sorted(__import__('dense_cases').EMUL))
+def test_dense_iteration_against_host_model(case, monkeypatch):
+    """Contractions, backbone (W in the device's form), the per-element update from the device's P, Q, S (side
+    products, +- split epilogues, Theta split and CSR product, the small-graph launches), the DFMC completion and the
+    bf16 G^T refresh of a second iteration -- one case per kernel family and schedule."""
+    import dense_cases as DC
+    dtype, schedule, n, ranks, rels, thetas, kw = DC.EMUL[case]
+    DC.dense_case(dtype, schedule, n, ranks, rels, thetas, 'emulator dense ' + case, monkeypatch, **kw)
