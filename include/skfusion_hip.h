@@ -96,7 +96,7 @@ enum {
                                  known entries of the WHOLE relation (the partial sums the processes exchange follow one
                                  convention per relation); also set on SKF_REL_ABSENT descriptors of such a relation.  known_bound
                                  then bounds the known entries of the LOCAL rows.  Other plans: ignored (the library decides). */
-    SKF_REL_BINARY = 16       /* every entry is 0 or 1 (checked at bind time; "movie has genre", "user tagged").
+    SKF_REL_BINARY = 16,      /* every entry is 0 or 1 (checked at bind time; "movie has genre", "user tagged").
                                  SKF_BF16 keeps such a relation as a BITMAP -- 1 bit instead of a bf16 per entry
                                  in HBM and on the way to the matrix cores, where it is expanded to bf16 0 / 1 in
                                  LDS: the same products as the dense form, bit for bit.  A sparse one also keeps
@@ -106,6 +106,14 @@ enum {
                                  order); with other ranks and at most 1 entry in 256 set, as gathers of the f32
                                  factor rows (exact f32 sums).  Ignored for masked relations and by the f32 / f64
                                  engines. */
+    SKF_REL_KNOWN_CSR = 64    /* SKF_DFMC: the relation is given as its KNOWN entries only, as CSR (the stored entries are the
+                                 known ones, every other entry is unknown) -- no dense form exists: `data` and `mask` are NULL,
+                                 known_bound is the EXACT number of entries (0 allowed) and skf_plan_set_known_entries hands the
+                                 lists over before skf_plan_bind_workspace.  Always kept as lists of its known entries (neither
+                                 SKF_DFMC_SPARSE nor the share rule applies: there is no dense form to fall back on); the lists
+                                 built at bind time are the ones the mask form of the same data builds, byte for byte.
+                                 SKF_E_INVALID: SKF_DFMF / SKF_TRANSFORM plans, row blocks / sliced / SKF_OPT_OWNED_ROWS plans,
+                                 a row type's rank above 1024, more than 2e9 entries. */
 };
 
 typedef struct {
@@ -155,6 +163,15 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
 int skf_plan_destroy(skf_plan* plan);
 
 int skf_plan_workspace_bytes(const skf_plan* plan, size_t* bytes);
+/* The known entries of relation `rel` (flagged SKF_REL_KNOWN_CSR), as device pointers: indptr[n_row + 1] (int64,
+ * indptr[0] = 0, indptr[n_row] = known_bound, non-decreasing), indices[known_bound] (int32 columns, strictly ascending
+ * within a row: canonical CSR, duplicates summed beforehand) and values[known_bound] of the element type of
+ * skf_relation_desc.data (SKF_BF16: bf16 bits).  Call it between skf_plan_create and skf_plan_bind_workspace; the buffers
+ * are read by skf_plan_bind_workspace and not referenced afterwards (the contract of `data`).  Bind validates them on the
+ * device before anything gathers through them: a non-monotone indptr, an index outside [0, n_col) or a row whose
+ * columns do not ascend strictly is SKF_E_INVALID, as is a SKF_REL_KNOWN_CSR relation without this call. */
+int skf_plan_set_known_entries(skf_plan* plan, int32_t rel, const int64_t* indptr, const int32_t* indices,
+                               const void* values);
 /* `workspace` must be 256-byte aligned device memory and stay valid for the plan's lifetime.
  * For DFMC the masked relations are copied into the workspace here (the caller's relation
  * data is never written: _dfmc.py:268, tests/test_dfmc.py:62,85). */

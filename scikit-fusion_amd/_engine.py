@@ -37,6 +37,76 @@ class PackedMask(object):
         self.known = int(known)         # number of KNOWN entries (mask == 0); 0 = not counted
 
 
+class KnownEntries(object):
+    """A relation given as its KNOWN entries only, canonical CSR on the host: `indptr` (n_row + 1), `indices` (columns,
+    strictly ascending within a row) and `values`; every entry not stored is unknown (SKF_REL_KNOWN_CSR).  The engine's
+    own container -- the API layer builds it from a ``scipy.sparse`` matrix (``Relation(..., unstored='unknown')``).
+    ``known`` is the number of entries; ``toarray`` / ``mask`` give the equivalent dense relation and completion mask."""
+
+    def __init__(self, indptr, indices, values, shape, fill=0.0):
+        self.indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        self.indices = np.ascontiguousarray(indices, dtype=np.int32)
+        self.values = np.ascontiguousarray(values, dtype=np.float64)
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.known = int(self.indices.size)
+        self.fill = float(fill)         # what the mask form holds beneath its unknown entries (read by the initialisers only)
+
+    def row_of_entries(self):
+        return np.repeat(np.arange(self.shape[0], dtype=np.int64), np.diff(self.indptr))
+
+    def toarray(self, fill=None):
+        """The dense relation of the mask form: the values on the known entries, `fill` (default: self.fill) elsewhere."""
+        out = np.full(self.shape, self.fill if fill is None else fill, dtype=np.float64)
+        out[self.row_of_entries(), self.indices] = self.values
+        return out
+
+    def mask(self):
+        """True = unknown (the DFMC convention)."""
+        m = np.ones(self.shape, dtype=bool)
+        m[self.row_of_entries(), self.indices] = False
+        return m
+
+    def validate(self):
+        """The device's checks on the host (skf_plan_set_known_entries), before anything is uploaded."""
+        from .fusion.base import DataFusionError
+        n_r, n_c = self.shape
+        p, ix = self.indptr, self.indices
+        if p.ndim != 1 or p.size != n_r + 1 or p[0] != 0 or p[-1] != ix.size or self.values.shape != ix.shape:
+            raise DataFusionError('known entries: indptr must run from 0 to the %d entries over %d rows' % (ix.size, n_r))
+        if (np.diff(p) < 0).any():
+            raise DataFusionError('known entries: indptr is not non-decreasing')
+        if ix.size and (ix.min() < 0 or ix.max() >= n_c):
+            raise DataFusionError('known entries: a column index outside [0, %d)' % n_c)
+        if ix.size > 1:
+            first = np.zeros(ix.size, dtype=bool)                   # entries that open a row: no step to check there
+            first[p[:-1][p[:-1] < ix.size]] = True
+            chunk = 1 << 24                                         # (no full-size temporaries: 80 M entries at config 5)
+            for c0 in range(0, ix.size - 1, chunk):
+                c1 = min(c0 + chunk, ix.size - 1)
+                if ((ix[c0 + 1:c1 + 1] <= ix[c0:c1]) & ~first[c0 + 1:c1 + 1]).any():
+                    raise DataFusionError('known entries: columns not strictly ascending within a row (canonical CSR)')
+
+
+class DeviceKnownEntries(object):
+    """KnownEntries uploaded ONCE in the engine's element type (upload_graph: shared by the plans of concurrent restarts)."""
+
+    def __init__(self, indptr, indices, values, shape, known):
+        self.indptr, self.indices, self.values = indptr, indices, values
+        self.shape, self.known = tuple(shape), int(known)
+
+
+def upload_known_entries(ke, dtype, mem):
+    """KnownEntries -> DeviceKnownEntries: validated on the host first (DataFusionError before any upload); values in the
+    element type of the relation data (SKF_BF16: bf16 bits, rounded as dense data is: f64 -> f32 -> bf16)."""
+    ke.validate()
+    code = nat.DTYPES[dtype] if isinstance(dtype, str) else dtype
+    vals = np.ascontiguousarray(ke.values, dtype=nat.NP_DTYPE[code])
+    if code == nat.SKF_BF16:
+        vals = nat.to_bf16_bits(vals)
+    keep = lambda a: mem.from_host(a if a.size else np.zeros(1, dtype=a.dtype))        # (no empty allocations)
+    return DeviceKnownEntries(keep(ke.indptr), keep(ke.indices), keep(vals), ke.shape, ke.known)
+
+
 def pack_mask(mask, mem):
     """Boolean host mask -> PackedMask (1/8 of the bytes cross PCIe; the engine reads one bit per entry)."""
     m = np.asarray(mask, dtype=bool)
@@ -421,10 +491,24 @@ class DevicePlan(object):
         for k in range(len(self.types)):
             tdesc[k].n_obj, tdesc[k].rank = self.n_obj[k], self.rank[k]
         rdesc = (nat.RelationDesc * max(len(relations), 1))()
+        csr = []                                         # (relation, DeviceKnownEntries): skf_plan_set_known_entries
         for k, rel in enumerate(relations):
             i, j, data, mask = rel[:4]
             block = rel[4] if len(rel) > 4 else None
             rdesc[k].row_type, rdesc[k].col_type = self.index[i], self.index[j]
+            if isinstance(data, (KnownEntries, DeviceKnownEntries)):
+                # the known entries only (SKF_REL_KNOWN_CSR): no dense form, no mask; always kept as lists
+                if mask is not None or block is not None:
+                    raise ValueError('relation (%s,%s): known entries take no mask and no row block' % (i, j))
+                if tuple(data.shape) != (n_obj[i], n_obj[j]):
+                    raise ValueError('relation (%s,%s) dimension mismatch: %r vs object counts (%d,%d)'
+                                     % (i, j, tuple(data.shape), n_obj[i], n_obj[j]))
+                dev = data if isinstance(data, DeviceKnownEntries) else upload_known_entries(data, self.dtype, mem)
+                self._keep_rel.append(dev)
+                rdesc[k].flags |= nat.SKF_REL_KNOWN_CSR
+                rdesc[k].known_bound = dev.known
+                csr.append((k, dev))
+                continue
             rows_here = n_obj[i]
             if block is not None:
                 rows_here = int(block['n_rows'])
@@ -508,6 +592,8 @@ class DevicePlan(object):
         self.owned = bool(owned)
         self.rt.call('skf_plan_create', len(self.types), tdesc, len(relations), rdesc, len(thetas),
                      hdesc, C.byref(opt), C.byref(self.handle))
+        for k, dev in csr:
+            self.rt.call('skf_plan_set_known_entries', self.handle, k, dev.indptr.ptr, dev.indices.ptr, dev.values.ptr)
         nbytes = C.c_size_t()
         self.rt.call('skf_plan_workspace_bytes', self.handle, C.byref(nbytes))
         self.workspace_bytes = nbytes.value
@@ -840,7 +926,10 @@ def upload_graph(rel_list, theta_list, dtype, runtime=None):
     rels, thetas = [], []
     for rel in rel_list:
         i, j, data, mask = rel[:4]
-        if not isinstance(data, DeviceMatrix):
+        if isinstance(data, KnownEntries):
+            rels.append((i, j, upload_known_entries(data, code, rt.mem), mask) + tuple(rel[4:]))
+            continue
+        if not isinstance(data, (DeviceMatrix, DeviceKnownEntries)):
             arr = np.ascontiguousarray(data, dtype=npd)
             up = nat.to_bf16_bits(arr) if code == nat.SKF_BF16 else arr
             binary = code == nat.SKF_BF16 and mask is None and is_binary_matrix(arr)
@@ -893,12 +982,13 @@ def iterate_rows_lockstep(plans, n_iters=1):
 
 def flatten_relations(R, M=None):
     """dict {(i,j): [matrix, ...]} -> [(i, j, matrix, mask)] in dict order, list order
-    (the order the reference walks `R`, _dfmf.py:249-251)."""
+    (the order the reference walks `R`, _dfmf.py:249-251).  A relation given as KnownEntries carries its own pattern of
+    known entries: its mask is None whatever M holds."""
     out = []
     for (i, j), mats in R.items():
         for l, m in enumerate(mats):
             mask = None
-            if M is not None and M.get((i, j)) is not None:
+            if M is not None and M.get((i, j)) is not None and not isinstance(m, KnownEntries):
                 mask = M[i, j][l]
             out.append((i, j, m, mask))
     return out

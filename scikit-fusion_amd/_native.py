@@ -16,6 +16,7 @@ SKF_DFMF, SKF_DFMC, SKF_TRANSFORM = 0, 1, 2
 SKF_ENGINE_MFMA, SKF_ENGINE_VALU = 0, 1
 SKF_REL_ABSENT, SKF_REL_NO_COL_SIDE, SKF_REL_MASKED, SKF_REL_MASK_BITS, SKF_REL_BINARY = 1, 2, 4, 8, 16
 SKF_REL_KNOWN_LISTS = 32
+SKF_REL_KNOWN_CSR = 64
 SKF_STAGE_CONTRACT, SKF_STAGE_BACKBONE, SKF_STAGE_ACCUMULATE, SKF_STAGE_UPDATE = 0, 1, 2, 3
 SKF_X_W, SKF_X_Q, SKF_X_QM, SKF_X_ED = 0, 1, 2, 3
 SKF_COMM_SINGLE, SKF_COMM_RCCL, SKF_COMM_CALLBACK, SKF_COMM_NULL = 0, 1, 2, 3
@@ -94,6 +95,7 @@ SIGNATURES = {
     'skf_plan_destroy': (C.c_int, [_P]),
     'skf_plan_workspace_bytes': (C.c_int, [_P, C.POINTER(C.c_size_t)]),
     'skf_plan_bind_workspace': (C.c_int, [_P, _P, C.c_size_t, _P]),
+    'skf_plan_set_known_entries': (C.c_int, [_P, C.c_int32, _P, _P, _P]),
     'skf_set_factor': (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
     'skf_get_factor': (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
     'skf_set_backbone': (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),

@@ -197,7 +197,10 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
                 SKF_FAIL(SKF_E_INVALID, "relation %d: type index out of range", r);
             if (d.row_type == d.col_type) SKF_FAIL(SKF_E_INVALID, "relation %d: row type == column type (pass it as a constraint)", r);
             const bool absent = (d.flags & SKF_REL_ABSENT) != 0;
-            if (!absent && (!d.data || d.ld < p->types[d.col_type].n))
+            const bool csr = (d.flags & SKF_REL_KNOWN_CSR) != 0;
+            if (csr && p->variant != SKF_DFMC) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR needs SKF_DFMC", r);
+            if (csr && (d.data || d.mask)) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR takes no data / mask", r);
+            if (!absent && !csr && (!d.data || d.ld < p->types[d.col_type].n))
                 SKF_FAIL(SKF_E_INVALID, "relation %d: dimension mismatch (ld %lld < %lld columns)", r, (long long)d.ld,
                          (long long)p->types[d.col_type].n);
             const int64_t n_row_type = p->types[d.row_type].n;
@@ -205,6 +208,7 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
                 SKF_FAIL(SKF_E_INVALID, "relation %d: row block [%lld, +%lld) outside the %lld objects of its row type",
                          r, (long long)d.row_begin, (long long)d.n_rows, (long long)n_row_type);
             const bool block = absent || (d.n_rows > 0 && d.n_rows < n_row_type) || (d.flags & SKF_REL_NO_COL_SIDE);
+            if (block && csr) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR relations are whole relations", r);
             if (block && p->variant == SKF_TRANSFORM)
                 SKF_FAIL(SKF_E_INVALID, "relation %d: row blocks are for SKF_DFMF / SKF_DFMC plans", r);
             if (block && p->bf16 && d.row_begin % 64 != 0)
@@ -237,6 +241,11 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
             }
             if (d.known_bound < 0) SKF_FAIL(SKF_E_INVALID, "relation %d: negative bound on the known entries", r);
             s.kn_cap = (s.mask && p->variant == SKF_DFMC) ? d.known_bound : 0;
+            if (csr) {                  // the known entries as CSR (skf_plan_set_known_entries): no dense form, no mask
+                s.kn_csr = s.masked = true;
+                s.R_in = s.R = nullptr;
+                s.kn_cap = d.known_bound;
+            }
         }
         // masked relations with few known entries are kept as lists of those entries (skf_known.h).  The three passes over the
         // lists gather rank_row-wide vectors -- ~70 ps per entry at rank 128 against ~2.2 ps per CELL for the four passes of
@@ -263,7 +272,13 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
             for (size_t rk = 0; rk < p->rels.size(); ++rk) {
                 RelState& s = p->rels[rk];
                 const int ci = p->types[s.row].c;
-                if (p->owned) {
+                if (s.kn_csr) {
+                    // lists whatever the share (no dense form to fall back on); the parts below follow from the exact count
+                    if (p->sliced) SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_KNOWN_CSR is for plans of whole relations", rk);
+                    if (ci > 64 * SRP_MAXREP || s.kn_cap > 2000000000LL)
+                        SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_KNOWN_CSR beyond the list limits (rank %d > %d or %lld > 2e9 entries)",
+                                 rk, ci, 64 * SRP_MAXREP, (long long)s.kn_cap);
+                } else if (p->owned) {
                     // ownership-aligned row blocks: the caller decided for ALL processes alike (SKF_REL_KNOWN_LISTS); a process
                     // without rows of the relation keeps the flag -- it adds the dense part of Q on ITS rows of the column type
                     const bool lists = (relations[rk].flags & SKF_REL_KNOWN_LISTS) != 0 && s.masked && p->variant == SKF_DFMC;
@@ -459,7 +474,7 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
                 // the known entries as row lists and column lists, the gathered vectors, the row-side product, c x c scratch
                 const size_t cap = (size_t)r.kn_cap;
                 r.ldmb = (tj.n + 127) / 128 * 16;
-                add_slot(p, r.Mb, (size_t)nr * r.ldmb);                         // (bind time only)
+                if (!r.kn_csr) add_slot(p, r.Mb, (size_t)nr * r.ldmb);          // (bind time only; CSR-fed: no mask at all)
                 add_slot(p, r.KrPtr, ((size_t)nr * r.kn_pc + 1) * 8);
                 add_slot(p, r.KrIdx, cap * 4);
                 add_slot(p, r.KrVal, cap * es);
@@ -675,6 +690,20 @@ int skf_plan_destroy(skf_plan* plan) {
     return SKF_OK;
 }
 
+int skf_plan_set_known_entries(skf_plan* plan, int32_t rel, const int64_t* indptr, const int32_t* indices, const void* values) {
+    return guarded([&] {
+        if (!plan) SKF_FAIL(SKF_E_INVALID, "null argument");
+        if (plan->ws_base) SKF_FAIL(SKF_E_STATE, "skf_plan_set_known_entries after skf_plan_bind_workspace");
+        if (rel < 0 || rel >= (int)plan->rels.size()) SKF_FAIL(SKF_E_INVALID, "relation %d out of range", rel);
+        RelState& r = plan->rels[rel];
+        if (!r.kn_csr) SKF_FAIL(SKF_E_INVALID, "relation %d is not flagged SKF_REL_KNOWN_CSR", rel);
+        if (!indptr || (r.kn_cap > 0 && (!indices || !values))) SKF_FAIL(SKF_E_INVALID, "relation %d: null CSR array", rel);
+        r.csr_ptr = indptr;
+        r.csr_idx = (const int*)indices;
+        r.csr_val = values;
+    });
+}
+
 int skf_plan_workspace_bytes(const skf_plan* plan, size_t* bytes) {
     return guarded([&] {
         if (!plan || !bytes) SKF_FAIL(SKF_E_INVALID, "null argument");
@@ -761,6 +790,11 @@ int skf_plan_bind_workspace(skf_plan* p, void* ws, size_t bytes, void* stream) {
         p->sw = Switches::read();          // the only place a plan looks at the environment
         hipStream_t st = as_stream(stream);
         for (RelState& r : p->rels) {
+            if (r.kn_csr) {                        // the caller's CSR, validated, then the same lists the mask form builds
+                if (!r.csr_ptr) SKF_FAIL(SKF_E_INVALID, "a SKF_REL_KNOWN_CSR relation without skf_plan_set_known_entries");
+                build_known_lists_csr(p, r, st);
+                continue;
+            }
             if (!r.mask) continue;
             // the mask in the engine's layout: one bit per entry, rows padded to whole 128-column tiles.
             // The caller's mask (bytes or bits) is not referenced after this call.

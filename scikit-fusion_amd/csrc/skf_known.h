@@ -669,4 +669,61 @@ __global__ __launch_bounds__(256) void known_col_values_kernel(const int64_t* __
             rvals[q] = (TM)GatherT<TR>::get(R[(int64_t)cidx[q] * ldr + c]);
 }
 
+// ---- bind time: the known entries handed over as CSR (SKF_REL_KNOWN_CSR) -------------------------------------------
+// A canonical CSR (columns strictly ascending within a row) already is the row order of the lists, and the column parts
+// are contiguous column ranges: KrIdx / KrVal are the caller's indices / values (values converted as known_row_fill_kernel
+// converts R), KrPtr the split points of every (row, column part) (parted_ptr_kernel).  The column side is built from
+// KrPtr / KrIdx alone, as for the mask form; its values come from the row lists.  Nothing gathers through the caller's
+// lists before known_csr_check_kernel has passed them.
+
+// bad[0] = 1 when the CSR is not canonical: indptr[0] != 0, indptr[rows] != nnz, a negative step, an index outside
+// [0, cols), columns not strictly ascending within a row.  One wave per row; a row whose bounds are off is not read.
+static __global__ __launch_bounds__(256) void known_csr_check_kernel(const int64_t* __restrict__ indptr, const int* __restrict__ idx,
+                                                                     int64_t rows, int64_t cols, int64_t nnz, int* __restrict__ bad) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    if (wave == 0 && lane == 0 && (indptr[0] != 0 || indptr[rows] != nnz)) *bad = 1;
+    for (int64_t r = wave; r < rows; r += nwaves) {
+        const int64_t a = indptr[r], b = indptr[r + 1];
+        if (a < 0 || b < a || b > nnz) {
+            if (lane == 0) *bad = 1;
+            continue;
+        }
+        int off = 0;
+        for (int64_t q = a + lane; q < b; q += 64) {
+            const int c = idx[q];
+            if (c < 0 || (int64_t)c >= cols || (q > a && idx[q - 1] >= c)) off = 1;
+        }
+        if (off) *bad = 1;
+    }
+}
+
+// rvals[q] = the caller's value q in the list value type (bf16 -> f32; f32 / f64 unchanged)
+template <typename TR, typename TM>
+__global__ __launch_bounds__(256) void known_csr_values_kernel(const TR* __restrict__ vals, int64_t nnz, TM* __restrict__ rvals) {
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nnz; q += (int64_t)gridDim.x * blockDim.x)
+        rvals[q] = (TM)GatherT<TR>::get(vals[q]);
+}
+
+// known_col_values_kernel without the dense relation: the value of CSC entry (row r, column c) is the one of the row
+// list entry of column c in row r -- a binary search of c in the ascending row segment (every CSC entry has one).
+// Plain loads and stores, no atomics: the same values, bit for bit, as R[r][c] gives in the mask form.
+template <typename TM>
+__global__ __launch_bounds__(256) void known_col_values_csr_kernel(const int64_t* __restrict__ cptr, const int* __restrict__ cidx, int cparts,
+                                                                   int64_t cols, const int64_t* __restrict__ rptr, const int* __restrict__ ridx,
+                                                                   int rparts, const TM* __restrict__ rvals_row, TM* __restrict__ rvals) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t c = wave; c < cols; c += nwaves)
+        for (int64_t q = cptr[c * cparts] + lane; q < cptr[(c + 1) * cparts]; q += 64) {
+            const int64_t r = cidx[q];
+            int64_t lo = rptr[r * rparts], hi = rptr[(r + 1) * rparts];
+            while (hi - lo > 1) {                               // ridx[lo] <= c < ridx[hi] (hi: one past the segment)
+                const int64_t mid = (lo + hi) >> 1;
+                if (ridx[mid] <= c) lo = mid; else hi = mid;
+            }
+            rvals[q] = rvals_row[lo];
+        }
+}
+
 }  // namespace skf

@@ -143,6 +143,10 @@ struct RelState {
     Slot KrPtr, KrIdx, KrVal;              // rows -> known columns (ascending), R there
     Slot KcPtr, KcIdx, KcVal, KcE;         // columns -> known rows (ascending), R there, residuals E of the last iteration
     Slot KCnt;                             // count / fill-position scratch of the bind-time build
+    bool kn_csr = false;                   // SKF_REL_KNOWN_CSR: the lists come from the caller's CSR, not from a mask
+    const int64_t* csr_ptr = nullptr;      // the caller's CSR (skf_plan_set_known_entries; read at bind time only)
+    const int* csr_idx = nullptr;
+    const void* csr_val = nullptr;
     Slot FiB;                              // SKF_BF16: bf16 rows of T = G_j S^T (n_j x ldf; the rows of G_i: TypeState::Grow)
     Slot Tm;                               // T = G_j S^T in the master type (n_j x c_i)
     Slot Apart, Qpart;                     // partial outputs of the parts, [parts][n][c_i] (only with more than one part)

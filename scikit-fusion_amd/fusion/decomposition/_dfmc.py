@@ -7,11 +7,23 @@ from ... import _native as nat
 from ._dfmf import run_fit, run_fit_sharded, run_fit_rows, run_fit_owned
 
 
+def _expand_known_entries(R, M):
+    """Relations given as their known entries (_engine.KnownEntries) -> their mask form (dense data + mask)."""
+    from ..._engine import KnownEntries
+    R2, M2 = {}, {}
+    for key, mats in R.items():
+        masks = (M or {}).get(key) or [None] * len(mats)
+        R2[key] = [m.toarray() if isinstance(m, KnownEntries) else m for m in mats]
+        M2[key] = [m.mask() if isinstance(m, KnownEntries) else mk for m, mk in zip(mats, masks)]
+    return R2, M2
+
+
 def dfmc(R, M, Theta, obj_types, obj_type2rank, max_iter=10, init_type="random_vcol",
          stopping=None, stopping_system=None, verbose=0, compute_err=False, callback=None,
          random_state=None, n_jobs=1, dtype='f64', G0=None, engine=None, shard=None):
     """Data fusion by matrix completion -- drop-in for reference ``dfmc`` (_dfmc.py:181)."""
     if shard in ('relations', 'rows', 'owned'):
+        R, M = _expand_known_entries(R, M)      # (the sharded fits take the mask form)
         fit = {'relations': run_fit_sharded, 'rows': run_fit_rows, 'owned': run_fit_owned}[shard]
         return fit(nat.SKF_DFMC, R, M, Theta, obj_types, obj_type2rank, max_iter,
                    init_type, random_state, dtype, G0, engine, stopping, stopping_system, compute_err, callback)

@@ -13,7 +13,7 @@ import numpy as np
 
 from ... import _native as nat
 from ..._engine import DevicePlan, flatten_relations, flatten_thetas, count_objects
-from ._init import initialize
+from ._init import initialize, host_view
 
 log = logging.getLogger('skfusion_amd')
 
@@ -153,7 +153,7 @@ def run_fit_owned(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init
     obj_types = list(obj_types)
     n_obj = count_objects(obj_types, R)
     if G0 is None:
-        R_first = {k: np.asarray(v[0], dtype=float) for k, v in R.items()}
+        R_first = {k: host_view(v[0]) for k, v in R.items()}
         G0 = initialize(obj_types, n_obj, obj_type2rank, R_first, init_type, _as_rs(random_state))
     rel_list = flatten_relations(R, M)
     rank, size = world()
@@ -189,7 +189,7 @@ def run_fit_rows(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_
     obj_types = list(obj_types)
     n_obj = count_objects(obj_types, R)
     if G0 is None:
-        R_first = {k: np.asarray(v[0], dtype=float) for k, v in R.items()}
+        R_first = {k: host_view(v[0]) for k, v in R.items()}
         G0 = initialize(obj_types, n_obj, obj_type2rank, R_first, init_type, _as_rs(random_state))
     rel_list = flatten_relations(R, M)
     rank, size = world()
@@ -229,7 +229,7 @@ def run_fit_sharded(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, in
     obj_types = list(obj_types)
     n_obj = count_objects(obj_types, R)
     if G0 is None:
-        R_first = {k: np.asarray(v[0], dtype=float) for k, v in R.items()}
+        R_first = {k: host_view(v[0]) for k, v in R.items()}
         G0 = initialize(obj_types, n_obj, obj_type2rank, R_first, init_type, _as_rs(random_state))
     rel_list = flatten_relations(R, M)
     theta_list = flatten_thetas(Theta)
@@ -338,7 +338,7 @@ def run_fit(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type,
     obj_types = list(obj_types)
     n_obj = count_objects(obj_types, R)
     if G0 is None:
-        R_first = {k: np.asarray(v[0], dtype=float) for k, v in R.items()}
+        R_first = {k: host_view(v[0]) for k, v in R.items()}
         G0 = initialize(obj_types, n_obj, obj_type2rank, R_first, init_type, _as_rs(random_state))
     rel_list = flatten_relations(R, M)
     plan = DevicePlan(obj_types, n_obj, obj_type2rank, rel_list, flatten_thetas(Theta), variant,

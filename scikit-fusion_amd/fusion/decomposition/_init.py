@@ -9,11 +9,63 @@ relation matrix of that pair (reference _dfmf.py:191).
 import numpy as np
 
 
+def host_view(mat):
+    """The first relation of a pair as the initialisers read it: a float ndarray, or the relation given as its known
+    entries (_engine.KnownEntries) -- whose column statistics are formed from the entries, never from a dense copy."""
+    from ..._engine import KnownEntries
+    return mat if isinstance(mat, KnownEntries) else np.asarray(mat, dtype=float)
+
+
+class _KnownView(object):
+    """A relation given as its known entries, oriented for one object type (transposed: the type is its column type),
+    with the constant `fill` on every entry not stored -- the mask form's data after ``filled()``.  Answers what the
+    initialisers ask of a dense view without forming it: its shape, the row means over a set of columns
+        sum over a set of entries = sum of the known ones + (unknown ones) * fill
+    and every column's 2-norm.  The norms rank the columns in a stable sort, and ratings take few distinct values, so
+    columns tie exactly: each norm is taken the reference's way (np.linalg.norm of the dense column, strided as a column
+    of the relation is, contiguous as a row is), one column buffer at a time, so that the ties fall as they do there."""
+
+    def __init__(self, ke, transposed):
+        self.rows = ke.row_of_entries()
+        self.cols = ke.indices.astype(np.int64)
+        if transposed:
+            self.rows, self.cols = self.cols, self.rows
+        self.transposed = transposed
+        self.shape = ke.shape[::-1] if transposed else ke.shape
+        self.values, self.fill = ke.values, ke.fill
+
+    def row_means(self, columns):
+        sel = np.zeros(self.shape[1], dtype=bool)
+        sel[columns] = True
+        hit = sel[self.cols]
+        known = np.bincount(self.rows[hit], weights=self.values[hit], minlength=self.shape[0])
+        count = np.bincount(self.rows[hit], minlength=self.shape[0])
+        take = len(columns)
+        return (known + (take - count) * self.fill) / take
+
+    def column_norms(self):
+        order = np.argsort(self.cols, kind='stable')
+        ptr = np.zeros(self.shape[1] + 1, dtype=np.int64)
+        np.cumsum(np.bincount(self.cols, minlength=self.shape[1]), out=ptr[1:])
+        rows, vals = self.rows[order], self.values[order]
+        col = np.empty(self.shape[0]) if self.transposed else np.empty((self.shape[0], 2))[:, 0]
+        norms = []
+        for k in range(self.shape[1]):
+            col[:] = self.fill
+            col[rows[ptr[k]:ptr[k + 1]]] = vals[ptr[k]:ptr[k + 1]]
+            norms.append(np.linalg.norm(col, 2))
+        return norms
+
+
 def _views_of(obj_type, R):
     """Every relation that touches obj_type, oriented so that its rows are obj_type's objects, with a key that names the
     oriented view ((pair, transposed?))."""
+    from ..._engine import KnownEntries
     for pair, mat in R.items():
         if obj_type in pair:
+            if isinstance(mat, KnownEntries):
+                yield _KnownView(mat, obj_type != pair[0]), (pair, obj_type != pair[0])
+                continue
             yield (mat if obj_type == pair[0] else mat.T), (pair, obj_type != pair[0])
 
 
@@ -40,7 +92,10 @@ def _column_means_init(obj_types, n_obj, rank, R, random_state, pool_of):
             part = np.zeros((n_obj[t], c))
             for k in range(c):
                 random_state.shuffle(pool)
-                part[:, k] = view[:, pool[:take]].mean(axis=1)
+                if isinstance(view, _KnownView):
+                    part[:, k] = view.row_means(pool[:take])
+                else:
+                    part[:, k] = view[:, pool[:take]].mean(axis=1)
             acc += np.abs(part)
         G[t, t] = acc
     return G
@@ -60,7 +115,10 @@ def _random_c(obj_types, n_obj, rank, R, random_state, pools=None):
         if pools is not None and key in pools:
             return list(pools[key])
         n_cols = view.shape[1]
-        norms = [np.linalg.norm(view[:, k], 2) for k in range(n_cols)]
+        if isinstance(view, _KnownView):
+            norms = view.column_norms()
+        else:
+            norms = [np.linalg.norm(view[:, k], 2) for k in range(n_cols)]
         order = sorted(range(n_cols), key=norms.__getitem__, reverse=True)   # stable, descending
         half = order[:int(.5 * n_cols)]
         if pools is not None:

@@ -8,6 +8,7 @@ Engine-specific keywords (``dtype``) are additions with behaviour-preserving def
 """
 from collections import defaultdict
 from itertools import product
+from numbers import Number
 
 import numpy as np
 
@@ -15,7 +16,7 @@ from ..base import FusionFit, FusionTransform
 from ..._distributed import my_runs, gather_runs
 from ..._engine import count_objects
 from . import _dfmf
-from ._init import initialize
+from ._init import initialize, host_view
 
 __all__ = ['Dfmf', 'DfmfTransform']
 
@@ -24,19 +25,34 @@ def _random_state(obj):
     return obj if isinstance(obj, np.random.RandomState) else np.random.RandomState(obj)
 
 
-def graph_matrices(fusion_graph, with_masks=False, device_dtype=None):
+def known_entries_apply(relation, known_entries):
+    """Whether `relation` enters the fit as its known entries only (``Relation(..., unstored='unknown')`` on the list path
+    of Dfmc: asked for by the caller, no preprocessor, fill 'mean' or a number, row type rank <= 1024 and at most 2e9
+    entries -- the limits of the library's known-entry lists).  Otherwise such a relation is expanded to its MaskedArray."""
+    if not (known_entries and relation.is_known_entries() and not relation.preprocessor):
+        return False
+    if relation.row_type == relation.col_type or int(relation.row_type.rank) > 1024 or relation.data.nnz > 2000000000:
+        return False
+    return isinstance(relation.fill_value, Number) or relation.fill_value == 'mean'
+
+
+def graph_matrices(fusion_graph, with_masks=False, device_dtype=None, known_entries=False):
     """FusionGraph -> (R, Theta[, M]) dictionaries in the reference's walking order
     (dfmf.py:70-85, dfmc.py:70-93): pairs from product(object_types, repeat=2), each relation
     filled, then preprocessed; relations between two different types go to R, same-type
     relations are constraints (Theta).  For a masked result the raw ``.data`` is used and,
     with ``with_masks``, the mask is kept as the completion mask.
     ``device_dtype``: relations (not constraints) without a preprocessor are filled ON THE DEVICE and enter the
-    dictionaries as device-resident matrices of that engine dtype (``Relation.filled_device``)."""
+    dictionaries as device-resident matrices of that engine dtype (``Relation.filled_device``).
+    ``known_entries`` (Dfmc, shard='runs'): relations given as their known entries enter as ``_engine.KnownEntries`` with
+    mask None where ``known_entries_apply`` says so (never filled on the device: nothing unknown is stored)."""
     R, Theta, M = {}, {}, {}
     for row_type, col_type in product(fusion_graph.object_types, repeat=2):
         for relation in fusion_graph.get_relations(row_type, col_type):
             mask = None
-            if device_dtype and not relation.preprocessor and relation.row_type != relation.col_type:
+            if known_entries_apply(relation, known_entries):
+                data = relation.known_entries()
+            elif device_dtype and not relation.preprocessor and relation.row_type != relation.col_type:
                 data, mask = relation.filled_device(device_dtype)
             else:
                 data = relation.filled()
@@ -61,7 +77,7 @@ def initial_factors(R, object_types, rank, init_type, random_state, n_run):
     many GPUs share the work."""
     n_obj = count_objects(object_types, R)
     # ('random' never reads the relations: they may live on the device already, `device_fill`)
-    R_first = {} if init_type == 'random' else {k: np.asarray(v[0], dtype=float) for k, v in R.items()}
+    R_first = {} if init_type == 'random' else {k: host_view(v[0]) for k, v in R.items()}
     pools = {}                                   # column rankings of `random_c`, shared by the restarts (R_first stays alive here)
     return [initialize(object_types, n_obj, rank, R_first, init_type, random_state, pools)
             for _ in range(n_run)]
@@ -116,7 +132,7 @@ def shared_launches(fuser):
         if rel.row_type is rel.col_type:
             n_theta += 1
             n = rel.data.shape[0]
-            nnz = int(np.count_nonzero(np.ma.getdata(rel.data)))
+            nnz = int(np.count_nonzero(np.ma.getdata(rel.dense_data())))
             if nnz == 0 or nnz > n * n // lim['constraint_nnz_divisor']:
                 return False
         else:
@@ -219,8 +235,8 @@ class DfmfTransform(FusionTransform):
         R, Theta = {}, {}
         for row_type, col_type in product(fusion_graph.object_types, repeat=2):
             for relation in fusion_graph.get_relations(row_type, col_type):
-                data = relation.preprocessor(relation.data) if relation.preprocessor \
-                    else relation.data
+                data = relation.preprocessor(relation.dense_data()) if relation.preprocessor \
+                    else relation.dense_data()
                 if np.ma.is_masked(data):
                     data.fill_value = self.fill_value
                     data = data.filled()

@@ -130,6 +130,16 @@ def fill_col(x):
 _FILLERS = {'mean': fill_mean, 'row_mean': fill_row, 'col_mean': fill_col}
 
 
+def _is_sparse(x):
+    if isinstance(x, np.ndarray):
+        return False
+    try:
+        import scipy.sparse
+    except ImportError:                          # (no scipy: nothing can be a scipy.sparse matrix)
+        return False
+    return scipy.sparse.issparse(x)
+
+
 class Relation(object):
     """A data matrix relating ``row_type`` objects (rows) to ``col_type`` objects (columns).
 
@@ -137,12 +147,27 @@ class Relation(object):
     imputed before factorisation; ``preprocessor`` / ``postprocessor``: optional callables
     applied to the filled data before fusion / to the reconstruction in ``complete()``.
     Extra keyword arguments become attributes.
+
+    ``data`` may also be a ``scipy.sparse`` matrix.  ``unstored`` says what its entries that are not stored mean:
+    'zero' (default, scipy's own meaning: the matrix is expanded with ``toarray()`` and fused as a dense one) or
+    'unknown': the relation is exactly the ``numpy.ma.MaskedArray`` whose stored entries are unmasked and whose unstored
+    entries are masked -- every result equals what that MaskedArray gives.  Stored zeros are known zeros; duplicate
+    entries are summed (as ``toarray()`` sums them); stored NaN / inf take the fill value and stay known, as in the
+    MaskedArray.  ``Dfmc`` (shard='runs', no preprocessor, fill_value 'mean' or a number, row type rank <= 1024, at most
+    2e9 stored entries) fits such a relation on its known entries alone and never forms the dense matrix; every other
+    use -- ``Dfmf`` / ``DfmfTransform``, a preprocessor, 'row_mean' / 'col_mean' (under numpy.ma they leave every entry
+    known), the other shard modes, larger ranks -- expands it on the host to that MaskedArray and runs unchanged.  The
+    column initialisers read their statistics from the entries; with fill_value='mean' the mean is summed over the
+    entries, not in NumPy's order over the dense matrix, so `random_c` may rank two near-equal columns the other way.
     """
 
     def __init__(self, data, row_type, col_type, name='', row_names=None, col_names=None,
                  fill_value='mean', row_metadata=None, col_metadata=None,
-                 preprocessor=None, postprocessor=None, **kwargs):
+                 preprocessor=None, postprocessor=None, unstored='zero', **kwargs):
+        if unstored not in ('zero', 'unknown'):
+            raise ValueError("unstored must be 'zero' or 'unknown', not %r" % (unstored,))
         self.data = data
+        self.unstored = unstored
         self.row_type = row_type
         self.col_type = col_type
         self.name = name
@@ -157,10 +182,50 @@ class Relation(object):
             setattr(self, key, value)
         self._id = name or uuid1()
 
-    def filled(self):
+    def is_known_entries(self):
+        """True for a scipy.sparse relation whose unstored entries are unknown (``unstored='unknown'``)."""
+        return self.unstored == 'unknown' and _is_sparse(self.data)
+
+    def known_entries(self):
+        """The stored entries as canonical CSR (``_engine.KnownEntries``): duplicates summed, columns sorted, stored zeros
+        kept; stored non-finite values replaced by the fill value (``fill_value`` 'mean' or a number), which the
+        container also carries for the entries that are not stored -- the mask form's data after ``filled()``."""
+        from .._engine import KnownEntries
+        import scipy.sparse
+        csr = scipy.sparse.csr_matrix(self.data, dtype=np.float64, copy=True)
+        csr.sum_duplicates()
+        csr.sort_indices()
+        vals = csr.data                              # (the copy's own array: float64)
         if isinstance(self.fill_value, Number):
-            return fill_const(self.data, self.fill_value)
-        return _FILLERS[self.fill_value](self.data)
+            fill = float(self.fill_value)
+        elif self.fill_value == 'mean':
+            counted = ~np.isnan(vals)                # numpy.nanmean over the known entries: an infinity counts
+            with np.errstate(invalid='ignore', divide='ignore'):
+                fill = float(np.true_divide(vals[counted].sum(), counted.sum()))
+        else:
+            raise ValueError("known entries are filled with 'mean' or a number, not %r" % (self.fill_value,))
+        vals[~np.isfinite(vals)] = fill
+        return KnownEntries(csr.indptr, csr.indices, vals, csr.shape, fill=fill)
+
+    def dense_data(self):
+        """``data`` as the reference would hold it: an ndarray / MaskedArray as given; a scipy.sparse matrix expanded --
+        ``unstored='zero'``: ``toarray()``, ``unstored='unknown'``: the MaskedArray with the stored entries unmasked."""
+        if not _is_sparse(self.data):
+            return self.data
+        if self.unstored == 'zero':
+            return self.data.toarray()
+        import scipy.sparse
+        csr = scipy.sparse.csr_matrix(self.data, dtype=np.float64, copy=True)
+        csr.sum_duplicates()
+        known = np.zeros(csr.shape, dtype=bool)
+        known[np.repeat(np.arange(csr.shape[0]), np.diff(csr.indptr)), csr.indices] = True
+        return np.ma.MaskedArray(csr.toarray(), mask=~known)
+
+    def filled(self):
+        data = self.dense_data()
+        if isinstance(self.fill_value, Number):
+            return fill_const(data, self.fill_value)
+        return _FILLERS[self.fill_value](data)
 
     def filled_device(self, dtype='f64', runtime=None):
         """``filled()`` on the device: the raw matrix (and its mask) are uploaded once and the unknown entries are
@@ -168,7 +233,7 @@ class Relation(object):
         the mask is what ``filled()`` would leave on the result -- kept by 'mean' and constants, dropped by
         'row_mean' / 'col_mean' (reference fusion_graph.py:475-489 under NumPy's masked-assignment rules)."""
         from .._engine import fill_unknown_device
-        x = self.data
+        x = self.dense_data()
         mask = np.ma.getmaskarray(x) if np.ma.isMaskedArray(x) and np.ma.is_masked(x) else None
         if isinstance(self.fill_value, Number):
             strategy, value = 'const', float(self.fill_value)

@@ -1,0 +1,83 @@
+"""DFMC on relations handed over as their known entries (SKF_REL_KNOWN_CSR, skf_plan_set_known_entries) against the same
+relations handed over as dense data + mask -- the SAME cases on the host emulator and on the GPU.  Both forms build the
+known-entry lists of csrc/skf_known.h (the mask form with SKF_DFMC_SPARSE=1), byte for byte the same lists, so every
+iteration after bind must agree bit for bit."""
+import numpy as np
+
+import skfusion_amd._native as nat
+from skfusion_amd._engine import DevicePlan, KnownEntries, pack_mask
+
+import known_cases as K
+
+
+def known_entries_of(R, M):
+    """Dense relation + mask (True = unknown) -> KnownEntries holding exactly its known entries."""
+    known = ~np.asarray(M, dtype=bool)
+    rows, cols = np.nonzero(known)                      # row-major: columns ascending within a row
+    indptr = np.zeros(R.shape[0] + 1, dtype=np.int64)
+    np.cumsum(known.sum(axis=1), out=indptr[1:])
+    return KnownEntries(indptr, cols, np.asarray(R, dtype=np.float64)[rows, cols], R.shape)
+
+
+def edited_graph(n, ranks, known_share, seed, edits):
+    """known_cases.masked_graph with the mask of the ratings relation edited: 'empty' (an empty row and column),
+    'full_row' (one row entirely known), 'none' (nothing known at all)."""
+    types, rels, thetas, G0 = K.masked_graph(n, ranks, known_share, seed)
+    i, j, R, M = rels[0]
+    M = M.copy()
+    if 'empty' in edits:
+        M[3, :] = True
+        M[:, 5] = True
+    if 'full_row' in edits:
+        M[7, :] = False
+    if 'none' in edits:
+        M[:] = True
+    rels[0] = (i, j, R, M)
+    return types, rels, thetas, G0
+
+
+def run_plan(types, n, ranks, rels, thetas, G0, dtype, iters):
+    plan = DevicePlan(types, n, ranks, rels, thetas, nat.SKF_DFMC, dtype=dtype)
+    try:
+        for t in types:
+            plan.set_factor(t, G0[t])
+        errs = []
+        for _ in range(iters):
+            plan.iterate(1)
+            errs.append([plan.relation_sqerr(k) for k in range(len(rels))])
+        G = {t: plan.get_factor(t) for t in types}
+        S = [plan.get_backbone(k) for k in range(len(rels))]
+        return G, S, np.array(errs), plan.workspace_bytes
+    finally:
+        plan.close()
+
+
+def csr_against_mask(n, ranks, known_share, dtype, parts, monkeypatch, seed=0, edits=(), iters=3):
+    """Both masked relations of the graph fed as known entries vs fed as dense + mask: G, S and every squared error
+    np.array_equal; the CSR-fed workspace smaller by at least the packed masks it never holds."""
+    monkeypatch.setenv('SKF_DFMC_SPARSE', '1')
+    monkeypatch.setenv('SKF_KNOWN_PARTS', str(parts))
+    types, rels, thetas, G0 = edited_graph(n, ranks, known_share, seed, edits)
+    mem = nat.get_runtime().mem
+    mask_rels, csr_rels = [], []
+    mb_bytes = 0
+    for (i, j, R, M) in rels:
+        if M is None:
+            mask_rels.append((i, j, R, None))
+            csr_rels.append((i, j, R, None))
+            continue
+        pm = pack_mask(M, mem)
+        pm.known = max(pm.known, 1)        # (a bound, not a count: with nothing known the mask form still takes lists)
+        mask_rels.append((i, j, R, pm))
+        csr_rels.append((i, j, known_entries_of(R, M), None))
+        mb_bytes += R.shape[0] * ((R.shape[1] + 127) // 128 * 16)
+    Gm, Sm, Em, wm = run_plan(types, n, ranks, mask_rels, thetas, G0, dtype, iters)
+    Gc, Sc, Ec, wc = run_plan(types, n, ranks, csr_rels, thetas, G0, dtype, iters)
+    for t in types:
+        assert np.array_equal(Gc[t], Gm[t]), 'G_%s: CSR-fed differs from mask-fed' % t
+        assert np.isfinite(Gc[t]).all()
+    for k in range(len(rels)):
+        assert np.array_equal(Sc[k], Sm[k]), 'S_%d: CSR-fed differs from mask-fed' % k
+    assert np.array_equal(Ec, Em), 'squared errors: CSR-fed differs from mask-fed'
+    assert wc <= wm - mb_bytes, 'workspace: CSR-fed %d B, mask-fed %d B, packed masks %d B' % (wc, wm, mb_bytes)
+    return Gc, Sc, Ec
