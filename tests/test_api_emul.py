@@ -86,6 +86,11 @@ def test_fold_in_of_several_runs_shares_launches():
     A.fold_in_of_several_runs_shares_launches('f64')
 
 
+def test_fold_in_of_17_runs_shares_launches():
+    """DfmfTransform(n_run=17): two launch chunks (16 + 1 plans) per iteration."""
+    A.fold_in_of_several_runs_shares_launches('f64', n_run=17)
+
+
 def test_chained_profiles_match_the_reference_examples():
     """f4: chained latent profiles (fit and transformer, both example forms) against the golden of the reference run."""
     assert A.chained_profiles_match_the_reference_examples('f64', 1e-12) < 1e-12

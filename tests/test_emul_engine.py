@@ -1054,3 +1054,22 @@ def test_dense_iteration_against_host_model(case, monkeypatch):
     import dense_cases as DC
     dtype, schedule, n, ranks, rels, thetas, kw = DC.EMUL[case]
     DC.dense_case(dtype, schedule, n, ranks, rels, thetas, 'emulator dense ' + case, monkeypatch, **kw)
+
+
+# ---- the fold-in held to the host model, stage by stage (tests/foldin_cases.py: error model and cases; the full matrix of
+# kernels, shapes and batch sizes runs on the GPU in tests/test_gpu_foldin_model.py)
+@pytest.mark.parametrize('case', sorted(__import__('foldin_cases').EMUL))
+def test_fold_in_against_host_model(case):
+    """Contractions, every iteration from the device's previous factor (fused: each foldin_step_kernel instantiation;
+    generic: dense / CSR constraints, the bf16 G^T refresh, VALU), iterate(k) against k single iterations, the
+    re-preparation after set_backbone / set_factor and relation_sqerr -- one case per kernel family."""
+    import foldin_cases as FC
+    FC.fold_case(*FC.EMUL[case], what='emulator fold-in ' + case)
+
+
+@pytest.mark.parametrize('case', sorted(__import__('foldin_cases').EMUL_BATCH))
+def test_batched_fold_ins_against_host_model(case):
+    """skf_iterate_batch over 17 plans (two launch chunks): every plan the bits of the plan alone and held to its own host
+    model; 65 plans and a plan with a target constraint refused."""
+    import foldin_cases as FC
+    FC.batch_case(*FC.EMUL_BATCH[case], what='emulator fold-in ' + case)

@@ -108,6 +108,11 @@ def test_fold_in_of_several_runs_shares_launches(dtype, tol):
     A.fold_in_of_several_runs_shares_launches(dtype, tol=tol)
 
 
+def test_fold_in_of_17_runs_shares_launches():
+    """DfmfTransform(n_run=17): two launch chunks (16 + 1 plans) per iteration."""
+    A.fold_in_of_several_runs_shares_launches('f64', tol=1e-9, n_run=17)
+
+
 def test_f32_engine_reaches_the_same_fixed_point():
     import numpy as np
     from skfusion_amd.fusion import Relation, ObjectType, FusionGraph
