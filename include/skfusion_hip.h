@@ -106,7 +106,7 @@ enum {
                                  order); with other ranks and at most 1 entry in 256 set, as gathers of the f32
                                  factor rows (exact f32 sums).  Ignored for masked relations and by the f32 / f64
                                  engines. */
-    SKF_REL_KNOWN_CSR = 64    /* SKF_DFMC: the relation is given as its KNOWN entries only, as CSR (the stored entries are the
+    SKF_REL_KNOWN_CSR = 64,   /* SKF_DFMC: the relation is given as its KNOWN entries only, as CSR (the stored entries are the
                                  known ones, every other entry is unknown) -- no dense form exists: `data` and `mask` are NULL,
                                  known_bound is the EXACT number of entries (0 allowed) and skf_plan_set_known_entries hands the
                                  lists over before skf_plan_bind_workspace.  Always kept as lists of its known entries (neither
@@ -114,6 +114,20 @@ enum {
                                  built at bind time are the ones the mask form of the same data builds, byte for byte.
                                  SKF_E_INVALID: SKF_DFMF / SKF_TRANSFORM plans, row blocks / sliced / SKF_OPT_OWNED_ROWS plans,
                                  a row type's rank above 1024, more than 2e9 entries. */
+    SKF_REL_SPARSE_CSR = 128  /* SKF_DFMF plans, and unmasked relations of SKF_DFMC plans: the relation is given as the CSR of its
+                                 STORED entries and every other entry is ZERO (what a scipy.sparse matrix means; the reference
+                                 multiplies its dense expansion, _dfmf.py:249-276, and forms its error from the dense
+                                 reconstruction, _dfmf.py:306-316).  `data` and `mask` are NULL, known_bound is the EXACT number of
+                                 stored entries (0 allowed: an all-zero relation) and skf_plan_set_known_entries hands the lists
+                                 over before skf_plan_bind_workspace -- values in the MASTER type: f64 / f32, SKF_BF16 plans f32
+                                 (the stored values are never rounded to bf16).  The relation is never expanded: P = R G_j is one
+                                 pass over its row lists, Q = R^T G_i one over its column lists (built at bind time, values
+                                 included), skf_relation_sqerr = tr(S^T Gram_i S Gram_j) + sum over the stored entries of
+                                 (r - x)^2 - x^2.  Workspace grows with the number of entries and n * c, never with n_i * n_j.
+                                 Such a plan runs the relation pipeline or the staged schedule, never the small-graph one.
+                                 Stored zeros stay entries.  SKF_E_INVALID: SKF_TRANSFORM plans, row blocks / sliced /
+                                 SKF_OPT_OWNED_ROWS plans, a rank above 1024, more than 2e9 entries, a mask, together with
+                                 SKF_REL_KNOWN_CSR. */
 };
 
 typedef struct {
@@ -163,13 +177,14 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
 int skf_plan_destroy(skf_plan* plan);
 
 int skf_plan_workspace_bytes(const skf_plan* plan, size_t* bytes);
-/* The known entries of relation `rel` (flagged SKF_REL_KNOWN_CSR), as device pointers: indptr[n_row + 1] (int64,
+/* The known entries of relation `rel` (flagged SKF_REL_KNOWN_CSR; or the stored entries of one flagged SKF_REL_SPARSE_CSR,
+ * whose values are of the master type -- SKF_BF16: f32), as device pointers: indptr[n_row + 1] (int64,
  * indptr[0] = 0, indptr[n_row] = known_bound, non-decreasing), indices[known_bound] (int32 columns, strictly ascending
  * within a row: canonical CSR, duplicates summed beforehand) and values[known_bound] of the element type of
  * skf_relation_desc.data (SKF_BF16: bf16 bits).  Call it between skf_plan_create and skf_plan_bind_workspace; the buffers
  * are read by skf_plan_bind_workspace and not referenced afterwards (the contract of `data`).  Bind validates them on the
  * device before anything gathers through them: a non-monotone indptr, an index outside [0, n_col) or a row whose
- * columns do not ascend strictly is SKF_E_INVALID, as is a SKF_REL_KNOWN_CSR relation without this call. */
+ * columns do not ascend strictly is SKF_E_INVALID, as is a SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR relation without this call. */
 int skf_plan_set_known_entries(skf_plan* plan, int32_t rel, const int64_t* indptr, const int32_t* indices,
                                const void* values);
 /* `workspace` must be 256-byte aligned device memory and stay valid for the plan's lifetime.
@@ -313,7 +328,10 @@ int skf_exchange_bytes(const skf_plan* plan, int32_t world, size_t* bytes);
 /* sum over the relation of (R - G_i S G_j^T)^2 with the current (G, S), written as one f64 to
  * the DEVICE address `out` (reconstruction error of _dfmf.py:306-316 without materialising the
  * n_i x n_j product).  For DFMC the working copy (completed entries) is used.  SKF_BF16: one pass
- * over the stored bf16 relation, bf16-rounded G_i S and G_j on the matrix cores, f32 residual. */
+ * over the stored bf16 relation, bf16-rounded G_i S and G_j on the matrix cores, f32 residual.
+ * A SKF_REL_SPARSE_CSR relation: tr(S^T Gram_i S Gram_j) from c x c f64 products plus one pass over the row lists,
+ * sum of (r - x)^2 - x^2 with x = <(G_i S)[row], G_j[col]> in the master type (SKF_BF16: the f32 masters, not the bf16
+ * rows), f64 partials per wave summed in a fixed order. */
 int skf_relation_sqerr(skf_plan* plan, int32_t rel, double* out, void* stream);
 
 /* The two contraction results the LAST iteration left in the workspace, for verification at sizes where the
@@ -323,11 +341,20 @@ int skf_relation_sqerr(skf_plan* plan, int32_t rel, double* out, void* stream);
  * which = 2 with the row-side product P S^T (n_row x rank_row) it computes instead, and which = 1 as usual. */
 int skf_get_contraction(const skf_plan* plan, int32_t rel, int32_t which, void* dst, int64_t ld, void* stream);
 
+/* The entry lists a relation keeps after bind (a masked relation kept as its known entries, a SKF_REL_KNOWN_CSR or a
+ * SKF_REL_SPARSE_CSR relation), for verification: by_col = 0 the row lists (rows -> ascending columns), 1 the column lists
+ * (columns -> ascending rows).  `parts` / `n_entries` (host) receive the number of parts the lists are cut into and the
+ * number of entries; `ptr` (device, n * parts + 1 int64: the segment pointers, every `parts`-th one opens a list), `idx`
+ * (device, n_entries int32) and `values` (device, n_entries of the master type) receive copies.  Null pointers are skipped. */
+int skf_get_relation_lists(const skf_plan* plan, int32_t rel, int32_t by_col, int32_t* parts, int64_t* n_entries, int64_t* ptr,
+                           int32_t* idx, void* values, void* stream);
+
 /* Optional hipEvent timing of the launches that walk a relation (P = R G_j, Q = R^T G_i -- the dominant
  * kernel -- and their sparse counterparts).  get_profile synchronises on the recorded events, returns the summed
  * duration [ms], the number of launches, the flops they EXECUTE (2*M*N*K for a product on the matrix cores, dense or
  * bitmap; 2 * ones * N for the row gathers of a very sparse 0/1 relation; 2 or 4 * known * c for a pass over the
- * known entries of a masked relation) and the relation bytes they read from HBM as stored (bf16 / f32 / f64 entries,
+ * known entries of a masked relation; 2 * stored * N for a pass over a SKF_REL_SPARSE_CSR relation, whose bytes are its
+ * index + value lists and the factor rows it gathers) and the relation bytes they read from HBM as stored (bf16 / f32 / f64 entries,
  * 1 bit per entry for a bitmap, index + value lists for the sparse forms) since the last call, and resets the counters. */
 int skf_plan_set_profiling(skf_plan* plan, int32_t enable);
 int skf_plan_get_profile(skf_plan* plan, double* total_ms, int64_t* launches, double* flops, double* bytes);

@@ -41,9 +41,17 @@ class KnownEntries(object):
     """A relation given as its KNOWN entries only, canonical CSR on the host: `indptr` (n_row + 1), `indices` (columns,
     strictly ascending within a row) and `values`; every entry not stored is unknown (SKF_REL_KNOWN_CSR).  The engine's
     own container -- the API layer builds it from a ``scipy.sparse`` matrix (``Relation(..., unstored='unknown')``).
-    ``known`` is the number of entries; ``toarray`` / ``mask`` give the equivalent dense relation and completion mask."""
+    ``known`` is the number of entries; ``toarray`` / ``mask`` give the equivalent dense relation and completion mask.
+    ``unstored='zero'``: the same container for a relation whose entries that are not stored are ZERO (what a scipy.sparse
+    matrix means; SKF_REL_SPARSE_CSR, DFMF and unmasked DFMC relations): `fill` is 0, there is no mask, ``toarray`` is the
+    dense relation itself."""
 
-    def __init__(self, indptr, indices, values, shape, fill=0.0):
+    def __init__(self, indptr, indices, values, shape, fill=0.0, unstored='unknown'):
+        if unstored not in ('unknown', 'zero'):
+            raise ValueError("unstored must be 'unknown' or 'zero', not %r" % (unstored,))
+        self.unstored = unstored
+        if unstored == 'zero':
+            fill = 0.0
         self.indptr = np.ascontiguousarray(indptr, dtype=np.int64)
         self.indices = np.ascontiguousarray(indices, dtype=np.int32)
         self.values = np.ascontiguousarray(values, dtype=np.float64)
@@ -62,6 +70,8 @@ class KnownEntries(object):
 
     def mask(self):
         """True = unknown (the DFMC convention)."""
+        if self.unstored == 'zero':
+            raise ValueError('a relation whose unstored entries are zero has no completion mask')
         m = np.ones(self.shape, dtype=bool)
         m[self.row_of_entries(), self.indices] = False
         return m
@@ -90,21 +100,23 @@ class KnownEntries(object):
 class DeviceKnownEntries(object):
     """KnownEntries uploaded ONCE in the engine's element type (upload_graph: shared by the plans of concurrent restarts)."""
 
-    def __init__(self, indptr, indices, values, shape, known):
+    def __init__(self, indptr, indices, values, shape, known, unstored='unknown'):
         self.indptr, self.indices, self.values = indptr, indices, values
         self.shape, self.known = tuple(shape), int(known)
+        self.unstored = unstored        # 'unknown': SKF_REL_KNOWN_CSR, 'zero': SKF_REL_SPARSE_CSR
 
 
 def upload_known_entries(ke, dtype, mem):
     """KnownEntries -> DeviceKnownEntries: validated on the host first (DataFusionError before any upload); values in the
-    element type of the relation data (SKF_BF16: bf16 bits, rounded as dense data is: f64 -> f32 -> bf16)."""
+    element type of the relation data (SKF_BF16: bf16 bits, rounded as dense data is: f64 -> f32 -> bf16).  Entries whose
+    unstored neighbours are zero (SKF_REL_SPARSE_CSR) go up in the master type: SKF_BF16 keeps them as f32."""
     ke.validate()
     code = nat.DTYPES[dtype] if isinstance(dtype, str) else dtype
     vals = np.ascontiguousarray(ke.values, dtype=nat.NP_DTYPE[code])
-    if code == nat.SKF_BF16:
+    if code == nat.SKF_BF16 and ke.unstored != 'zero':
         vals = nat.to_bf16_bits(vals)
     keep = lambda a: mem.from_host(a if a.size else np.zeros(1, dtype=a.dtype))        # (no empty allocations)
-    return DeviceKnownEntries(keep(ke.indptr), keep(ke.indices), keep(vals), ke.shape, ke.known)
+    return DeviceKnownEntries(keep(ke.indptr), keep(ke.indices), keep(vals), ke.shape, ke.known, ke.unstored)
 
 
 def pack_mask(mask, mem):
@@ -497,7 +509,8 @@ class DevicePlan(object):
             block = rel[4] if len(rel) > 4 else None
             rdesc[k].row_type, rdesc[k].col_type = self.index[i], self.index[j]
             if isinstance(data, (KnownEntries, DeviceKnownEntries)):
-                # the known entries only (SKF_REL_KNOWN_CSR): no dense form, no mask; always kept as lists
+                # the known entries only (SKF_REL_KNOWN_CSR), or the stored entries of a relation that is zero elsewhere
+                # (SKF_REL_SPARSE_CSR): no dense form, no mask; always kept as lists
                 if mask is not None or block is not None:
                     raise ValueError('relation (%s,%s): known entries take no mask and no row block' % (i, j))
                 if tuple(data.shape) != (n_obj[i], n_obj[j]):
@@ -505,7 +518,7 @@ class DevicePlan(object):
                                      % (i, j, tuple(data.shape), n_obj[i], n_obj[j]))
                 dev = data if isinstance(data, DeviceKnownEntries) else upload_known_entries(data, self.dtype, mem)
                 self._keep_rel.append(dev)
-                rdesc[k].flags |= nat.SKF_REL_KNOWN_CSR
+                rdesc[k].flags |= nat.SKF_REL_SPARSE_CSR if dev.unstored == 'zero' else nat.SKF_REL_KNOWN_CSR
                 rdesc[k].known_bound = dev.known
                 csr.append((k, dev))
                 continue
@@ -707,6 +720,24 @@ class DevicePlan(object):
         self.rt.call('skf_get_contraction', self.handle, rel, which, buf.ptr, shape[1], self.stream)
         self.rt.mem.synchronize()
         return self.rt.mem.to_host(buf, shape, self.np_dtype)
+
+    def relation_lists(self, rel, by_col=False):
+        """(indptr, indices, values) of the entry lists relation `rel` keeps (verification accessor): the row lists, or with
+        by_col the column lists -- canonical CSR / CSC whatever the number of parts the engine cut them into."""
+        i, j = self.relations[rel][0], self.relations[rel][1]
+        n_out = self.n_obj[self.index[j if by_col else i]]
+        parts, nnz = C.c_int32(), C.c_int64()
+        self.rt.call('skf_get_relation_lists', self.handle, rel, int(bool(by_col)), C.byref(parts), C.byref(nnz), None, None,
+                     None, self.stream)
+        mem, item = self.rt.mem, np.dtype(self.np_dtype).itemsize
+        bp = mem.empty((n_out * parts.value + 1) * 8)
+        bi, bv = mem.empty(max(nnz.value, 1) * 4), mem.empty(max(nnz.value, 1) * item)
+        self.rt.call('skf_get_relation_lists', self.handle, rel, int(bool(by_col)), None, None, bp.ptr, bi.ptr, bv.ptr,
+                     self.stream)
+        mem.synchronize()
+        ptr = mem.to_host(bp, (n_out * parts.value + 1,), np.int64)[::parts.value].copy()
+        return (ptr, mem.to_host(bi, (max(nnz.value, 1),), np.int32)[:nnz.value].copy(),
+                mem.to_host(bv, (max(nnz.value, 1),), self.np_dtype)[:nnz.value].copy())
 
     def set_graph(self, enable=True):
         """Replay one captured hipGraph per iteration (concurrent restarts: include/skfusion_hip.h)."""

@@ -200,7 +200,12 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
             const bool csr = (d.flags & SKF_REL_KNOWN_CSR) != 0;
             if (csr && p->variant != SKF_DFMC) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR needs SKF_DFMC", r);
             if (csr && (d.data || d.mask)) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR takes no data / mask", r);
-            if (!absent && !csr && (!d.data || d.ld < p->types[d.col_type].n))
+            const bool sp0 = (d.flags & SKF_REL_SPARSE_CSR) != 0;      // the stored entries as CSR, every other entry zero
+            if (sp0 && csr) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR and SKF_REL_SPARSE_CSR exclude each other", r);
+            if (sp0 && p->variant == SKF_TRANSFORM) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_SPARSE_CSR is for SKF_DFMF / SKF_DFMC plans", r);
+            if (sp0 && (d.data || d.mask || (d.flags & (SKF_REL_MASKED | SKF_REL_MASK_BITS))))
+                SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_SPARSE_CSR takes no data / mask", r);
+            if (!absent && !csr && !sp0 && (!d.data || d.ld < p->types[d.col_type].n))
                 SKF_FAIL(SKF_E_INVALID, "relation %d: dimension mismatch (ld %lld < %lld columns)", r, (long long)d.ld,
                          (long long)p->types[d.col_type].n);
             const int64_t n_row_type = p->types[d.row_type].n;
@@ -208,7 +213,7 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
                 SKF_FAIL(SKF_E_INVALID, "relation %d: row block [%lld, +%lld) outside the %lld objects of its row type",
                          r, (long long)d.row_begin, (long long)d.n_rows, (long long)n_row_type);
             const bool block = absent || (d.n_rows > 0 && d.n_rows < n_row_type) || (d.flags & SKF_REL_NO_COL_SIDE);
-            if (block && csr) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR relations are whole relations", r);
+            if (block && (csr || sp0)) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR relations are whole relations", r);
             if (block && p->variant == SKF_TRANSFORM)
                 SKF_FAIL(SKF_E_INVALID, "relation %d: row blocks are for SKF_DFMF / SKF_DFMC plans", r);
             if (block && p->bf16 && d.row_begin % 64 != 0)
@@ -246,6 +251,12 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
                 s.R_in = s.R = nullptr;
                 s.kn_cap = d.known_bound;
             }
+            if (sp0) {                  // the stored entries as CSR (skf_plan_set_known_entries): no dense form in any type
+                s.sp0 = true;
+                s.binary = false;
+                s.R_in = s.R = nullptr;
+                s.kn_cap = d.known_bound;
+            }
         }
         // masked relations with few known entries are kept as lists of those entries (skf_known.h).  The three passes over the
         // lists gather rank_row-wide vectors -- ~70 ps per entry at rank 128 against ~2.2 ps per CELL for the four passes of
@@ -272,6 +283,21 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
             for (size_t rk = 0; rk < p->rels.size(); ++rk) {
                 RelState& s = p->rels[rk];
                 const int ci = p->types[s.row].c;
+                if (s.sp0) {
+                    // valued lists whatever the density (the caller chose the form; no dense one to fall back on).  P gathers
+                    // rank_col-wide rows of G_j through the row lists, Q rank_row-wide rows of G_i through the column lists
+                    const int cj = p->types[s.col].c;
+                    if (p->sliced) SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_SPARSE_CSR is for plans of whole relations", rk);
+                    if (ci > 64 * SRP_MAXREP || cj > 64 * SRP_MAXREP || s.kn_cap > 2000000000LL)
+                        SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_SPARSE_CSR beyond the list limits (a rank above %d or %lld > 2e9 entries)",
+                                 rk, 64 * SRP_MAXREP, (long long)s.kn_cap);
+                    s.kn_pc = pick_parts(p->types[s.col].n, s.nr, cj, s.kn_cap);
+                    s.kn_pr = pick_parts(s.nr, p->types[s.col].n, ci, s.kn_cap);
+                    s.kn_pw = ((p->types[s.col].n + s.kn_pc - 1) / s.kn_pc + 63) / 64 * 64;
+                    s.kn_ph = ((s.nr + s.kn_pr - 1) / s.kn_pr + 63) / 64 * 64;
+                    if (p->bf16) p->types[s.row].need_rows = p->types[s.col].need_rows = true;
+                    continue;
+                }
                 if (s.kn_csr) {
                     // lists whatever the share (no dense form to fall back on); the parts below follow from the exact count
                     if (p->sliced) SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_KNOWN_CSR is for plans of whole relations", rk);
@@ -505,6 +531,30 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
                 if (waves > sq_elems) sq_elems = waves;
                 continue;
             }
+            if (r.sp0) {
+                // the stored entries as row lists and column lists with their values, the partial outputs of the parts, the
+                // c x c Gram matrices of the error's trace term: everything ~ entries or n * c, nothing ~ n_i * n_j
+                const size_t cap = (size_t)r.kn_cap;
+                add_slot(p, r.KrPtr, ((size_t)nr * r.kn_pc + 1) * 8);
+                add_slot(p, r.KrIdx, cap * 4);
+                add_slot(p, r.KrVal, cap * es);
+                add_slot(p, r.KcPtr, ((size_t)tj.n * r.kn_pr + 1) * 8);
+                add_slot(p, r.KcIdx, cap * 4);
+                add_slot(p, r.KcVal, cap * es);
+                add_slot(p, r.KCnt, std::max((size_t)nr * r.kn_pc, 2 * (size_t)tj.n * r.kn_pr) * 4);
+                if (r.kn_pc > 1) add_slot(p, r.Apart, (size_t)r.kn_pc * nr * tj.c * es);
+                if (r.kn_pr > 1) add_slot(p, r.Qpart, (size_t)r.kn_pr * tj.n * ti.c * es);
+                add_slot(p, r.Xi, (size_t)ti.c * ti.c * 8);
+                add_slot(p, r.Xj, (size_t)tj.c * tj.c * 8);
+                want_part(ti.c, ti.c, (int)nr, true);                           // Gram matrices of the error's trace term
+                want_part(tj.c, tj.c, (int)tj.n, true);
+                want_part((int)nr, tj.c, ti.c, p->f64);                         // H = G_i S
+                want_part((int)nr, ti.c, tj.c, p->f64);                         // side products
+                want_part((int)tj.n, tj.c, ti.c, p->f64);
+                const size_t waves = (size_t)r.kn_pc * ((size_t)nr + 32) + 64;  // error partials: one per wave of the row pass
+                if (waves > sq_elems) sq_elems = waves;
+                continue;
+            }
             if (r.mask && !p->bf16) add_slot(p, r.Rw, (size_t)nr * tj.n * es);
             if (r.mask) {
                 r.ldmb = (tj.n + 127) / 128 * 16;               // bytes per packed mask row: whole 128-column tiles
@@ -568,7 +618,7 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
             // on the relation contractions are worth the big tiles of the general schedule)
             for (const TypeState& t : p->types) ok = ok && t.c <= SMALLC && t.n <= SM_MAX_OBJECTS;
             for (const ThetaState& th : p->thetas) ok = ok && th.sparse;
-            for (const RelState& r : p->rels) ok = ok && !r.absent && !r.masked;
+            for (const RelState& r : p->rels) ok = ok && !r.absent && !r.masked && !r.sp0;
             p->small_fused = ok;
             if (ok) {
                 size_t wdoubles = 0, gdoubles = 0;
@@ -696,7 +746,7 @@ int skf_plan_set_known_entries(skf_plan* plan, int32_t rel, const int64_t* indpt
         if (plan->ws_base) SKF_FAIL(SKF_E_STATE, "skf_plan_set_known_entries after skf_plan_bind_workspace");
         if (rel < 0 || rel >= (int)plan->rels.size()) SKF_FAIL(SKF_E_INVALID, "relation %d out of range", rel);
         RelState& r = plan->rels[rel];
-        if (!r.kn_csr) SKF_FAIL(SKF_E_INVALID, "relation %d is not flagged SKF_REL_KNOWN_CSR", rel);
+        if (!r.kn_csr && !r.sp0) SKF_FAIL(SKF_E_INVALID, "relation %d is flagged neither SKF_REL_KNOWN_CSR nor SKF_REL_SPARSE_CSR", rel);
         if (!indptr || (r.kn_cap > 0 && (!indices || !values))) SKF_FAIL(SKF_E_INVALID, "relation %d: null CSR array", rel);
         r.csr_ptr = indptr;
         r.csr_idx = (const int*)indices;
@@ -790,8 +840,8 @@ int skf_plan_bind_workspace(skf_plan* p, void* ws, size_t bytes, void* stream) {
         p->sw = Switches::read();          // the only place a plan looks at the environment
         hipStream_t st = as_stream(stream);
         for (RelState& r : p->rels) {
-            if (r.kn_csr) {                        // the caller's CSR, validated, then the same lists the mask form builds
-                if (!r.csr_ptr) SKF_FAIL(SKF_E_INVALID, "a SKF_REL_KNOWN_CSR relation without skf_plan_set_known_entries");
+            if (r.kn_csr || r.sp0) {               // the caller's CSR, validated, then the same lists the mask form builds
+                if (!r.csr_ptr) SKF_FAIL(SKF_E_INVALID, "a SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR relation without skf_plan_set_known_entries");
                 build_known_lists_csr(p, r, st);
                 continue;
             }
@@ -854,7 +904,7 @@ int skf_plan_bind_workspace(skf_plan* p, void* ws, size_t bytes, void* stream) {
                 if (t.Grow.bytes) SKF_HIP(hipMemsetAsync(t.Grow.ptr, 0, t.Grow.bytes, st));
             }
             for (RelState& r : p->rels) {
-                if (r.absent || r.kn) continue;
+                if (r.absent || r.kn || r.sp0) continue;
                 const int64_t rows = r.nr, cols = p->types[r.col].n;
                 if (r.binary) {
                     int* bad = (int*)p->sqpart.ptr;                  // (scratch word; bind is not on the hot path)
@@ -1474,25 +1524,41 @@ int skf_relation_sqerr(skf_plan* p, int32_t rel, double* out, void* stream) {
             SKF_HIP(hipMemsetAsync(out, 0, sizeof(double), st));
             return;
         }
+        double* acc = (double*)p->sqpart.ptr;
+        auto trace_term = [&](const void* Ai, const void* S1, const void* Bj, const void* S2, double scale, bool first) {
+            GemmArgs h = gemm_args(Ai, ci, 1, S1, cj, 1, r.U.ptr, cj, ci, cj, ci, EPI_STORE, 0);          // U = A_i S1
+            small_gemm(p, h, st);
+            h = gemm_args(r.U.ptr, cj, 1, Bj, cj, 1, r.T1.ptr, cj, ci, cj, cj, EPI_STORE, 0);             // T1 = U B_j
+            small_gemm(p, h, st);
+            hipLaunchKernelGGL(dot_small_kernel, dim3(1), dim3(256), 0, st, (const double*)S2, (const double*)r.T1.ptr,
+                               (int64_t)ci * cj, scale, acc, first ? 0 : 1);
+            check_launch("dot_small");
+        };
+        auto gram_of = [&](const void* A, const void* B, void* C, int c, int64_t n) {                      // C = A^T B (c x c)
+            GemmArgs h = gemm_args(A, 1, c, B, c, 1, C, c, c, c, (int)n, EPI_STORE, 0);
+            wide_gemm(p, h, st);
+        };
+        if (r.sp0) {
+            // |R - X|^2 = |X|^2 - 2 <R, X> + |R|^2 with X = G_i S G_j^T and R zero off its stored entries:
+            //     |X|^2 = tr(S^T Gram_i S Gram_j)   (c x c, f64)
+            //     |R|^2 - 2 <R, X> = sum over the stored entries of (r - x)^2 - x^2 ,  x = <(G_i S)[row], G_j[col]>
+            // -- one pass over the row lists, never the n_i x n_j reconstruction (reference: _dfmf.py:306-316 on the dense form).
+            // (slot 0 of the partials collects the trace term, the pass writes behind it)
+            gram_of(ti.G.ptr, ti.G.ptr, r.Xi.ptr, ci, r.nr);
+            gram_of(tj.G.ptr, tj.G.ptr, r.Xj.ptr, cj, tj.n);
+            trace_term(r.Xi.ptr, r.S.ptr, r.Xj.ptr, r.S.ptr, 1.0, true);
+            GemmArgs h = gemm_args(ti.G.ptr, ci, 1, r.S.ptr, cj, 1, r.H.ptr, cj, ni, cj, ci, EPI_STORE, 0);       // H = G_i S
+            mixed_gemm(p, h, st);
+            const int waves = sparse_pass(p, r, false, true, nullptr, st, 1);
+            hipLaunchKernelGGL((sum_partials_kernel<double>), dim3(1), dim3(256), 0, st, (const double*)p->sqpart.ptr, waves + 1, out);
+            check_launch("sum_partials");
+            return;
+        }
         if (r.kn) {
             // The completed relation of _dfmc.py:385-386 is X_o + E (X_o = G_i,prev S_prev G_j,prev^T, E the stored residuals);
             // with X_n = G_i S G_j^T of the current factors
             //     |R_c - X_n|^2 = |X_o - X_n|^2 + sum over the known entries of (r - x_n)^2 - (x_o - x_n)^2 ,  x_o = r - e
             // the first term from c x c Gram / cross-Gram products, the second from one pass over the column lists.
-            double* acc = (double*)p->sqpart.ptr;
-            auto trace_term = [&](const void* Ai, const void* S1, const void* Bj, const void* S2, double scale, bool first) {
-                GemmArgs h = gemm_args(Ai, ci, 1, S1, cj, 1, r.U.ptr, cj, ci, cj, ci, EPI_STORE, 0);          // U = A_i S1
-                small_gemm(p, h, st);
-                h = gemm_args(r.U.ptr, cj, 1, Bj, cj, 1, r.T1.ptr, cj, ci, cj, cj, EPI_STORE, 0);             // T1 = U B_j
-                small_gemm(p, h, st);
-                hipLaunchKernelGGL(dot_small_kernel, dim3(1), dim3(256), 0, st, (const double*)S2, (const double*)r.T1.ptr,
-                                   (int64_t)ci * cj, scale, acc, first ? 0 : 1);
-                check_launch("dot_small");
-            };
-            auto gram_of = [&](const void* A, const void* B, void* C, int c, int64_t n) {                      // C = A^T B (c x c)
-                GemmArgs h = gemm_args(A, 1, c, B, c, 1, C, c, c, c, (int)n, EPI_STORE, 0);
-                wide_gemm(p, h, st);
-            };
             // (the partial slots [1, waves] belong to the pass below; slot 0 collects the trace terms)
             const void* Gi_b = rows_of(p, ti.G, ti, r.r0);                   // the rows of the block (row ownership: the local ones)
             const void* Gp_b = ti.Gp.ptr ? rows_of(p, ti.Gp, ti, r.r0) : nullptr;
@@ -1568,6 +1634,27 @@ int skf_get_contraction(const skf_plan* p, int32_t rel, int32_t which, void* dst
         if (!src.ptr || rows <= 0) SKF_FAIL(SKF_E_STATE, "relation %d keeps no %s here", rel, which == 0 ? "P" : "Q");
         if (ld < cols) SKF_FAIL(SKF_E_INVALID, "ld too small");
         copy2d(dst, ld, src.ptr, cols, rows, cols, p->esz, as_stream(stream));
+    });
+}
+
+int skf_get_relation_lists(const skf_plan* p, int32_t rel, int32_t by_col, int32_t* parts, int64_t* n_entries, int64_t* ptr,
+                           int32_t* idx, void* values, void* stream) {
+    return guarded([&] {
+        check_bound(p);
+        if (rel < 0 || rel >= (int)p->rels.size()) SKF_FAIL(SKF_E_INVALID, "bad relation index");
+        const RelState& r = p->rels[rel];
+        if (!(r.kn || r.sp0) || r.absent) SKF_FAIL(SKF_E_STATE, "relation %d keeps no entry lists here", rel);
+        const int pc = by_col ? r.kn_pr : r.kn_pc;
+        const int64_t n_out = by_col ? p->types[r.col].n : r.nr;
+        if (parts) *parts = pc;
+        if (n_entries) *n_entries = r.kn_nnz;
+        hipStream_t st = as_stream(stream);
+        const Slot& sp = by_col ? r.KcPtr : r.KrPtr;
+        const Slot& si = by_col ? r.KcIdx : r.KrIdx;
+        const Slot& sv = by_col ? r.KcVal : r.KrVal;
+        if (ptr) SKF_HIP(hipMemcpyAsync(ptr, sp.ptr, ((size_t)n_out * pc + 1) * 8, hipMemcpyDeviceToDevice, st));
+        if (idx && r.kn_nnz > 0) SKF_HIP(hipMemcpyAsync(idx, si.ptr, (size_t)r.kn_nnz * 4, hipMemcpyDeviceToDevice, st));
+        if (values && r.kn_nnz > 0) SKF_HIP(hipMemcpyAsync(values, sv.ptr, (size_t)r.kn_nnz * p->esz, hipMemcpyDeviceToDevice, st));
     });
 }
 

@@ -147,6 +147,12 @@ struct RelState {
     const int64_t* csr_ptr = nullptr;      // the caller's CSR (skf_plan_set_known_entries; read at bind time only)
     const int* csr_idx = nullptr;
     const void* csr_val = nullptr;
+    // SKF_REL_SPARSE_CSR: the relation is the CSR of its stored entries, every other entry ZERO (DFMF, unmasked DFMC relations).
+    // Row lists KrPtr / KrIdx / KrVal and column lists KcPtr / KcIdx / KcVal as above (parts kn_pc / kn_pr, values in the master
+    // type), built at bind time from the caller's CSR; P = R G_j and Q = R^T G_i are SRP_APPLY passes over them with the stored
+    // values where the known-entry form keeps residuals (sparse_pass), partial outputs of the parts in Apart / Qpart; the error
+    // is tr(S^T Gram_i S Gram_j) (Xi, Xj) + one SRP_ERR pass with e = r.  No dense copy in any type.
+    bool sp0 = false;
     Slot FiB;                              // SKF_BF16: bf16 rows of T = G_j S^T (n_j x ldf; the rows of G_i: TypeState::Grow)
     Slot Tm;                               // T = G_j S^T in the master type (n_j x c_i)
     Slot Apart, Qpart;                     // partial outputs of the parts, [parts][n][c_i] (only with more than one part)
@@ -314,7 +320,13 @@ static hipEvent_t next_event(skf_plan* p) {
 }
 
 // one of the two contractions that stream a relation matrix: P = R G_j or Q = R^T G_i
+static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void* dst, hipStream_t st, int sq_first = 0);
 static void relation_gemm(skf_plan* p, GemmArgs g, hipStream_t st, const RelState* r = nullptr, bool is_q = false) {
+    if (r && r->sp0) {             // the stored entries as valued lists (every engine): no matrix to stream
+        if (g.ldc != g.N) SKF_FAIL(SKF_E_STATE, "SKF_REL_SPARSE_CSR relation: strided contraction output");
+        sparse_pass(p, *r, is_q, false, g.C, st);
+        return;
+    }
     if (p->profiling) SKF_HIP(hipEventRecord(next_event(p), st));
     if (p->bf16) {
         const TypeState& ti = p->types[r->row];

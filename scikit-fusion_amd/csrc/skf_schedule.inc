@@ -536,7 +536,8 @@ static void build_known_lists_t(skf_plan* p, RelState& r, hipStream_t st) {
 // The same lists from the caller's CSR (SKF_REL_KNOWN_CSR): validated on the device first -- nothing gathers through them
 // before the host has read the verdict --, then the row lists are copies of the CSR with the part split points found by
 // binary search, and the column side is built as above, its values taken from the row lists.  Byte for byte the lists
-// build_known_lists_t makes from a dense relation + mask holding the same entries.
+// build_known_lists_t makes from a dense relation + mask holding the same entries.  The stored entries of a
+// SKF_REL_SPARSE_CSR relation (unstored = zero) take the same way: same validation, same lists, no residual list.
 template <typename TR, typename TM>
 static void build_known_lists_csr_t(skf_plan* p, RelState& r, hipStream_t st) {
     const int64_t rows = r.nr, cols = p->types[r.col].n, tot = r.kn_cap;
@@ -550,9 +551,9 @@ static void build_known_lists_csr_t(skf_plan* p, RelState& r, hipStream_t st) {
     SKF_HIP(hipMemcpyAsync(&bad, cnt, sizeof(int), hipMemcpyDeviceToHost, st));
     SKF_HIP(hipStreamSynchronize(st));
     if (bad)
-        SKF_FAIL(SKF_E_INVALID, "SKF_REL_KNOWN_CSR: the lists are not a canonical CSR of %lld x %lld with %lld entries (indptr from 0 "
+        SKF_FAIL(SKF_E_INVALID, "%s: the lists are not a canonical CSR of %lld x %lld with %lld entries (indptr from 0 "
                  "to the count, non-decreasing; columns in range and strictly ascending within a row)",
-                 (long long)rows, (long long)cols, (long long)tot);
+                 r.sp0 ? "SKF_REL_SPARSE_CSR" : "SKF_REL_KNOWN_CSR", (long long)rows, (long long)cols, (long long)tot);
     r.kn_nnz = tot;
     hipLaunchKernelGGL(parted_ptr_kernel, dim3(elem_grid(rows * pc + 1)), dim3(256), 0, st, r.csr_ptr, r.csr_idx, rows, pc, r.kn_pw,
                        (int64_t*)r.KrPtr.ptr);
@@ -586,16 +587,19 @@ static void build_known_lists_csr_t(skf_plan* p, RelState& r, hipStream_t st) {
                            (const int*)r.KcIdx.ptr, pr, cols, (const int64_t*)r.KrPtr.ptr, (const int*)r.KrIdx.ptr, pc,
                            (const TM*)r.KrVal.ptr, (TM*)r.KcVal.ptr);
         check_launch("known_csr_cols");
-        SKF_HIP(hipMemcpyAsync(r.KcE.ptr, r.KcVal.ptr, (size_t)tot * sizeof(TM), hipMemcpyDeviceToDevice, st));
+        // (known entries: E = R before the first iteration; a SKF_REL_SPARSE_CSR relation keeps no residuals)
+        if (r.KcE.ptr) SKF_HIP(hipMemcpyAsync(r.KcE.ptr, r.KcVal.ptr, (size_t)tot * sizeof(TM), hipMemcpyDeviceToDevice, st));
     }
-    SKF_HIP(hipMemsetAsync(r.Sp.ptr, 0, r.Sp.bytes, st));
+    if (r.Sp.ptr) SKF_HIP(hipMemsetAsync(r.Sp.ptr, 0, r.Sp.bytes, st));
     if (r.FiB.bytes) SKF_HIP(hipMemsetAsync(r.FiB.ptr, 0, r.FiB.bytes, st));
     SKF_HIP(hipStreamSynchronize(st));                      // the host vectors die here; bind is not on the hot path
     r.R = nullptr;
     r.csr_ptr = nullptr; r.csr_idx = nullptr; r.csr_val = nullptr;      // not referenced after bind
 }
 static void build_known_lists_csr(skf_plan* p, RelState& r, hipStream_t st) {
-    if (p->bf16) build_known_lists_csr_t<uint16_t, float>(p, r, st);
+    // (SKF_REL_SPARSE_CSR hands its values over in the master type -- SKF_BF16: f32, never rounded to bf16)
+    if (p->bf16 && r.sp0) build_known_lists_csr_t<float, float>(p, r, st);
+    else if (p->bf16) build_known_lists_csr_t<uint16_t, float>(p, r, st);
     else if (p->f64) build_known_lists_csr_t<double, double>(p, r, st);
     else build_known_lists_csr_t<float, float>(p, r, st);
 }

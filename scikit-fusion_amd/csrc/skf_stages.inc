@@ -128,6 +128,77 @@ static int known_pass(skf_plan* p, RelState& r, bool by_col, int mode, hipStream
     return waves;
 }
 
+// One pass over the stored entries of a SKF_REL_SPARSE_CSR relation (every entry not stored is zero; reference: the dense
+// products of _dfmf.py:249-276 and the error of _dfmf.py:306-316):
+//   err == false, is_q == false   P = R G_j    over the row lists, gathering rows of G_j   (SRP_APPLY, e = the stored value)
+//   err == false, is_q == true    Q = R^T G_i  over the column lists, gathering rows of G_i
+//   err == true                   sum over the row lists of (r - x)^2 - x^2, x = <(G_i S)[row], G_j[col]>: SRP_ERR with the
+//                                 stored values as residuals as well ((r - e - x) = -x exactly); r.H = G_i S must be
+//                                 current; one f64 partial per wave from slot `sq_first` of p->sqpart, count returned
+// SKF_BF16: f32 values, bf16 factor rows (TypeState::Grow), f32 sums; f32 / f64: the master factors themselves.  The error pass
+// of SKF_BF16 gathers the f32 masters too: |R|^2 - 2 <R, X> is a sum of same-signed terms r x over the stored entries that
+// has to cancel against the exact trace term, so bf16 roundings of x (2^-9 each, not averaged out by differing signs as in
+// a sum of squared residuals) would show in the error at 4e-4 relative; the pass is not on the hot path.
+static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void* dst, hipStream_t st, int sq_first) {
+    const TypeState& ti = p->types[r.row];
+    const TypeState& tj = p->types[r.col];
+    const TypeState& tin = is_q ? ti : tj;                   // the gathered factor
+    const int64_t n_out = is_q ? tj.n : r.nr;
+    const int parts = is_q ? r.kn_pr : r.kn_pc;
+    const int w = tin.c;
+    if (err) {
+        const int64_t need = ((n_out + 3) / 4 + (8 / parts) - 1) / (8 / parts) * 8 * 4 + sq_first;
+        if ((size_t)need > p->sq_elems) SKF_FAIL(SKF_E_STATE, "residual partials: %lld > %zu slots", (long long)need, p->sq_elems);
+    }
+    void* out = (parts > 1 && !err) ? (is_q ? r.Qpart.ptr : r.Apart.ptr) : dst;
+    if (p->profiling) SKF_HIP(hipEventRecord(next_event(p), st));
+    int waves = 0;
+    auto fill = [&](auto& a, auto* vals, auto* Fi, int64_t ldi, auto* Fo, int64_t ldo, auto* o) {
+        memset(&a, 0, sizeof a);
+        a.ptr = (const int64_t*)(is_q ? r.KcPtr.ptr : r.KrPtr.ptr);
+        a.idx = (const int*)(is_q ? r.KcIdx.ptr : r.KrIdx.ptr);
+        a.rvals = vals; a.evals = vals;                      // (never written: SRP_APPLY / SRP_ERR only read the residual list)
+        a.Fi = Fi; a.ldi = ldi; a.Fo = Fo; a.ldo = ldo; a.out = o;
+        a.ld_out = w; a.part_stride = n_out * w; a.n_out = n_out;
+        a.w = w; a.parts = parts; a.mode = err ? SRP_ERR : SRP_APPLY;
+        a.sq = (double*)p->sqpart.ptr + sq_first;
+    };
+    void* vals = is_q ? r.KcVal.ptr : r.KrVal.ptr;
+    if (p->f64) {
+        SrpArgs<double, double> a;
+        fill(a, (double*)vals, (const double*)tin.G.ptr, (int64_t)w, (const double*)r.H.ptr, (int64_t)w, (double*)out);
+        waves = launch_srp(a, st, false);
+    } else if (p->bf16 && !err) {
+        SrpArgs<uint16_t, float> a;
+        fill(a, (float*)vals, (const uint16_t*)tin.Grow.ptr, tin.ldrow, (const uint16_t*)nullptr, tin.ldrow, (float*)out);
+        // slots past the end of a list point at the all-zero row behind the gathered rows (32-bit byte offsets in the v6 kernel)
+        const int64_t zoff = tin.n * tin.ldrow * 2;
+        a.zero_off = (zoff + tin.ldrow * 2 < (int64_t)0xffffffffLL) ? (uint32_t)zoff : 0u;
+        waves = launch_srp(a, st, false);
+    } else {
+        SrpArgs<float, float> a;
+        fill(a, (float*)vals, (const float*)tin.G.ptr, (int64_t)w, (const float*)r.H.ptr, (int64_t)w, (float*)out);
+        waves = launch_srp(a, st, false);
+    }
+    if (parts > 1 && !err) {
+        const int64_t total = n_out * w;
+        if (p->f64)
+            hipLaunchKernelGGL((sum_parts_kernel<double>), dim3(elem_grid(total)), dim3(256), 0, st, (double*)dst, (const double*)out,
+                               total, parts, total);
+        else
+            hipLaunchKernelGGL((sum_parts_kernel<float>), dim3(elem_grid(total)), dim3(256), 0, st, (float*)dst, (const float*)out,
+                               total, parts, total);
+        check_launch("sum_parts");
+    }
+    if (p->profiling) {
+        SKF_HIP(hipEventRecord(next_event(p), st));
+        // what the pass executes and reads: index + value lists, one gathered factor row per entry (include/skfusion_hip.h)
+        p->prof_flops += 2.0 * (double)r.kn_nnz * w;
+        p->prof_bytes += (double)r.kn_nnz * (4.0 + (double)p->esz + (double)w * (p->bf16 ? 2.0 : (double)p->esz));
+        p->prof_launches += 1;
+    }
+    return waves;
+}
 
 // W = G_i^T R_c G_j for the backbone (_dfmc.py:311-314) with R_c = G_i,prev S_prev G_j,prev^T + E_prev:
 //     W = (G_i^T G_i,prev) S_prev (G_j,prev^T G_j) + (E_prev^T G_i)^T G_j

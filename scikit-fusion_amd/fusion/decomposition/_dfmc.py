@@ -14,7 +14,8 @@ def _expand_known_entries(R, M):
     for key, mats in R.items():
         masks = (M or {}).get(key) or [None] * len(mats)
         R2[key] = [m.toarray() if isinstance(m, KnownEntries) else m for m in mats]
-        M2[key] = [m.mask() if isinstance(m, KnownEntries) else mk for m, mk in zip(mats, masks)]
+        M2[key] = [m.mask() if isinstance(m, KnownEntries) and m.unstored != 'zero' else (None if isinstance(m, KnownEntries) else mk)
+                   for m, mk in zip(mats, masks)]
     return R2, M2
 
 

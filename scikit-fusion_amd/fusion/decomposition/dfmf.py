@@ -36,7 +36,37 @@ def known_entries_apply(relation, known_entries):
     return isinstance(relation.fill_value, Number) or relation.fill_value == 'mean'
 
 
-def graph_matrices(fusion_graph, with_masks=False, device_dtype=None, known_entries=False):
+SPARSE_RULE = 4.0       # density * max(rank_row, rank_col) at which the entry lists stop paying
+
+
+def stored_entries_apply(relation, sparse_relations, shard='runs'):
+    """Whether a ``scipy.sparse`` relation with ``unstored='zero'`` enters the fit as its stored entries (never expanded):
+    shard='runs', no preprocessor, row type != column type, ranks <= 1024 and at most 2e9 entries (the limits of the
+    library's lists), and sparse enough -- `sparse_relations` None: density * max(rank_row, rank_col) <= 4, the rule of the
+    known-entry lists, for relations beyond the limits of the small-graph schedule (a rank above 64 or more than 8192
+    objects on a side, ``skf_small_graph_limits``: below them an iteration is bound by its launches, the three-launch
+    schedule is the measured path and the lists would take the graph off it); True: whenever eligible; False: never
+    (``toarray()``, as before the sparse path existed)."""
+    if sparse_relations is False or shard != 'runs':
+        return False
+    if not relation.is_zero_unstored() or relation.preprocessor or relation.row_type == relation.col_type:
+        return False
+    rank = max(int(relation.row_type.rank), int(relation.col_type.rank))
+    nnz = int(relation.data.nnz)
+    if rank > 1024 or nnz > 2000000000:
+        return False
+    if sparse_relations:
+        return True
+    from ..._engine import small_graph_limits
+    lim = small_graph_limits()
+    if rank <= lim['max_rank'] and max(relation.data.shape) <= lim['max_objects']:
+        return False
+    cells = float(relation.data.shape[0]) * float(relation.data.shape[1])
+    return cells > 0 and nnz / cells * rank <= SPARSE_RULE
+
+
+def graph_matrices(fusion_graph, with_masks=False, device_dtype=None, known_entries=False, sparse_relations=False,
+                   shard='runs'):
     """FusionGraph -> (R, Theta[, M]) dictionaries in the reference's walking order
     (dfmf.py:70-85, dfmc.py:70-93): pairs from product(object_types, repeat=2), each relation
     filled, then preprocessed; relations between two different types go to R, same-type
@@ -45,13 +75,17 @@ def graph_matrices(fusion_graph, with_masks=False, device_dtype=None, known_entr
     ``device_dtype``: relations (not constraints) without a preprocessor are filled ON THE DEVICE and enter the
     dictionaries as device-resident matrices of that engine dtype (``Relation.filled_device``).
     ``known_entries`` (Dfmc, shard='runs'): relations given as their known entries enter as ``_engine.KnownEntries`` with
-    mask None where ``known_entries_apply`` says so (never filled on the device: nothing unknown is stored)."""
+    mask None where ``known_entries_apply`` says so (never filled on the device: nothing unknown is stored).
+    ``sparse_relations`` / ``shard``: scipy.sparse relations whose unstored entries are zero enter as their stored entries
+    (``_engine.KnownEntries`` with ``unstored='zero'``, mask None) where ``stored_entries_apply`` says so."""
     R, Theta, M = {}, {}, {}
     for row_type, col_type in product(fusion_graph.object_types, repeat=2):
         for relation in fusion_graph.get_relations(row_type, col_type):
             mask = None
             if known_entries_apply(relation, known_entries):
                 data = relation.known_entries()
+            elif stored_entries_apply(relation, sparse_relations, shard):
+                data = relation.stored_entries()
             elif device_dtype and not relation.preprocessor and relation.row_type != relation.col_type:
                 data, mask = relation.filled_device(device_dtype)
             else:
@@ -166,11 +200,15 @@ class Dfmf(FusionFit):
     balanced row blocks of the relations -- all-reduces of W, Q and E / D per iteration; or the rows of
     every object type with the matching rows of its relations -- a reduce-scatter of each partial Q and an
     all-gather of the updated factor rows, the form with the least exchange).
+    sparse_relations=None | True | False: a ``scipy.sparse`` relation (``unstored='zero'``) is fitted on its stored entries
+    alone, never expanded, with shard='runs', no preprocessor and two different object types -- None: when
+    density * max(rank_row, rank_col) <= 4 and the relation is beyond the small-graph limits (a rank above 64 or more
+    than 8192 objects on a side); True: always; False: never (``toarray()``).
     """
 
     def __init__(self, max_iter=100, init_type='random_c', n_run=1, stopping=None,
                  stopping_system=None, verbose=0, compute_err=False, callback=None,
-                 random_state=None, n_jobs=1, dtype='f64', shard='runs', device_fill=False):
+                 random_state=None, n_jobs=1, dtype='f64', shard='runs', device_fill=False, sparse_relations=None):
         super(Dfmf, self).__init__()
         self._set_params(vars())
 
@@ -179,7 +217,8 @@ class Dfmf(FusionFit):
         self.random_state = _random_state(self.random_state)
         object_types = list(fusion_graph.object_types)
         rank = {ot: int(ot.rank) for ot in object_types}
-        R, Theta = graph_matrices(fusion_graph, device_dtype=device_fill_dtype(self))
+        R, Theta = graph_matrices(fusion_graph, device_dtype=device_fill_dtype(self),
+                                  sparse_relations=getattr(self, 'sparse_relations', None), shard=self.shard)
         G0 = initial_factors(R, object_types, rank, self.init_type, self.random_state, self.n_run)
         kw = dict(R=R, Theta=Theta, obj_types=object_types, obj_type2rank=rank,
                   max_iter=self.max_iter, init_type=self.init_type, stopping=self.stopping,

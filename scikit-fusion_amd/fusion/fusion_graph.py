@@ -149,7 +149,9 @@ class Relation(object):
     Extra keyword arguments become attributes.
 
     ``data`` may also be a ``scipy.sparse`` matrix.  ``unstored`` says what its entries that are not stored mean:
-    'zero' (default, scipy's own meaning: the matrix is expanded with ``toarray()`` and fused as a dense one) or
+    'zero' (default, scipy's own meaning: the result is the one of fusing ``toarray()``; ``Dfmf`` / ``Dfmc`` with
+    shard='runs' fit a sparse enough one on its stored entries alone and never expand it -- see their
+    ``sparse_relations`` keyword -- and everything else expands it) or
     'unknown': the relation is exactly the ``numpy.ma.MaskedArray`` whose stored entries are unmasked and whose unstored
     entries are masked -- every result equals what that MaskedArray gives.  Stored zeros are known zeros; duplicate
     entries are summed (as ``toarray()`` sums them); stored NaN / inf take the fill value and stay known, as in the
@@ -206,6 +208,20 @@ class Relation(object):
             raise ValueError("known entries are filled with 'mean' or a number, not %r" % (self.fill_value,))
         vals[~np.isfinite(vals)] = fill
         return KnownEntries(csr.indptr, csr.indices, vals, csr.shape, fill=fill)
+
+    def is_zero_unstored(self):
+        """True for a scipy.sparse relation whose unstored entries are zero (``unstored='zero'``, the default)."""
+        return self.unstored == 'zero' and _is_sparse(self.data)
+
+    def stored_entries(self):
+        """The stored entries as canonical CSR (``_engine.KnownEntries`` with ``unstored='zero'``): duplicates summed, columns
+        sorted, stored zeros kept, values as stored (``toarray()`` keeps a stored non-finite value too)."""
+        from .._engine import KnownEntries
+        import scipy.sparse
+        csr = scipy.sparse.csr_matrix(self.data, dtype=np.float64, copy=True)
+        csr.sum_duplicates()
+        csr.sort_indices()
+        return KnownEntries(csr.indptr, csr.indices, csr.data, csr.shape, unstored='zero')
 
     def dense_data(self):
         """``data`` as the reference would hold it: an ndarray / MaskedArray as given; a scipy.sparse matrix expanded --
