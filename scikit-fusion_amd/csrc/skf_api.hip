@@ -385,17 +385,16 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
         const size_t es = p->esz;
         size_t part_bytes = 0;
         size_t sp_part_bytes = 0;
-        auto want_part = [&](int M, int N, int K, bool out_f64, bool sym = false) {
-            TileCfg t = pick_tile(out_f64, p->engine, M, N);
-            int sl = pick_splits(t, M, N, K);
-            if (sym) sl = std::max(sl, pick_splits(t, M, N, K, true));     // (X^T X on the tiles on / below the diagonal: fewer tiles, more slices)
-            if (!p->bf16 && (int64_t)cdiv(M, t.bm) * cdiv(N, t.bn) >= 256) {      // (relation contractions of the f32 / f64 engines)
-                const int rs = pick_splits_relation(t, M, N, K, out_f64);
-                if (rs > sl) sl = rs;
-            }
-            size_t need = (size_t)sl * (size_t)M * (size_t)N * (out_f64 ? 8 : 4);
-            if (need > part_bytes) part_bytes = need;
+        // split-K scratch: every product that runs on it is sized by the decision its launch takes (kind_part_bytes -> slice_gemm)
+        size_t aux_bytes = 0, gram_group = 0;
+        auto want_part = [&](const ProductKind& k, int64_t M, int64_t N, int64_t K, bool aux_too = false) {
+            const size_t need = kind_part_bytes(p, k, M, N, K);
+            part_bytes = std::max(part_bytes, need);
+            if (aux_too) aux_bytes = std::max(aux_bytes, need);     // (launched on the second stream as well: that stream's scratch)
+            return need;
         };
+        const ProductKind k_plan = kind_plan(p), k_rel = kind_relation(p), k_small = kind_small(p), k_wide = kind_wide(p),
+                          k_gram = kind_gram(p), k_mixed = kind_mixed(p);
         int maxn = 2;
         // the E / D accumulators of all types form ONE contiguous range of the workspace, so that
         // a relation-sharded run sums them over the ranks with a single all-reduce
@@ -425,13 +424,11 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
         p->xg_bytes = p->ws_bytes - p->xg_off;
         for (int i = 0; i < n_types; ++i) {
             TypeState& t = p->types[i];
-            const bool active = (p->variant != SKF_TRANSFORM) || i == p->target;
-            (void)active;
             if (p->bf16) {
                 t.ldgt = pad64(t.n);
                 add_slot(p, t.GTb, (size_t)t.c * t.ldgt * 2);
             }
-            want_part(t.c, t.c, (int)t.n, true, true);
+            gram_group += want_part(k_gram, t.c, t.c, t.n, true);             // Gram = G^T G (gram_all: either stream)
             if (t.keep_prev) add_slot(p, t.Gp, (size_t)t.n * t.c * es);
             if (p->bf16 && t.need_rows) {
                 t.ldrow = (t.c + 7) / 8 * 8;
@@ -488,11 +485,13 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
             if (p->variant != SKF_TRANSFORM) {
                 add_slot(p, r.T1, cc);
                 if (!p->f64) add_slot(p, r.S32, cc / 2);
-                if (nr > 0) want_part(ti.c, tj.c, (int)nr, true);
+                if (nr > 0) want_part(k_wide, ti.c, tj.c, nr);                  // W = G_i^T P
+                if (nr > 0) want_part(k_wide, ti.c, tj.c, tj.n);                // W = (R^T G_i)^T G_j ; known entries: W = Y^T G_j
             }
-            want_part(ti.c, tj.c, ti.c > tj.c ? ti.c : tj.c, true);
-            want_part(ti.c, ti.c, tj.c, true);
-            want_part(tj.c, tj.c, ti.c, true);
+            want_part(k_small, ti.c, tj.c, tj.c, true);                         // c x c algebra (small_gemm: either stream): S Gram_j,
+            want_part(k_small, ti.c, tj.c, ti.c, true);                         // Gram_i S,
+            want_part(k_small, ti.c, ti.c, tj.c, true);                         // B = U S^T,
+            want_part(k_small, tj.c, tj.c, ti.c, true);                         // D = S^T U
             if (nr <= 0 && r.kn) add_slot(p, r.U2, cc);             // (owned rows, none of this relation's here: the dense part of Q
                                                                     //  is still added on this process's rows of the column type)
             if (nr <= 0) continue;
@@ -522,11 +521,10 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
                 add_slot(p, r.Xi, (size_t)ti.c * ti.c * 8);
                 add_slot(p, r.Xj, (size_t)tj.c * tj.c * 8);
                 add_slot(p, r.Bf, (size_t)ti.c * ti.c * 8);
-                want_part(ti.c, tj.c, (int)tj.n, true);                         // W = Y^T G_j
-                want_part(ti.c, ti.c, (int)nr, true);                           // G_i'^T G_i
-                want_part(tj.c, tj.c, (int)tj.n, true);                         // G_j^T G_j'
-                want_part((int)tj.n, ti.c, tj.c, p->f64);                       // T = G_j S^T ; Q += G_j (S^T Gram_i)
-                want_part((int)nr, ti.c, ti.c, p->f64);                         // A += G_i (S Gram_j S^T)
+                want_part(k_wide, ti.c, ti.c, nr);                              // G_i'^T G_i
+                want_part(k_wide, tj.c, tj.c, tj.n);                            // G_j^T G_j'
+                want_part(k_mixed, tj.n, ti.c, tj.c);                           // T = G_j S^T ; Q += G_j (S^T Gram_i)
+                want_part(k_mixed, nr, ti.c, ti.c);                             // A += G_i (S Gram_j S^T)
                 const size_t waves = (size_t)r.kn_pr * ((size_t)tj.n + 32) + 64;   // error partials: one per wave of the column pass
                 if (waves > sq_elems) sq_elems = waves;
                 continue;
@@ -546,11 +544,11 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
                 if (r.kn_pr > 1) add_slot(p, r.Qpart, (size_t)r.kn_pr * tj.n * ti.c * es);
                 add_slot(p, r.Xi, (size_t)ti.c * ti.c * 8);
                 add_slot(p, r.Xj, (size_t)tj.c * tj.c * 8);
-                want_part(ti.c, ti.c, (int)nr, true);                           // Gram matrices of the error's trace term
-                want_part(tj.c, tj.c, (int)tj.n, true);
-                want_part((int)nr, tj.c, ti.c, p->f64);                         // H = G_i S
-                want_part((int)nr, ti.c, tj.c, p->f64);                         // side products
-                want_part((int)tj.n, tj.c, ti.c, p->f64);
+                want_part(k_wide, ti.c, ti.c, nr);                              // Gram matrices of the error's trace term
+                want_part(k_wide, tj.c, tj.c, tj.n);
+                want_part(k_mixed, nr, tj.c, ti.c);                             // H = G_i S
+                want_part(k_mixed, nr, ti.c, tj.c);                             // side products
+                want_part(k_mixed, tj.n, tj.c, ti.c);
                 const size_t waves = (size_t)r.kn_pc * ((size_t)nr + 32) + 64;  // error partials: one per wave of the row pass
                 if (waves > sq_elems) sq_elems = waves;
                 continue;
@@ -603,10 +601,12 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
                 if (b1 > part_bytes) part_bytes = b1;
                 if (b2 > part_bytes) part_bytes = b2;
             }
-            want_part((int)nr, tj.c, (int)tj.n, p->f64);
-            want_part((int)tj.n, ti.c, (int)nr, p->f64);
-            want_part((int)nr, ti.c, tj.c, p->f64);
-            want_part((int)tj.n, tj.c, ti.c, p->f64);
+            if (!p->bf16) want_part(k_rel, nr, tj.c, tj.n);                     // P = R G_j
+            if (!p->bf16) want_part(k_rel, tj.n, ti.c, nr);                     // Q = R^T G_i
+            want_part(k_mixed, nr, tj.c, ti.c);                                 // H = G_i S
+            want_part(k_mixed, nr, ti.c, tj.c);                                 // side products
+            want_part(k_mixed, tj.n, tj.c, ti.c);
+            if (r.mask && !p->bf16) want_part(k_plan, nr, tj.n, tj.c);          // the completion H G_j^T
             size_t blocks = (size_t)cdiv(nr, 32) * cdiv(tj.n, 32);           // smallest tile any engine uses
             if (blocks > sq_elems) sq_elems = blocks;
         }
@@ -675,7 +675,7 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
                 add_slot(p, th.Vv, (size_t)th.nnz_cap * es);
                 continue;
             }
-            want_part((int)t.n, t.c, (int)t.n, p->f64);
+            if (!p->bf16) want_part(k_plan, t.n, t.c, t.n);                     // dense Theta G
             if (p->bf16) {
                 th.ldb = pad64(t.n);
                 add_slot(p, th.Pb, (size_t)t.n * th.ldb * 2);
@@ -687,32 +687,14 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
         }
         if (!p->thetas.empty()) add_slot(p, p->theta_flags, p->thetas.size() * 2 * sizeof(int));
         if (theta_tmp_bytes) add_slot(p, p->theta_tmp, theta_tmp_bytes);
-        {   // the Gram products of all types side by side in one launch (gram_all): every product's slices at once
-            std::vector<std::pair<int, int64_t>> cn;
-            for (const TypeState& t : p->types) cn.emplace_back(t.c, t.n);
-            if (cn.size() >= 2 && cn.size() <= 4) part_bytes = std::max(part_bytes, gram_group_bytes(p->engine, cn));
+        // the Gram products of all types side by side in one launch (gram_all): every product's slices at once
+        if (n_types >= 2 && n_types <= 4) {
+            part_bytes = std::max(part_bytes, gram_group);
+            aux_bytes = std::max(aux_bytes, gram_group);
         }
         p->part_bytes = part_bytes;
         add_slot(p, p->part, part_bytes);
         if (sp_part_bytes) add_slot(p, p->sp_part, sp_part_bytes);
-        size_t aux_bytes = 0;
-        for (TypeState& t : p->types) {
-            TileCfg tc = pick_tile(true, p->engine, t.c, t.c);
-            const int sl = std::max(pick_splits(tc, t.c, t.c, (int)t.n), pick_splits(tc, t.c, t.c, (int)t.n, true));   // (gram(.., on_aux): symmetric)
-            size_t need = (size_t)sl * (size_t)t.c * t.c * 8;
-            if (need > aux_bytes) aux_bytes = need;
-        }
-        for (RelState& r : p->rels) {          // W = G_i^T P on the second stream (pipelined schedule)
-            const int ci = p->types[r.row].c, cj = p->types[r.col].c;
-            TileCfg tc = pick_tile(true, p->engine, ci, cj);
-            size_t need = (size_t)pick_splits(tc, ci, cj, (int)r.nr) * (size_t)ci * cj * 8;
-            if (need > aux_bytes) aux_bytes = need;
-        }
-        {
-            std::vector<std::pair<int, int64_t>> cn;
-            for (const TypeState& t : p->types) cn.emplace_back(t.c, t.n);
-            if (cn.size() >= 2 && cn.size() <= 4) aux_bytes = std::max(aux_bytes, gram_group_bytes(p->engine, cn));
-        }
         p->part_aux_bytes = aux_bytes;
         add_slot(p, p->part_aux, aux_bytes);
         p->sq_elems = sq_elems;

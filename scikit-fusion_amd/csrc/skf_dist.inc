@@ -265,7 +265,7 @@ static void iterate_owned(skf_plan* p, hipStream_t st) {
         void* part = gram_aux ? p->part_aux.ptr : p->part.ptr;
         const size_t bytes = gram_aux ? p->part_aux_bytes : p->part_bytes;
         if (!gram_group_try(p, shares.data(), (int)shares.size(), part, bytes, sg))
-            for (const GemmArgs& g : shares) run_gemm(GemmTypes{SKF_F64, p->mt, p->mt}, p->engine, g, 0, part, bytes, sg);
+            for (const GemmArgs& g : shares) kind_gemm(p, kind_gram(p), g, sg, gram_aux);
     }
     rec(p->ev_own[0], sg);
     wait(cs, p->ev_own[0]);

@@ -1,5 +1,6 @@
 // skf_gemm_launch.inc -- part of the one translation unit skf_api.hip (textually included there, inside its namespaces; not a
-// header of its own): tile choice, split-K models and the launches of the f32 / f64 GEMM kernels and of the bf16 relation contraction.
+// header of its own): tile choice, split-K models, the ONE slicing decision per product family (slice_gemm, slice_bf16: launches
+// and scratch sizing alike) and the launches of the f32 / f64 GEMM kernels and of the bf16 relation contraction.
 // ------------------------------------------------------------------------------------------
 // GEMM dispatch
 // ------------------------------------------------------------------------------------------
@@ -127,15 +128,71 @@ static int big_tile_modes(GemmTypes ty, const GemmArgs& g, bool relation) {
     if (ty.c == SKF_F64) return fm == FM_RR ? fm : -1;           // (f64, f32, f32)
     return fm == FM_KR ? fm : -1;                                // (f32, f32, f64)
 }
-// the tile a product runs on (run_gemm, and callers that size per-workgroup outputs: skf_relation_sqerr)
+static bool is_big_tile(const TileCfg& t, bool is_f64) {
+    const TileCfg big = is_f64 ? Tiles<double>::big() : Tiles<float>::big();
+    return t.bm == big.bm && t.bn == big.bn && t.bk == big.bk;
+}
+// the tile a product runs on (slice_gemm, and callers that size per-workgroup outputs: skf_relation_sqerr)
 static TileCfg gemm_tile(GemmTypes ty, int engine, const GemmArgs& g, bool deep_ok, bool relation) {
     const bool is_f64 = (ty.c == SKF_F64);
     const TileCfg t = pick_tile(is_f64, engine, g.M, g.N, g.K, deep_ok);
-    if (engine != SKF_ENGINE_MFMA) return t;
-    const TileCfg big = is_f64 ? Tiles<double>::big() : Tiles<float>::big();
-    if (t.bm == big.bm && t.bn == big.bn && t.bk == big.bk && big_tile_modes(ty, g, relation) < 0)
+    if (engine == SKF_ENGINE_MFMA && is_big_tile(t, is_f64) && big_tile_modes(ty, g, relation) < 0)
         return is_f64 ? Tiles<double>::small() : Tiles<float>::small();
     return t;
+}
+
+// How a product is cut into K slices: decided HERE and nowhere else (slice_gemm: f32 / f64 products, slice_bf16: the bf16 contraction),
+// for the launches and for the scratch sizing of skf_plan_create alike.  The slice count fixes the summation order, hence the bits.
+struct Slicing {
+    TileCfg t;
+    int splits, k_chunk, sym;       // K slices, K elements per slice, the GemmArgs::sym word of the launch
+    bool clamped; int wanted;       // a scratch was given and the `wanted` slices of the MODEL did not fit it
+    bool sym_ok;                    // the symmetric model applied (whether or not the launch ends up split)
+    size_t part_elems;              // scratch elements the launch is checked against: the slices BEFORE the K-tile rounding (0: one)
+};
+constexpr int64_t SCRATCH_NONE = -1, SCRATCH_ANY = INT64_MAX;     // `avail`: no scratch at all / as much as the product asks for
+// `splits` slices of `per` elements each, clamped to the scratch, then whole K tiles per slice
+static void fit_slices(Slicing& d, int splits, size_t per, int K, int want_splits, int64_t avail) {
+    if (splits > 1 && (avail < 0 || per * splits > (size_t)avail)) {
+        d.clamped = avail >= 0 && want_splits <= 0;
+        d.wanted = splits;
+        splits = avail >= 0 ? (int)((size_t)avail / per) : 1;
+    }
+    if (splits < 1) splits = 1;
+    d.part_elems = splits > 1 ? per * splits : 0;
+    const int ktiles = cdiv(K > 0 ? K : 1, d.t.bk);
+    if (splits > ktiles) splits = ktiles;
+    d.k_chunk = cdiv(ktiles, splits) * d.t.bk;
+    d.splits = cdiv(K > 0 ? K : 1, d.k_chunk);
+}
+static Slicing slice_gemm_on(const TileCfg& t, GemmTypes ty, int engine, const GemmArgs& g, int want_splits, bool relation, int64_t avail) {
+    Slicing d{t, 1, 0, 0, false, 0, false, 0};
+    d.sym_ok = g.sym && g.M == g.N && engine == SKF_ENGINE_MFMA && t.bn > t.bm && g.epi == EPI_STORE;
+    int splits = want_splits > 0 ? want_splits : pick_splits(t, g.M, g.N, g.K, d.sym_ok);
+    if (want_splits <= 0 && relation && engine == SKF_ENGINE_MFMA && g.epi == EPI_STORE && t.bm >= 64 &&
+        (int64_t)cdiv(g.M, t.bm) * cdiv(g.N, t.bn) >= 256)
+        splits = pick_splits_relation(t, g.M, g.N, g.K, ty.c == SKF_F64);
+    if (g.epi == EPI_SQDIFF) splits = 1;
+    fit_slices(d, splits, (size_t)g.M * g.N, g.K, want_splits, avail);
+    // a symmetric product (the caller says so: Gram = G^T G) computes the tiles on and below the diagonal only; the reduce of
+    // the K slices mirrors the rest (GemmArgs::sym).  Unsplit launches write C themselves and compute every tile.
+    d.sym = (d.sym_ok && d.splits > 1) ? (t.bm | (t.bn << 16)) : 0;
+    return d;
+}
+static Slicing slice_gemm(GemmTypes ty, int engine, const GemmArgs& g, int want_splits, bool relation, int64_t avail) {
+    const bool all_f64 = (ty.c == SKF_F64 && ty.a == SKF_F64 && ty.b == SKF_F64);
+    return slice_gemm_on(gemm_tile(ty, engine, g, all_f64 && want_splits <= 1, relation), ty, engine, g, want_splits, relation, avail);
+}
+// Scratch elements a plan's launch of this product can ask for (`g`: sizes, epilogue, sym flag).  skf_plan_create knows no operand address
+// yet, and gemm_tile leaves the big tile when layout or alignment have no big-tile instantiation: the larger of the two outcomes.
+static size_t gemm_part_elems(GemmTypes ty, int engine, const GemmArgs& g, bool relation) {
+    if (g.M <= 0 || g.N <= 0) return 0;
+    const bool is_f64 = (ty.c == SKF_F64);
+    const TileCfg t = pick_tile(is_f64, engine, g.M, g.N, g.K, is_f64 && ty.a == SKF_F64 && ty.b == SKF_F64);
+    size_t e = slice_gemm_on(t, ty, engine, g, 0, relation, SCRATCH_ANY).part_elems;
+    if (engine == SKF_ENGINE_MFMA && is_big_tile(t, is_f64))
+        e = std::max(e, slice_gemm_on(is_f64 ? Tiles<double>::small() : Tiles<float>::small(), ty, engine, g, 0, relation, SCRATCH_ANY).part_elems);
+    return e;
 }
 
 template <typename T, typename TA, typename TB>
@@ -190,48 +247,29 @@ static void launch_gemm_t(int engine, const TileCfg& t, GemmArgs g, int splits, 
     }
 }
 
-// `part`/`part_bytes`: scratch for split-K partials; splits is clamped to fit.
+// `part`/`part_bytes`: scratch for split-K partials; the slices are clamped to fit (slice_gemm), and a clamped model is counted.
 static void run_gemm(GemmTypes ty, int engine, GemmArgs g, int want_splits, void* part, size_t part_bytes,
                      hipStream_t st, bool relation = false) {
     if (g.M <= 0 || g.N <= 0) return;
-    const bool is_f64 = (ty.c == SKF_F64);
-    const bool all_f64 = (ty.c == SKF_F64 && ty.a == SKF_F64 && ty.b == SKF_F64);
-    const TileCfg t = gemm_tile(ty, engine, g, all_f64 && want_splits <= 1, relation);
-    const bool sym_ok = g.sym && g.M == g.N && engine == SKF_ENGINE_MFMA && t.bn > t.bm && g.epi == EPI_STORE;
-    int splits = want_splits > 0 ? want_splits : pick_splits(t, g.M, g.N, g.K, sym_ok);
-    if (want_splits <= 0 && relation && engine == SKF_ENGINE_MFMA && g.epi == EPI_STORE && t.bm >= 64 &&
-        (int64_t)cdiv(g.M, t.bm) * cdiv(g.N, t.bn) >= 256) {
-        splits = pick_splits_relation(t, g.M, g.N, g.K, is_f64);
+    const int64_t avail = part ? (int64_t)(part_bytes / (ty.c == SKF_F64 ? 8 : 4)) : SCRATCH_NONE;
+    const Slicing d = slice_gemm(ty, engine, g, want_splits, relation, avail);
+    if (d.clamped) {
+        ++g_split_clamps;
+        if (env_int("SKF_DEBUG_CLAMP", 0))
+            fprintf(stderr, "skf: split-K clamp, gemm %dx%dx%d types %d/%d/%d tile %dx%d relation %d sym %d: %d slices wanted, scratch holds %zu\n",
+                    g.M, g.N, g.K, ty.c, ty.a, ty.b, d.t.bm, d.t.bn, (int)relation, (int)d.sym_ok, d.wanted, (size_t)avail / ((size_t)g.M * g.N));
     }
-    if (g.epi == EPI_SQDIFF) splits = 1;
-    const size_t per = (size_t)g.M * g.N;
-    const size_t part_elems = part_bytes / (is_f64 ? 8 : 4);
-    if (splits > 1 && (part == nullptr || per * splits > part_elems)) {
-        if (part != nullptr && want_splits <= 0) {                      // (a scratch was given and the MODEL's slices do not fit it)
-            ++g_split_clamps;
-            if (env_int("SKF_DEBUG_CLAMP", 0))
-                fprintf(stderr, "skf: split-K clamp, gemm %dx%dx%d types %d/%d/%d tile %dx%d relation %d sym %d: %d slices wanted, scratch holds %zu\n",
-                        g.M, g.N, g.K, ty.c, ty.a, ty.b, t.bm, t.bn, (int)relation, (int)sym_ok, splits, part_elems / per);
-        }
-        splits = part ? (int)(part_elems / per) : 1;
-        if (splits < 1) splits = 1;
-    }
-    int ktiles = cdiv(g.K > 0 ? g.K : 1, t.bk);
-    if (splits > ktiles) splits = ktiles;
-    g.k_chunk = cdiv(ktiles, splits) * t.bk;
-    splits = cdiv(g.K > 0 ? g.K : 1, g.k_chunk);
+    g.k_chunk = d.k_chunk;
     g.part = part;
-    // a symmetric product (the caller says so: Gram = G^T G) computes the tiles on and below the diagonal only; the reduce of
-    // the K slices mirrors the rest (GemmArgs::sym).  Unsplit launches write C themselves and compute every tile.
-    g.sym = (sym_ok && splits > 1) ? (t.bm | (t.bn << 16)) : 0;
+    g.sym = d.sym;
     if (ty.c == SKF_F64 && ty.a == SKF_F64 && ty.b == SKF_F64)
-        launch_gemm_t<double, double, double>(engine, t, g, splits, relation, st);
+        launch_gemm_t<double, double, double>(engine, d.t, g, d.splits, relation, st);
     else if (ty.c == SKF_F32 && ty.a == SKF_F32 && ty.b == SKF_F32)
-        launch_gemm_t<float, float, float>(engine, t, g, splits, relation, st);
+        launch_gemm_t<float, float, float>(engine, d.t, g, d.splits, relation, st);
     else if (ty.c == SKF_F64 && ty.a == SKF_F32 && ty.b == SKF_F32)
-        launch_gemm_t<double, float, float>(engine, t, g, splits, relation, st);
+        launch_gemm_t<double, float, float>(engine, d.t, g, d.splits, relation, st);
     else if (ty.c == SKF_F32 && ty.a == SKF_F32 && ty.b == SKF_F64)
-        launch_gemm_t<float, float, double>(engine, t, g, splits, relation, st);
+        launch_gemm_t<float, float, double>(engine, d.t, g, d.splits, relation, st);
     else
         SKF_FAIL(SKF_E_INVALID, "unsupported operand type combination (c=%d a=%d b=%d)", ty.c, ty.a, ty.b);
 }
@@ -240,21 +278,20 @@ static void run_gemm(GemmTypes ty, int engine, GemmArgs g, int want_splits, void
 // unsplit tile of the matrix-core engine -- what run_gemm picks for them one by one; anything else: two launches.
 static void run_gemm_pair_f64(int engine, GemmArgs a, GemmArgs b, hipStream_t st, bool allow) {
     const GemmTypes ty{SKF_F64, SKF_F64, SKF_F64};
-    auto deep = [&](const GemmArgs& g) {
-        if (g.M <= 0 || g.N <= 0 || g.sym || g.epi == EPI_SQDIFF) return false;
-        const TileCfg t = gemm_tile(ty, engine, g, true, false);
-        return engine == SKF_ENGINE_MFMA && t.bk == 64 && t.bm == 32 && pick_splits(t, g.M, g.N, g.K, false) == 1;
+    auto deep = [&](const GemmArgs& g) {            // deep tile, one slice?
+        if (engine != SKF_ENGINE_MFMA || g.M <= 0 || g.N <= 0 || g.sym || g.epi == EPI_SQDIFF) return false;
+        const Slicing d = slice_gemm(ty, engine, g, 0, false, SCRATCH_ANY);
+        return d.t.bk == 64 && d.t.bm == 32 && d.splits == 1;
     };
     if (!allow || !deep(a) || !deep(b)) {
         run_gemm(ty, engine, a, 0, nullptr, 0, st);
         run_gemm(ty, engine, b, 0, nullptr, 0, st);
         return;
     }
-    const TileCfg t = gemm_tile(ty, engine, a, true, false);
+    const TileCfg t = Tiles<double>::deep();
     for (GemmArgs* g : {&a, &b}) {                  // (as run_gemm sets an unsplit launch up)
-        g->k_chunk = cdiv(g->K > 0 ? g->K : 1, t.bk) * t.bk;
+        g->k_chunk = slice_gemm(ty, engine, *g, 0, false, SCRATCH_ANY).k_chunk;
         g->part = nullptr;
-        g->sym = 0;
     }
     const int gx = std::max(cdiv(a.N, t.bn), cdiv(b.N, t.bn)), gy = std::max(cdiv(a.M, t.bm), cdiv(b.M, t.bm));
     hipLaunchKernelGGL((gemm_mfma_pair_kernel<double, double, double, 1, 1, 64, 0>), dim3(gx, gy, 2), dim3(GEMM_THREADS), 0, st, a, b);
@@ -264,13 +301,12 @@ static void run_gemm_pair_f64(int engine, GemmArgs a, GemmArgs b, hipStream_t st
 // The symmetric split-K products G^T G of several types in ONE product launch and ONE reduce launch (gemm_mfma_group_kernel,
 // round 6) when every one of them is what run_gemm would launch as a big-tile symmetric split with at least 8 slices and the
 // scratch holds all their slices side by side; returns false otherwise (the caller then issues them one by one).  Tile,
-// slices, K chunk and reduce order per product are run_gemm's: the results are the same bits.
+// slices, K chunk and sym word per product come from slice_gemm, as run_gemm's do: the results are the same bits.
 template <typename TM>
 static bool run_gram_group_t(int engine, const GemmArgs* gs, int n, void* part, size_t part_bytes, hipStream_t st) {
     constexpr bool m64 = std::is_same<TM, double>::value;
     const GemmTypes ty{SKF_F64, m64 ? SKF_F64 : SKF_F32, m64 ? SKF_F64 : SKF_F32};
     if (engine != SKF_ENGINE_MFMA || n < 2 || n > 4 || part == nullptr) return false;
-    const TileCfg big = Tiles<double>::big();
     GemmGroup m;
     memset(&m, 0, sizeof m);
     size_t off = 0;                      // f64 elements of the scratch handed out so far
@@ -282,25 +318,21 @@ static bool run_gram_group_t(int engine, const GemmArgs* gs, int n, void* part, 
         // what the group saves is two launch boundaries per product; a product of several GFLOP runs for 0.1 ms and more and
         // loses that to sharing its rounds with the others (same box, config 3: 1/10 scale +5.3 %, 1/5 +2.2 %, full size -0.7 %)
         if (2.0 * (double)g.K * (double)g.M * (double)g.N > 4.0e9) return false;
-        const TileCfg t = gemm_tile(ty, engine, g, m64, false);
-        if (t.bm != big.bm || t.bn != big.bn || t.bk != big.bk || big_tile_modes(ty, g, false) != FM_RR) return false;
-        int splits = pick_splits(t, g.M, g.N, g.K, true);
-        const int ktiles = cdiv(g.K > 0 ? g.K : 1, t.bk);
-        if (splits > ktiles) splits = ktiles;
-        g.k_chunk = cdiv(ktiles, splits) * t.bk;
-        splits = cdiv(g.K > 0 ? g.K : 1, g.k_chunk);
-        if (splits < 8) return false;                                    // (the many-slice reduce; a small type: nothing to gain)
-        const size_t per = (size_t)g.M * g.N;
-        if ((off + per * splits) * 8 > part_bytes) return false;
+        const Slicing d = slice_gemm(ty, engine, g, 0, false, SCRATCH_ANY);
+        if (!is_big_tile(d.t, true) || big_tile_modes(ty, g, false) != FM_RR) return false;
+        if (d.splits < 8) return false;                                  // (the many-slice reduce; a small type: nothing to gain)
+        const size_t slices = (size_t)g.M * g.N * d.splits;
+        if ((off + slices) * 8 > part_bytes) return false;
         g.part = (double*)part + off;
-        off += per * splits;
-        g.sym = t.bm | (t.bn << 16);
+        off += slices;
+        g.k_chunk = d.k_chunk;
+        g.sym = d.sym;
         m.g[i] = g;
-        m.tiles[i] = sym_tiles(t, g.M);
-        m.splits[i] = splits;
+        m.tiles[i] = sym_tiles(d.t, g.M);
+        m.splits[i] = d.splits;
         max_tiles = std::max(max_tiles, m.tiles[i]);
-        max_splits = std::max(max_splits, splits);
-        max_elems = std::max(max_elems, (int64_t)per);
+        max_splits = std::max(max_splits, d.splits);
+        max_elems = std::max(max_elems, (int64_t)g.M * g.N);
     }
     constexpr int WRB = BigWave<double>::WR, WCB = BigWave<double>::WC, BKT = Tiles<double>::BK;
     hipLaunchKernelGGL((gemm_mfma_group_kernel<double, TM, TM, WRB, WCB, BKT, 0, FM_RR>), dim3(max_tiles, n, max_splits),
@@ -309,15 +341,6 @@ static bool run_gram_group_t(int engine, const GemmArgs* gs, int n, void* part, 
     hipLaunchKernelGGL((splitk_reduce_z16_group_kernel<double>), dim3(elem_grid(max_elems * 16), n), dim3(256), 0, st, m);
     check_launch("splitk_reduce_group");
     return true;
-}
-// scratch the grouped launch of these Gram products needs (skf_plan_create sizes the plans' scratch with it)
-static size_t gram_group_bytes(int engine, const std::vector<std::pair<int, int64_t>>& c_and_n) {
-    size_t bytes = 0;
-    for (const auto& cn : c_and_n) {
-        const TileCfg t = pick_tile(true, engine, cn.first, cn.first);
-        bytes += (size_t)pick_splits(t, cn.first, cn.first, (int)cn.second, true) * (size_t)cn.first * cn.first * 8;
-    }
-    return bytes;
 }
 
 // ---- bf16 relation contraction --------------------------------------------------------------
@@ -371,6 +394,18 @@ static void allow_dynamic_lds(DeviceOnce& once, K kernel, int bytes) {
     if (err != hipSuccess) SKF_FAIL(SKF_E_HIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(err));
 }
 
+// the bf16 contraction (rows256: a transposed or bitmap A operand -- always the 256-row kernel; `avail` in f32 elements)
+static Slicing slice_bf16(int M, int N, int Kp, bool rows256, int want_splits, int64_t avail) {
+    Slicing d{{bf16_block_rows(M, rows256), (N <= 128) ? 128 : 256, 64}, 1, 0, 0, false, 0, false, 0};
+    const int splits = want_splits > 0 ? want_splits
+                                       : pick_splits_bf16((int64_t)cdiv(M, d.t.bm) * cdiv(N, d.t.bn), Kp / 64, d.t.bm, (int64_t)M * N);
+    fit_slices(d, splits, (size_t)M * N, Kp, want_splits, avail);
+    return d;
+}
+static size_t bf16_part_bytes(int M, int N, int Kp, bool rows256) {
+    return slice_bf16(M, N, Kp, rows256, 0, SCRATCH_ANY).part_elems * sizeof(float);
+}
+
 // C[M x N] (f32) = op(A) * Bt^T, bf16 operands:  at == false: A is [M][lda] (K contiguous);
 // at == true: A is [Kp][lda] row-major with the OUTPUT rows along its columns (lda >= M, rows zero-padded to Kp)
 static void run_gemm_bf16(const uint16_t* A, int64_t lda, const uint16_t* Bt, int64_t ldb, float* C, int64_t ldc,
@@ -383,31 +418,21 @@ static void run_gemm_bf16(const uint16_t* A, int64_t lda, const uint16_t* Bt, in
         SKF_FAIL(SKF_E_INVALID, "bf16 contraction: inner dimension must be padded to 64 (Kp=%d lda=%lld ldb=%lld)", Kp,
                  (long long)lda, (long long)ldb);
     if ((((uintptr_t)A) | ((uintptr_t)Bt)) & 15) SKF_FAIL(SKF_E_INVALID, "bf16 operands must be 16-byte aligned");
-    const int bn = (N <= 128) ? 128 : 256;
-    const int bm = bf16_block_rows(M, at || abits);
-    const int ktiles = Kp / 64;
-    const int64_t units = (int64_t)cdiv(M, bm) * cdiv(N, bn);
-    int splits = want_splits > 0 ? want_splits : pick_splits_bf16(units, ktiles, bm, (int64_t)M * N);
-    const size_t per = (size_t)M * N * sizeof(float);
-    if (splits > 1 && (!part || per * splits > part_bytes)) {
-        if (part && want_splits <= 0) {
-            ++g_split_clamps;
-            if (env_int("SKF_DEBUG_CLAMP", 0))
-                fprintf(stderr, "skf: split-K clamp, bf16 contraction %dx%dx%d at %d bits %d: %d slices wanted, scratch holds %zu\n", M, N, Kp,
-                        (int)at, (int)abits, splits, part_bytes / per);
-        }
-        splits = part ? (int)(part_bytes / per) : 1;
+    const Slicing d = slice_bf16(M, N, Kp, at || abits, want_splits, part ? (int64_t)(part_bytes / sizeof(float)) : SCRATCH_NONE);
+    if (d.clamped) {
+        ++g_split_clamps;
+        if (env_int("SKF_DEBUG_CLAMP", 0))
+            fprintf(stderr, "skf: split-K clamp, bf16 contraction %dx%dx%d at %d bits %d: %d slices wanted, scratch holds %zu\n", M, N, Kp,
+                    (int)at, (int)abits, d.wanted, part_bytes / sizeof(float) / ((size_t)M * N));
     }
-    if (splits < 1) splits = 1;
-    if (splits > ktiles) splits = ktiles > 0 ? ktiles : 1;
+    const int bm = d.t.bm, bn = d.t.bn, splits = d.splits;
     Bf16GemmArgs g;
     memset(&g, 0, sizeof g);
     g.A = A; g.Bt = Bt; g.C = C; g.part = (float*)part;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.M = M; g.N = N; g.Kp = Kp;
     g.a_kstep = 64; g.b_kstep = 64;
-    g.k_chunk = cdiv(ktiles > 0 ? ktiles : 1, splits) * 64;
-    splits = cdiv(Kp > 0 ? Kp : 1, g.k_chunk);
+    g.k_chunk = d.k_chunk;
     dim3 grid(cdiv(N, bn), cdiv(M, bm), splits);
     if (bm == 256) {
         // 256 x BN tile, LDS rings in dynamic shared memory (> 64 KiB needs the attribute)
@@ -455,13 +480,6 @@ static void run_gemm_bf16(const uint16_t* A, int64_t lda, const uint16_t* Bt, in
                            (const float*)part, M, N, splits);
         check_launch("bf16_splitk_reduce");
     }
-}
-
-static size_t bf16_part_bytes(int M, int N, int Kp, bool at) {      // (a bitmap operand always takes the 256-row kernel)
-    const int bn = (N <= 128) ? 128 : 256;
-    const int bm = bf16_block_rows(M, at);
-    const int s = pick_splits_bf16((int64_t)cdiv(M, bm) * cdiv(N, bn), Kp / 64, bm, (int64_t)M * N);
-    return s > 1 ? (size_t)s * M * N * sizeof(float) : 0;
 }
 
 template <typename TS>

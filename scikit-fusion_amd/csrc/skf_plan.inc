@@ -285,30 +285,40 @@ static GemmArgs gemm_args(const void* A, int64_t sa_m, int64_t sa_k, const void*
     return g;
 }
 
-// master x master -> master
-static void plan_gemm(skf_plan* p, GemmArgs g, hipStream_t st) {
-    run_gemm(GemmTypes{p->mt, p->mt, p->mt}, p->engine, g, 0, p->part.ptr, p->part_bytes, st);
+// The product kinds of a plan: operand / result types and the relation / symmetric flags of their launches.  The launches below
+// and the scratch sizing of skf_plan_create (kind_part_bytes) take them from here, so the two cannot drift apart.
+struct ProductKind { GemmTypes ty; bool relation, sym; };
+// master x master -> master: dense Theta, the reconstruction H G_j^T
+static ProductKind kind_plan(const skf_plan* p) { return {{p->mt, p->mt, p->mt}, false, false}; }
+// the same streaming a relation matrix (f32 / f64 engines): P = R G_j, Q = R^T G_i
+static ProductKind kind_relation(const skf_plan* p) { return {{p->mt, p->mt, p->mt}, true, false}; }
+// c x c algebra: f64 x f64 -> f64
+static ProductKind kind_small(const skf_plan*) { return {{SKF_F64, SKF_F64, SKF_F64}, false, false}; }
+// master x master -> f64 (W = G_i^T P, cross-Gram: long f64 accumulation over the object dimension) ...
+static ProductKind kind_wide(const skf_plan* p) { return {{SKF_F64, p->mt, p->mt}, false, false}; }
+// ... and Gram = G^T G, symmetric (where SKF_GRAM_SYM leaves it on: fewer tiles never ask for fewer slices, so sizing with it covers both)
+static ProductKind kind_gram(const skf_plan* p) { return {{SKF_F64, p->mt, p->mt}, false, true}; }
+// master x f64 -> master (n x c x c products with an f64 backbone / B / D matrix: H = G_i S, the side products)
+static ProductKind kind_mixed(const skf_plan* p) { return {{p->mt, p->mt, SKF_F64}, false, false}; }
+// split-K scratch a launch of kind `k` with these sizes can ask for
+static size_t kind_part_bytes(const skf_plan* p, const ProductKind& k, int64_t M, int64_t N, int64_t K) {
+    GemmArgs g;
+    memset(&g, 0, sizeof g);
+    g.M = (int)M; g.N = (int)N; g.K = (int)K; g.epi = EPI_STORE; g.sym = k.sym;
+    return gemm_part_elems(k.ty, p->engine, g, k.relation) * (k.ty.c == SKF_F64 ? 8 : 4);
 }
-// c x c algebra: f64 x f64 -> f64.  A launch on the second stream takes that stream's split-K scratch (ranks above 512 leave
-// the deep unsplit tile and are cut into K slices: the main stream's partials may be in flight in `part` at that moment)
-static void small_gemm(skf_plan* p, GemmArgs g, hipStream_t st) {
-    const bool on_aux = p->aux != nullptr && st == p->aux;
-    run_gemm(GemmTypes{SKF_F64, SKF_F64, SKF_F64}, p->engine, g, 0, on_aux ? p->part_aux.ptr : p->part.ptr,
-             on_aux ? p->part_aux_bytes : p->part_bytes, st);
+// A launch on the second stream takes that stream's split-K scratch (the main stream's partials may be in flight in `part`)
+static void kind_gemm(skf_plan* p, const ProductKind& k, const GemmArgs& g, hipStream_t st, bool on_aux = false) {
+    run_gemm(k.ty, p->engine, g, 0, on_aux ? p->part_aux.ptr : p->part.ptr, on_aux ? p->part_aux_bytes : p->part_bytes, st, k.relation);
 }
-// master x master -> f64 (Gram, G^T P: long f64 accumulation over the object dimension)
-static void wide_gemm(skf_plan* p, GemmArgs g, hipStream_t st) {
-    run_gemm(GemmTypes{SKF_F64, p->mt, p->mt}, p->engine, g, 0, p->part.ptr, p->part_bytes, st);
-}
-// master x f64 -> master (n x c x c products with an f64 backbone / B / D matrix)
-static void mixed_gemm(skf_plan* p, GemmArgs g, hipStream_t st) {
-    run_gemm(GemmTypes{p->mt, p->mt, SKF_F64}, p->engine, g, 0, p->part.ptr, p->part_bytes, st);
-}
+static void plan_gemm(skf_plan* p, GemmArgs g, hipStream_t st) { kind_gemm(p, kind_plan(p), g, st); }
+// (c x c algebra on the second stream: ranks above 512 leave the deep unsplit tile and are cut into K slices)
+static void small_gemm(skf_plan* p, GemmArgs g, hipStream_t st) { kind_gemm(p, kind_small(p), g, st, p->aux != nullptr && st == p->aux); }
+static void wide_gemm(skf_plan* p, GemmArgs g, hipStream_t st) { kind_gemm(p, kind_wide(p), g, st); }
+static void mixed_gemm(skf_plan* p, GemmArgs g, hipStream_t st) { kind_gemm(p, kind_mixed(p), g, st); }
 
 // the same on the second stream: one K slice (the split-K scratch belongs to the main stream)
-static void mixed_gemm_unsplit(skf_plan* p, GemmArgs g, hipStream_t st) {
-    run_gemm(GemmTypes{p->mt, p->mt, SKF_F64}, p->engine, g, 1, nullptr, 0, st);
-}
+static void mixed_gemm_unsplit(skf_plan* p, GemmArgs g, hipStream_t st) { run_gemm(kind_mixed(p).ty, p->engine, g, 1, nullptr, 0, st); }
 
 static hipEvent_t next_event(skf_plan* p) {
     if (p->ev_used == p->ev_pool.size()) {
@@ -385,7 +395,7 @@ static void relation_gemm(skf_plan* p, GemmArgs g, hipStream_t st, const RelStat
             run_gemm_bf16((const uint16_t*)r->Rb.ptr, r->ldrb, (const uint16_t*)ti.GTb.ptr + r->r0, ti.ldgt, (float*)g.C,
                           g.ldc, g.M, g.N, (int)r->kq, 0, p->part.ptr, p->part_bytes, true, st, true);
     } else {
-        run_gemm(GemmTypes{p->mt, p->mt, p->mt}, p->engine, g, 0, p->part.ptr, p->part_bytes, st, true);
+        kind_gemm(p, kind_relation(p), g, st);
     }
     if (p->profiling) {
         SKF_HIP(hipEventRecord(next_event(p), st));
@@ -655,8 +665,7 @@ static void gram(skf_plan* p, TypeState& t, int nan, hipStream_t st, bool on_aux
     // Gram = G^T G : A = G^T (m-contiguous), B = G; f64 accumulation
     GemmArgs g = gemm_args(t.G.ptr, 1, t.c, t.G.ptr, t.c, 1, t.Gram.ptr, t.c, t.c, t.c, (int)t.n, EPI_STORE, nan);
     g.sym = p->sw.gram_sym;
-    run_gemm(GemmTypes{SKF_F64, p->mt, p->mt}, p->engine, g, 0, on_aux ? p->part_aux.ptr : p->part.ptr,
-             on_aux ? p->part_aux_bytes : p->part_bytes, st);
+    kind_gemm(p, kind_gram(p), g, st, on_aux);
 }
 
 // several Gram products (GemmArgs::sym set) in one grouped launch, where the switches allow it and run_gram_group_t takes them

@@ -204,19 +204,17 @@ static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void
 //     W = (G_i^T G_i,prev) S_prev (G_j,prev^T G_j) + (E_prev^T G_i)^T G_j
 // first iteration: R_c = the known entries, zeros elsewhere (_dfmc.py:287-292), i.e. E_prev = R on the lists, S_prev = 0
 // the two cross-Gram matrices of W: Xi = G_i^T G_i,prev, Xj = G_j,prev^T G_j (f64 accumulation over the objects)
-static void known_cross(skf_plan* p, RelState& r, hipStream_t st, bool on_aux) {
+static void known_cross(skf_plan* p, RelState& r, hipStream_t st) {
     if (p->kn_first) return;
     TypeState& ti = p->types[r.row];
     TypeState& tj = p->types[r.col];
     const int ci = ti.c, cj = tj.c;
-    void* part = on_aux ? p->part_aux.ptr : p->part.ptr;
-    const size_t part_bytes = on_aux ? p->part_aux_bytes : p->part_bytes;
     // (over the rows of the block: under row ownership the block's own share of W, summed over the processes with the rest)
     GemmArgs g = gemm_args(rows_of(p, ti.G, ti, r.r0), 1, ci, rows_of(p, ti.Gp, ti, r.r0), ci, 1, r.Xi.ptr, ci, ci, ci, (int)r.nr,
                            EPI_STORE, 0);                                                                         // Xi = G_i^T G_i,prev
-    run_gemm(GemmTypes{SKF_F64, p->mt, p->mt}, p->engine, g, 0, part, part_bytes, st);
+    wide_gemm(p, g, st);
     g = gemm_args(tj.Gp.ptr, 1, cj, tj.G.ptr, cj, 1, r.Xj.ptr, cj, cj, cj, (int)tj.n, EPI_STORE, 0);             // Xj = G_j,prev^T G_j
-    run_gemm(GemmTypes{SKF_F64, p->mt, p->mt}, p->engine, g, 0, part, part_bytes, st);
+    wide_gemm(p, g, st);
 }
 static void known_w(skf_plan* p, RelState& r, hipStream_t st) {
     TypeState& ti = p->types[r.row];
@@ -226,7 +224,7 @@ static void known_w(skf_plan* p, RelState& r, hipStream_t st) {
     GemmArgs g = gemm_args(r.Q.ptr, 1, ci, tj.G.ptr, cj, 1, r.W.ptr, cj, ci, cj, (int)tj.n, EPI_STORE, 0);
     wide_gemm(p, g, st);                                                                // W = Y^T G_j
     if (p->kn_first) return;
-    known_cross(p, r, st, false);
+    known_cross(p, r, st);
     g = gemm_args(r.Sp.ptr, cj, 1, r.Xj.ptr, cj, 1, r.U.ptr, cj, ci, cj, cj, EPI_STORE, 0);             // U = S_prev Xj
     small_gemm(p, g, st);
     g = gemm_args(r.Xi.ptr, ci, 1, r.U.ptr, cj, 1, r.W.ptr, cj, ci, cj, ci, EPI_ACC, 0);                // W += Xi U

@@ -198,6 +198,7 @@ def dense_case(dtype, schedule, n, ranks, rels, thetas, what, monkeypatch, varia
                     'P': [plan.get_contraction(k, 0).astype(np.float64) for k in range(len(rel_list))],
                     'Q': [plan.get_contraction(k, 1).astype(np.float64) for k in range(len(rel_list))]}
             G = {t: plan.get_factor(t) for t in types}
+            assert all(np.isfinite(G[t]).all() for t in types), '%s: non-finite factor' % what
             snap['G1'] = G
             snap['sq'] = [plan.relation_sqerr(k) if m is not None else None for k, (_, _, _, m) in enumerate(rel_list)]
             snaps.append(snap)
