@@ -114,7 +114,7 @@ enum {
                                  built at bind time are the ones the mask form of the same data builds, byte for byte.
                                  SKF_E_INVALID: SKF_DFMF / SKF_TRANSFORM plans, row blocks / sliced / SKF_OPT_OWNED_ROWS plans,
                                  a row type's rank above 1024, more than 2e9 entries. */
-    SKF_REL_SPARSE_CSR = 128  /* SKF_DFMF plans, and unmasked relations of SKF_DFMC plans: the relation is given as the CSR of its
+    SKF_REL_SPARSE_CSR = 128, /* SKF_DFMF plans, and unmasked relations of SKF_DFMC plans: the relation is given as the CSR of its
                                  STORED entries and every other entry is ZERO (what a scipy.sparse matrix means; the reference
                                  multiplies its dense expansion, _dfmf.py:249-276, and forms its error from the dense
                                  reconstruction, _dfmf.py:306-316).  `data` and `mask` are NULL, known_bound is the EXACT number of
@@ -128,6 +128,26 @@ enum {
                                  Stored zeros stay entries.  SKF_E_INVALID: SKF_TRANSFORM plans, row blocks / sliced /
                                  SKF_OPT_OWNED_ROWS plans, a rank above 1024, more than 2e9 entries, a mask, together with
                                  SKF_REL_KNOWN_CSR. */
+    SKF_REL_FOLD_CSR = 256    /* SKF_TRANSFORM plans only: the NEW relation is given as its STORED entries, every other entry ZERO,
+                                 compressed along the TARGET's side -- indptr[n_target + 1] (int64), indices (int32, into the
+                                 partner type, strictly ascending within a target object) and values in the MASTER type (f64 /
+                                 f32; SKF_BF16 plans: f32, never rounded to bf16).  A relation whose row type is the target: its
+                                 canonical CSR; one whose column type is the target: its canonical CSC (the CSR of the
+                                 transpose).  `data` and `mask` are NULL, known_bound is the EXACT number of entries (0 allowed)
+                                 and skf_plan_set_known_entries hands the lists over before skf_plan_bind_workspace, which
+                                 validates them (rows = target objects, columns = partner objects) and copies them into the
+                                 workspace: re-preparation after skf_set_backbone / skf_set_factor finds them there.  Nothing
+                                 else is built -- no parts, no second orientation: everything that reads the relation is
+                                 independent of the moving factor, so the preparation is T = G_p S^T (row side; G_p S on the
+                                 column side; n_partner x c_target, master type) and ONE pass Ec += (R T)+, Dc += (R T)-
+                                 (skf_fold_lists; reference _dfmf.py:394-398,408-412 on the dense relation), and an iteration
+                                 never touches the relation.  Dense relations of the same plan are untouched.  skf_relation_sqerr:
+                                 the trace term as for SKF_REL_SPARSE_CSR plus one pass over the lists with x = <H[o], G_p[idx]>,
+                                 H = G_t S (row side) / G_t S^T (column side), master rows in every engine.  No P / Q is ever
+                                 formed (skf_get_contraction: SKF_E_INVALID); workspace grows with entries + n * c, never with
+                                 n_t * n_p.  SKF_E_INVALID: SKF_DFMF / SKF_DFMC plans, together with SKF_REL_KNOWN_CSR /
+                                 SKF_REL_SPARSE_CSR, a mask, a row block, a rank above 1024, more than 2e9 entries, a missing
+                                 hand-over, a broken list.  (SKF_REL_SPARSE_CSR stays an error on SKF_TRANSFORM plans.) */
 };
 
 typedef struct {
@@ -177,8 +197,9 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
 int skf_plan_destroy(skf_plan* plan);
 
 int skf_plan_workspace_bytes(const skf_plan* plan, size_t* bytes);
-/* The known entries of relation `rel` (flagged SKF_REL_KNOWN_CSR; or the stored entries of one flagged SKF_REL_SPARSE_CSR,
- * whose values are of the master type -- SKF_BF16: f32), as device pointers: indptr[n_row + 1] (int64,
+/* The known entries of relation `rel` (flagged SKF_REL_KNOWN_CSR; or the stored entries of one flagged SKF_REL_SPARSE_CSR
+ * or SKF_REL_FOLD_CSR -- the latter compressed along the target's side, see the flag --, whose values are of the master
+ * type -- SKF_BF16: f32), as device pointers: indptr[n_row + 1] (int64,
  * indptr[0] = 0, indptr[n_row] = known_bound, non-decreasing), indices[known_bound] (int32 columns, strictly ascending
  * within a row: canonical CSR, duplicates summed beforehand) and values[known_bound] of the element type of
  * skf_relation_desc.data (SKF_BF16: bf16 bits).  Call it between skf_plan_create and skf_plan_bind_workspace; the buffers
@@ -331,14 +352,15 @@ int skf_exchange_bytes(const skf_plan* plan, int32_t world, size_t* bytes);
  * over the stored bf16 relation, bf16-rounded G_i S and G_j on the matrix cores, f32 residual.
  * A SKF_REL_SPARSE_CSR relation: tr(S^T Gram_i S Gram_j) from c x c f64 products plus one pass over the row lists,
  * sum of (r - x)^2 - x^2 with x = <(G_i S)[row], G_j[col]> in the master type (SKF_BF16: the f32 masters, not the bf16
- * rows), f64 partials per wave summed in a fixed order. */
+ * rows), f64 partials per wave summed in a fixed order.  A SKF_REL_FOLD_CSR relation: the same, over its one set of lists. */
 int skf_relation_sqerr(skf_plan* plan, int32_t rel, double* out, void* stream);
 
 /* The two contraction results the LAST iteration left in the workspace, for verification at sizes where the
  * host cannot recompute them: which = 0: P = R G_j (local rows x rank_col), 1: Q = R^T G_i (n_col x rank_row),
  * both from the factors BEFORE that iteration's update (like the backbone), master dtype, copied to `dst`.
  * A masked relation kept as known entries only (skf_relation_desc.known_bound) never forms P: it answers
- * which = 2 with the row-side product P S^T (n_row x rank_row) it computes instead, and which = 1 as usual. */
+ * which = 2 with the row-side product P S^T (n_row x rank_row) it computes instead, and which = 1 as usual.
+ * A SKF_REL_FOLD_CSR relation forms neither: SKF_E_INVALID. */
 int skf_get_contraction(const skf_plan* plan, int32_t rel, int32_t which, void* dst, int64_t ld, void* stream);
 
 /* The entry lists a relation keeps after bind (a masked relation kept as its known entries, a SKF_REL_KNOWN_CSR or a
@@ -411,6 +433,16 @@ int skf_gemm_bits(const void* A, int64_t lda_bytes, const void* Bt, int64_t ldb,
 int skf_to_bf16(void* dst, int64_t ldd, int32_t src_dtype, const void* src, int64_t lds,
                 int64_t rows, int64_t cols, int32_t transpose, void* stream);
 
+/* Ec[o][q] += max(x, 0), Dc[o][q] += max(-x, 0) with x = sum over the list of output object o, in LIST ORDER, of
+ * fma(values[k], T[indices[k]][q], x), for o < n_out and q < c (1 .. 1024): the constant numerator / denominator sums of a
+ * fold-in through a sparse relation (reference _dfmf.py:394-398,408-412: tmp1 = R G_j S^T resp. R^T G_i S split into its
+ * positive and negative part) on the caller's buffers.  dtype SKF_F64 / SKF_F32 is the type of values, T, Ec and Dc;
+ * indptr[n_out + 1] (int64) and indices (int32 rows of T) are not validated here (skf_plan_bind_workspace validates the
+ * lists of a SKF_REL_FOLD_CSR relation before this pass runs over them).  Every (o, q) is owned by one lane: no atomics, no
+ * cross-lane sum -- the result is the host loop's, bit for bit.  Memory past column c of a row is not touched. */
+int skf_fold_lists(int32_t dtype, const int64_t* indptr, const int32_t* indices, const void* values, int64_t n_out,
+                   const void* T, int64_t ldt, int32_t c, void* Ec, int64_t lde, void* Dc, int64_t ldd, void* stream);
+
 /* K = pinv(A) for symmetric A (n x n): f64 Jacobi eigen-decomposition + the singular-value
  * cut-off of scipy.linalg.pinv (reference _dfmf.py:232, _dfmc.py:307). */
 int skf_pinv_sym_workspace_bytes(int32_t n, size_t* bytes);
@@ -458,7 +490,8 @@ const char* skf_last_error(void);
 const char* skf_version(void);
 /* Layout version of the structs and signatures above (SKF_ABI_VERSION).  A binding built against another version must not
  * call the library: descriptors grew between versions (skf_relation_desc.known_bound: 3, skf_options.flags: 4; version 5
- * adds entry points only -- skf_small_graph_limits, skf_comm_info, skf_launch_count -- the structs are those of version 4). */
+ * adds entry points only -- skf_small_graph_limits, skf_comm_info, skf_launch_count; later: skf_fold_lists and the flag
+ * SKF_REL_FOLD_CSR -- the structs are those of version 4). */
 #define SKF_ABI_VERSION 5
 int skf_abi_version(void);
 

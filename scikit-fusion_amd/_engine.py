@@ -44,12 +44,18 @@ class KnownEntries(object):
     ``known`` is the number of entries; ``toarray`` / ``mask`` give the equivalent dense relation and completion mask.
     ``unstored='zero'``: the same container for a relation whose entries that are not stored are ZERO (what a scipy.sparse
     matrix means; SKF_REL_SPARSE_CSR, DFMF and unmasked DFMC relations): `fill` is 0, there is no mask, ``toarray`` is the
-    dense relation itself."""
+    dense relation itself.
+    ``by_col=True`` (``unstored='zero'`` only): the lists are compressed along the COLUMN type -- `indptr` has n_col + 1
+    entries and `indices` are rows, the canonical CSC -- which is what a fold-in whose target is the relation's column type
+    hands to the library (SKF_REL_FOLD_CSR: lists compressed along the target's side).  `shape` stays the relation's."""
 
-    def __init__(self, indptr, indices, values, shape, fill=0.0, unstored='unknown'):
+    def __init__(self, indptr, indices, values, shape, fill=0.0, unstored='unknown', by_col=False):
         if unstored not in ('unknown', 'zero'):
             raise ValueError("unstored must be 'unknown' or 'zero', not %r" % (unstored,))
+        if by_col and unstored != 'zero':
+            raise ValueError("lists compressed along the column type need unstored='zero'")
         self.unstored = unstored
+        self.by_col = bool(by_col)
         if unstored == 'zero':
             fill = 0.0
         self.indptr = np.ascontiguousarray(indptr, dtype=np.int64)
@@ -60,12 +66,18 @@ class KnownEntries(object):
         self.fill = float(fill)         # what the mask form holds beneath its unknown entries (read by the initialisers only)
 
     def row_of_entries(self):
-        return np.repeat(np.arange(self.shape[0], dtype=np.int64), np.diff(self.indptr))
+        """The outer object of every entry: its row (by_col: its column)."""
+        return np.repeat(np.arange(self.shape[1 if self.by_col else 0], dtype=np.int64), np.diff(self.indptr))
+
+    def rows_cols(self):
+        """(row, column) of every entry, in list order."""
+        outer, inner = self.row_of_entries(), self.indices.astype(np.int64)
+        return (inner, outer) if self.by_col else (outer, inner)
 
     def toarray(self, fill=None):
         """The dense relation of the mask form: the values on the known entries, `fill` (default: self.fill) elsewhere."""
         out = np.full(self.shape, self.fill if fill is None else fill, dtype=np.float64)
-        out[self.row_of_entries(), self.indices] = self.values
+        out[self.rows_cols()] = self.values
         return out
 
     def mask(self):
@@ -79,7 +91,7 @@ class KnownEntries(object):
     def validate(self):
         """The device's checks on the host (skf_plan_set_known_entries), before anything is uploaded."""
         from .fusion.base import DataFusionError
-        n_r, n_c = self.shape
+        n_r, n_c = self.shape[::-1] if self.by_col else self.shape        # (lists, range of their indices)
         p, ix = self.indptr, self.indices
         if p.ndim != 1 or p.size != n_r + 1 or p[0] != 0 or p[-1] != ix.size or self.values.shape != ix.shape:
             raise DataFusionError('known entries: indptr must run from 0 to the %d entries over %d rows' % (ix.size, n_r))
@@ -100,10 +112,11 @@ class KnownEntries(object):
 class DeviceKnownEntries(object):
     """KnownEntries uploaded ONCE in the engine's element type (upload_graph: shared by the plans of concurrent restarts)."""
 
-    def __init__(self, indptr, indices, values, shape, known, unstored='unknown'):
+    def __init__(self, indptr, indices, values, shape, known, unstored='unknown', by_col=False):
         self.indptr, self.indices, self.values = indptr, indices, values
         self.shape, self.known = tuple(shape), int(known)
-        self.unstored = unstored        # 'unknown': SKF_REL_KNOWN_CSR, 'zero': SKF_REL_SPARSE_CSR
+        self.unstored = unstored        # 'unknown': SKF_REL_KNOWN_CSR, 'zero': SKF_REL_SPARSE_CSR (fits) / SKF_REL_FOLD_CSR (fold-ins)
+        self.by_col = bool(by_col)      # lists compressed along the column type (fold-ins whose target it is)
 
 
 def upload_known_entries(ke, dtype, mem):
@@ -116,7 +129,7 @@ def upload_known_entries(ke, dtype, mem):
     if code == nat.SKF_BF16 and ke.unstored != 'zero':
         vals = nat.to_bf16_bits(vals)
     keep = lambda a: mem.from_host(a if a.size else np.zeros(1, dtype=a.dtype))        # (no empty allocations)
-    return DeviceKnownEntries(keep(ke.indptr), keep(ke.indices), keep(vals), ke.shape, ke.known, ke.unstored)
+    return DeviceKnownEntries(keep(ke.indptr), keep(ke.indices), keep(vals), ke.shape, ke.known, ke.unstored, ke.by_col)
 
 
 def pack_mask(mask, mem):
@@ -518,6 +531,17 @@ class DevicePlan(object):
                                      % (i, j, tuple(data.shape), n_obj[i], n_obj[j]))
                 dev = data if isinstance(data, DeviceKnownEntries) else upload_known_entries(data, self.dtype, mem)
                 self._keep_rel.append(dev)
+                if variant == nat.SKF_TRANSFORM and dev.unstored == 'zero':
+                    # a fold-in: the stored entries compressed along the target's side (SKF_REL_FOLD_CSR)
+                    if dev.by_col != (j == target and i != target):
+                        raise ValueError('relation (%s,%s): a fold-in takes the lists compressed along the target %s'
+                                         % (i, j, target))
+                    rdesc[k].flags |= nat.SKF_REL_FOLD_CSR
+                    rdesc[k].known_bound = dev.known
+                    csr.append((k, dev))
+                    continue
+                if dev.by_col:
+                    raise ValueError('relation (%s,%s): lists compressed along the column type are for fold-ins' % (i, j))
                 rdesc[k].flags |= nat.SKF_REL_SPARSE_CSR if dev.unstored == 'zero' else nat.SKF_REL_KNOWN_CSR
                 rdesc[k].known_bound = dev.known
                 csr.append((k, dev))

@@ -205,7 +205,13 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
             if (sp0 && p->variant == SKF_TRANSFORM) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_SPARSE_CSR is for SKF_DFMF / SKF_DFMC plans", r);
             if (sp0 && (d.data || d.mask || (d.flags & (SKF_REL_MASKED | SKF_REL_MASK_BITS))))
                 SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_SPARSE_CSR takes no data / mask", r);
-            if (!absent && !csr && !sp0 && (!d.data || d.ld < p->types[d.col_type].n))
+            const bool fold = (d.flags & SKF_REL_FOLD_CSR) != 0;      // fold-in: the stored entries compressed along the target's side
+            if (fold && p->variant != SKF_TRANSFORM) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR is for SKF_TRANSFORM plans", r);
+            if (fold && (csr || sp0))
+                SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR excludes SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR", r);
+            if (fold && (d.data || d.mask || (d.flags & (SKF_REL_MASKED | SKF_REL_MASK_BITS))))
+                SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR takes no data / mask", r);
+            if (!absent && !csr && !sp0 && !fold && (!d.data || d.ld < p->types[d.col_type].n))
                 SKF_FAIL(SKF_E_INVALID, "relation %d: dimension mismatch (ld %lld < %lld columns)", r, (long long)d.ld,
                          (long long)p->types[d.col_type].n);
             const int64_t n_row_type = p->types[d.row_type].n;
@@ -214,6 +220,7 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
                          r, (long long)d.row_begin, (long long)d.n_rows, (long long)n_row_type);
             const bool block = absent || (d.n_rows > 0 && d.n_rows < n_row_type) || (d.flags & SKF_REL_NO_COL_SIDE);
             if (block && (csr || sp0)) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR relations are whole relations", r);
+            if (block && fold) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR relations are whole relations", r);
             if (block && p->variant == SKF_TRANSFORM)
                 SKF_FAIL(SKF_E_INVALID, "relation %d: row blocks are for SKF_DFMF / SKF_DFMC plans", r);
             if (block && p->bf16 && d.row_begin % 64 != 0)
@@ -257,6 +264,15 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
                 s.R_in = s.R = nullptr;
                 s.kn_cap = d.known_bound;
             }
+            if (fold) {                 // one set of lists along the target (skf_plan_set_known_entries): no dense form, no P / Q
+                if (p->types[d.row_type].c > 1024 || p->types[d.col_type].c > 1024 || d.known_bound > 2000000000LL)
+                    SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR beyond the list limits (a rank above 1024 or %lld > 2e9 entries)",
+                             r, (long long)d.known_bound);
+                s.fold = true;
+                s.binary = false;
+                s.R_in = s.R = nullptr;
+                s.kn_cap = d.known_bound;
+            }
         }
         // masked relations with few known entries are kept as lists of those entries (skf_known.h).  The three passes over the
         // lists gather rank_row-wide vectors -- ~70 ps per entry at rank 128 against ~2.2 ps per CELL for the four passes of
@@ -283,6 +299,7 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
             for (size_t rk = 0; rk < p->rels.size(); ++rk) {
                 RelState& s = p->rels[rk];
                 const int ci = p->types[s.row].c;
+                if (s.fold) continue;               // (one set of lists as handed over: no parts, nothing decided here)
                 if (s.sp0) {
                     // valued lists whatever the density (the caller chose the form; no dense one to fall back on).  P gathers
                     // rank_col-wide rows of G_j through the row lists, Q rank_row-wide rows of G_i through the column lists
@@ -479,6 +496,32 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
             if (p->variant == SKF_TRANSFORM) { r.nr = ti.n; r.r0 = 0; }
             add_slot(p, r.S, cc);
             add_slot(p, r.U, cc);
+            if (r.fold) {
+                // the lists as handed over, T = G_p S', H and the c x c matrices of the error: ~ entries + n * c, never n_t * n_p
+                const bool row_side = r.row == p->target;
+                const TypeState& tt = p->types[p->target];
+                const TypeState& tp = row_side ? tj : ti;
+                const size_t cap = (size_t)r.kn_cap;
+                add_slot(p, r.KrPtr, ((size_t)tt.n + 1) * 8);
+                add_slot(p, r.KrIdx, cap * 4);
+                add_slot(p, r.KrVal, cap * es);
+                add_slot(p, r.Tm, (size_t)tp.n * tt.c * es);
+                add_slot(p, r.H, (size_t)tt.n * tp.c * es);
+                add_slot(p, r.T1, cc);
+                add_slot(p, r.Xi, (size_t)ti.c * ti.c * 8);
+                add_slot(p, r.Xj, (size_t)tj.c * tj.c * 8);
+                want_part(k_small, ti.c, tj.c, tj.c, true);
+                want_part(k_small, ti.c, tj.c, ti.c, true);
+                want_part(k_small, ti.c, ti.c, tj.c, true);
+                want_part(k_small, tj.c, tj.c, ti.c, true);
+                want_part(k_wide, ti.c, ti.c, ti.n);                            // Gram matrices of the error's trace term
+                want_part(k_wide, tj.c, tj.c, tj.n);
+                want_part(k_mixed, tp.n, tt.c, tp.c);                           // T = G_p S'
+                want_part(k_mixed, tt.n, tp.c, tt.c);                           // H = G_t S / G_t S^T
+                const size_t waves = ((size_t)tt.n + 3) / 4 + 8;                // error partials: one per wave of the pass
+                if (waves * 4 + 64 > sq_elems) sq_elems = waves * 4 + 64;
+                continue;
+            }
             if (nr > 0 && !r.kn) add_slot(p, r.H, (size_t)nr * tj.c * es);
             if (nr > 0 && !r.kn && (p->variant != SKF_TRANSFORM || r.row == p->target)) add_slot(p, r.P, (size_t)nr * tj.c * es);
             if (p->variant == SKF_TRANSFORM && r.col == p->target) add_slot(p, r.Q, (size_t)tj.n * ti.c * es);
@@ -728,7 +771,8 @@ int skf_plan_set_known_entries(skf_plan* plan, int32_t rel, const int64_t* indpt
         if (plan->ws_base) SKF_FAIL(SKF_E_STATE, "skf_plan_set_known_entries after skf_plan_bind_workspace");
         if (rel < 0 || rel >= (int)plan->rels.size()) SKF_FAIL(SKF_E_INVALID, "relation %d out of range", rel);
         RelState& r = plan->rels[rel];
-        if (!r.kn_csr && !r.sp0) SKF_FAIL(SKF_E_INVALID, "relation %d is flagged neither SKF_REL_KNOWN_CSR nor SKF_REL_SPARSE_CSR", rel);
+        if (!r.kn_csr && !r.sp0 && !r.fold)
+            SKF_FAIL(SKF_E_INVALID, "relation %d is flagged neither SKF_REL_KNOWN_CSR, SKF_REL_SPARSE_CSR nor SKF_REL_FOLD_CSR", rel);
         if (!indptr || (r.kn_cap > 0 && (!indices || !values))) SKF_FAIL(SKF_E_INVALID, "relation %d: null CSR array", rel);
         r.csr_ptr = indptr;
         r.csr_idx = (const int*)indices;
@@ -822,6 +866,33 @@ int skf_plan_bind_workspace(skf_plan* p, void* ws, size_t bytes, void* stream) {
         p->sw = Switches::read();          // the only place a plan looks at the environment
         hipStream_t st = as_stream(stream);
         for (RelState& r : p->rels) {
+            if (r.fold) {
+                // the caller's lists along the target: validated on the device (rows = target objects, columns = partner
+                // objects) before anything gathers through them, then copied as they are -- no other list is built
+                if (!r.csr_ptr) SKF_FAIL(SKF_E_INVALID, "a SKF_REL_FOLD_CSR relation without skf_plan_set_known_entries");
+                const bool row_side = r.row == p->target;
+                const int64_t rows = p->types[p->target].n, cols = p->types[row_side ? r.col : r.row].n, tot = r.kn_cap;
+                int* flag = (int*)p->sqpart.ptr;                 // (scratch word; bind is not on the hot path)
+                SKF_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
+                const int wgrid = (int)((rows + 3) / 4 < 2048 ? (rows + 3) / 4 : 2048);
+                hipLaunchKernelGGL(known_csr_check_kernel, dim3(wgrid), dim3(256), 0, st, r.csr_ptr, r.csr_idx, rows, cols, tot, flag);
+                check_launch("known_csr_check");
+                int bad = 0;
+                SKF_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+                SKF_HIP(hipStreamSynchronize(st));
+                if (bad)
+                    SKF_FAIL(SKF_E_INVALID, "SKF_REL_FOLD_CSR: the lists are not canonical for %lld target x %lld partner objects with %lld "
+                             "entries (indptr from 0 to the count, non-decreasing; indices in range and strictly ascending within a list)",
+                             (long long)rows, (long long)cols, (long long)tot);
+                r.kn_nnz = tot;
+                SKF_HIP(hipMemcpyAsync(r.KrPtr.ptr, r.csr_ptr, ((size_t)rows + 1) * 8, hipMemcpyDeviceToDevice, st));
+                if (tot > 0) {
+                    SKF_HIP(hipMemcpyAsync(r.KrIdx.ptr, r.csr_idx, (size_t)tot * 4, hipMemcpyDeviceToDevice, st));
+                    SKF_HIP(hipMemcpyAsync(r.KrVal.ptr, r.csr_val, (size_t)tot * p->esz, hipMemcpyDeviceToDevice, st));
+                }
+                r.csr_ptr = nullptr; r.csr_idx = nullptr; r.csr_val = nullptr;      // not referenced after bind
+                continue;
+            }
             if (r.kn_csr || r.sp0) {               // the caller's CSR, validated, then the same lists the mask form builds
                 if (!r.csr_ptr) SKF_FAIL(SKF_E_INVALID, "a SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR relation without skf_plan_set_known_entries");
                 build_known_lists_csr(p, r, st);
@@ -886,7 +957,7 @@ int skf_plan_bind_workspace(skf_plan* p, void* ws, size_t bytes, void* stream) {
                 if (t.Grow.bytes) SKF_HIP(hipMemsetAsync(t.Grow.ptr, 0, t.Grow.bytes, st));
             }
             for (RelState& r : p->rels) {
-                if (r.absent || r.kn || r.sp0) continue;
+                if (r.absent || r.kn || r.sp0 || r.fold) continue;
                 const int64_t rows = r.nr, cols = p->types[r.col].n;
                 if (r.binary) {
                     int* bad = (int*)p->sqpart.ptr;                  // (scratch word; bind is not on the hot path)
@@ -1520,6 +1591,20 @@ int skf_relation_sqerr(skf_plan* p, int32_t rel, double* out, void* stream) {
             GemmArgs h = gemm_args(A, 1, c, B, c, 1, C, c, c, c, (int)n, EPI_STORE, 0);
             wide_gemm(p, h, st);
         };
+        if (r.fold) {
+            // as for SKF_REL_SPARSE_CSR below: tr(S^T Gram_i S Gram_j) + sum over the stored entries of (r - x)^2 - x^2, the lists
+            // compressed along the target: x = <H[o], G_p[idx]>, H = G_t S (row side) or G_t S^T (column side)
+            gram_of(ti.G.ptr, ti.G.ptr, r.Xi.ptr, ci, ti.n);
+            gram_of(tj.G.ptr, tj.G.ptr, r.Xj.ptr, cj, tj.n);
+            trace_term(r.Xi.ptr, r.S.ptr, r.Xj.ptr, r.S.ptr, 1.0, true);
+            GemmArgs h = r.row == p->target ? gemm_args(ti.G.ptr, ci, 1, r.S.ptr, cj, 1, r.H.ptr, cj, (int)ti.n, cj, ci, EPI_STORE, 0)
+                                            : gemm_args(tj.G.ptr, cj, 1, r.S.ptr, 1, cj, r.H.ptr, ci, nj, ci, cj, EPI_STORE, 0);
+            mixed_gemm(p, h, st);
+            const int waves = fold_err_pass(p, r, st, 1);
+            hipLaunchKernelGGL((sum_partials_kernel<double>), dim3(1), dim3(256), 0, st, (const double*)p->sqpart.ptr, waves + 1, out);
+            check_launch("sum_partials");
+            return;
+        }
         if (r.sp0) {
             // |R - X|^2 = |X|^2 - 2 <R, X> + |R|^2 with X = G_i S G_j^T and R zero off its stored entries:
             //     |X|^2 = tr(S^T Gram_i S Gram_j)   (c x c, f64)
@@ -1600,6 +1685,7 @@ int skf_get_contraction(const skf_plan* p, int32_t rel, int32_t which, void* dst
         const RelState& r = p->rels[rel];
         const TypeState& ti = p->types[r.row];
         const TypeState& tj = p->types[r.col];
+        if (r.fold) SKF_FAIL(SKF_E_INVALID, "relation %d (SKF_REL_FOLD_CSR) forms neither P nor Q", rel);
         if (which == 2 && !r.kn) SKF_FAIL(SKF_E_STATE, "relation %d forms P, not P S^T (which = 2 is for known-entries relations)", rel);
         const Slot& src = which == 0 ? r.P : which == 1 ? r.Q : r.A;
         const int64_t rows = which == 1 ? tj.n : r.nr, cols = which == 0 ? tj.c : ti.c;
@@ -1742,6 +1828,20 @@ int skf_to_bf16(void* dst, int64_t ldd, int32_t src_dtype, const void* src, int6
         else if (src_dtype == SKF_F32) launch_to_bf16<float>((uint16_t*)dst, ldd, (const float*)src, lds, rows, cols, transpose != 0, st);
         else if (src_dtype == SKF_BF16) launch_to_bf16<uint16_t>((uint16_t*)dst, ldd, (const uint16_t*)src, lds, rows, cols, transpose != 0, st);
         else SKF_FAIL(SKF_E_INVALID, "bad source dtype");
+    });
+}
+
+int skf_fold_lists(int32_t dtype, const int64_t* indptr, const int32_t* indices, const void* values, int64_t n_out, const void* T,
+                   int64_t ldt, int32_t c, void* Ec, int64_t lde, void* Dc, int64_t ldd, void* stream) {
+    return guarded([&] {
+        if (dtype != SKF_F64 && dtype != SKF_F32) SKF_FAIL(SKF_E_INVALID, "skf_fold_lists: dtype must be SKF_F64 / SKF_F32");
+        if (!indptr || !indices || !values || !T || !Ec || !Dc) SKF_FAIL(SKF_E_INVALID, "null argument");
+        if (n_out < 0 || n_out > 2000000000LL || c < 1 || c > 1024) SKF_FAIL(SKF_E_INVALID, "skf_fold_lists: n_out %lld / width %d", (long long)n_out, c);
+        if (ldt < c || lde < c || ldd < c) SKF_FAIL(SKF_E_INVALID, "ld too small");
+        if (dtype == SKF_F64)
+            launch_fold_lists<double>(indptr, (const int*)indices, values, n_out, T, ldt, c, Ec, lde, Dc, ldd, as_stream(stream));
+        else
+            launch_fold_lists<float>(indptr, (const int*)indices, values, n_out, T, ldt, c, Ec, lde, Dc, ldd, as_stream(stream));
     });
 }
 

@@ -726,4 +726,80 @@ __global__ __launch_bounds__(256) void known_col_values_csr_kernel(const int64_t
         }
 }
 
+// ------------------------------------------------------------------------------------------
+// Fold-in through a sparse relation (SKF_REL_FOLD_CSR, skf_fold_lists; reference _dfmf.py:394-398,408-412 on the dense
+// relation): the constant sums of prepare_transform straight from the stored entries,
+//     x[o][q] = sum over the list of target object o of values[k] * T[indices[k]][q]      T = G_p S_r' (n_partner x c)
+//     Ec[o][q] += max(x, 0) ,  Dc[o][q] += max(-x, 0)
+// The lists are compressed along the target's side and read ONCE per preparation, so there are no parts and no second
+// orientation.  Every (o, q) belongs to one lane: x is ONE fma chain in list order whatever the lane mapping -- no atomics,
+// no cross-lane sum, and a host loop repeats the bits.  Mapping: `lanes` (a power of two, >= min(c, 64)) adjacent lanes
+// share an object and read adjacent columns of a gathered row (one contiguous request per row); c <= 64: 256 / lanes
+// objects per workgroup, c > 64: a lane owns CPL = 4 columns 64 apart and blockIdx.y walks the 256-column chunks.
+// U entries are taken per trip: their indices / values (one address per lane group) and their U * CPL gathers are issued
+// back to back before the dependent fma chain consumes the first -- the pass is bound by the latency of the gathers.
+// A very long list runs serially in its lanes (profiles/r10_sparse_foldin.txt: measured, accepted: once per preparation).
+template <typename T>
+struct FoldListArgs {
+    const int64_t* ptr;         // [n_out + 1]
+    const int* idx;             // partner object of every entry
+    const T* val;
+    const T* Tm;                // [n_partner][ldt]
+    T* Ec;                      // [n_out][lde]
+    T* Dc;                      // [n_out][ldd]
+    int64_t n_out, ldt, lde, ldd;
+    int c, lanes;
+};
+
+__device__ __forceinline__ float fold_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fold_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+template <typename T, int CPL, int U>
+__global__ __launch_bounds__(256) void fold_lists_kernel(FoldListArgs<T> a) {
+    const int lanes = a.lanes;
+    const int64_t o = (int64_t)blockIdx.x * (256 / lanes) + (int)threadIdx.x / lanes;
+    const int q0 = (int)blockIdx.y * (64 * CPL) + (int)threadIdx.x % lanes;
+    if (o >= a.n_out || q0 >= a.c) return;
+    bool live[CPL];
+    T x[CPL];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+        live[j] = q0 + 64 * j < a.c;
+        x[j] = (T)0;
+    }
+    const T* Tq = a.Tm + q0;
+    int64_t k = a.ptr[o];
+    const int64_t ke = a.ptr[o + 1];
+    for (; k + U <= ke; k += U) {
+        int64_t row[U];
+        T v[U], g[U][CPL];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            row[u] = (int64_t)a.idx[k + u] * a.ldt;
+            v[u] = a.val[k + u];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) g[u][j] = live[j] ? Tq[row[u] + 64 * j] : (T)0;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) x[j] = fold_fma(v[u], g[u][j], x[j]);
+    }
+    for (; k < ke; ++k) {
+        const int64_t row = (int64_t)a.idx[k] * a.ldt;
+        const T v = a.val[k];
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) x[j] = fold_fma(v, live[j] ? Tq[row + 64 * j] : (T)0, x[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+        if (!live[j]) continue;
+        const int q = q0 + 64 * j;
+        a.Ec[o * a.lde + q] += x[j] > (T)0 ? x[j] : (T)0;
+        a.Dc[o * a.ldd + q] += x[j] < (T)0 ? -x[j] : (T)0;
+    }
+}
+
 }  // namespace skf

@@ -153,6 +153,10 @@ struct RelState {
     // values where the known-entry form keeps residuals (sparse_pass), partial outputs of the parts in Apart / Qpart; the error
     // is tr(S^T Gram_i S Gram_j) (Xi, Xj) + one SRP_ERR pass with e = r.  No dense copy in any type.
     bool sp0 = false;
+    // SKF_REL_FOLD_CSR (SKF_TRANSFORM): the new relation as ONE set of lists compressed along the target's side, copied into
+    // KrPtr / KrIdx / KrVal at bind time (master type); Tm = G_p S^T (row side) / G_p S (column side), n_partner x c_target;
+    // H = G_t S / G_t S^T (n_target x c_partner) and Xi / Xj / T1 for skf_relation_sqerr.  No P, no Q, no parts.
+    bool fold = false;
     Slot FiB;                              // SKF_BF16: bf16 rows of T = G_j S^T (n_j x ldf; the rows of G_i: TypeState::Grow)
     Slot Tm;                               // T = G_j S^T in the master type (n_j x c_i)
     Slot Apart, Qpart;                     // partial outputs of the parts, [parts][n][c_i] (only with more than one part)

@@ -390,6 +390,13 @@ static void prepare_transform(skf_plan* p, hipStream_t st) {
         TypeState& ti = p->types[r.row];
         TypeState& tj = p->types[r.col];
         const int ni = (int)ti.n, nj = (int)tj.n, ci = ti.c, cj = tj.c;
+        if (r.fold) {                         // the stored entries, compressed along the target: T = G_p S', one pass into Ec / Dc
+            fold_prepare(p, r, st);
+            const bool row_side = r.row == p->target;
+            relation_small_terms(p, r, 0, EPI_SPLIT_ACC, row_side ? tt.Bp_tot.ptr : nullptr, row_side ? tt.Bn_tot.ptr : nullptr,
+                                 row_side ? nullptr : tt.Bp_tot.ptr, row_side ? nullptr : tt.Bn_tot.ptr, row_side, !row_side, st);
+            continue;
+        }
         if (r.row == p->target) {             // _dfmf.py:392-405
             GemmArgs g = gemm_args(r.R, r.ldr, 1, tj.G.ptr, cj, 1, r.P.ptr, cj, ni, cj, nj, EPI_STORE, 0);
             relation_gemm(p, g, st, &r, false);

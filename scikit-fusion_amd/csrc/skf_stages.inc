@@ -200,6 +200,78 @@ static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void
     return waves;
 }
 
+// ------------------------------------------------------------------------------------------
+// Fold-in through a sparse relation (SKF_REL_FOLD_CSR, fold_lists_kernel in skf_known.h)
+// ------------------------------------------------------------------------------------------
+template <typename T>
+static void launch_fold_lists(const int64_t* ptr, const int* idx, const void* val, int64_t n_out, const void* Tm, int64_t ldt, int c,
+                              void* Ec, int64_t lde, void* Dc, int64_t ldd, hipStream_t st) {
+    if (n_out <= 0 || c <= 0) return;
+    FoldListArgs<T> a;
+    a.ptr = ptr; a.idx = idx; a.val = (const T*)val; a.Tm = (const T*)Tm; a.Ec = (T*)Ec; a.Dc = (T*)Dc;
+    a.n_out = n_out; a.ldt = ldt; a.lde = lde; a.ldd = ldd; a.c = c;
+    int lanes = 1;
+    while (lanes < 64 && lanes < c) lanes *= 2;
+    a.lanes = lanes;
+    const int64_t per = 256 / lanes;
+    const dim3 grid((unsigned)((n_out + per - 1) / per), c > 64 ? (unsigned)cdiv(c, 256) : 1u);
+    // c <= 64: one column per lane, 8 rows in flight per lane group; wider: 4 columns per lane, 4 x 4 gathers in flight
+    if (c <= 64) hipLaunchKernelGGL((fold_lists_kernel<T, 1, 8>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((fold_lists_kernel<T, 4, 4>), grid, dim3(256), 0, st, a);
+    check_launch("fold_lists");
+}
+
+// The constant sums of prepare_transform for a SKF_REL_FOLD_CSR relation: T = G_p S^T (the target is the row type,
+// _dfmf.py:394-398) or G_p S (column type, _dfmf.py:408-412) in the master type, then one pass over the lists into Ec / Dc.
+// Several relations of a plan accumulate by plain read-modify-write in relation order on the one stream.
+static void fold_prepare(skf_plan* p, RelState& r, hipStream_t st) {
+    TypeState& ti = p->types[r.row];
+    TypeState& tj = p->types[r.col];
+    TypeState& tt = p->types[p->target];
+    const int ci = ti.c, cj = tj.c;
+    const bool row_side = r.row == p->target;
+    GemmArgs g = row_side ? gemm_args(tj.G.ptr, cj, 1, r.S.ptr, 1, cj, r.Tm.ptr, ci, (int)tj.n, ci, cj, EPI_STORE, 0)      // G_j S^T
+                          : gemm_args(ti.G.ptr, ci, 1, r.S.ptr, cj, 1, r.Tm.ptr, cj, (int)ti.n, cj, ci, EPI_STORE, 0);     // G_i S
+    mixed_gemm(p, g, st);
+    if (p->f64)
+        launch_fold_lists<double>((const int64_t*)r.KrPtr.ptr, (const int*)r.KrIdx.ptr, r.KrVal.ptr, tt.n, r.Tm.ptr, tt.c, tt.c,
+                                  tt.Ec.ptr, tt.c, tt.Dc.ptr, tt.c, st);
+    else
+        launch_fold_lists<float>((const int64_t*)r.KrPtr.ptr, (const int*)r.KrIdx.ptr, r.KrVal.ptr, tt.n, r.Tm.ptr, tt.c, tt.c,
+                                 tt.Ec.ptr, tt.c, tt.Dc.ptr, tt.c, st);
+}
+
+// The list part of skf_relation_sqerr for such a relation: sum over the stored entries of (r - x)^2 - x^2 with
+// x = <H[o], G_p[idx]> -- the SRP_ERR launch of the fit's error pass (sparse_pass) pointed at the workspace copy of the
+// lists, parts = 1, the stored values as residuals as well; r.H must be current.  Master rows in every engine (the reason
+// sparse_pass gives).  One f64 partial per wave from slot `sq_first` of p->sqpart; their number is returned.
+static int fold_err_pass(skf_plan* p, const RelState& r, hipStream_t st, int sq_first) {
+    const bool row_side = r.row == p->target;
+    const TypeState& tp = p->types[row_side ? r.col : r.row];          // the partner: its factor rows are gathered
+    const int64_t n_out = p->types[p->target].n;
+    const int w = tp.c;
+    const int64_t need = ((n_out + 3) / 4 + 7) / 8 * 8 * 4 + sq_first;
+    if ((size_t)need > p->sq_elems) SKF_FAIL(SKF_E_STATE, "residual partials: %lld > %zu slots", (long long)need, p->sq_elems);
+    auto fill = [&](auto& a, auto* vals, auto* Fi, auto* Fo) {
+        memset(&a, 0, sizeof a);
+        a.ptr = (const int64_t*)r.KrPtr.ptr;
+        a.idx = (const int*)r.KrIdx.ptr;
+        a.rvals = vals; a.evals = vals;                      // (never written: SRP_ERR only reads the residual list)
+        a.Fi = Fi; a.ldi = w; a.Fo = Fo; a.ldo = w;
+        a.ld_out = w; a.part_stride = n_out * w; a.n_out = n_out;
+        a.w = w; a.parts = 1; a.mode = SRP_ERR;
+        a.sq = (double*)p->sqpart.ptr + sq_first;
+    };
+    if (p->f64) {
+        SrpArgs<double, double> a;
+        fill(a, (double*)r.KrVal.ptr, (const double*)tp.G.ptr, (const double*)r.H.ptr);
+        return launch_srp(a, st, false);
+    }
+    SrpArgs<float, float> a;
+    fill(a, (float*)r.KrVal.ptr, (const float*)tp.G.ptr, (const float*)r.H.ptr);
+    return launch_srp(a, st, false);
+}
+
 // W = G_i^T R_c G_j for the backbone (_dfmc.py:311-314) with R_c = G_i,prev S_prev G_j,prev^T + E_prev:
 //     W = (G_i^T G_i,prev) S_prev (G_j,prev^T G_j) + (E_prev^T G_i)^T G_j
 // first iteration: R_c = the known entries, zeros elsewhere (_dfmc.py:287-292), i.e. E_prev = R on the lists, S_prev = 0

@@ -403,7 +403,7 @@ def transform_runs(R_ij, Theta_i, target_obj_type, obj_type2rank, models, max_it
     types, n_obj, n_t = _transform_graph(R_ij, t, models[0][0])
     rs = _as_rs(random_state)
     if G0 is None:
-        R_first = {k: np.asarray(v[0], dtype=float) for k, v in R_ij.items()}
+        R_first = {k: host_view(v[0]) for k, v in R_ij.items()}        # (stored entries are read as such, never expanded)
         G0 = [initialize([t], {t: n_t}, obj_type2rank, R_first, init_type, rs)[t, t] for _ in models]
     rt = nat.get_runtime()
     rel_list, theta_list = upload_graph(flatten_relations(R_ij), flatten_thetas(Theta_i), dtype, rt)
@@ -445,7 +445,7 @@ def transform(R_ij, Theta_i, target_obj_type, obj_type2rank, G, S, max_iter=10,
         raise DataFusionError("Target object type: %s size mismatch" % t)
     n_t = sizes[0]
     if G0 is None:
-        R_first = {k: np.asarray(v[0], dtype=float) for k, v in R_ij.items()}
+        R_first = {k: host_view(v[0]) for k, v in R_ij.items()}        # (stored entries are read as such, never expanded)
         G0 = initialize([t], {t: n_t}, obj_type2rank, R_first, init_type,
                         _as_rs(random_state))[t, t]
     # object types taking part: the target + every partner type of the new relations

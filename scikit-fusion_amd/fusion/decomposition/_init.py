@@ -26,8 +26,7 @@ class _KnownView(object):
     of the relation is, contiguous as a row is), one column buffer at a time, so that the ties fall as they do there."""
 
     def __init__(self, ke, transposed):
-        self.rows = ke.row_of_entries()
-        self.cols = ke.indices.astype(np.int64)
+        self.rows, self.cols = ke.rows_cols()           # (whichever side the lists are compressed along)
         if transposed:
             self.rows, self.cols = self.cols, self.rows
         self.transposed = transposed

@@ -65,6 +65,30 @@ def stored_entries_apply(relation, sparse_relations, shard='runs'):
     return cells > 0 and nnz / cells * rank <= SPARSE_RULE
 
 
+FOLD_MIN_CELLS = 1 << 20       # fold-ins, default rule: below this many cells the dense upload is free and nothing changes
+
+
+def fold_entries_apply(relation, sparse_relations):
+    """Whether a ``scipy.sparse`` relation with ``unstored='zero'`` enters a fold-in (``DfmfTransform``) as its stored
+    entries, compressed along the target's side and never expanded: no preprocessor, two different object types, ranks
+    <= 1024 and at most 2e9 entries (the limits of the library's lists).  `sparse_relations` True: whenever eligible;
+    False: never; None: when also density * max(rank_row, rank_col) <= SPARSE_RULE (the fit's constant: a dense-fed
+    preparation streams every cell once, a list-fed one gathers a c-wide row per entry, the trade of the fit's passes;
+    DESIGN.md section 2 says what was measured for the fold-in) and the relation has at least 2^20 cells."""
+    if sparse_relations is False:
+        return False
+    if not relation.is_zero_unstored() or relation.preprocessor or relation.row_type == relation.col_type:
+        return False
+    rank = max(int(relation.row_type.rank), int(relation.col_type.rank))
+    nnz = int(relation.data.nnz)
+    if rank > 1024 or nnz > 2000000000:
+        return False
+    if sparse_relations:
+        return True
+    cells = float(relation.data.shape[0]) * float(relation.data.shape[1])
+    return cells >= FOLD_MIN_CELLS and nnz / cells * rank <= SPARSE_RULE
+
+
 def graph_matrices(fusion_graph, with_masks=False, device_dtype=None, known_entries=False, sparse_relations=False,
                    shard='runs'):
     """FusionGraph -> (R, Theta[, M]) dictionaries in the reference's walking order
@@ -252,12 +276,18 @@ class DfmfTransform(FusionTransform):
 
     Parameters (identical to the reference): max_iter=100, init_type=None (use the fuser's),
     n_run=1, stopping=None, stopping_system=None, fill_value=0, verbose=0, compute_err=False,
-    callback=None, random_state=None, n_jobs=1.  Addition: dtype.
+    callback=None, random_state=None, n_jobs=1.  Additions: dtype;
+    sparse_relations=None | True | False: a new ``scipy.sparse`` relation (``unstored='zero'``, no preprocessor, two
+    different object types, ranks <= 1024) enters as its stored entries compressed along the target's side and is never
+    expanded -- True: whenever eligible; False: never (``toarray()``); None: when density * max(rank) <= 4 and the relation
+    has at least 2^20 cells (below that the dense upload is free and results stay bit for bit).  Stored non-finite values
+    take `fill_value`, as in the dense path; entries that are not stored are zeros, not unknowns, and never filled.  A
+    relation given with ``unstored='unknown'`` is still expanded: the reference's fold-in fills it.
     """
 
     def __init__(self, max_iter=100, init_type=None, n_run=1, stopping=None,
                  stopping_system=None, fill_value=0, verbose=0, compute_err=False,
-                 callback=None, random_state=None, n_jobs=1, dtype='f64'):
+                 callback=None, random_state=None, n_jobs=1, dtype='f64', sparse_relations=None):
         super(DfmfTransform, self).__init__()
         self._set_params(vars())
 
@@ -274,6 +304,13 @@ class DfmfTransform(FusionTransform):
         R, Theta = {}, {}
         for row_type, col_type in product(fusion_graph.object_types, repeat=2):
             for relation in fusion_graph.get_relations(row_type, col_type):
+                if fold_entries_apply(relation, getattr(self, 'sparse_relations', None)):
+                    # the stored entries, compressed along the target's side; `data[~isfinite] = fill_value` of the dense
+                    # path on the stored values (what is not stored is zero, not unknown: nothing else to fill)
+                    data = relation.stored_entries(by_col=relation.row_type != target)
+                    data.values[~np.isfinite(data.values)] = self.fill_value
+                    R.setdefault((relation.row_type, relation.col_type), []).append(data)
+                    continue
                 data = relation.preprocessor(relation.dense_data()) if relation.preprocessor \
                     else relation.dense_data()
                 if np.ma.is_masked(data):

@@ -150,8 +150,8 @@ class Relation(object):
 
     ``data`` may also be a ``scipy.sparse`` matrix.  ``unstored`` says what its entries that are not stored mean:
     'zero' (default, scipy's own meaning: the result is the one of fusing ``toarray()``; ``Dfmf`` / ``Dfmc`` with
-    shard='runs' fit a sparse enough one on its stored entries alone and never expand it -- see their
-    ``sparse_relations`` keyword -- and everything else expands it) or
+    shard='runs' fit a sparse enough one on its stored entries alone and never expand it, and ``DfmfTransform`` folds new
+    objects in through one the same way -- see their ``sparse_relations`` keyword -- and everything else expands it) or
     'unknown': the relation is exactly the ``numpy.ma.MaskedArray`` whose stored entries are unmasked and whose unstored
     entries are masked -- every result equals what that MaskedArray gives.  Stored zeros are known zeros; duplicate
     entries are summed (as ``toarray()`` sums them); stored NaN / inf take the fill value and stay known, as in the
@@ -213,11 +213,17 @@ class Relation(object):
         """True for a scipy.sparse relation whose unstored entries are zero (``unstored='zero'``, the default)."""
         return self.unstored == 'zero' and _is_sparse(self.data)
 
-    def stored_entries(self):
+    def stored_entries(self, by_col=False):
         """The stored entries as canonical CSR (``_engine.KnownEntries`` with ``unstored='zero'``): duplicates summed, columns
-        sorted, stored zeros kept, values as stored (``toarray()`` keeps a stored non-finite value too)."""
+        sorted, stored zeros kept, values as stored (``toarray()`` keeps a stored non-finite value too).  ``by_col``: as
+        canonical CSC instead, from ``tocsc()`` -- the lists a fold-in whose target is the column type hands over."""
         from .._engine import KnownEntries
         import scipy.sparse
+        if by_col:
+            csc = scipy.sparse.csc_matrix(self.data, dtype=np.float64, copy=True)
+            csc.sum_duplicates()
+            csc.sort_indices()
+            return KnownEntries(csc.indptr, csc.indices, csc.data, csc.shape, unstored='zero', by_col=True)
         csr = scipy.sparse.csr_matrix(self.data, dtype=np.float64, copy=True)
         csr.sum_duplicates()
         csr.sort_indices()
