@@ -443,6 +443,38 @@ int skf_to_bf16(void* dst, int64_t ldd, int32_t src_dtype, const void* src, int6
 int skf_fold_lists(int32_t dtype, const int64_t* indptr, const int32_t* indices, const void* values, int64_t n_out,
                    const void* T, int64_t ldt, int32_t c, void* Ec, int64_t lde, void* Dc, int64_t ldd, void* stream);
 
+/* The k best columns of every row of X = H Gc^T, H = G_row[rows] S (m x c, formed by the caller with skf_gemm), Gc = G_col
+ * (n_cols x c), without X: the reference materialises X on the host (fusion/base/base.py `complete`: np.dot(G1, np.dot(S,
+ * G2.T))) and its users rank or index that array (examples/movielens_completion.py:121-126).  Score tiles are formed on the
+ * matrix cores and selected on the compute unit; nothing of size m x n_cols is written anywhere.
+ *   Order: higher score first, equal scores by lower column; a NaN score is never selected.  score(r, j) is summed in the
+ *     same order whatever the tile, col_splits or launch geometry: the output is bit-identical for every col_splits.
+ *   Exclusion (optional; both pointers NULL = none): CSR over the m rows, excl_indptr[m + 1] (int64, from 0, non-decreasing;
+ *     excl_indptr[m] is the number of entries), excl_indices (int32 columns, in range, strictly ascending within a row).  A
+ *     listed column is never a candidate.  The lists are validated on the device before the pass; an invalid list is refused
+ *     (SKF_E_INVALID, outputs not written), not read out of bounds.
+ *   Output: out_idx[r * ld_idx + s] (int32) and out_val[r * ld_val + s] (dtype), s < k, best first; slots no candidate fills
+ *     hold -1 and -inf.
+ *   col_splits: the column range is cut into that many parts (each a whole number of 64-column tiles, at most 32 parts and
+ *     never more than there are tiles), one workgroup per (64 rows, part), merged by a second kernel under the same order;
+ *     0 = the library chooses (few rows still fill the chip).  skf_complete_topk_workspace_bytes with the same m, n_cols, k
+ *     and col_splits sizes the workspace (256-byte aligned; 0 sizes for what the launch will choose).
+ *   dtype SKF_F64 / SKF_F32 (the type of H, Gc and out_val); 1 <= c <= 1024, 1 <= k <= SKF_TOPK_MAX, m and n_cols < 2^31. */
+#define SKF_TOPK_MAX 64
+int skf_complete_topk_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int32_t k, int32_t col_splits, size_t* bytes);
+int skf_complete_topk(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols,
+                      int32_t c, int32_t k, const int64_t* excl_indptr, const int32_t* excl_indices,
+                      int32_t* out_idx, int64_t ld_idx, void* out_val, int64_t ld_val,
+                      int32_t col_splits /* 0 = choose */, void* workspace, size_t workspace_bytes, void* stream);
+
+/* out[e] = sum over q < c of H[rows[e]][q] * Gc[cols[e]][q] for e < n: the predictions at given pairs (what the reference
+ * reads as R12_pred[hidden] from the dense product, examples/movielens_completion.py:121-126).  rows (int32, into the m rows
+ * of H) and cols (int32, into the n_cols rows of Gc) are checked on the device before the pass: an index out of range gives
+ * SKF_E_INVALID and leaves out as it was.  16 adjacent lanes share an entry and fold their partial sums in a fixed order:
+ * two runs give the same bits.  dtype SKF_F64 / SKF_F32; 1 <= c <= 1024. */
+int skf_complete_entries(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols,
+                         int32_t c, const int32_t* rows, const int32_t* cols, int64_t n, void* out, void* stream);
+
 /* K = pinv(A) for symmetric A (n x n): f64 Jacobi eigen-decomposition + the singular-value
  * cut-off of scipy.linalg.pinv (reference _dfmf.py:232, _dfmc.py:307). */
 int skf_pinv_sym_workspace_bytes(int32_t n, size_t* bytes);
@@ -491,7 +523,8 @@ const char* skf_version(void);
 /* Layout version of the structs and signatures above (SKF_ABI_VERSION).  A binding built against another version must not
  * call the library: descriptors grew between versions (skf_relation_desc.known_bound: 3, skf_options.flags: 4; version 5
  * adds entry points only -- skf_small_graph_limits, skf_comm_info, skf_launch_count; later: skf_fold_lists and the flag
- * SKF_REL_FOLD_CSR -- the structs are those of version 4). */
+ * SKF_REL_FOLD_CSR; skf_complete_topk_workspace_bytes, skf_complete_topk, skf_complete_entries and SKF_TOPK_MAX -- the
+ * structs are those of version 4). */
 #define SKF_ABI_VERSION 5
 int skf_abi_version(void);
 

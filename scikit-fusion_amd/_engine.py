@@ -1167,3 +1167,147 @@ def chain_backbone(backbones, runtime=None):
 def device_reconstruct(G_row_block, S, G_col, dtype='f64', runtime=None):
     """One block (S and G_col uploaded for this call only; `DeviceReconstructor` keeps them resident)."""
     return DeviceReconstructor(S, G_col, dtype, runtime).block(G_row_block)
+
+
+class DeviceCompleter(object):
+    """The consuming side of a completion model without the dense reconstruction: for ``X = G_row S G_col^T`` the ``k`` best
+    columns of every row (``topk``) and the predictions at given pairs (``entries``), both on the device
+    (csrc/skf_complete.h).  The reference forms ``X`` on the host (fusion/base/base.py ``complete``) and its users rank or
+    index that array (examples/movielens_completion.py:121-126).  ``S`` and ``G_col`` are uploaded ONCE and stay resident
+    across blocks (the contract of ``DeviceReconstructor``); per block only ``H = G_row[block] S`` (``skf_gemm``), the
+    block's exclusion lists, its outputs and the partial lists of the column splits live in HBM -- never anything of size
+    ``n_i x n_j``.  ``dtype`` 'bf16' scores in f32 on the f32 masters, as ``DeviceReconstructor`` does.  A fold-in user
+    passes ``transformer.factor(target)`` as the row factor."""
+
+    ENTRY_CHUNK = 1 << 22                # entries per skf_complete_entries call
+
+    def __init__(self, S, G_col, dtype='f64', runtime=None):
+        self.rt = runtime or nat.get_runtime()
+        code = nat.DTYPES[dtype]
+        self.code = nat.SKF_F32 if code == nat.SKF_BF16 else code
+        self.npd = nat.NP_DTYPE[self.code]
+        self.es = np.dtype(self.npd).itemsize
+        Sm = np.ascontiguousarray(S, dtype=self.npd)
+        B = np.ascontiguousarray(G_col, dtype=self.npd)
+        if Sm.ndim != 2 or B.ndim != 2 or B.shape[1] != Sm.shape[1]:
+            raise ValueError('shape mismatch in completion')
+        self.ci, self.cj = Sm.shape
+        self.nj = B.shape[0]
+        self.s = self.rt.mem.from_host(Sm)
+        self.b = self.rt.mem.from_host(B)
+        self.uploads = 2                 # H2D copies of S / G_col so far (does not grow with the block count)
+        self._bufs = {}                  # name -> scratch Buffer, grown to the largest block seen, then reused
+        self._transient = 0              # bytes of the current call's uploads (row block, exclusion lists, pairs)
+        self.peak_bytes = 0              # largest device_bytes at a launch so far
+
+    @property
+    def device_bytes(self):
+        """Everything this completer currently holds in HBM: the resident factors, the scratch of the largest block seen
+        and the uploads of the call in flight."""
+        return self.s.nbytes + self.b.nbytes + sum(b.nbytes for b in self._bufs.values()) + self._transient
+
+    def _scratch(self, name, nbytes):
+        have = self._bufs.get(name)
+        if have is None or have.nbytes < nbytes:
+            self._bufs[name] = have = self.rt.mem.empty(nbytes)
+        return have
+
+    def _upload(self, arrays):
+        bufs = [self.rt.mem.from_host(a if a.size else np.zeros(1, dtype=a.dtype), sync=False) for a in arrays]
+        self.rt.mem.synchronize()
+        self._transient = sum(b.nbytes for b in bufs)
+        return bufs
+
+    def _h(self, A):
+        """H = A S into the scratch (m x c_j, master type); returns its Buffer."""
+        m = A.shape[0]
+        (a,) = self._upload([A])
+        h = self._scratch('h', max(m, 1) * self.cj * self.es)
+        if m:
+            _device_gemm(self.rt, self.code, a.ptr, self.ci, 1, self.s.ptr, self.cj, 1, h.ptr, self.cj, m, self.cj, self.ci)
+        return h, a
+
+    def _rows_of(self, G_row_block):
+        A = np.ascontiguousarray(G_row_block, dtype=self.npd)
+        if A.ndim != 2 or A.shape[1] != self.ci:
+            raise ValueError('shape mismatch in completion')
+        return A
+
+    def topk(self, G_row_block, k, exclude=None, col_splits=0):
+        """``(idx int32 [m, k], val float64 [m, k])``: per row of the block the ``k`` best columns, best first -- higher
+        score first, equal scores by lower column, NaN never; slots no candidate fills hold ``-1`` / ``-inf``.
+        ``exclude = (indptr, indices)``: CSR over the rows of THIS block (columns strictly ascending within a row) of the
+        columns that are no candidates; validated on the device.  ``col_splits`` 0 lets the library choose; the result
+        does not depend on it."""
+        A = self._rows_of(G_row_block)
+        m, k = A.shape[0], int(k)
+        rt, mem = self.rt, self.rt.mem
+        need = C.c_size_t()
+        rt.call('skf_complete_topk_workspace_bytes', self.code, m, self.nj, k, int(col_splits), C.byref(need))
+        if m == 0:
+            return np.zeros((0, k), dtype=np.int32), np.zeros((0, k), dtype=np.float64)
+        xp = xi = None
+        keep = []
+        if exclude is not None:
+            indptr = np.ascontiguousarray(exclude[0], dtype=np.int64)
+            indices = np.ascontiguousarray(exclude[1], dtype=np.int32)
+            if indptr.shape != (m + 1,):
+                raise ValueError('exclude: indptr must have one entry per row of the block, plus one')
+            keep = [indptr, indices]
+        h, a = self._h(A)
+        held = self._transient
+        if keep:
+            xp, xi = self._upload(keep)
+            self._transient += held
+        ws = self._scratch('ws', need.value)
+        oi = self._scratch('idx', m * k * 4)
+        ov = self._scratch('val', m * k * self.es)
+        self.peak_bytes = max(self.peak_bytes, self.device_bytes)
+        try:
+            rt.call('skf_complete_topk', self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, k,
+                    xp.ptr if xp else None, xi.ptr if xi else None, oi.ptr, k, ov.ptr, k, int(col_splits), ws.ptr, ws.nbytes,
+                    mem.stream)
+            mem.synchronize()
+            return mem.to_host(oi, (m, k), np.int32), mem.to_host(ov, (m, k), self.npd).astype(np.float64)
+        finally:
+            del a, xp, xi
+            self._transient = 0
+
+    def entries(self, G_row, rows, cols):
+        """``float64 [n]``: ``X[rows[e], cols[e]]``.  Only the DISTINCT rows of ``G_row`` that ``rows`` names are uploaded
+        (remapped); the pairs go through in chunks of ``ENTRY_CHUNK``, so ``n`` has no limit."""
+        rows = np.asarray(rows).reshape(-1)
+        cols = np.asarray(cols).reshape(-1)
+        if rows.shape != cols.shape:
+            raise ValueError('rows and cols must have the same length')
+        G_row = np.asarray(G_row)
+        if G_row.ndim != 2 or G_row.shape[1] != self.ci:
+            raise ValueError('shape mismatch in completion')
+        out = np.empty(rows.size, dtype=np.float64)
+        if rows.size == 0:
+            return out
+        if rows.min() < 0 or rows.max() >= G_row.shape[0]:
+            raise ValueError('a row index is outside the row factor')
+        if cols.min() < -2 ** 31 or cols.max() >= 2 ** 31:
+            raise ValueError('a column index is outside the column factor')
+        used, local = np.unique(rows, return_inverse=True)
+        h, a = self._h(self._rows_of(G_row[used]))
+        held = self._transient
+        rt, mem = self.rt, self.rt.mem
+        try:
+            for e0 in range(0, rows.size, self.ENTRY_CHUNK):
+                sl = slice(e0, min(e0 + self.ENTRY_CHUNK, rows.size))
+                n = sl.stop - sl.start
+                br, bc = self._upload([local[sl].astype(np.int32), cols[sl].astype(np.int32)])
+                self._transient += held
+                o = self._scratch('entries', n * self.es)
+                self.peak_bytes = max(self.peak_bytes, self.device_bytes)
+                rt.call('skf_complete_entries', self.code, h.ptr, self.cj, used.size, self.b.ptr, self.cj, self.nj, self.cj,
+                        br.ptr, bc.ptr, n, o.ptr, mem.stream)
+                mem.synchronize()
+                out[sl] = mem.to_host(o, (n,), self.npd)
+                del br, bc
+        finally:
+            del a
+            self._transient = 0
+        return out

@@ -73,6 +73,7 @@ class Options(C.Structure):
 
 
 SKF_OPT_OWNED_ROWS = 1
+SKF_TOPK_MAX = 64            # include/skfusion_hip.h: longest list skf_complete_topk keeps per row
 SKF_ABI_VERSION = 5          # include/skfusion_hip.h: the struct layouts above belong to this version
 
 
@@ -143,6 +144,11 @@ SIGNATURES = {
                                C.c_int32, _P, C.c_size_t, _P]),
     'skf_to_bf16': (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P]),
     'skf_fold_lists': (C.c_int, [C.c_int32, _P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P]),
+    'skf_complete_topk_workspace_bytes': (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    'skf_complete_topk': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P,
+                                    _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_size_t, _P]),
+    'skf_complete_entries': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int64,
+                                       _P, _P]),
     'skf_pinv_sym_workspace_bytes': (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
     'skf_pinv_sym': (C.c_int, [C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_size_t, _P]),
     'skf_fill_uniform': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, C.c_int64, C.c_uint64,

@@ -15,6 +15,7 @@
 #include "skf_kernels.h"
 #include "skf_known.h"
 #include "skf_small.h"
+#include "skf_complete.h"
 // the product build compiles the GEMM-class kernel templates in units of their own, side by side with this file
 // (tools/gen_inst_units.py, __graft_entry__.build); a build of this file alone (emulator, probes) instantiates them here
 #ifdef SKF_SPLIT_BUILD
@@ -1842,6 +1843,168 @@ int skf_fold_lists(int32_t dtype, const int64_t* indptr, const int32_t* indices,
             launch_fold_lists<double>(indptr, (const int*)indices, values, n_out, T, ldt, c, Ec, lde, Dc, ldd, as_stream(stream));
         else
             launch_fold_lists<float>(indptr, (const int*)indices, values, n_out, T, ldt, c, Ec, lde, Dc, ldd, as_stream(stream));
+    });
+}
+
+}  // extern "C"
+
+// ---- top-k completion and entry predictions (skf_complete.h) ---------------------------------------------------------
+static_assert(SKF_TOPK_MAX == SKF_TOPK_MAX_K, "include/skfusion_hip.h and skf_complete.h disagree on the list length");
+
+// The ONE place the column splits of a top-k launch are decided: the workspace query and the launch both call it, so a
+// query with col_splits = 0 sizes for what the launch will choose.  A split is a whole number of 64-column tiles; a chosen
+// count aims at two workgroups per compute unit (256 CUs) and keeps at least four tiles per split, so that the partial
+// lists and their merge stay small next to the pass; a requested count is only clamped to what exists.
+static int topk_col_splits(int64_t m, int64_t n_cols, int want) {
+    const int64_t ntiles = std::max<int64_t>(1, (n_cols + TOPK_BN - 1) / TOPK_BN);
+    const int64_t row_tiles = std::max<int64_t>(1, (m + TOPK_BM - 1) / TOPK_BM);
+    int64_t s = want;
+    if (want <= 0) {
+        s = (512 + row_tiles - 1) / row_tiles;
+        s = std::min<int64_t>(s, std::max<int64_t>(1, ntiles / 4));
+    }
+    s = std::min<int64_t>(std::min<int64_t>(s, TOPK_MAX_SPLITS), ntiles);
+    return (int)std::max<int64_t>(1, s);
+}
+
+// [0, 256): the flag of the exclusion check; then, for more than one split, the partial lists: values [splits][m][k],
+// indices [splits][m][k]
+static size_t topk_workspace(size_t esz, int64_t m, int k, int splits) {
+    size_t b = 256;
+    if (splits > 1) b += align_up((size_t)splits * m * k * esz, 256) + align_up((size_t)splits * m * k * sizeof(int), 256);
+    return b;
+}
+
+static void topk_check_shape(int32_t dtype, int64_t m, int64_t n_cols, int32_t k, int32_t col_splits) {
+    if (dtype != SKF_F64 && dtype != SKF_F32) SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: dtype must be SKF_F64 / SKF_F32");
+    if (k < 1 || k > SKF_TOPK_MAX) SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: k = %d outside 1 .. %d", k, SKF_TOPK_MAX);
+    if (m < 0 || m >= (1LL << 31) || n_cols < 0 || n_cols >= (1LL << 31))
+        SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: m = %lld / n_cols = %lld outside 0 .. 2^31 - 1", (long long)m, (long long)n_cols);
+    if (col_splits < 0) SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: col_splits = %d is negative", col_splits);
+}
+
+template <typename T>
+static void launch_complete_topk(const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int c, int k,
+                                 const int64_t* xptr, const int* xidx, int* out_idx, int64_t ld_idx, void* out_val, int64_t ld_val,
+                                 int splits, char* ws, hipStream_t st) {
+    TopkArgs<T> a;
+    a.H = (const T*)H; a.ldh = ldh; a.m = m;
+    a.Gc = (const T*)Gc; a.ldg = ldg; a.n_cols = n_cols;
+    a.c = c; a.k = k;
+    a.xptr = xptr; a.xidx = xidx;
+    const int64_t ntiles = (n_cols + TOPK_BN - 1) / TOPK_BN;
+    a.tiles_per_split = (int)std::max<int64_t>(1, (ntiles + splits - 1) / splits);
+    a.out_idx = out_idx; a.ld_idx = ld_idx; a.out_val = (T*)out_val; a.ld_val = ld_val;
+    a.part_val = (T*)(ws + 256);
+    a.part_idx = (int*)(ws + 256 + align_up((size_t)splits * m * k * sizeof(T), 256));
+    static DeviceOnce once;
+    allow_dynamic_lds(once, complete_topk_kernel<T>, (int)topk_list_bytes(SKF_TOPK_MAX, sizeof(T)));
+    const int row_tiles = cdiv(m, TOPK_BM);
+    hipLaunchKernelGGL((complete_topk_kernel<T>), dim3(row_tiles, splits), dim3(TOPK_THREADS), topk_list_bytes(k, sizeof(T)), st, a);
+    check_launch("complete_topk");
+    if (splits > 1) {
+        hipLaunchKernelGGL((complete_topk_merge_kernel<T>), dim3(elem_grid(m)), dim3(256), 0, st, a.part_idx, a.part_val, m, k, splits,
+                           out_idx, ld_idx, (T*)out_val, ld_val);
+        check_launch("complete_topk_merge");
+    }
+}
+
+template <typename T>
+static void launch_complete_entries(const void* H, int64_t ldh, const void* Gc, int64_t ldg, int c, const int* rows, const int* cols,
+                                    int64_t n, void* out, hipStream_t st) {
+    const int64_t waves = (n + 3) / 4;                      // four entries per wave and step
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, 4096));
+    hipLaunchKernelGGL((complete_entries_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)H, ldh, (const T*)Gc, ldg, c, rows, cols, n,
+                       (T*)out);
+    check_launch("complete_entries");
+}
+
+extern "C" {
+
+int skf_complete_topk_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int32_t k, int32_t col_splits, size_t* bytes) {
+    return guarded([&] {
+        if (!bytes) SKF_FAIL(SKF_E_INVALID, "null argument");
+        topk_check_shape(dtype, m, n_cols, k, col_splits);
+        *bytes = topk_workspace(dtype == SKF_F64 ? 8 : 4, m, k, topk_col_splits(m, n_cols, col_splits));
+    });
+}
+
+int skf_complete_topk(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int32_t c,
+                      int32_t k, const int64_t* excl_indptr, const int32_t* excl_indices, int32_t* out_idx, int64_t ld_idx,
+                      void* out_val, int64_t ld_val, int32_t col_splits, void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded([&] {
+        topk_check_shape(dtype, m, n_cols, k, col_splits);
+        if (c < 1 || c > 1024) SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: width c = %d outside 1 .. 1024", c);
+        if (!H || !Gc || !out_idx || !out_val) SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: null argument");
+        if ((excl_indptr == nullptr) != (excl_indices == nullptr))
+            SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: excl_indptr and excl_indices come together (both NULL: no exclusion)");
+        if (ldh < c || ldg < c || ld_idx < k || ld_val < k) SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: ld too small");
+        const size_t esz = dtype == SKF_F64 ? 8 : 4;
+        const int splits = topk_col_splits(m, n_cols, col_splits);
+        const size_t need = topk_workspace(esz, m, k, splits);
+        if (!workspace || workspace_bytes < need)
+            SKF_FAIL(SKF_E_WORKSPACE, "skf_complete_topk: workspace %zu B < required %zu B (or null)", workspace ? workspace_bytes : (size_t)0, need);
+        if (((uintptr_t)workspace & 255) != 0) SKF_FAIL(SKF_E_WORKSPACE, "skf_complete_topk: workspace must be 256-byte aligned");
+        if (m == 0) return;
+        hipStream_t st = as_stream(stream);
+        if (excl_indptr) {
+            // the number of entries is the list's own last pointer; everything else is checked against it on the device
+            // before anything walks the lists
+            int64_t nnz = -1;
+            SKF_HIP(hipMemcpyAsync(&nnz, excl_indptr + m, sizeof nnz, hipMemcpyDeviceToHost, st));
+            SKF_HIP(hipStreamSynchronize(st));
+            int bad = nnz < 0 ? 1 : 0;
+            if (!bad) {
+                int* flag = (int*)workspace;
+                SKF_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
+                const int wgrid = (int)((m + 3) / 4 < 2048 ? (m + 3) / 4 : 2048);
+                hipLaunchKernelGGL(known_csr_check_kernel, dim3(wgrid), dim3(256), 0, st, excl_indptr, (const int*)excl_indices, m, n_cols, nnz, flag);
+                check_launch("known_csr_check");
+                SKF_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+                SKF_HIP(hipStreamSynchronize(st));
+            }
+            if (bad)
+                SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: the exclusion lists are not canonical for %lld rows x %lld columns (indptr from 0 "
+                         "to the count, non-decreasing; indices in range and strictly ascending within a row)", (long long)m, (long long)n_cols);
+        }
+        if (dtype == SKF_F64)
+            launch_complete_topk<double>(H, ldh, m, Gc, ldg, n_cols, c, k, excl_indptr, (const int*)excl_indices, out_idx, ld_idx, out_val,
+                                         ld_val, splits, (char*)workspace, st);
+        else
+            launch_complete_topk<float>(H, ldh, m, Gc, ldg, n_cols, c, k, excl_indptr, (const int*)excl_indices, out_idx, ld_idx, out_val,
+                                        ld_val, splits, (char*)workspace, st);
+    });
+}
+
+int skf_complete_entries(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int32_t c,
+                         const int32_t* rows, const int32_t* cols, int64_t n, void* out, void* stream) {
+    return guarded([&] {
+        if (dtype != SKF_F64 && dtype != SKF_F32) SKF_FAIL(SKF_E_INVALID, "skf_complete_entries: dtype must be SKF_F64 / SKF_F32");
+        if (c < 1 || c > 1024) SKF_FAIL(SKF_E_INVALID, "skf_complete_entries: width c = %d outside 1 .. 1024", c);
+        if (m < 0 || m >= (1LL << 31) || n_cols < 0 || n_cols >= (1LL << 31) || n < 0)
+            SKF_FAIL(SKF_E_INVALID, "skf_complete_entries: m = %lld / n_cols = %lld / n = %lld", (long long)m, (long long)n_cols, (long long)n);
+        if (!H || !Gc || !rows || !cols || !out) SKF_FAIL(SKF_E_INVALID, "skf_complete_entries: null argument");
+        if (ldh < c || ldg < c) SKF_FAIL(SKF_E_INVALID, "skf_complete_entries: ld too small");
+        if (n == 0) return;
+        hipStream_t st = as_stream(stream);
+        // the index check needs one device word and this operator has no workspace: the first word of `out` serves (every
+        // out[e] is overwritten by the pass) and gets its old content back when the entries are refused
+        int keep = 0, bad = 0;
+        int* flag = (int*)out;
+        SKF_HIP(hipMemcpyAsync(&keep, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+        SKF_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
+        hipLaunchKernelGGL(complete_entries_check_kernel, dim3(elem_grid(n)), dim3(256), 0, st, (const int*)rows, (const int*)cols, n, m, n_cols, flag);
+        check_launch("complete_entries_check");
+        SKF_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+        SKF_HIP(hipStreamSynchronize(st));
+        if (bad) {
+            SKF_HIP(hipMemcpyAsync(flag, &keep, sizeof(int), hipMemcpyHostToDevice, st));
+            SKF_HIP(hipStreamSynchronize(st));
+            SKF_FAIL(SKF_E_INVALID, "skf_complete_entries: an entry names a row outside 0 .. %lld or a column outside 0 .. %lld",
+                     (long long)m - 1, (long long)n_cols - 1);
+        }
+        if (dtype == SKF_F64) launch_complete_entries<double>(H, ldh, Gc, ldg, c, (const int*)rows, (const int*)cols, n, out, st);
+        else launch_complete_entries<float>(H, ldh, Gc, ldg, c, (const int*)rows, (const int*)cols, n, out, st);
     });
 }
 

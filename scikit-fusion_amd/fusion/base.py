@@ -220,6 +220,124 @@ class FusionFit(FusionBase):
                 block = relation.postprocessor(block)
             yield sl, block
 
+    # ---- predictions at given pairs and the k best columns of a row, on the device, never densified ----------------------
+    # The reference answers both from the dense product (base.py:119-146; examples/movielens_completion.py:121-126 reads
+    # R12_pred[hidden]); here nothing of size n_i x n_j is formed on the host or in HBM (`_engine.DeviceCompleter`).
+    def _check_relation_types(self, relation):
+        types = self.fusion_graph.object_types
+        if relation.row_type not in types or relation.col_type not in types:
+            raise DataFusionError("Object type %s or %s are not included in the fusion scheme"
+                                  % (relation.row_type.name, relation.col_type.name))
+
+    def _completer(self, relation, run, dtype):
+        from .._engine import DeviceCompleter
+        return (np.asarray(self.factor(relation.row_type, run)),
+                DeviceCompleter(self.backbone(relation, run), self.factor(relation.col_type, run), dtype=dtype))
+
+    def complete_entries(self, relation, rows, cols, run=None, dtype='f64'):
+        """Predictions ``complete(relation)[rows, cols]`` at the given pairs (float64 vector) without the reconstruction:
+        only the distinct rows of the row factor that ``rows`` names go to the device, the pairs in chunks.  The relation's
+        postprocessor is applied to the vector (exact for element-wise postprocessors, as in ``complete_blocks``).  The
+        products run in the master type of ``dtype`` ('f64' | 'f32' | 'bf16' -> f32).  ``n_run > 1`` and ``run=None``: a
+        generator over the runs.  Extension of the reference API."""
+        self._check_relation_types(relation)
+        rows = np.asarray(rows).reshape(-1)
+        cols = np.asarray(cols).reshape(-1)
+        if rows.shape != cols.shape or rows.dtype.kind not in 'iu' or cols.dtype.kind not in 'iu':
+            raise DataFusionError("rows and cols must be integer arrays of one length")
+        n_i, n_j = np.shape(self.factor(relation.row_type, 0))[0], np.shape(self.factor(relation.col_type, 0))[0]
+        if rows.size and (rows.min() < 0 or rows.max() >= n_i or cols.min() < 0 or cols.max() >= n_j):
+            raise DataFusionError("A pair lies outside the %d x %d relation" % (n_i, n_j))
+
+        def one(k):
+            G1, comp = self._completer(relation, k, dtype)
+            out = comp.entries(G1, rows, cols)
+            return relation.postprocessor(out) if relation.postprocessor else out
+        if self.n_run > 1 and run is None:
+            return (one(k) for k in range(self.n_run))
+        return one(0 if run is None else run)
+
+    def _exclusion_lists(self, relation, exclude, shape):
+        """None, or a function ``rows -> (indptr int64, indices int32)``: the excluded columns of the given rows as CSR
+        with strictly ascending columns.  Nothing dense is built beyond a block of a mask the caller already holds."""
+        if exclude is None:
+            return None
+        import scipy.sparse
+        if isinstance(exclude, str):
+            if exclude != 'known':
+                raise DataFusionError("exclude must be None, 'known' or a scipy.sparse matrix, not %r" % (exclude,))
+            data = relation.data
+            if scipy.sparse.issparse(data):
+                exclude = data                      # the stored entries, whatever the unstored ones mean
+            elif np.ma.isMaskedArray(data):
+                mask = np.ma.getmaskarray(data)
+
+                def from_mask(rows):
+                    known = ~mask[rows]
+                    indptr = np.zeros(len(rows) + 1, dtype=np.int64)
+                    np.cumsum(known.sum(axis=1), out=indptr[1:])
+                    return indptr, np.nonzero(known)[1].astype(np.int32)
+                return from_mask
+            else:
+                raise DataFusionError("exclude='known': relation %s -> %s is a plain array, every entry of it is known "
+                                      "(give the excluded pairs as a scipy.sparse matrix)"
+                                      % (relation.row_type.name, relation.col_type.name))
+        if not scipy.sparse.issparse(exclude):
+            raise DataFusionError("exclude must be None, 'known' or a scipy.sparse matrix, not %s" % type(exclude).__name__)
+        if tuple(exclude.shape) != tuple(shape):
+            raise DataFusionError("exclude has shape %r, the relation %r" % (tuple(exclude.shape), tuple(shape)))
+        csr = scipy.sparse.csr_matrix(exclude)      # (duplicates of a COO matrix are summed; stored zeros stay entries)
+        if not csr.has_sorted_indices:
+            csr = csr.sorted_indices()
+
+        def from_csr(rows):
+            sub = csr[rows]
+            if not sub.has_sorted_indices:
+                sub.sort_indices()
+            return sub.indptr.astype(np.int64), sub.indices.astype(np.int32)
+        return from_csr
+
+    def complete_topk(self, relation, k, rows=None, exclude=None, run=None, dtype='f64', block_rows=8192):
+        """``(indices int32 [n, k], scores float64 [n, k])``: for each of ``rows`` (default: every row object; otherwise an
+        integer array, results in that order) the ``k`` columns the model ranks highest, best first -- higher score
+        first, equal scores by lower column index; slots without a candidate hold ``-1`` / ``-inf``.  ``exclude``: None;
+        ``'known'`` -- the relation's own known entries (unmasked entries of a MaskedArray relation, stored entries of a
+        scipy.sparse relation of either ``unstored=`` kind); or a scipy.sparse matrix of the relation's shape whose stored
+        entries are excluded (any format; converted to CSR with sorted indices, never expanded).  Score tiles are formed and
+        selected on the device ``block_rows`` rows at a time; the backbone and the column factor stay resident across the
+        blocks.  A relation with a postprocessor is refused: the ranking is that of the raw scores and a ranking of
+        post-processed values cannot be promised (``complete_blocks(device=True)`` refuses for the same reason).
+        ``1 <= k <= 64``.  ``n_run > 1`` and ``run=None``: a generator over the runs.  Extension of the reference API."""
+        self._check_relation_types(relation)
+        if relation.postprocessor:
+            raise DataFusionError("complete_topk ranks raw device scores; relation %s -> %s has a "
+                                  "postprocessor (rank complete_blocks(device=False) yourself)"
+                                  % (relation.row_type.name, relation.col_type.name))
+        from .._native import SKF_TOPK_MAX
+        k = int(k)
+        if not 1 <= k <= SKF_TOPK_MAX:
+            raise DataFusionError("k = %d outside 1 .. %d" % (k, SKF_TOPK_MAX))
+        n_i, n_j = np.shape(self.factor(relation.row_type, 0))[0], np.shape(self.factor(relation.col_type, 0))[0]
+        if rows is None:
+            rows = np.arange(n_i)
+        rows = np.asarray(rows).reshape(-1)
+        if rows.dtype.kind not in 'iu' or (rows.size and (rows.min() < 0 or rows.max() >= n_i)):
+            raise DataFusionError("rows must be integers in 0 .. %d" % (n_i - 1))
+        lists = self._exclusion_lists(relation, exclude, (n_i, n_j))
+        step = max(1, int(block_rows))
+
+        def one(r):
+            G1, comp = self._completer(relation, r, dtype)
+            idx = np.empty((rows.size, k), dtype=np.int32)
+            val = np.empty((rows.size, k), dtype=np.float64)
+            for b0 in range(0, rows.size, step):
+                blk = rows[b0:b0 + step]
+                idx[b0:b0 + step], val[b0:b0 + step] = comp.topk(G1[blk], k, exclude=lists(blk) if lists else None)
+            return idx, val
+        if self.n_run > 1 and run is None:
+            return (one(r) for r in range(self.n_run))
+        return one(0 if run is None else run)
+
 
 # ---- persistence of a fitted model (SURVEY.md 8 f4; the reference has none: its accessors base.py:35-56,
 # 169-189 are the only consumers of factors_ / backbones_) ----------------------------------------------

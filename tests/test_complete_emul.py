@@ -1,0 +1,64 @@
+"""Top-k completion and entry predictions (csrc/skf_complete.h, skf_complete_topk / skf_complete_entries, DeviceCompleter,
+FusionFit.complete_topk / complete_entries) on the host emulator: the small subset of tests/complete_cases.py -- exact
+lattice cases index for index and bit for bit, the random cases within their derived bound, every refusal, the public API."""
+import ctypes as C
+import os
+
+import pytest
+
+import skfusion_amd._native as nat
+from emul.runtime import emulated_runtime, use_runtime
+
+import complete_cases as CC
+
+
+@pytest.fixture(scope='module', autouse=True)
+def emul():
+    from skfusion_amd._engine import split_clamps
+    with use_runtime(emulated_runtime()) as rt:
+        yield rt
+        assert split_clamps(rt) == 0
+
+
+@pytest.mark.parametrize('ranks', [(5, 1), (5, 7), (64, 65)])
+@pytest.mark.parametrize('n_cols', [7, 203])
+@pytest.mark.parametrize('dtype', ['f64', 'f32'])
+def test_exact_index_for_index_bit_for_bit(dtype, n_cols, ranks):
+    CC.exact_case(dtype, 67, n_cols, ranks)
+
+
+@pytest.mark.parametrize('dtype', ['f64', 'f32'])
+def test_random_within_the_derived_bound(dtype):
+    CC.random_case(dtype, (20, 64), m=67, n_cols=203, label='emulator')
+
+
+def test_bf16_name_scores_on_the_f32_masters():
+    a = CC.random_case('f32', (20, 64), m=67, n_cols=203, pattern='none', label='emulator')
+    b = CC.random_case('bf16', (20, 64), m=67, n_cols=203, pattern='none', label='emulator')
+    for x, y in zip(a, b):
+        assert x.tobytes() == y.tobytes()
+
+
+def test_refusals():
+    CC.refusals_case('f64')
+    CC.refusals_case('f32')
+
+
+def test_refusals_need_no_device():
+    """The product library (cross-compiled for gfx950), no device: these checks answer before any HIP call."""
+    if not os.path.exists(nat.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    lib = nat.load_library()
+    keep = (C.c_uint8 * 4096)()
+    CC.refusals_without_device(lib, C.addressof(keep))
+
+
+@pytest.mark.parametrize('dtype', ['f64', 'f32'])
+@pytest.mark.parametrize('kind', ['dfmc-masked', 'dfmf-csr'])
+def test_public_api(kind, dtype, monkeypatch):
+    CC.api_case(kind, dtype, monkeypatch)
+
+
+def test_public_api_runs():
+    CC.api_runs_case()
