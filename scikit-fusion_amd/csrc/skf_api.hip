@@ -104,6 +104,13 @@ static inline int elem_grid(int64_t total) {
     if (b > 2048) b = 2048;           // grid-stride the rest (256 CUs x 8 blocks)
     return (int)b;
 }
+// one wave per row, four rows per workgroup of 256 threads; the rows past 2048 workgroups by grid stride
+static inline int wave_grid(int64_t rows) {
+    int64_t b = (rows + 3) / 4;
+    if (b < 1) b = 1;
+    if (b > 2048) b = 2048;
+    return (int)b;
+}
 
 #include "skf_gemm_launch.inc"
 
@@ -115,9 +122,654 @@ static inline int elem_grid(int64_t total) {
 
 #include "skf_schedule.inc"
 
+#include "skf_bind.inc"
+
 }  // namespace skf
 
 using namespace skf;
+
+// ---- plan creation, in the order skf_plan_create calls its steps ----------------------------------------------------------
+
+// the options and the object types: sizes, ranks, and the rows of every type this process holds
+static void plan_describe_types(skf_plan* p, int32_t n_types, const skf_type_desc* types, const skf_options* opt) {
+    p->dtype = opt->dtype;
+    p->variant = opt->variant;
+    p->engine = opt->engine;
+    p->f64 = (opt->dtype == SKF_F64);
+    p->bf16 = (opt->dtype == SKF_BF16);
+    p->esz = p->f64 ? 8 : 4;
+    p->mt = p->f64 ? SKF_F64 : SKF_F32;
+    p->target = opt->target_type;
+    if (p->variant == SKF_TRANSFORM && (p->target < 0 || p->target >= n_types))
+        SKF_FAIL(SKF_E_INVALID, "target type %d out of range", p->target);
+    p->types.resize(n_types);
+    for (int i = 0; i < n_types; ++i) {
+        if (types[i].n_obj <= 0 || types[i].rank <= 0 || types[i].rank > EIGH_MAXN - 1)
+            SKF_FAIL(SKF_E_INVALID, "object type %d: n_obj=%lld rank=%d invalid", i, (long long)types[i].n_obj,
+                     types[i].rank);
+        if (types[i].n_obj > 2000000000LL) SKF_FAIL(SKF_E_INVALID, "object type %d too large", i);
+        p->types[i].n = types[i].n_obj;
+        p->types[i].c = types[i].rank;
+        p->types[i].n_pad = (types[i].rank + 1) / 2 * 2;
+        p->types[i].t0 = 0;
+        p->types[i].tn = types[i].n_obj;
+        p->types[i].n_alloc = types[i].n_obj;
+        if (opt->flags & SKF_OPT_OWNED_ROWS) {      // the rows this process owns (skf_owned_rows)
+            if (opt->part_count < 1 || opt->part_index < 0 || opt->part_index >= opt->part_count)
+                SKF_FAIL(SKF_E_INVALID, "SKF_OPT_OWNED_ROWS: part_index %d outside [0, %d)", opt->part_index, opt->part_count);
+            const int64_t ch = owned_chunk(opt->dtype, types[i].n_obj, opt->part_count);
+            int64_t lo = ch * opt->part_index, hi = lo + ch;
+            if (lo > types[i].n_obj) lo = types[i].n_obj;
+            if (hi > types[i].n_obj) hi = types[i].n_obj;
+            p->types[i].t0 = lo;
+            p->types[i].tn = hi - lo;
+            p->types[i].chunk = ch;
+            p->types[i].n_alloc = ch * opt->part_count;
+        } else if (opt->part_count > 1) {      // even shares of the rows, boundaries at multiples of 64
+            if (opt->part_index < 0 || opt->part_index >= opt->part_count)
+                SKF_FAIL(SKF_E_INVALID, "part_index %d outside [0, %d)", opt->part_index, opt->part_count);
+            const int64_t per = (types[i].n_obj + opt->part_count - 1) / opt->part_count;
+            const int64_t step = (per + 63) / 64 * 64;
+            int64_t lo = step * opt->part_index, hi = lo + step;
+            if (lo > types[i].n_obj) lo = types[i].n_obj;
+            if (hi > types[i].n_obj) hi = types[i].n_obj;
+            p->types[i].t0 = lo;
+            p->types[i].tn = hi - lo;
+        }
+    }
+    if (opt->part_count > 1) p->sliced = true;
+    if (opt->flags & SKF_OPT_OWNED_ROWS) {
+        if (p->variant == SKF_TRANSFORM) SKF_FAIL(SKF_E_INVALID, "SKF_OPT_OWNED_ROWS is for SKF_DFMF / SKF_DFMC plans");
+        p->owned = p->sliced = true;
+        p->part_index = opt->part_index;
+        p->part_count = opt->part_count;
+    }
+}
+
+// the relations: which form each one comes in, and whether that form goes with the plan
+static void plan_describe_relations(skf_plan* p, int32_t n_types, int32_t n_relations, const skf_relation_desc* relations) {
+    p->rels.resize(n_relations);
+    for (int r = 0; r < n_relations; ++r) {
+        const skf_relation_desc& d = relations[r];
+        if (d.row_type < 0 || d.row_type >= n_types || d.col_type < 0 || d.col_type >= n_types)
+            SKF_FAIL(SKF_E_INVALID, "relation %d: type index out of range", r);
+        if (d.row_type == d.col_type) SKF_FAIL(SKF_E_INVALID, "relation %d: row type == column type (pass it as a constraint)", r);
+        const bool absent = (d.flags & SKF_REL_ABSENT) != 0;
+        const bool csr = (d.flags & SKF_REL_KNOWN_CSR) != 0;
+        if (csr && p->variant != SKF_DFMC) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR needs SKF_DFMC", r);
+        if (csr && (d.data || d.mask)) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR takes no data / mask", r);
+        const bool sp0 = (d.flags & SKF_REL_SPARSE_CSR) != 0;      // the stored entries as CSR, every other entry zero
+        if (sp0 && csr) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR and SKF_REL_SPARSE_CSR exclude each other", r);
+        if (sp0 && p->variant == SKF_TRANSFORM) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_SPARSE_CSR is for SKF_DFMF / SKF_DFMC plans", r);
+        if (sp0 && (d.data || d.mask || (d.flags & (SKF_REL_MASKED | SKF_REL_MASK_BITS))))
+            SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_SPARSE_CSR takes no data / mask", r);
+        const bool fold = (d.flags & SKF_REL_FOLD_CSR) != 0;      // fold-in: the stored entries compressed along the target's side
+        if (fold && p->variant != SKF_TRANSFORM) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR is for SKF_TRANSFORM plans", r);
+        if (fold && (csr || sp0))
+            SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR excludes SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR", r);
+        if (fold && (d.data || d.mask || (d.flags & (SKF_REL_MASKED | SKF_REL_MASK_BITS))))
+            SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR takes no data / mask", r);
+        if (!absent && !csr && !sp0 && !fold && (!d.data || d.ld < p->types[d.col_type].n))
+            SKF_FAIL(SKF_E_INVALID, "relation %d: dimension mismatch (ld %lld < %lld columns)", r, (long long)d.ld,
+                     (long long)p->types[d.col_type].n);
+        const int64_t n_row_type = p->types[d.row_type].n;
+        if (d.row_begin < 0 || d.n_rows < 0 || d.row_begin + d.n_rows > n_row_type)
+            SKF_FAIL(SKF_E_INVALID, "relation %d: row block [%lld, +%lld) outside the %lld objects of its row type",
+                     r, (long long)d.row_begin, (long long)d.n_rows, (long long)n_row_type);
+        const bool block = absent || (d.n_rows > 0 && d.n_rows < n_row_type) || (d.flags & SKF_REL_NO_COL_SIDE);
+        if (block && (csr || sp0)) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR relations are whole relations", r);
+        if (block && fold) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR relations are whole relations", r);
+        if (block && p->variant == SKF_TRANSFORM)
+            SKF_FAIL(SKF_E_INVALID, "relation %d: row blocks are for SKF_DFMF / SKF_DFMC plans", r);
+        if (block && p->bf16 && d.row_begin % 64 != 0)
+            SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_BF16 row blocks must start at a multiple of 64", r);
+        if (block) p->sliced = true;
+        if ((d.mask || (d.flags & SKF_REL_MASKED)) && p->variant != SKF_DFMC)
+            SKF_FAIL(SKF_E_INVALID, "relation %d: masks need SKF_DFMC", r);
+        if (d.mask && d.mask_ld < ((d.flags & SKF_REL_MASK_BITS) ? (p->types[d.col_type].n + 7) / 8 : p->types[d.col_type].n))
+            SKF_FAIL(SKF_E_INVALID, "relation %d: mask ld", r);
+        if (p->variant == SKF_TRANSFORM && d.row_type != p->target && d.col_type != p->target)
+            SKF_FAIL(SKF_E_INVALID, "relation %d must include the target object type", r);
+        RelState& s = p->rels[r];
+        s.row = d.row_type; s.col = d.col_type;
+        s.R_in = d.data; s.ld_in = d.ld; s.mask = d.mask; s.ldmask = d.mask_ld;
+        s.mask_is_bits = (d.flags & SKF_REL_MASK_BITS) != 0;
+        s.binary = p->bf16 && (d.flags & SKF_REL_BINARY) != 0 && !d.mask && !absent;
+        s.R = d.data; s.ldr = d.ld;
+        s.absent = absent;
+        s.r0 = absent ? 0 : d.row_begin;
+        s.nr = absent ? 0 : (d.n_rows > 0 ? d.n_rows : n_row_type - d.row_begin);
+        s.col_side = (d.flags & SKF_REL_NO_COL_SIDE) == 0;
+        s.masked = d.mask != nullptr || (d.flags & SKF_REL_MASKED) != 0;
+        if (absent) { s.R_in = s.R = nullptr; s.mask = nullptr; }
+        if (p->owned) {         // the block of a relation is the owned range of its row type, nothing else
+            const TypeState& ti = p->types[d.row_type];
+            if (ti.tn == 0 ? !absent : (absent || s.r0 != ti.t0 || s.nr != ti.tn))
+                SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_OPT_OWNED_ROWS wants the rows [%lld, +%lld) of its row type here (skf_owned_rows)",
+                         r, (long long)ti.t0, (long long)ti.tn);
+            s.col_side = true;  // every process adds the column-side terms of ITS rows of the column type
+        }
+        if (d.known_bound < 0) SKF_FAIL(SKF_E_INVALID, "relation %d: negative bound on the known entries", r);
+        s.kn_cap = (s.mask && p->variant == SKF_DFMC) ? d.known_bound : 0;
+        if (csr) {                  // the known entries as CSR (skf_plan_set_known_entries): no dense form, no mask
+            s.kn_csr = s.masked = true;
+            s.R_in = s.R = nullptr;
+            s.kn_cap = d.known_bound;
+        }
+        if (sp0) {                  // the stored entries as CSR (skf_plan_set_known_entries): no dense form in any type
+            s.sp0 = true;
+            s.binary = false;
+            s.R_in = s.R = nullptr;
+            s.kn_cap = d.known_bound;
+        }
+        if (fold) {                 // one set of lists along the target (skf_plan_set_known_entries): no dense form, no P / Q
+            if (p->types[d.row_type].c > 1024 || p->types[d.col_type].c > 1024 || d.known_bound > 2000000000LL)
+                SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR beyond the list limits (a rank above 1024 or %lld > 2e9 entries)",
+                         r, (long long)d.known_bound);
+            s.fold = true;
+            s.binary = false;
+            s.R_in = s.R = nullptr;
+            s.kn_cap = d.known_bound;
+        }
+    }
+}
+
+// masked relations with few known entries are kept as lists of those entries (skf_known.h).  The three passes over the
+// lists gather rank_row-wide vectors -- ~70 ps per entry at rank 128 against ~2.2 ps per CELL for the four passes of
+// the dense path over the completed relation (config 5, bf16) -- hence: known share * rank_row <= 4 (1/32 at rank
+// 128).  SKF_DFMC_SPARSE=0: never; =1: whenever a bound is given (up to a quarter of the relation).  Plans with row
+// blocks keep the dense form.
+static void plan_decide_lists(skf_plan* p, const skf_relation_desc* relations) {
+    const Switches sw0 = Switches::read();          // (plan creation: the plan's own copy is read when its workspace is bound)
+    const int mode = sw0.dfmc_sparse;
+    // Parts of the lists (skf_known.h): with srp_bf16_v6_kernel the passes are no longer bound by instruction issue and
+    // pinning slices of the gathered matrix to XCDs pays (profiles/r03_srp_v6.txt: 25.6 MB of user factors, 8 parts:
+    // 1.75 -> 1.10 ms; 10 MB, 4 parts: 1.41 -> 1.25 ms) -- the smallest power of two that brings a slice under the
+    // 4 MiB L2 of an XCD, as long as a segment still holds a batch of entries.  Other engines / widths: 1 (their
+    // kernels are issue-bound; measured neutral in round 3).  SKF_KNOWN_PARTS=1|2|4|8 overrides.
+    const int parts_env = sw0.known_parts;
+    auto pick_parts = [&](int64_t n_in, int64_t n_out, int ci, int64_t cap) {
+        if (parts_env) return parts_env;
+        if (!p->bf16 || (ci != 128 && ci != 256)) return 1;
+        int q = 1;
+        while (q < 8 && (double)n_in * ci * 2.0 / q > 3.5 * 1048576.0) q *= 2;
+        while (q > 1 && (double)cap / ((double)n_out * q) < 64.0) q /= 2;
+        return q;
+    };
+    // the parts of a relation's lists: the row lists gather vectors of c_rl numbers of the column objects, the column lists
+    // vectors of c_cl numbers of the row objects; a part covers whole blocks of 64 objects of the gathered side
+    auto set_parts = [&](RelState& s, int c_rl, int c_cl) {
+        const int64_t cols = p->types[s.col].n;
+        s.kn_pc = pick_parts(cols, s.nr, c_rl, s.kn_cap);
+        s.kn_pr = pick_parts(s.nr, cols, c_cl, s.kn_cap);
+        s.kn_pw = ((cols + s.kn_pc - 1) / s.kn_pc + 63) / 64 * 64;
+        s.kn_ph = ((s.nr + s.kn_pr - 1) / s.kn_pr + 63) / 64 * 64;
+    };
+    for (size_t rk = 0; rk < p->rels.size(); ++rk) {
+        RelState& s = p->rels[rk];
+        const int ci = p->types[s.row].c;
+        if (s.fold) continue;               // (one set of lists as handed over: no parts, nothing decided here)
+        if (s.sp0) {
+            // valued lists whatever the density (the caller chose the form; no dense one to fall back on).  P gathers
+            // rank_col-wide rows of G_j through the row lists, Q rank_row-wide rows of G_i through the column lists
+            const int cj = p->types[s.col].c;
+            if (p->sliced) SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_SPARSE_CSR is for plans of whole relations", rk);
+            if (ci > 64 * SRP_MAXREP || cj > 64 * SRP_MAXREP || s.kn_cap > 2000000000LL)
+                SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_SPARSE_CSR beyond the list limits (a rank above %d or %lld > 2e9 entries)",
+                         rk, 64 * SRP_MAXREP, (long long)s.kn_cap);
+            set_parts(s, cj, ci);
+            if (p->bf16) p->types[s.row].need_rows = p->types[s.col].need_rows = true;
+            continue;
+        }
+        if (s.kn_csr) {
+            // lists whatever the share (no dense form to fall back on); the parts below follow from the exact count
+            if (p->sliced) SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_KNOWN_CSR is for plans of whole relations", rk);
+            if (ci > 64 * SRP_MAXREP || s.kn_cap > 2000000000LL)
+                SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_KNOWN_CSR beyond the list limits (rank %d > %d or %lld > 2e9 entries)",
+                         rk, ci, 64 * SRP_MAXREP, (long long)s.kn_cap);
+        } else if (p->owned) {
+            // ownership-aligned row blocks: the caller decided for ALL processes alike (SKF_REL_KNOWN_LISTS); a process
+            // without rows of the relation keeps the flag -- it adds the dense part of Q on ITS rows of the column type
+            const bool lists = (relations[rk].flags & SKF_REL_KNOWN_LISTS) != 0 && s.masked && p->variant == SKF_DFMC;
+            if (lists && (ci > 64 * SRP_MAXREP || s.kn_cap > 2000000000LL || (!s.absent && s.kn_cap <= 0)))
+                SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_KNOWN_LISTS needs a bound on the known entries of the local rows", rk);
+            if (!lists) {
+                s.kn_cap = 0;
+                continue;
+            }
+        } else {
+            if (s.kn_cap <= 0) continue;
+            const double cells = (double)s.nr * (double)p->types[s.col].n;
+            const double share = cells > 0 ? (double)s.kn_cap / cells : 1.0;
+            if (p->sliced || mode == 0 || share > 0.25 || (mode != 1 && share * ci > 4.0) || ci > 64 * SRP_MAXREP ||
+                s.kn_cap > 2000000000LL) {
+                s.kn_cap = 0;
+                continue;
+            }
+        }
+        s.kn = true;
+        if (s.absent) continue;             // (no lists here: only the flag)
+        set_parts(s, ci, ci);               // (both sides gather rank_row-wide vectors: T = G_j S^T and G_i)
+        p->types[s.row].keep_prev = p->types[s.col].keep_prev = true;
+        if (p->bf16) p->types[s.row].need_rows = true;              // the column lists gather the row type's bf16 rows
+    }
+    // sparse 0/1 relations as lists over bf16 factor rows (srp_bf16_v6_kernel<.., SRP_ONES>): both ranks 64 / 128 / 256
+    auto gather_rank = [](int c) { return c == 64 || c == 128 || c == 256; };
+    for (RelState& s : p->rels) {
+        s.sp_gather = p->bf16 && s.binary && !s.masked && !s.absent && gather_rank(p->types[s.row].c) &&
+                      gather_rank(p->types[s.col].c);
+        if (!s.sp_gather) continue;
+        p->types[s.row].need_rows = p->types[s.col].need_rows = true;
+        // parts by the size of the gathered matrix alone (the number of ones is known at bind time, which may lower them)
+        auto by_bytes = [&](int64_t n_in, int c) {
+            if (parts_env) return parts_env;
+            int q = 1;
+            while (q < 8 && (double)n_in * c * 2.0 / q > 3.5 * 1048576.0) q *= 2;
+            return q;
+        };
+        s.sp_pc = by_bytes(p->types[s.col].n, p->types[s.col].c);    // P: rows of G_j by the column index
+        s.sp_pr = by_bytes(p->types[s.row].n, p->types[s.row].c);    // Q: rows of G_i by the row index
+    }
+}
+
+// the constraints, and what the owners of rows keep of the other owners' factors
+static void plan_describe_constraints(skf_plan* p, int32_t n_types, int32_t n_thetas, const skf_theta_desc* thetas) {
+    p->thetas.resize(n_thetas);
+    for (int t = 0; t < n_thetas; ++t) {
+        if (thetas[t].type < 0 || thetas[t].type >= n_types || !thetas[t].data ||
+            thetas[t].ld < p->types[thetas[t].type].n)
+            SKF_FAIL(SKF_E_INVALID, "constraint %d invalid", t);
+        if (p->variant == SKF_TRANSFORM && thetas[t].type != p->target)
+            SKF_FAIL(SKF_E_INVALID, "constraint %d must be on the target object type", t);
+        p->thetas[t].type = thetas[t].type;
+        p->thetas[t].data = thetas[t].data;
+        p->thetas[t].ld = thetas[t].ld;
+        const int64_t nn = p->types[thetas[t].type].n;
+        if (thetas[t].nnz < 0) SKF_FAIL(SKF_E_INVALID, "constraint %d: negative non-zero bound", t);
+        if (thetas[t].nnz > 0 && thetas[t].nnz <= nn * nn / SKF_THETA_SPARSE_DIV) {
+            p->thetas[t].sparse = true;
+            p->thetas[t].nnz_cap = thetas[t].nnz;
+        }
+    }
+    if (p->owned) {
+        // SKF_BF16: the other owners' rows of a factor are read as bf16 operands only -- unless a constraint on the type
+        // multiplies the f32 rows (theta_spmm_kernel / dense Theta).  Every type keeps its bf16 rows (the gathered form).
+        for (TypeState& t : p->types) {
+            t.gather_master = !p->bf16;
+            if (p->bf16) t.need_rows = true;
+        }
+        for (const ThetaState& th : p->thetas) p->types[th.type].gather_master = true;
+        // ... and the types of a masked relation (the same on every process, whatever it holds of the relation): the
+        // known-entry form multiplies the f32 rows of both factors (cross-Gram matrices, T = G_j S^T, the dense part of Q)
+        for (const RelState& r : p->rels)
+            if (r.masked) p->types[r.row].gather_master = p->types[r.col].gather_master = true;
+    }
+}
+
+// small graphs: every rank <= 64, sparse constraints only, a few thousand objects per type -> the fused schedule
+static void plan_layout_small_graph(skf_plan* p) {
+    const int n_types = (int)p->types.size(), n_relations = (int)p->rels.size(), n_thetas = (int)p->thetas.size();
+    const size_t es = p->esz;
+    bool ok = p->variant == SKF_DFMF && p->engine == SKF_ENGINE_MFMA && !p->bf16 && !p->sliced && n_types <= SM_MAXT &&
+              n_relations >= 1 && n_relations <= SM_MAXR && n_thetas <= SM_MAXTH;
+    // (object counts: the Q shares of the schedule grow with n_i / 256 * n_j * c_i, and from a few thousand objects
+    // on the relation contractions are worth the big tiles of the general schedule)
+    for (const TypeState& t : p->types) ok = ok && t.c <= SMALLC && t.n <= SM_MAX_OBJECTS;
+    for (const ThetaState& th : p->thetas) ok = ok && th.sparse;
+    for (const RelState& r : p->rels) ok = ok && !r.absent && !r.masked && !r.sp0;
+    p->small_fused = ok;
+    if (ok) {
+        size_t wdoubles = 0, gdoubles = 0;
+        for (size_t k = 0; k < p->rels.size(); ++k) {
+            RelState& r = p->rels[k];
+            const TypeState& ti = p->types[r.row];
+            const TypeState& tj = p->types[r.col];
+            int part = 0;
+            for (int64_t r0 = 0; r0 < ti.n; r0 += 64) p->sm_j1.push_back(SmJob{SMJ_P, (int)k, (int)r0, (int)std::min<int64_t>(64, ti.n - r0), part++, 0, 0, 0});
+            // Q = R^T G_i: a long inner dimension (the rows of the relation) over a small output -> shares of SM_QROWS rows
+            int qpart = 0;
+            for (int64_t k0 = 0; k0 < ti.n; k0 += SM_QROWS, ++qpart)
+                for (int64_t c0 = 0; c0 < tj.n; c0 += 64)
+                    p->sm_j1.push_back(SmJob{SMJ_Q, (int)k, (int)c0, (int)std::min<int64_t>(64, tj.n - c0), qpart, (int)k0,
+                                             (int)std::min<int64_t>(SM_QROWS, ti.n - k0), 0});
+            r.sm_qparts = qpart;
+            wdoubles += align_up((size_t)part * ti.c * tj.c, 16);      // (shares of different relations / types never share a cache line)
+            add_slot(p, r.SmQ, (size_t)qpart * tj.n * ti.c * es);
+            add_slot(p, r.SmBp, (size_t)ti.c * ti.c * 8);
+            add_slot(p, r.SmBn, (size_t)ti.c * ti.c * 8);
+            add_slot(p, r.SmDp, (size_t)tj.c * tj.c * 8);
+            add_slot(p, r.SmDn, (size_t)tj.c * tj.c * 8);
+        }
+        for (size_t i = 0; i < p->types.size(); ++i) {
+            const TypeState& t = p->types[i];
+            int part = 0;
+            for (int64_t r0 = 0; r0 < t.n; r0 += SM_GROWS) p->sm_j1.push_back(SmJob{SMJ_GRAM, (int)i, (int)r0, (int)std::min<int64_t>(SM_GROWS, t.n - r0), part++, 0, 0, 0});
+            gdoubles += align_up((size_t)part * t.c * t.c, 16);
+            for (int64_t r0 = 0; r0 < t.n; r0 += 64) p->sm_j3.push_back(SmJob{0, (int)i, (int)r0, (int)std::min<int64_t>(64, t.n - r0), 0, 0, 0, 0});
+            bool constrained = false;
+            for (const ThetaState& th : p->thetas) constrained = constrained || th.type == (int)i;
+            if (constrained)      // one wave per row, four rows per workgroup
+                for (int64_t r0 = 0; r0 < t.n; r0 += 4) p->sm_j1.push_back(SmJob{SMJ_THETA, (int)i, (int)r0, (int)std::min<int64_t>(4, t.n - r0), 0, 0, 0, 0});
+        }
+        // Gram shares first (the inverse hangs off the last of them), then P (W hangs off the last of those), Q, constraints
+        auto prio = [](const SmJob& j) { return j.kind == SMJ_GRAM ? 0 : (j.kind == SMJ_P ? 1 : (j.kind == SMJ_Q ? 2 : 3)); };
+        std::stable_sort(p->sm_j1.begin(), p->sm_j1.end(), [&](const SmJob& a, const SmJob& b) { return prio(a) < prio(b); });
+        add_slot(p, p->sm_tables, sizeof(SmTables));
+        add_slot(p, p->sm_jobs1, p->sm_j1.size() * sizeof(SmJob));
+        add_slot(p, p->sm_jobs3, p->sm_j3.size() * sizeof(SmJob));
+        add_slot(p, p->sm_wpart, wdoubles * 8);
+        add_slot(p, p->sm_gpart, gdoubles * 8);
+        add_slot(p, p->sm_tickets, (p->types.size() + p->rels.size()) * sizeof(int));
+        add_slot(p, p->sm_batch, SKF_MAX_BATCH * sizeof(void*));          // table of tables: [0] = this plan's
+    }
+}
+
+// The row lists and the column lists of a relation kept as its entries, `pc` / `pr` parts each: pointers per (row, part) /
+// (column, part), `cap` indices and values a side, the residuals beside the column values (known entries only), and the
+// counters of the bind-time build (build_known_lists_t / _csr_t, skf_bind.inc)
+static void add_list_slots(skf_plan* p, RelState& r, int64_t rows, int64_t cols, int pc, int pr, size_t cap, bool residuals) {
+    add_slot(p, r.KrPtr, ((size_t)rows * pc + 1) * 8);
+    add_slot(p, r.KrIdx, cap * 4);
+    add_slot(p, r.KrVal, cap * p->esz);
+    add_slot(p, r.KcPtr, ((size_t)cols * pr + 1) * 8);
+    add_slot(p, r.KcIdx, cap * 4);
+    add_slot(p, r.KcVal, cap * p->esz);
+    if (residuals) add_slot(p, r.KcE, cap * p->esz);
+    add_slot(p, r.KCnt, std::max((size_t)rows * pc, 2 * (size_t)cols * pr) * 4);
+}
+
+// ---- workspace layout: n-sized buffers in the master type, every c x c matrix in f64
+static void plan_layout(skf_plan* p) {
+    const int n_types = (int)p->types.size();
+    const size_t es = p->esz;
+    size_t part_bytes = 0;
+    size_t sp_part_bytes = 0;
+    // split-K scratch: every product that runs on it is sized by the decision its launch takes (kind_part_bytes -> slice_gemm)
+    size_t aux_bytes = 0, gram_group = 0;
+    auto want_part = [&](const ProductKind& k, int64_t M, int64_t N, int64_t K, bool aux_too = false) {
+        const size_t need = kind_part_bytes(p, k, M, N, K);
+        part_bytes = std::max(part_bytes, need);
+        if (aux_too) aux_bytes = std::max(aux_bytes, need);     // (launched on the second stream as well: that stream's scratch)
+        return need;
+    };
+    const ProductKind k_plan = kind_plan(p), k_rel = kind_relation(p), k_small = kind_small(p), k_wide = kind_wide(p),
+                      k_gram = kind_gram(p), k_mixed = kind_mixed(p);
+    int maxn = 2;
+    // the E / D accumulators of all types form ONE contiguous range of the workspace, so that
+    // a relation-sharded run sums them over the ranks with a single all-reduce
+    // Three regions with the SAME internal layout -- all E, all D, all G (every type at the same offset in each) -- so
+    // that the distributed iteration can cut them into `world` equal element ranges: reduce-scatter of E and of D,
+    // update of the owned range of G, all-gather of G (skf_iterate_dist).  A pad behind each region takes the rounding
+    // of the last range.
+    p->acc_off = p->ws_bytes;
+    for (int region = 0; region < 3; ++region) {
+        const size_t begin = p->ws_bytes;
+        for (int i = 0; i < n_types; ++i) {
+            TypeState& t = p->types[i];
+            const bool active = (p->variant != SKF_TRANSFORM) || i == p->target;
+            if (region < 2 && !active) continue;
+            add_slot(p, region == 0 ? t.E : region == 1 ? t.D : t.G, (size_t)t.n_alloc * t.c * es);
+        }
+        const size_t bytes = p->ws_bytes - begin;
+        if (region == 0) { p->flat_e_off = begin; p->flat_bytes = bytes; }
+        if (region == 1) p->flat_d_off = begin;
+        if (region == 2) p->flat_g_off = begin;
+        add_slot(p, p->flat_pad[region], 64 * 1024);
+        if (region == 1) p->acc_bytes = p->ws_bytes - p->acc_off;
+    }
+    // the Gram matrices of all types form one range (SKF_OPT_OWNED_ROWS: one all-reduce of the partial sums)
+    p->xg_off = p->ws_bytes;
+    for (int i = 0; i < n_types; ++i) add_slot(p, p->types[i].Gram, (size_t)p->types[i].c * p->types[i].c * 8);
+    p->xg_bytes = p->ws_bytes - p->xg_off;
+    for (int i = 0; i < n_types; ++i) {
+        TypeState& t = p->types[i];
+        if (p->bf16) {
+            t.ldgt = pad64(t.n);
+            add_slot(p, t.GTb, (size_t)t.c * t.ldgt * 2);
+        }
+        gram_group += want_part(k_gram, t.c, t.c, t.n, true);             // Gram = G^T G (gram_all: either stream)
+        if (t.keep_prev) add_slot(p, t.Gp, (size_t)t.n * t.c * es);
+        if (p->bf16 && t.need_rows) {
+            t.ldrow = (t.c + 7) / 8 * 8;
+            add_slot(p, t.Grow, ((size_t)t.n_alloc + 1) * t.ldrow * 2);     // (+ 1: the all-zero row of the v6 list kernel)
+        }
+        if (p->variant != SKF_TRANSFORM) {
+            add_slot(p, t.K, (size_t)t.c * t.c * 8);
+            if (!p->f64) {
+                add_slot(p, t.Bp32, (size_t)t.c * t.c * 4);
+                add_slot(p, t.Bn32, (size_t)t.c * t.c * 4);
+            }
+            if (t.n_pad > maxn) maxn = t.n_pad;
+        } else if (i == p->target) {
+            add_slot(p, t.Ec, (size_t)t.n * t.c * es);
+            add_slot(p, t.Dc, (size_t)t.n * t.c * es);
+            add_slot(p, t.Galt, (size_t)t.n * t.c * es);
+            add_slot(p, t.Bp_tot, (size_t)t.c * t.c * 8);
+            add_slot(p, t.Bn_tot, (size_t)t.c * t.c * 8);
+        }
+    }
+    size_t sq_elems = 1;
+    if (p->variant != SKF_TRANSFORM) {
+        // the per-type sums of B+ / B- form one range: one memset per iteration clears them all
+        p->btot_off = p->ws_bytes;
+        for (TypeState& t : p->types) {
+            add_slot(p, t.Bp_tot, (size_t)t.c * t.c * 8);
+            add_slot(p, t.Bn_tot, (size_t)t.c * t.c * 8);
+        }
+        p->btot_bytes = p->ws_bytes - p->btot_off;
+        // exchange ranges of row-block sharding: all W; then Q of unmasked, then of masked relations
+        p->xw_off = p->ws_bytes;
+        for (RelState& r : p->rels) add_slot(p, r.W, (size_t)p->types[r.row].c * p->types[r.col].c * 8);
+        p->xw_bytes = p->ws_bytes - p->xw_off;
+        p->xq_off = p->ws_bytes;
+        for (RelState& r : p->rels)
+            if (!r.masked) add_slot(p, r.Q, (size_t)p->types[r.col].n_alloc * p->types[r.row].c * es);
+        p->xq_bytes = p->ws_bytes - p->xq_off;
+        p->xqm_off = p->ws_bytes;
+        for (RelState& r : p->rels)
+            if (r.masked) add_slot(p, r.Q, (size_t)p->types[r.col].n_alloc * p->types[r.row].c * es);
+        p->xqm_bytes = p->ws_bytes - p->xqm_off;
+    }
+    for (RelState& r : p->rels) {
+        TypeState& ti = p->types[r.row];
+        TypeState& tj = p->types[r.col];
+        const size_t cc = (size_t)ti.c * tj.c * 8;
+        const int64_t nr = p->variant == SKF_TRANSFORM ? ti.n : r.nr;      // local rows
+        if (p->variant == SKF_TRANSFORM) { r.nr = ti.n; r.r0 = 0; }
+        add_slot(p, r.S, cc);
+        add_slot(p, r.U, cc);
+        if (r.fold) {
+            // the lists as handed over, T = G_p S', H and the c x c matrices of the error: ~ entries + n * c, never n_t * n_p
+            const bool row_side = r.row == p->target;
+            const TypeState& tt = p->types[p->target];
+            const TypeState& tp = row_side ? tj : ti;
+            const size_t cap = (size_t)r.kn_cap;
+            add_slot(p, r.KrPtr, ((size_t)tt.n + 1) * 8);
+            add_slot(p, r.KrIdx, cap * 4);
+            add_slot(p, r.KrVal, cap * es);
+            add_slot(p, r.Tm, (size_t)tp.n * tt.c * es);
+            add_slot(p, r.H, (size_t)tt.n * tp.c * es);
+            add_slot(p, r.T1, cc);
+            add_slot(p, r.Xi, (size_t)ti.c * ti.c * 8);
+            add_slot(p, r.Xj, (size_t)tj.c * tj.c * 8);
+            want_part(k_small, ti.c, tj.c, tj.c, true);
+            want_part(k_small, ti.c, tj.c, ti.c, true);
+            want_part(k_small, ti.c, ti.c, tj.c, true);
+            want_part(k_small, tj.c, tj.c, ti.c, true);
+            want_part(k_wide, ti.c, ti.c, ti.n);                            // Gram matrices of the error's trace term
+            want_part(k_wide, tj.c, tj.c, tj.n);
+            want_part(k_mixed, tp.n, tt.c, tp.c);                           // T = G_p S'
+            want_part(k_mixed, tt.n, tp.c, tt.c);                           // H = G_t S / G_t S^T
+            const size_t waves = ((size_t)tt.n + 3) / 4 + 8;                // error partials: one per wave of the pass
+            if (waves * 4 + 64 > sq_elems) sq_elems = waves * 4 + 64;
+            continue;
+        }
+        if (nr > 0 && !r.kn) add_slot(p, r.H, (size_t)nr * tj.c * es);
+        if (nr > 0 && !r.kn && (p->variant != SKF_TRANSFORM || r.row == p->target)) add_slot(p, r.P, (size_t)nr * tj.c * es);
+        if (p->variant == SKF_TRANSFORM && r.col == p->target) add_slot(p, r.Q, (size_t)tj.n * ti.c * es);
+        if (p->variant != SKF_TRANSFORM) {
+            add_slot(p, r.T1, cc);
+            if (!p->f64) add_slot(p, r.S32, cc / 2);
+            if (nr > 0) want_part(k_wide, ti.c, tj.c, nr);                  // W = G_i^T P
+            if (nr > 0) want_part(k_wide, ti.c, tj.c, tj.n);                // W = (R^T G_i)^T G_j ; known entries: W = Y^T G_j
+        }
+        want_part(k_small, ti.c, tj.c, tj.c, true);                         // c x c algebra (small_gemm: either stream): S Gram_j,
+        want_part(k_small, ti.c, tj.c, ti.c, true);                         // Gram_i S,
+        want_part(k_small, ti.c, ti.c, tj.c, true);                         // B = U S^T,
+        want_part(k_small, tj.c, tj.c, ti.c, true);                         // D = S^T U
+        if (nr <= 0 && r.kn) add_slot(p, r.U2, cc);             // (owned rows, none of this relation's here: the dense part of Q
+                                                                //  is still added on this process's rows of the column type)
+        if (nr <= 0) continue;
+        if (r.kn) {
+            // the known entries as row lists and column lists, the gathered vectors, the row-side product, c x c scratch
+            const size_t cap = (size_t)r.kn_cap;
+            r.ldmb = (tj.n + 127) / 128 * 16;
+            if (!r.kn_csr) add_slot(p, r.Mb, (size_t)nr * r.ldmb);          // (bind time only; CSR-fed: no mask at all)
+            add_list_slots(p, r, nr, tj.n, r.kn_pc, r.kn_pr, cap, true);
+            r.kn_ldf = p->bf16 ? (ti.c + 7) / 8 * 8 : ti.c;
+            if (p->bf16) add_slot(p, r.FiB, ((size_t)tj.n + 1) * r.kn_ldf * 2);  // (+ 1: the all-zero row of the v6 list kernel;
+                                                                                //  the row type's vectors: ti.Grow)
+            add_slot(p, r.Tm, (size_t)tj.n * ti.c * es);
+            add_slot(p, r.A, (size_t)nr * ti.c * es);
+            if (r.kn_pc > 1) add_slot(p, r.Apart, (size_t)r.kn_pc * nr * ti.c * es);
+            if (r.kn_pr > 1) add_slot(p, r.Qpart, (size_t)r.kn_pr * tj.n * ti.c * es);
+            add_slot(p, r.Sp, cc);
+            add_slot(p, r.U2, cc);
+            add_slot(p, r.Xi, (size_t)ti.c * ti.c * 8);
+            add_slot(p, r.Xj, (size_t)tj.c * tj.c * 8);
+            add_slot(p, r.Bf, (size_t)ti.c * ti.c * 8);
+            want_part(k_wide, ti.c, ti.c, nr);                              // G_i'^T G_i
+            want_part(k_wide, tj.c, tj.c, tj.n);                            // G_j^T G_j'
+            want_part(k_mixed, tj.n, ti.c, tj.c);                           // T = G_j S^T ; Q += G_j (S^T Gram_i)
+            want_part(k_mixed, nr, ti.c, ti.c);                             // A += G_i (S Gram_j S^T)
+            const size_t waves = (size_t)r.kn_pr * ((size_t)tj.n + 32) + 64;   // error partials: one per wave of the column pass
+            if (waves > sq_elems) sq_elems = waves;
+            continue;
+        }
+        if (r.sp0) {
+            // the stored entries as row lists and column lists with their values, the partial outputs of the parts, the
+            // c x c Gram matrices of the error's trace term: everything ~ entries or n * c, nothing ~ n_i * n_j
+            const size_t cap = (size_t)r.kn_cap;
+            add_list_slots(p, r, nr, tj.n, r.kn_pc, r.kn_pr, cap, false);
+            if (r.kn_pc > 1) add_slot(p, r.Apart, (size_t)r.kn_pc * nr * tj.c * es);
+            if (r.kn_pr > 1) add_slot(p, r.Qpart, (size_t)r.kn_pr * tj.n * ti.c * es);
+            add_slot(p, r.Xi, (size_t)ti.c * ti.c * 8);
+            add_slot(p, r.Xj, (size_t)tj.c * tj.c * 8);
+            want_part(k_wide, ti.c, ti.c, nr);                              // Gram matrices of the error's trace term
+            want_part(k_wide, tj.c, tj.c, tj.n);
+            want_part(k_mixed, nr, tj.c, ti.c);                             // H = G_i S
+            want_part(k_mixed, nr, ti.c, tj.c);                             // side products
+            want_part(k_mixed, tj.n, tj.c, ti.c);
+            const size_t waves = (size_t)r.kn_pc * ((size_t)nr + 32) + 64;  // error partials: one per wave of the row pass
+            if (waves > sq_elems) sq_elems = waves;
+            continue;
+        }
+        if (r.mask && !p->bf16) add_slot(p, r.Rw, (size_t)nr * tj.n * es);
+        if (r.mask) {
+            r.ldmb = (tj.n + 127) / 128 * 16;               // bytes per packed mask row: whole 128-column tiles
+            add_slot(p, r.Mb, (size_t)nr * r.ldmb);
+        }
+        if (p->bf16 && r.mask) {
+            // known entries as compact per-tile lists, up to 1/8 of the relation (beyond that the completion
+            // blends through the mask): 4 bytes per entry = at most a quarter of the bf16 relation's bytes
+            const size_t tiles = (size_t)cdiv(nr, 256) * cdiv(tj.n, 128);     // (128-column tiles: the finer grid)
+            r.kcap = (size_t)nr * tj.n / 8 + 4096;
+            add_slot(p, r.Kcnt, tiles * 4);
+            add_slot(p, r.Koff, (tiles + 1) * 4);
+            add_slot(p, r.Klist, r.kcap * 4);
+        }
+        if (p->bf16) {                                       // completion / residual tiles
+            r.ldhb = pad64(tj.c);
+            add_slot(p, r.Hb, (size_t)nr * r.ldhb * 2);
+            add_slot(p, r.Gb, (size_t)tj.n * r.ldhb * 2);
+        }
+        if (p->bf16) {
+            r.ldrb = pad64(tj.n);
+            r.kq = pad64(nr);
+            if (r.binary) {
+                r.ldbb = r.ldrb / 8;
+                add_slot(p, r.Bb, (size_t)r.kq * r.ldbb);
+                if (!r.masked) {                       // room for the CSR / CSC form of a sparse relation
+                    const int64_t per = r.sp_gather ? 80 : 256;            // (one entry in 80 / in 256 set, see build_sparse_pattern)
+                    r.sp_cap = (int64_t)nr * tj.n / per > 0 ? (int64_t)nr * tj.n / per : 1;
+                    if (r.sp_gather) {
+                        if (r.sp_pc > 1) add_slot(p, r.SpRpP, ((size_t)nr * r.sp_pc + 1) * 8);
+                        if (r.sp_pr > 1) add_slot(p, r.SpCpP, ((size_t)tj.n * r.sp_pr + 1) * 8);
+                        const size_t pb = std::max(r.sp_pc > 1 ? (size_t)r.sp_pc * nr * tj.c * 4 : (size_t)0,
+                                                   r.sp_pr > 1 ? (size_t)r.sp_pr * tj.n * ti.c * 4 : (size_t)0);
+                        if (pb > sp_part_bytes) sp_part_bytes = pb;
+                    }
+                    add_slot(p, r.SpRp, (size_t)(nr + 1) * 8);
+                    add_slot(p, r.SpCp, (size_t)(tj.n + 1) * 8);
+                    add_slot(p, r.SpCi, (size_t)r.sp_cap * 4);
+                    add_slot(p, r.SpRi, (size_t)r.sp_cap * 4);
+                    add_slot(p, r.SpCnt, (size_t)(nr + 2 * tj.n + 8) * 4);
+                }
+            } else {
+                add_slot(p, r.Rb, (size_t)r.kq * r.ldrb * 2);
+            }
+            size_t b1 = bf16_part_bytes((int)nr, tj.c, (int)r.ldrb, r.binary), b2 = bf16_part_bytes((int)tj.n, ti.c, (int)r.kq, true);
+            if (b1 > part_bytes) part_bytes = b1;
+            if (b2 > part_bytes) part_bytes = b2;
+        }
+        if (!p->bf16) want_part(k_rel, nr, tj.c, tj.n);                     // P = R G_j
+        if (!p->bf16) want_part(k_rel, tj.n, ti.c, nr);                     // Q = R^T G_i
+        want_part(k_mixed, nr, tj.c, ti.c);                                 // H = G_i S
+        want_part(k_mixed, nr, ti.c, tj.c);                                 // side products
+        want_part(k_mixed, tj.n, tj.c, ti.c);
+        if (r.mask && !p->bf16) want_part(k_plan, nr, tj.n, tj.c);          // the completion H G_j^T
+        size_t blocks = (size_t)cdiv(nr, 32) * cdiv(tj.n, 32);           // smallest tile any engine uses
+        if (blocks > sq_elems) sq_elems = blocks;
+    }
+    plan_layout_small_graph(p);
+    size_t theta_tmp_bytes = 0;
+    for (ThetaState& th : p->thetas) {
+        TypeState& t = p->types[th.type];
+        if (th.sparse) {
+            add_slot(p, th.Cnt, (size_t)t.n * sizeof(int));
+            add_slot(p, th.Rp, (size_t)(t.n + 1) * sizeof(int64_t));
+            add_slot(p, th.Ci, (size_t)th.nnz_cap * sizeof(int));
+            add_slot(p, th.Vv, (size_t)th.nnz_cap * es);
+            continue;
+        }
+        if (!p->bf16) want_part(k_plan, t.n, t.c, t.n);                     // dense Theta G
+        if (p->bf16) {
+            th.ldb = pad64(t.n);
+            add_slot(p, th.Pb, (size_t)t.n * th.ldb * 2);
+            add_slot(p, th.Nb, (size_t)t.n * th.ldb * 2);
+            const size_t b = bf16_part_bytes((int)t.n, t.c, (int)th.ldb, false);
+            if (b > part_bytes) part_bytes = b;
+            if ((size_t)t.n * t.c * 4 > theta_tmp_bytes) theta_tmp_bytes = (size_t)t.n * t.c * 4;
+        }
+    }
+    if (!p->thetas.empty()) add_slot(p, p->theta_flags, p->thetas.size() * 2 * sizeof(int));
+    if (theta_tmp_bytes) add_slot(p, p->theta_tmp, theta_tmp_bytes);
+    // the Gram products of all types side by side in one launch (gram_all): every product's slices at once
+    if (n_types >= 2 && n_types <= 4) {
+        part_bytes = std::max(part_bytes, gram_group);
+        aux_bytes = std::max(aux_bytes, gram_group);
+    }
+    p->part_bytes = part_bytes;
+    add_slot(p, p->part, part_bytes);
+    if (sp_part_bytes) add_slot(p, p->sp_part, sp_part_bytes);
+    p->part_aux_bytes = aux_bytes;
+    add_slot(p, p->part_aux, aux_bytes);
+    p->sq_elems = sq_elems;
+    add_slot(p, p->sqpart, sq_elems * 8);
+    if (p->variant != SKF_TRANSFORM) {
+        p->eig_maxn = maxn;
+        p->eig_stride = (int64_t)maxn * maxn;
+        const size_t mat = (size_t)p->eig_stride * n_types * sizeof(double);
+        add_slot(p, p->eigA, mat);
+        add_slot(p, p->eigV, mat);
+        add_slot(p, p->eigVs, mat);
+        add_slot(p, p->eigW, (size_t)maxn * n_types * sizeof(double));
+        add_slot(p, p->eigN, (size_t)n_types * sizeof(int));
+        add_slot(p, p->eigNorig, (size_t)n_types * sizeof(int));
+        add_slot(p, p->eigOk, (size_t)n_types * sizeof(int));
+        if (maxn > SWEEP_MAXN && n_types <= PINV_MAXB) add_slot(p, p->eigX, defl_scratch_bytes(n_types, p->eig_stride));
+    }
+}
 
 extern "C" {
 
@@ -139,623 +791,11 @@ int skf_plan_create(int32_t n_types, const skf_type_desc* types, int32_t n_relat
         if (opt->engine != SKF_ENGINE_MFMA && opt->engine != SKF_ENGINE_VALU) SKF_FAIL(SKF_E_INVALID, "bad engine");
         skf_plan* p = new skf_plan();
         struct Guard { skf_plan* p; ~Guard() { delete p; } } guard{p};
-        p->dtype = opt->dtype;
-        p->variant = opt->variant;
-        p->engine = opt->engine;
-        p->f64 = (opt->dtype == SKF_F64);
-        p->bf16 = (opt->dtype == SKF_BF16);
-        p->esz = p->f64 ? 8 : 4;
-        p->mt = p->f64 ? SKF_F64 : SKF_F32;
-        p->target = opt->target_type;
-        if (p->variant == SKF_TRANSFORM && (p->target < 0 || p->target >= n_types))
-            SKF_FAIL(SKF_E_INVALID, "target type %d out of range", p->target);
-        p->types.resize(n_types);
-        for (int i = 0; i < n_types; ++i) {
-            if (types[i].n_obj <= 0 || types[i].rank <= 0 || types[i].rank > EIGH_MAXN - 1)
-                SKF_FAIL(SKF_E_INVALID, "object type %d: n_obj=%lld rank=%d invalid", i, (long long)types[i].n_obj,
-                         types[i].rank);
-            if (types[i].n_obj > 2000000000LL) SKF_FAIL(SKF_E_INVALID, "object type %d too large", i);
-            p->types[i].n = types[i].n_obj;
-            p->types[i].c = types[i].rank;
-            p->types[i].n_pad = (types[i].rank + 1) / 2 * 2;
-            p->types[i].t0 = 0;
-            p->types[i].tn = types[i].n_obj;
-            p->types[i].n_alloc = types[i].n_obj;
-            if (opt->flags & SKF_OPT_OWNED_ROWS) {      // the rows this process owns (skf_owned_rows)
-                if (opt->part_count < 1 || opt->part_index < 0 || opt->part_index >= opt->part_count)
-                    SKF_FAIL(SKF_E_INVALID, "SKF_OPT_OWNED_ROWS: part_index %d outside [0, %d)", opt->part_index, opt->part_count);
-                const int64_t ch = owned_chunk(opt->dtype, types[i].n_obj, opt->part_count);
-                int64_t lo = ch * opt->part_index, hi = lo + ch;
-                if (lo > types[i].n_obj) lo = types[i].n_obj;
-                if (hi > types[i].n_obj) hi = types[i].n_obj;
-                p->types[i].t0 = lo;
-                p->types[i].tn = hi - lo;
-                p->types[i].chunk = ch;
-                p->types[i].n_alloc = ch * opt->part_count;
-            } else if (opt->part_count > 1) {      // even shares of the rows, boundaries at multiples of 64
-                if (opt->part_index < 0 || opt->part_index >= opt->part_count)
-                    SKF_FAIL(SKF_E_INVALID, "part_index %d outside [0, %d)", opt->part_index, opt->part_count);
-                const int64_t per = (types[i].n_obj + opt->part_count - 1) / opt->part_count;
-                const int64_t step = (per + 63) / 64 * 64;
-                int64_t lo = step * opt->part_index, hi = lo + step;
-                if (lo > types[i].n_obj) lo = types[i].n_obj;
-                if (hi > types[i].n_obj) hi = types[i].n_obj;
-                p->types[i].t0 = lo;
-                p->types[i].tn = hi - lo;
-            }
-        }
-        if (opt->part_count > 1) p->sliced = true;
-        if (opt->flags & SKF_OPT_OWNED_ROWS) {
-            if (p->variant == SKF_TRANSFORM) SKF_FAIL(SKF_E_INVALID, "SKF_OPT_OWNED_ROWS is for SKF_DFMF / SKF_DFMC plans");
-            p->owned = p->sliced = true;
-            p->part_index = opt->part_index;
-            p->part_count = opt->part_count;
-        }
-        p->rels.resize(n_relations);
-        for (int r = 0; r < n_relations; ++r) {
-            const skf_relation_desc& d = relations[r];
-            if (d.row_type < 0 || d.row_type >= n_types || d.col_type < 0 || d.col_type >= n_types)
-                SKF_FAIL(SKF_E_INVALID, "relation %d: type index out of range", r);
-            if (d.row_type == d.col_type) SKF_FAIL(SKF_E_INVALID, "relation %d: row type == column type (pass it as a constraint)", r);
-            const bool absent = (d.flags & SKF_REL_ABSENT) != 0;
-            const bool csr = (d.flags & SKF_REL_KNOWN_CSR) != 0;
-            if (csr && p->variant != SKF_DFMC) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR needs SKF_DFMC", r);
-            if (csr && (d.data || d.mask)) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR takes no data / mask", r);
-            const bool sp0 = (d.flags & SKF_REL_SPARSE_CSR) != 0;      // the stored entries as CSR, every other entry zero
-            if (sp0 && csr) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR and SKF_REL_SPARSE_CSR exclude each other", r);
-            if (sp0 && p->variant == SKF_TRANSFORM) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_SPARSE_CSR is for SKF_DFMF / SKF_DFMC plans", r);
-            if (sp0 && (d.data || d.mask || (d.flags & (SKF_REL_MASKED | SKF_REL_MASK_BITS))))
-                SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_SPARSE_CSR takes no data / mask", r);
-            const bool fold = (d.flags & SKF_REL_FOLD_CSR) != 0;      // fold-in: the stored entries compressed along the target's side
-            if (fold && p->variant != SKF_TRANSFORM) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR is for SKF_TRANSFORM plans", r);
-            if (fold && (csr || sp0))
-                SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR excludes SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR", r);
-            if (fold && (d.data || d.mask || (d.flags & (SKF_REL_MASKED | SKF_REL_MASK_BITS))))
-                SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR takes no data / mask", r);
-            if (!absent && !csr && !sp0 && !fold && (!d.data || d.ld < p->types[d.col_type].n))
-                SKF_FAIL(SKF_E_INVALID, "relation %d: dimension mismatch (ld %lld < %lld columns)", r, (long long)d.ld,
-                         (long long)p->types[d.col_type].n);
-            const int64_t n_row_type = p->types[d.row_type].n;
-            if (d.row_begin < 0 || d.n_rows < 0 || d.row_begin + d.n_rows > n_row_type)
-                SKF_FAIL(SKF_E_INVALID, "relation %d: row block [%lld, +%lld) outside the %lld objects of its row type",
-                         r, (long long)d.row_begin, (long long)d.n_rows, (long long)n_row_type);
-            const bool block = absent || (d.n_rows > 0 && d.n_rows < n_row_type) || (d.flags & SKF_REL_NO_COL_SIDE);
-            if (block && (csr || sp0)) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR relations are whole relations", r);
-            if (block && fold) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR relations are whole relations", r);
-            if (block && p->variant == SKF_TRANSFORM)
-                SKF_FAIL(SKF_E_INVALID, "relation %d: row blocks are for SKF_DFMF / SKF_DFMC plans", r);
-            if (block && p->bf16 && d.row_begin % 64 != 0)
-                SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_BF16 row blocks must start at a multiple of 64", r);
-            if (block) p->sliced = true;
-            if ((d.mask || (d.flags & SKF_REL_MASKED)) && p->variant != SKF_DFMC)
-                SKF_FAIL(SKF_E_INVALID, "relation %d: masks need SKF_DFMC", r);
-            if (d.mask && d.mask_ld < ((d.flags & SKF_REL_MASK_BITS) ? (p->types[d.col_type].n + 7) / 8 : p->types[d.col_type].n))
-                SKF_FAIL(SKF_E_INVALID, "relation %d: mask ld", r);
-            if (p->variant == SKF_TRANSFORM && d.row_type != p->target && d.col_type != p->target)
-                SKF_FAIL(SKF_E_INVALID, "relation %d must include the target object type", r);
-            RelState& s = p->rels[r];
-            s.row = d.row_type; s.col = d.col_type;
-            s.R_in = d.data; s.ld_in = d.ld; s.mask = d.mask; s.ldmask = d.mask_ld;
-            s.mask_is_bits = (d.flags & SKF_REL_MASK_BITS) != 0;
-            s.binary = p->bf16 && (d.flags & SKF_REL_BINARY) != 0 && !d.mask && !absent;
-            s.R = d.data; s.ldr = d.ld;
-            s.absent = absent;
-            s.r0 = absent ? 0 : d.row_begin;
-            s.nr = absent ? 0 : (d.n_rows > 0 ? d.n_rows : n_row_type - d.row_begin);
-            s.col_side = (d.flags & SKF_REL_NO_COL_SIDE) == 0;
-            s.masked = d.mask != nullptr || (d.flags & SKF_REL_MASKED) != 0;
-            if (absent) { s.R_in = s.R = nullptr; s.mask = nullptr; }
-            if (p->owned) {         // the block of a relation is the owned range of its row type, nothing else
-                const TypeState& ti = p->types[d.row_type];
-                if (ti.tn == 0 ? !absent : (absent || s.r0 != ti.t0 || s.nr != ti.tn))
-                    SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_OPT_OWNED_ROWS wants the rows [%lld, +%lld) of its row type here (skf_owned_rows)",
-                             r, (long long)ti.t0, (long long)ti.tn);
-                s.col_side = true;  // every process adds the column-side terms of ITS rows of the column type
-            }
-            if (d.known_bound < 0) SKF_FAIL(SKF_E_INVALID, "relation %d: negative bound on the known entries", r);
-            s.kn_cap = (s.mask && p->variant == SKF_DFMC) ? d.known_bound : 0;
-            if (csr) {                  // the known entries as CSR (skf_plan_set_known_entries): no dense form, no mask
-                s.kn_csr = s.masked = true;
-                s.R_in = s.R = nullptr;
-                s.kn_cap = d.known_bound;
-            }
-            if (sp0) {                  // the stored entries as CSR (skf_plan_set_known_entries): no dense form in any type
-                s.sp0 = true;
-                s.binary = false;
-                s.R_in = s.R = nullptr;
-                s.kn_cap = d.known_bound;
-            }
-            if (fold) {                 // one set of lists along the target (skf_plan_set_known_entries): no dense form, no P / Q
-                if (p->types[d.row_type].c > 1024 || p->types[d.col_type].c > 1024 || d.known_bound > 2000000000LL)
-                    SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR beyond the list limits (a rank above 1024 or %lld > 2e9 entries)",
-                             r, (long long)d.known_bound);
-                s.fold = true;
-                s.binary = false;
-                s.R_in = s.R = nullptr;
-                s.kn_cap = d.known_bound;
-            }
-        }
-        // masked relations with few known entries are kept as lists of those entries (skf_known.h).  The three passes over the
-        // lists gather rank_row-wide vectors -- ~70 ps per entry at rank 128 against ~2.2 ps per CELL for the four passes of
-        // the dense path over the completed relation (config 5, bf16) -- hence: known share * rank_row <= 4 (1/32 at rank
-        // 128).  SKF_DFMC_SPARSE=0: never; =1: whenever a bound is given (up to a quarter of the relation).  Plans with row
-        // blocks keep the dense form.
-        {
-            const Switches sw0 = Switches::read();          // (plan creation: the plan's own copy is read when its workspace is bound)
-            const int mode = sw0.dfmc_sparse;
-            // Parts of the lists (skf_known.h): with srp_bf16_v6_kernel the passes are no longer bound by instruction issue and
-            // pinning slices of the gathered matrix to XCDs pays (profiles/r03_srp_v6.txt: 25.6 MB of user factors, 8 parts:
-            // 1.75 -> 1.10 ms; 10 MB, 4 parts: 1.41 -> 1.25 ms) -- the smallest power of two that brings a slice under the
-            // 4 MiB L2 of an XCD, as long as a segment still holds a batch of entries.  Other engines / widths: 1 (their
-            // kernels are issue-bound; measured neutral in round 3).  SKF_KNOWN_PARTS=1|2|4|8 overrides.
-            const int parts_env = sw0.known_parts;
-            auto pick_parts = [&](int64_t n_in, int64_t n_out, int ci, int64_t cap) {
-                if (parts_env) return parts_env;
-                if (!p->bf16 || (ci != 128 && ci != 256)) return 1;
-                int q = 1;
-                while (q < 8 && (double)n_in * ci * 2.0 / q > 3.5 * 1048576.0) q *= 2;
-                while (q > 1 && (double)cap / ((double)n_out * q) < 64.0) q /= 2;
-                return q;
-            };
-            for (size_t rk = 0; rk < p->rels.size(); ++rk) {
-                RelState& s = p->rels[rk];
-                const int ci = p->types[s.row].c;
-                if (s.fold) continue;               // (one set of lists as handed over: no parts, nothing decided here)
-                if (s.sp0) {
-                    // valued lists whatever the density (the caller chose the form; no dense one to fall back on).  P gathers
-                    // rank_col-wide rows of G_j through the row lists, Q rank_row-wide rows of G_i through the column lists
-                    const int cj = p->types[s.col].c;
-                    if (p->sliced) SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_SPARSE_CSR is for plans of whole relations", rk);
-                    if (ci > 64 * SRP_MAXREP || cj > 64 * SRP_MAXREP || s.kn_cap > 2000000000LL)
-                        SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_SPARSE_CSR beyond the list limits (a rank above %d or %lld > 2e9 entries)",
-                                 rk, 64 * SRP_MAXREP, (long long)s.kn_cap);
-                    s.kn_pc = pick_parts(p->types[s.col].n, s.nr, cj, s.kn_cap);
-                    s.kn_pr = pick_parts(s.nr, p->types[s.col].n, ci, s.kn_cap);
-                    s.kn_pw = ((p->types[s.col].n + s.kn_pc - 1) / s.kn_pc + 63) / 64 * 64;
-                    s.kn_ph = ((s.nr + s.kn_pr - 1) / s.kn_pr + 63) / 64 * 64;
-                    if (p->bf16) p->types[s.row].need_rows = p->types[s.col].need_rows = true;
-                    continue;
-                }
-                if (s.kn_csr) {
-                    // lists whatever the share (no dense form to fall back on); the parts below follow from the exact count
-                    if (p->sliced) SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_KNOWN_CSR is for plans of whole relations", rk);
-                    if (ci > 64 * SRP_MAXREP || s.kn_cap > 2000000000LL)
-                        SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_KNOWN_CSR beyond the list limits (rank %d > %d or %lld > 2e9 entries)",
-                                 rk, ci, 64 * SRP_MAXREP, (long long)s.kn_cap);
-                } else if (p->owned) {
-                    // ownership-aligned row blocks: the caller decided for ALL processes alike (SKF_REL_KNOWN_LISTS); a process
-                    // without rows of the relation keeps the flag -- it adds the dense part of Q on ITS rows of the column type
-                    const bool lists = (relations[rk].flags & SKF_REL_KNOWN_LISTS) != 0 && s.masked && p->variant == SKF_DFMC;
-                    if (lists && (ci > 64 * SRP_MAXREP || s.kn_cap > 2000000000LL || (!s.absent && s.kn_cap <= 0)))
-                        SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_KNOWN_LISTS needs a bound on the known entries of the local rows", rk);
-                    if (!lists) {
-                        s.kn_cap = 0;
-                        continue;
-                    }
-                } else {
-                    if (s.kn_cap <= 0) continue;
-                    const double cells = (double)s.nr * (double)p->types[s.col].n;
-                    const double share = cells > 0 ? (double)s.kn_cap / cells : 1.0;
-                    if (p->sliced || mode == 0 || share > 0.25 || (mode != 1 && share * ci > 4.0) || ci > 64 * SRP_MAXREP ||
-                        s.kn_cap > 2000000000LL) {
-                        s.kn_cap = 0;
-                        continue;
-                    }
-                }
-                s.kn = true;
-                if (s.absent) continue;             // (no lists here: only the flag)
-                s.kn_pc = pick_parts(p->types[s.col].n, s.nr, ci, s.kn_cap);        // row lists gather the column objects' vectors
-                s.kn_pr = pick_parts(s.nr, p->types[s.col].n, ci, s.kn_cap);        // column lists gather the row objects' vectors
-                s.kn_pw = ((p->types[s.col].n + s.kn_pc - 1) / s.kn_pc + 63) / 64 * 64;
-                s.kn_ph = ((s.nr + s.kn_pr - 1) / s.kn_pr + 63) / 64 * 64;
-                p->types[s.row].keep_prev = p->types[s.col].keep_prev = true;
-                if (p->bf16) p->types[s.row].need_rows = true;              // the column lists gather the row type's bf16 rows
-            }
-            // sparse 0/1 relations as lists over bf16 factor rows (srp_bf16_v6_kernel<.., SRP_ONES>): both ranks 64 / 128 / 256
-            auto gather_rank = [](int c) { return c == 64 || c == 128 || c == 256; };
-            for (RelState& s : p->rels) {
-                s.sp_gather = p->bf16 && s.binary && !s.masked && !s.absent && gather_rank(p->types[s.row].c) &&
-                              gather_rank(p->types[s.col].c);
-                if (!s.sp_gather) continue;
-                p->types[s.row].need_rows = p->types[s.col].need_rows = true;
-                // parts by the size of the gathered matrix alone (the number of ones is known at bind time, which may lower them)
-                auto by_bytes = [&](int64_t n_in, int c) {
-                    if (parts_env) return parts_env;
-                    int q = 1;
-                    while (q < 8 && (double)n_in * c * 2.0 / q > 3.5 * 1048576.0) q *= 2;
-                    return q;
-                };
-                s.sp_pc = by_bytes(p->types[s.col].n, p->types[s.col].c);    // P: rows of G_j by the column index
-                s.sp_pr = by_bytes(p->types[s.row].n, p->types[s.row].c);    // Q: rows of G_i by the row index
-            }
-        }
-        p->thetas.resize(n_thetas);
-        for (int t = 0; t < n_thetas; ++t) {
-            if (thetas[t].type < 0 || thetas[t].type >= n_types || !thetas[t].data ||
-                thetas[t].ld < p->types[thetas[t].type].n)
-                SKF_FAIL(SKF_E_INVALID, "constraint %d invalid", t);
-            if (p->variant == SKF_TRANSFORM && thetas[t].type != p->target)
-                SKF_FAIL(SKF_E_INVALID, "constraint %d must be on the target object type", t);
-            p->thetas[t].type = thetas[t].type;
-            p->thetas[t].data = thetas[t].data;
-            p->thetas[t].ld = thetas[t].ld;
-            const int64_t nn = p->types[thetas[t].type].n;
-            if (thetas[t].nnz < 0) SKF_FAIL(SKF_E_INVALID, "constraint %d: negative non-zero bound", t);
-            if (thetas[t].nnz > 0 && thetas[t].nnz <= nn * nn / SKF_THETA_SPARSE_DIV) {
-                p->thetas[t].sparse = true;
-                p->thetas[t].nnz_cap = thetas[t].nnz;
-            }
-        }
-        if (p->owned) {
-            // SKF_BF16: the other owners' rows of a factor are read as bf16 operands only -- unless a constraint on the type
-            // multiplies the f32 rows (theta_spmm_kernel / dense Theta).  Every type keeps its bf16 rows (the gathered form).
-            for (TypeState& t : p->types) {
-                t.gather_master = !p->bf16;
-                if (p->bf16) t.need_rows = true;
-            }
-            for (const ThetaState& th : p->thetas) p->types[th.type].gather_master = true;
-            // ... and the types of a masked relation (the same on every process, whatever it holds of the relation): the
-            // known-entry form multiplies the f32 rows of both factors (cross-Gram matrices, T = G_j S^T, the dense part of Q)
-            for (const RelState& r : p->rels)
-                if (r.masked) p->types[r.row].gather_master = p->types[r.col].gather_master = true;
-        }
-        // ---- workspace layout: n-sized buffers in the master type, every c x c matrix in f64
-        const size_t es = p->esz;
-        size_t part_bytes = 0;
-        size_t sp_part_bytes = 0;
-        // split-K scratch: every product that runs on it is sized by the decision its launch takes (kind_part_bytes -> slice_gemm)
-        size_t aux_bytes = 0, gram_group = 0;
-        auto want_part = [&](const ProductKind& k, int64_t M, int64_t N, int64_t K, bool aux_too = false) {
-            const size_t need = kind_part_bytes(p, k, M, N, K);
-            part_bytes = std::max(part_bytes, need);
-            if (aux_too) aux_bytes = std::max(aux_bytes, need);     // (launched on the second stream as well: that stream's scratch)
-            return need;
-        };
-        const ProductKind k_plan = kind_plan(p), k_rel = kind_relation(p), k_small = kind_small(p), k_wide = kind_wide(p),
-                          k_gram = kind_gram(p), k_mixed = kind_mixed(p);
-        int maxn = 2;
-        // the E / D accumulators of all types form ONE contiguous range of the workspace, so that
-        // a relation-sharded run sums them over the ranks with a single all-reduce
-        // Three regions with the SAME internal layout -- all E, all D, all G (every type at the same offset in each) -- so
-        // that the distributed iteration can cut them into `world` equal element ranges: reduce-scatter of E and of D,
-        // update of the owned range of G, all-gather of G (skf_iterate_dist).  A pad behind each region takes the rounding
-        // of the last range.
-        p->acc_off = p->ws_bytes;
-        for (int region = 0; region < 3; ++region) {
-            const size_t begin = p->ws_bytes;
-            for (int i = 0; i < n_types; ++i) {
-                TypeState& t = p->types[i];
-                const bool active = (p->variant != SKF_TRANSFORM) || i == p->target;
-                if (region < 2 && !active) continue;
-                add_slot(p, region == 0 ? t.E : region == 1 ? t.D : t.G, (size_t)t.n_alloc * t.c * es);
-            }
-            const size_t bytes = p->ws_bytes - begin;
-            if (region == 0) { p->flat_e_off = begin; p->flat_bytes = bytes; }
-            if (region == 1) p->flat_d_off = begin;
-            if (region == 2) p->flat_g_off = begin;
-            add_slot(p, p->flat_pad[region], 64 * 1024);
-            if (region == 1) p->acc_bytes = p->ws_bytes - p->acc_off;
-        }
-        // the Gram matrices of all types form one range (SKF_OPT_OWNED_ROWS: one all-reduce of the partial sums)
-        p->xg_off = p->ws_bytes;
-        for (int i = 0; i < n_types; ++i) add_slot(p, p->types[i].Gram, (size_t)p->types[i].c * p->types[i].c * 8);
-        p->xg_bytes = p->ws_bytes - p->xg_off;
-        for (int i = 0; i < n_types; ++i) {
-            TypeState& t = p->types[i];
-            if (p->bf16) {
-                t.ldgt = pad64(t.n);
-                add_slot(p, t.GTb, (size_t)t.c * t.ldgt * 2);
-            }
-            gram_group += want_part(k_gram, t.c, t.c, t.n, true);             // Gram = G^T G (gram_all: either stream)
-            if (t.keep_prev) add_slot(p, t.Gp, (size_t)t.n * t.c * es);
-            if (p->bf16 && t.need_rows) {
-                t.ldrow = (t.c + 7) / 8 * 8;
-                add_slot(p, t.Grow, ((size_t)t.n_alloc + 1) * t.ldrow * 2);     // (+ 1: the all-zero row of the v6 list kernel)
-            }
-            if (p->variant != SKF_TRANSFORM) {
-                add_slot(p, t.K, (size_t)t.c * t.c * 8);
-                if (!p->f64) {
-                    add_slot(p, t.Bp32, (size_t)t.c * t.c * 4);
-                    add_slot(p, t.Bn32, (size_t)t.c * t.c * 4);
-                }
-                if (t.n_pad > maxn) maxn = t.n_pad;
-            } else if (i == p->target) {
-                add_slot(p, t.Ec, (size_t)t.n * t.c * es);
-                add_slot(p, t.Dc, (size_t)t.n * t.c * es);
-                add_slot(p, t.Galt, (size_t)t.n * t.c * es);
-                add_slot(p, t.Bp_tot, (size_t)t.c * t.c * 8);
-                add_slot(p, t.Bn_tot, (size_t)t.c * t.c * 8);
-            }
-        }
-        size_t sq_elems = 1;
-        if (p->variant != SKF_TRANSFORM) {
-            // the per-type sums of B+ / B- form one range: one memset per iteration clears them all
-            p->btot_off = p->ws_bytes;
-            for (TypeState& t : p->types) {
-                add_slot(p, t.Bp_tot, (size_t)t.c * t.c * 8);
-                add_slot(p, t.Bn_tot, (size_t)t.c * t.c * 8);
-            }
-            p->btot_bytes = p->ws_bytes - p->btot_off;
-            // exchange ranges of row-block sharding: all W; then Q of unmasked, then of masked relations
-            p->xw_off = p->ws_bytes;
-            for (RelState& r : p->rels) add_slot(p, r.W, (size_t)p->types[r.row].c * p->types[r.col].c * 8);
-            p->xw_bytes = p->ws_bytes - p->xw_off;
-            p->xq_off = p->ws_bytes;
-            for (RelState& r : p->rels)
-                if (!r.masked) add_slot(p, r.Q, (size_t)p->types[r.col].n_alloc * p->types[r.row].c * es);
-            p->xq_bytes = p->ws_bytes - p->xq_off;
-            p->xqm_off = p->ws_bytes;
-            for (RelState& r : p->rels)
-                if (r.masked) add_slot(p, r.Q, (size_t)p->types[r.col].n_alloc * p->types[r.row].c * es);
-            p->xqm_bytes = p->ws_bytes - p->xqm_off;
-        }
-        for (RelState& r : p->rels) {
-            TypeState& ti = p->types[r.row];
-            TypeState& tj = p->types[r.col];
-            const size_t cc = (size_t)ti.c * tj.c * 8;
-            const int64_t nr = p->variant == SKF_TRANSFORM ? ti.n : r.nr;      // local rows
-            if (p->variant == SKF_TRANSFORM) { r.nr = ti.n; r.r0 = 0; }
-            add_slot(p, r.S, cc);
-            add_slot(p, r.U, cc);
-            if (r.fold) {
-                // the lists as handed over, T = G_p S', H and the c x c matrices of the error: ~ entries + n * c, never n_t * n_p
-                const bool row_side = r.row == p->target;
-                const TypeState& tt = p->types[p->target];
-                const TypeState& tp = row_side ? tj : ti;
-                const size_t cap = (size_t)r.kn_cap;
-                add_slot(p, r.KrPtr, ((size_t)tt.n + 1) * 8);
-                add_slot(p, r.KrIdx, cap * 4);
-                add_slot(p, r.KrVal, cap * es);
-                add_slot(p, r.Tm, (size_t)tp.n * tt.c * es);
-                add_slot(p, r.H, (size_t)tt.n * tp.c * es);
-                add_slot(p, r.T1, cc);
-                add_slot(p, r.Xi, (size_t)ti.c * ti.c * 8);
-                add_slot(p, r.Xj, (size_t)tj.c * tj.c * 8);
-                want_part(k_small, ti.c, tj.c, tj.c, true);
-                want_part(k_small, ti.c, tj.c, ti.c, true);
-                want_part(k_small, ti.c, ti.c, tj.c, true);
-                want_part(k_small, tj.c, tj.c, ti.c, true);
-                want_part(k_wide, ti.c, ti.c, ti.n);                            // Gram matrices of the error's trace term
-                want_part(k_wide, tj.c, tj.c, tj.n);
-                want_part(k_mixed, tp.n, tt.c, tp.c);                           // T = G_p S'
-                want_part(k_mixed, tt.n, tp.c, tt.c);                           // H = G_t S / G_t S^T
-                const size_t waves = ((size_t)tt.n + 3) / 4 + 8;                // error partials: one per wave of the pass
-                if (waves * 4 + 64 > sq_elems) sq_elems = waves * 4 + 64;
-                continue;
-            }
-            if (nr > 0 && !r.kn) add_slot(p, r.H, (size_t)nr * tj.c * es);
-            if (nr > 0 && !r.kn && (p->variant != SKF_TRANSFORM || r.row == p->target)) add_slot(p, r.P, (size_t)nr * tj.c * es);
-            if (p->variant == SKF_TRANSFORM && r.col == p->target) add_slot(p, r.Q, (size_t)tj.n * ti.c * es);
-            if (p->variant != SKF_TRANSFORM) {
-                add_slot(p, r.T1, cc);
-                if (!p->f64) add_slot(p, r.S32, cc / 2);
-                if (nr > 0) want_part(k_wide, ti.c, tj.c, nr);                  // W = G_i^T P
-                if (nr > 0) want_part(k_wide, ti.c, tj.c, tj.n);                // W = (R^T G_i)^T G_j ; known entries: W = Y^T G_j
-            }
-            want_part(k_small, ti.c, tj.c, tj.c, true);                         // c x c algebra (small_gemm: either stream): S Gram_j,
-            want_part(k_small, ti.c, tj.c, ti.c, true);                         // Gram_i S,
-            want_part(k_small, ti.c, ti.c, tj.c, true);                         // B = U S^T,
-            want_part(k_small, tj.c, tj.c, ti.c, true);                         // D = S^T U
-            if (nr <= 0 && r.kn) add_slot(p, r.U2, cc);             // (owned rows, none of this relation's here: the dense part of Q
-                                                                    //  is still added on this process's rows of the column type)
-            if (nr <= 0) continue;
-            if (r.kn) {
-                // the known entries as row lists and column lists, the gathered vectors, the row-side product, c x c scratch
-                const size_t cap = (size_t)r.kn_cap;
-                r.ldmb = (tj.n + 127) / 128 * 16;
-                if (!r.kn_csr) add_slot(p, r.Mb, (size_t)nr * r.ldmb);          // (bind time only; CSR-fed: no mask at all)
-                add_slot(p, r.KrPtr, ((size_t)nr * r.kn_pc + 1) * 8);
-                add_slot(p, r.KrIdx, cap * 4);
-                add_slot(p, r.KrVal, cap * es);
-                add_slot(p, r.KcPtr, ((size_t)tj.n * r.kn_pr + 1) * 8);
-                add_slot(p, r.KcIdx, cap * 4);
-                add_slot(p, r.KcVal, cap * es);
-                add_slot(p, r.KcE, cap * es);
-                const size_t cnt = std::max((size_t)nr * r.kn_pc, 2 * (size_t)tj.n * r.kn_pr);
-                add_slot(p, r.KCnt, cnt * 4);
-                r.kn_ldf = p->bf16 ? (ti.c + 7) / 8 * 8 : ti.c;
-                if (p->bf16) add_slot(p, r.FiB, ((size_t)tj.n + 1) * r.kn_ldf * 2);  // (+ 1: the all-zero row of the v6 list kernel;
-                                                                                    //  the row type's vectors: ti.Grow)
-                add_slot(p, r.Tm, (size_t)tj.n * ti.c * es);
-                add_slot(p, r.A, (size_t)nr * ti.c * es);
-                if (r.kn_pc > 1) add_slot(p, r.Apart, (size_t)r.kn_pc * nr * ti.c * es);
-                if (r.kn_pr > 1) add_slot(p, r.Qpart, (size_t)r.kn_pr * tj.n * ti.c * es);
-                add_slot(p, r.Sp, cc);
-                add_slot(p, r.U2, cc);
-                add_slot(p, r.Xi, (size_t)ti.c * ti.c * 8);
-                add_slot(p, r.Xj, (size_t)tj.c * tj.c * 8);
-                add_slot(p, r.Bf, (size_t)ti.c * ti.c * 8);
-                want_part(k_wide, ti.c, ti.c, nr);                              // G_i'^T G_i
-                want_part(k_wide, tj.c, tj.c, tj.n);                            // G_j^T G_j'
-                want_part(k_mixed, tj.n, ti.c, tj.c);                           // T = G_j S^T ; Q += G_j (S^T Gram_i)
-                want_part(k_mixed, nr, ti.c, ti.c);                             // A += G_i (S Gram_j S^T)
-                const size_t waves = (size_t)r.kn_pr * ((size_t)tj.n + 32) + 64;   // error partials: one per wave of the column pass
-                if (waves > sq_elems) sq_elems = waves;
-                continue;
-            }
-            if (r.sp0) {
-                // the stored entries as row lists and column lists with their values, the partial outputs of the parts, the
-                // c x c Gram matrices of the error's trace term: everything ~ entries or n * c, nothing ~ n_i * n_j
-                const size_t cap = (size_t)r.kn_cap;
-                add_slot(p, r.KrPtr, ((size_t)nr * r.kn_pc + 1) * 8);
-                add_slot(p, r.KrIdx, cap * 4);
-                add_slot(p, r.KrVal, cap * es);
-                add_slot(p, r.KcPtr, ((size_t)tj.n * r.kn_pr + 1) * 8);
-                add_slot(p, r.KcIdx, cap * 4);
-                add_slot(p, r.KcVal, cap * es);
-                add_slot(p, r.KCnt, std::max((size_t)nr * r.kn_pc, 2 * (size_t)tj.n * r.kn_pr) * 4);
-                if (r.kn_pc > 1) add_slot(p, r.Apart, (size_t)r.kn_pc * nr * tj.c * es);
-                if (r.kn_pr > 1) add_slot(p, r.Qpart, (size_t)r.kn_pr * tj.n * ti.c * es);
-                add_slot(p, r.Xi, (size_t)ti.c * ti.c * 8);
-                add_slot(p, r.Xj, (size_t)tj.c * tj.c * 8);
-                want_part(k_wide, ti.c, ti.c, nr);                              // Gram matrices of the error's trace term
-                want_part(k_wide, tj.c, tj.c, tj.n);
-                want_part(k_mixed, nr, tj.c, ti.c);                             // H = G_i S
-                want_part(k_mixed, nr, ti.c, tj.c);                             // side products
-                want_part(k_mixed, tj.n, tj.c, ti.c);
-                const size_t waves = (size_t)r.kn_pc * ((size_t)nr + 32) + 64;  // error partials: one per wave of the row pass
-                if (waves > sq_elems) sq_elems = waves;
-                continue;
-            }
-            if (r.mask && !p->bf16) add_slot(p, r.Rw, (size_t)nr * tj.n * es);
-            if (r.mask) {
-                r.ldmb = (tj.n + 127) / 128 * 16;               // bytes per packed mask row: whole 128-column tiles
-                add_slot(p, r.Mb, (size_t)nr * r.ldmb);
-            }
-            if (p->bf16 && r.mask) {
-                // known entries as compact per-tile lists, up to 1/8 of the relation (beyond that the completion
-                // blends through the mask): 4 bytes per entry = at most a quarter of the bf16 relation's bytes
-                const size_t tiles = (size_t)cdiv(nr, 256) * cdiv(tj.n, 128);     // (128-column tiles: the finer grid)
-                r.kcap = (size_t)nr * tj.n / 8 + 4096;
-                add_slot(p, r.Kcnt, tiles * 4);
-                add_slot(p, r.Koff, (tiles + 1) * 4);
-                add_slot(p, r.Klist, r.kcap * 4);
-            }
-            if (p->bf16) {                                       // completion / residual tiles
-                r.ldhb = pad64(tj.c);
-                add_slot(p, r.Hb, (size_t)nr * r.ldhb * 2);
-                add_slot(p, r.Gb, (size_t)tj.n * r.ldhb * 2);
-            }
-            if (p->bf16) {
-                r.ldrb = pad64(tj.n);
-                r.kq = pad64(nr);
-                if (r.binary) {
-                    r.ldbb = r.ldrb / 8;
-                    add_slot(p, r.Bb, (size_t)r.kq * r.ldbb);
-                    if (!r.masked) {                       // room for the CSR / CSC form of a sparse relation
-                        const int64_t per = r.sp_gather ? 80 : 256;            // (one entry in 80 / in 256 set, see build_sparse_pattern)
-                        r.sp_cap = (int64_t)nr * tj.n / per > 0 ? (int64_t)nr * tj.n / per : 1;
-                        if (r.sp_gather) {
-                            if (r.sp_pc > 1) add_slot(p, r.SpRpP, ((size_t)nr * r.sp_pc + 1) * 8);
-                            if (r.sp_pr > 1) add_slot(p, r.SpCpP, ((size_t)tj.n * r.sp_pr + 1) * 8);
-                            const size_t pb = std::max(r.sp_pc > 1 ? (size_t)r.sp_pc * nr * tj.c * 4 : (size_t)0,
-                                                       r.sp_pr > 1 ? (size_t)r.sp_pr * tj.n * ti.c * 4 : (size_t)0);
-                            if (pb > sp_part_bytes) sp_part_bytes = pb;
-                        }
-                        add_slot(p, r.SpRp, (size_t)(nr + 1) * 8);
-                        add_slot(p, r.SpCp, (size_t)(tj.n + 1) * 8);
-                        add_slot(p, r.SpCi, (size_t)r.sp_cap * 4);
-                        add_slot(p, r.SpRi, (size_t)r.sp_cap * 4);
-                        add_slot(p, r.SpCnt, (size_t)(nr + 2 * tj.n + 8) * 4);
-                    }
-                } else {
-                    add_slot(p, r.Rb, (size_t)r.kq * r.ldrb * 2);
-                }
-                size_t b1 = bf16_part_bytes((int)nr, tj.c, (int)r.ldrb, r.binary), b2 = bf16_part_bytes((int)tj.n, ti.c, (int)r.kq, true);
-                if (b1 > part_bytes) part_bytes = b1;
-                if (b2 > part_bytes) part_bytes = b2;
-            }
-            if (!p->bf16) want_part(k_rel, nr, tj.c, tj.n);                     // P = R G_j
-            if (!p->bf16) want_part(k_rel, tj.n, ti.c, nr);                     // Q = R^T G_i
-            want_part(k_mixed, nr, tj.c, ti.c);                                 // H = G_i S
-            want_part(k_mixed, nr, ti.c, tj.c);                                 // side products
-            want_part(k_mixed, tj.n, tj.c, ti.c);
-            if (r.mask && !p->bf16) want_part(k_plan, nr, tj.n, tj.c);          // the completion H G_j^T
-            size_t blocks = (size_t)cdiv(nr, 32) * cdiv(tj.n, 32);           // smallest tile any engine uses
-            if (blocks > sq_elems) sq_elems = blocks;
-        }
-        // small graphs: every rank <= 64, sparse constraints only, a few thousand objects per type -> the fused schedule
-        {
-            bool ok = p->variant == SKF_DFMF && p->engine == SKF_ENGINE_MFMA && !p->bf16 && !p->sliced && n_types <= SM_MAXT &&
-                      n_relations >= 1 && n_relations <= SM_MAXR && n_thetas <= SM_MAXTH;
-            // (object counts: the Q shares of the schedule grow with n_i / 256 * n_j * c_i, and from a few thousand objects
-            // on the relation contractions are worth the big tiles of the general schedule)
-            for (const TypeState& t : p->types) ok = ok && t.c <= SMALLC && t.n <= SM_MAX_OBJECTS;
-            for (const ThetaState& th : p->thetas) ok = ok && th.sparse;
-            for (const RelState& r : p->rels) ok = ok && !r.absent && !r.masked && !r.sp0;
-            p->small_fused = ok;
-            if (ok) {
-                size_t wdoubles = 0, gdoubles = 0;
-                for (size_t k = 0; k < p->rels.size(); ++k) {
-                    RelState& r = p->rels[k];
-                    const TypeState& ti = p->types[r.row];
-                    const TypeState& tj = p->types[r.col];
-                    int part = 0;
-                    for (int64_t r0 = 0; r0 < ti.n; r0 += 64) p->sm_j1.push_back(SmJob{SMJ_P, (int)k, (int)r0, (int)std::min<int64_t>(64, ti.n - r0), part++, 0, 0, 0});
-                    // Q = R^T G_i: a long inner dimension (the rows of the relation) over a small output -> shares of SM_QROWS rows
-                    int qpart = 0;
-                    for (int64_t k0 = 0; k0 < ti.n; k0 += SM_QROWS, ++qpart)
-                        for (int64_t c0 = 0; c0 < tj.n; c0 += 64)
-                            p->sm_j1.push_back(SmJob{SMJ_Q, (int)k, (int)c0, (int)std::min<int64_t>(64, tj.n - c0), qpart, (int)k0,
-                                                     (int)std::min<int64_t>(SM_QROWS, ti.n - k0), 0});
-                    r.sm_qparts = qpart;
-                    wdoubles += align_up((size_t)part * ti.c * tj.c, 16);      // (shares of different relations / types never share a cache line)
-                    add_slot(p, r.SmQ, (size_t)qpart * tj.n * ti.c * es);
-                    add_slot(p, r.SmBp, (size_t)ti.c * ti.c * 8);
-                    add_slot(p, r.SmBn, (size_t)ti.c * ti.c * 8);
-                    add_slot(p, r.SmDp, (size_t)tj.c * tj.c * 8);
-                    add_slot(p, r.SmDn, (size_t)tj.c * tj.c * 8);
-                }
-                for (size_t i = 0; i < p->types.size(); ++i) {
-                    const TypeState& t = p->types[i];
-                    int part = 0;
-                    for (int64_t r0 = 0; r0 < t.n; r0 += SM_GROWS) p->sm_j1.push_back(SmJob{SMJ_GRAM, (int)i, (int)r0, (int)std::min<int64_t>(SM_GROWS, t.n - r0), part++, 0, 0, 0});
-                    gdoubles += align_up((size_t)part * t.c * t.c, 16);
-                    for (int64_t r0 = 0; r0 < t.n; r0 += 64) p->sm_j3.push_back(SmJob{0, (int)i, (int)r0, (int)std::min<int64_t>(64, t.n - r0), 0, 0, 0, 0});
-                    bool constrained = false;
-                    for (const ThetaState& th : p->thetas) constrained = constrained || th.type == (int)i;
-                    if (constrained)      // one wave per row, four rows per workgroup
-                        for (int64_t r0 = 0; r0 < t.n; r0 += 4) p->sm_j1.push_back(SmJob{SMJ_THETA, (int)i, (int)r0, (int)std::min<int64_t>(4, t.n - r0), 0, 0, 0, 0});
-                }
-                // Gram shares first (the inverse hangs off the last of them), then P (W hangs off the last of those), Q, constraints
-                auto prio = [](const SmJob& j) { return j.kind == SMJ_GRAM ? 0 : (j.kind == SMJ_P ? 1 : (j.kind == SMJ_Q ? 2 : 3)); };
-                std::stable_sort(p->sm_j1.begin(), p->sm_j1.end(), [&](const SmJob& a, const SmJob& b) { return prio(a) < prio(b); });
-                add_slot(p, p->sm_tables, sizeof(SmTables));
-                add_slot(p, p->sm_jobs1, p->sm_j1.size() * sizeof(SmJob));
-                add_slot(p, p->sm_jobs3, p->sm_j3.size() * sizeof(SmJob));
-                add_slot(p, p->sm_wpart, wdoubles * 8);
-                add_slot(p, p->sm_gpart, gdoubles * 8);
-                add_slot(p, p->sm_tickets, (p->types.size() + p->rels.size()) * sizeof(int));
-                add_slot(p, p->sm_batch, SKF_MAX_BATCH * sizeof(void*));          // table of tables: [0] = this plan's
-            }
-        }
-        size_t theta_tmp_bytes = 0;
-        for (ThetaState& th : p->thetas) {
-            TypeState& t = p->types[th.type];
-            if (th.sparse) {
-                add_slot(p, th.Cnt, (size_t)t.n * sizeof(int));
-                add_slot(p, th.Rp, (size_t)(t.n + 1) * sizeof(int64_t));
-                add_slot(p, th.Ci, (size_t)th.nnz_cap * sizeof(int));
-                add_slot(p, th.Vv, (size_t)th.nnz_cap * es);
-                continue;
-            }
-            if (!p->bf16) want_part(k_plan, t.n, t.c, t.n);                     // dense Theta G
-            if (p->bf16) {
-                th.ldb = pad64(t.n);
-                add_slot(p, th.Pb, (size_t)t.n * th.ldb * 2);
-                add_slot(p, th.Nb, (size_t)t.n * th.ldb * 2);
-                const size_t b = bf16_part_bytes((int)t.n, t.c, (int)th.ldb, false);
-                if (b > part_bytes) part_bytes = b;
-                if ((size_t)t.n * t.c * 4 > theta_tmp_bytes) theta_tmp_bytes = (size_t)t.n * t.c * 4;
-            }
-        }
-        if (!p->thetas.empty()) add_slot(p, p->theta_flags, p->thetas.size() * 2 * sizeof(int));
-        if (theta_tmp_bytes) add_slot(p, p->theta_tmp, theta_tmp_bytes);
-        // the Gram products of all types side by side in one launch (gram_all): every product's slices at once
-        if (n_types >= 2 && n_types <= 4) {
-            part_bytes = std::max(part_bytes, gram_group);
-            aux_bytes = std::max(aux_bytes, gram_group);
-        }
-        p->part_bytes = part_bytes;
-        add_slot(p, p->part, part_bytes);
-        if (sp_part_bytes) add_slot(p, p->sp_part, sp_part_bytes);
-        p->part_aux_bytes = aux_bytes;
-        add_slot(p, p->part_aux, aux_bytes);
-        p->sq_elems = sq_elems;
-        add_slot(p, p->sqpart, sq_elems * 8);
-        if (p->variant != SKF_TRANSFORM) {
-            p->eig_maxn = maxn;
-            p->eig_stride = (int64_t)maxn * maxn;
-            const size_t mat = (size_t)p->eig_stride * n_types * sizeof(double);
-            add_slot(p, p->eigA, mat);
-            add_slot(p, p->eigV, mat);
-            add_slot(p, p->eigVs, mat);
-            add_slot(p, p->eigW, (size_t)maxn * n_types * sizeof(double));
-            add_slot(p, p->eigN, (size_t)n_types * sizeof(int));
-            add_slot(p, p->eigNorig, (size_t)n_types * sizeof(int));
-            add_slot(p, p->eigOk, (size_t)n_types * sizeof(int));
-            if (maxn > SWEEP_MAXN && n_types <= PINV_MAXB) add_slot(p, p->eigX, defl_scratch_bytes(n_types, p->eig_stride));
-        }
+        plan_describe_types(p, n_types, types, opt);
+        plan_describe_relations(p, n_types, n_relations, relations);
+        plan_decide_lists(p, relations);
+        plan_describe_constraints(p, n_types, n_thetas, thetas);
+        plan_layout(p);
         guard.p = nullptr;
         *out = p;
     });
@@ -788,75 +828,6 @@ int skf_plan_workspace_bytes(const skf_plan* plan, size_t* bytes) {
     });
 }
 
-// CSR + CSC of a very sparse binary relation from its bitmap (bind time): per-row counts on the device, prefix sums on the
-// host; kept only when the ones fit the slots sized at plan creation (1 entry in 256)
-static void build_sparse_pattern(skf_plan* p, RelState& r, hipStream_t st) {
-    r.sparse = false;
-    if (r.sp_cap <= 0 || !r.SpRp.ptr) return;
-    const int64_t rows = r.nr, cols = p->types[r.col].n;
-    if (rows <= 0 || cols <= 0) return;
-    const int wgrid = (int)((rows + 3) / 4 < 2048 ? (rows + 3) / 4 : 2048);
-    int* rowcnt = (int*)r.SpCnt.ptr;
-    int* colcnt = rowcnt + rows;
-    int* fillpos = colcnt + cols;
-    hipLaunchKernelGGL(bits_row_count_kernel, dim3(wgrid), dim3(256), 0, st, (const uint8_t*)r.Bb.ptr, r.ldbb, rows, rowcnt);
-    check_launch("bits_row_count");
-    std::vector<int> cnt((size_t)(rows > cols ? rows : cols));
-    SKF_HIP(hipMemcpyAsync(cnt.data(), rowcnt, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
-    SKF_HIP(hipStreamSynchronize(st));
-    std::vector<int64_t> ptr((size_t)(rows > cols ? rows : cols) + 1);
-    int64_t tot = 0;
-    for (int64_t k = 0; k < rows; ++k) { ptr[k] = tot; tot += cnt[k]; }
-    ptr[rows] = tot;
-    // the form by the count: lists over bf16 factor rows (srp_bf16_v6_kernel<.., SRP_ONES>) up to 1 entry in 80 -- measured
-    // at config 5 (profiles/r03_srp_v6.txt): ~14-22 ps per one and contraction against ~0.28 ps per CELL of the bitmap
-    // kernels, break-even near 1 in 64 --; without that form (other ranks) lists over the f32 rows up to 1 in 256
-    if (tot > r.sp_cap || (!r.sp_gather && tot > rows * cols / 256)) return;
-    r.sp_nnz = tot;
-    SKF_HIP(hipMemcpyAsync(r.SpRp.ptr, ptr.data(), (size_t)(rows + 1) * 8, hipMemcpyHostToDevice, st));
-    SKF_HIP(hipMemsetAsync(colcnt, 0, (size_t)cols * 2 * 4, st));
-    SKF_HIP(hipStreamSynchronize(st));                       // (`ptr` is reused below)
-    if (tot > 0) {
-        hipLaunchKernelGGL(bits_csr_fill_kernel, dim3(wgrid), dim3(256), 0, st, (const uint8_t*)r.Bb.ptr, r.ldbb, rows,
-                           (const int64_t*)r.SpRp.ptr, (int*)r.SpCi.ptr);
-        hipLaunchKernelGGL(csr_col_count_kernel, dim3(elem_grid(tot)), dim3(256), 0, st, (const int*)r.SpCi.ptr, tot, colcnt);
-        check_launch("bits_csr_fill");
-    }
-    SKF_HIP(hipMemcpyAsync(cnt.data(), colcnt, (size_t)cols * 4, hipMemcpyDeviceToHost, st));
-    SKF_HIP(hipStreamSynchronize(st));
-    int64_t t2 = 0;
-    for (int64_t k = 0; k < cols; ++k) { ptr[k] = t2; t2 += cnt[k]; }
-    ptr[cols] = t2;
-    SKF_HIP(hipMemcpyAsync(r.SpCp.ptr, ptr.data(), (size_t)(cols + 1) * 8, hipMemcpyHostToDevice, st));
-    if (tot > 0) {
-        hipLaunchKernelGGL(csr_transpose_fill_kernel, dim3(wgrid), dim3(256), 0, st, (const int64_t*)r.SpRp.ptr,
-                           (const int*)r.SpCi.ptr, rows, (const int64_t*)r.SpCp.ptr, fillpos, (int*)r.SpRi.ptr);
-        hipLaunchKernelGGL(csc_sort_kernel, dim3(elem_grid(cols)), dim3(256), 0, st, (const int64_t*)r.SpCp.ptr,
-                           (int*)r.SpRi.ptr, cols);
-        check_launch("csc_build");
-    }
-    if (r.sp_gather) {          // lists in parts pinned to XCDs, as long as a segment still holds a batch of entries
-        const bool forced = p->sw.known_parts_forced;                    // (tests: short lists in parts too)
-        auto fit = [&](int q, int64_t n_out) {
-            while (!forced && q > 1 && (double)tot / ((double)n_out * q) < 64.0) q /= 2;
-            return q;
-        };
-        r.sp_pc = fit(r.SpRpP.ptr ? r.sp_pc : 1, rows);
-        r.sp_pr = fit(r.SpCpP.ptr ? r.sp_pr : 1, cols);
-        r.sp_pw = ((cols + r.sp_pc - 1) / r.sp_pc + 63) / 64 * 64;
-        r.sp_ph = ((rows + r.sp_pr - 1) / r.sp_pr + 63) / 64 * 64;
-        if (r.sp_pc > 1)
-            hipLaunchKernelGGL(parted_ptr_kernel, dim3(elem_grid(rows * r.sp_pc + 1)), dim3(256), 0, st, (const int64_t*)r.SpRp.ptr,
-                               (const int*)r.SpCi.ptr, rows, r.sp_pc, r.sp_pw, (int64_t*)r.SpRpP.ptr);
-        if (r.sp_pr > 1)
-            hipLaunchKernelGGL(parted_ptr_kernel, dim3(elem_grid(cols * r.sp_pr + 1)), dim3(256), 0, st, (const int64_t*)r.SpCp.ptr,
-                               (const int*)r.SpRi.ptr, cols, r.sp_pr, r.sp_ph, (int64_t*)r.SpCpP.ptr);
-        check_launch("parted_ptr");
-    }
-    SKF_HIP(hipStreamSynchronize(st));
-    r.sparse = true;
-}
-
 int skf_plan_bind_workspace(skf_plan* p, void* ws, size_t bytes, void* stream) {
     return guarded([&] {
         if (!p || !ws) SKF_FAIL(SKF_E_INVALID, "null argument");
@@ -866,290 +837,14 @@ int skf_plan_bind_workspace(skf_plan* p, void* ws, size_t bytes, void* stream) {
         p->ws_base = ws;
         p->sw = Switches::read();          // the only place a plan looks at the environment
         hipStream_t st = as_stream(stream);
-        for (RelState& r : p->rels) {
-            if (r.fold) {
-                // the caller's lists along the target: validated on the device (rows = target objects, columns = partner
-                // objects) before anything gathers through them, then copied as they are -- no other list is built
-                if (!r.csr_ptr) SKF_FAIL(SKF_E_INVALID, "a SKF_REL_FOLD_CSR relation without skf_plan_set_known_entries");
-                const bool row_side = r.row == p->target;
-                const int64_t rows = p->types[p->target].n, cols = p->types[row_side ? r.col : r.row].n, tot = r.kn_cap;
-                int* flag = (int*)p->sqpart.ptr;                 // (scratch word; bind is not on the hot path)
-                SKF_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
-                const int wgrid = (int)((rows + 3) / 4 < 2048 ? (rows + 3) / 4 : 2048);
-                hipLaunchKernelGGL(known_csr_check_kernel, dim3(wgrid), dim3(256), 0, st, r.csr_ptr, r.csr_idx, rows, cols, tot, flag);
-                check_launch("known_csr_check");
-                int bad = 0;
-                SKF_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-                SKF_HIP(hipStreamSynchronize(st));
-                if (bad)
-                    SKF_FAIL(SKF_E_INVALID, "SKF_REL_FOLD_CSR: the lists are not canonical for %lld target x %lld partner objects with %lld "
-                             "entries (indptr from 0 to the count, non-decreasing; indices in range and strictly ascending within a list)",
-                             (long long)rows, (long long)cols, (long long)tot);
-                r.kn_nnz = tot;
-                SKF_HIP(hipMemcpyAsync(r.KrPtr.ptr, r.csr_ptr, ((size_t)rows + 1) * 8, hipMemcpyDeviceToDevice, st));
-                if (tot > 0) {
-                    SKF_HIP(hipMemcpyAsync(r.KrIdx.ptr, r.csr_idx, (size_t)tot * 4, hipMemcpyDeviceToDevice, st));
-                    SKF_HIP(hipMemcpyAsync(r.KrVal.ptr, r.csr_val, (size_t)tot * p->esz, hipMemcpyDeviceToDevice, st));
-                }
-                r.csr_ptr = nullptr; r.csr_idx = nullptr; r.csr_val = nullptr;      // not referenced after bind
-                continue;
-            }
-            if (r.kn_csr || r.sp0) {               // the caller's CSR, validated, then the same lists the mask form builds
-                if (!r.csr_ptr) SKF_FAIL(SKF_E_INVALID, "a SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR relation without skf_plan_set_known_entries");
-                build_known_lists_csr(p, r, st);
-                continue;
-            }
-            if (!r.mask) continue;
-            // the mask in the engine's layout: one bit per entry, rows padded to whole 128-column tiles.
-            // The caller's mask (bytes or bits) is not referenced after this call.
-            const int64_t rows = r.nr, cols = p->types[r.col].n;
-            if (r.mask_is_bits) {
-                SKF_HIP(hipMemsetAsync(r.Mb.ptr, 0, r.Mb.bytes, st));
-                hipLaunchKernelGGL(copy_mask_bits_kernel, dim3(elem_grid(rows * ((cols + 7) / 8))), dim3(256), 0, st,
-                                   (uint8_t*)r.Mb.ptr, r.ldmb, r.mask, r.ldmask, rows, cols);
-            } else {
-                hipLaunchKernelGGL(pack_mask_kernel, dim3(elem_grid(rows * r.ldmb)), dim3(256), 0, st, (uint8_t*)r.Mb.ptr,
-                                   r.ldmb, r.mask, r.ldmask, rows, cols);
-            }
-            check_launch("pack_mask");
-            if (r.kn) {                            // the known entries as lists; no working copy of the relation
-                build_known_lists(p, r, st);
-                continue;
-            }
-            if (p->bf16) {
-                // known entries of every tile of the completion pass (256 rows x epi_tile columns) as a compact list
-                // (count, prefix sum on the host, fill)
-                const int tx = cdiv(rows, 256), ty = cdiv(cols, 128);
-                const size_t tiles = (size_t)tx * ty;
-                KnownArgs ka;
-                ka.mbits = (const uint8_t*)r.Mb.ptr; ka.ldmb = r.ldmb;
-                ka.Rin = (const uint16_t*)r.R_in; ka.ldin = r.ld_in;
-                ka.rows = (int)rows; ka.cols = (int)cols;
-                ka.tile_cols = 128;
-                ka.counts = (uint32_t*)r.Kcnt.ptr; ka.off = nullptr; ka.list = nullptr;
-                hipLaunchKernelGGL(known_entries_kernel, dim3(tx, ty), dim3(256), 0, st, ka);
-                check_launch("known_entries(count)");
-                std::vector<uint32_t> cnt(tiles), off(tiles + 1);
-                SKF_HIP(hipMemcpyAsync(cnt.data(), r.Kcnt.ptr, tiles * 4, hipMemcpyDeviceToHost, st));
-                SKF_HIP(hipStreamSynchronize(st));
-                uint64_t tot = 0;
-                for (size_t t = 0; t < tiles; ++t) { off[t] = (uint32_t)tot; tot += cnt[t]; }
-                off[tiles] = (uint32_t)tot;
-                r.use_klist = tot <= r.kcap && tot < 0xFFFFFFFFull;
-                if (r.use_klist) {
-                    SKF_HIP(hipMemcpyAsync(r.Koff.ptr, off.data(), (tiles + 1) * 4, hipMemcpyHostToDevice, st));
-                    ka.off = (const uint32_t*)r.Koff.ptr; ka.list = (uint32_t*)r.Klist.ptr;
-                    hipLaunchKernelGGL(known_entries_kernel, dim3(tx, ty), dim3(256), 0, st, ka);
-                    check_launch("known_entries(fill)");
-                    SKF_HIP(hipStreamSynchronize(st));          // `off` dies here; bind is not on the hot path
-                }
-                continue;                          // bf16: the padded copy below is the working set
-            }
-            copy2d(r.Rw.ptr, cols, r.R_in, r.ld_in, rows, cols, p->esz, st);
-            r.R = r.Rw.ptr;
-            r.ldr = cols;
-        }
-        if (p->bf16) {
-            // the caller's bf16 relation is copied ONCE into a zero-padded row-major layout (rows to a multiple of
-            // 64: the inner dimension of Q = R^T G_i; columns to a multiple of 64: the inner dimension of
-            // P = R G_j); it is not referenced after this call
-            for (TypeState& t : p->types) {
-                SKF_HIP(hipMemsetAsync(t.GTb.ptr, 0, t.GTb.bytes, st));
-                if (t.Grow.bytes) SKF_HIP(hipMemsetAsync(t.Grow.ptr, 0, t.Grow.bytes, st));
-            }
-            for (RelState& r : p->rels) {
-                if (r.absent || r.kn || r.sp0 || r.fold) continue;
-                const int64_t rows = r.nr, cols = p->types[r.col].n;
-                if (r.binary) {
-                    int* bad = (int*)p->sqpart.ptr;                  // (scratch word; bind is not on the hot path)
-                    SKF_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
-                    hipLaunchKernelGGL(pack_binary_kernel, dim3(elem_grid(r.kq * r.ldbb)), dim3(256), 0, st, (uint8_t*)r.Bb.ptr,
-                                       r.ldbb, r.kq, (const uint16_t*)r.R_in, r.ld_in, rows, cols, bad);
-                    check_launch("pack_binary");
-                    int hbad = 0;
-                    SKF_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-                    SKF_HIP(hipStreamSynchronize(st));
-                    if (hbad) SKF_FAIL(SKF_E_INVALID, "a relation flagged SKF_REL_BINARY holds an entry that is neither 0 nor 1");
-                    if (r.Hb.bytes) {
-                        SKF_HIP(hipMemsetAsync(r.Hb.ptr, 0, r.Hb.bytes, st));
-                        SKF_HIP(hipMemsetAsync(r.Gb.ptr, 0, r.Gb.bytes, st));
-                    }
-                    r.R = r.Bb.ptr;
-                    r.ldr = r.ldrb;
-                    build_sparse_pattern(p, r, st);
-                    continue;
-                }
-                SKF_HIP(hipMemsetAsync(r.Rb.ptr, 0, r.Rb.bytes, st));
-                if (r.Hb.bytes) {
-                    SKF_HIP(hipMemsetAsync(r.Hb.ptr, 0, r.Hb.bytes, st));
-                    SKF_HIP(hipMemsetAsync(r.Gb.ptr, 0, r.Gb.bytes, st));
-                }
-                launch_to_bf16<uint16_t>((uint16_t*)r.Rb.ptr, r.ldrb, (const uint16_t*)r.R_in, r.ld_in, rows, cols, false, st);
-                r.R = r.Rb.ptr;
-                r.ldr = r.ldrb;
-            }
-        }
-        for (ThetaState& th : p->thetas) {
-            if (!th.sparse) continue;
-            // CSR of a sparse constraint: per-row counts on the device, prefix sum on the host, fill on the device
-            const int64_t n = p->types[th.type].n;
-            const int grid = (int)((n + 3) / 4 < 2048 ? (n + 3) / 4 : 2048);
-            if (p->f64)
-                hipLaunchKernelGGL((theta_row_count_kernel<double>), dim3(grid), dim3(256), 0, st, (const double*)th.data, th.ld, n, (int*)th.Cnt.ptr);
-            else
-                hipLaunchKernelGGL((theta_row_count_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)th.data, th.ld, n, (int*)th.Cnt.ptr);
-            check_launch("theta_row_count");
-            std::vector<int> cnt((size_t)n);
-            SKF_HIP(hipMemcpyAsync(cnt.data(), th.Cnt.ptr, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
-            SKF_HIP(hipStreamSynchronize(st));
-            std::vector<int64_t> rp((size_t)n + 1);
-            int64_t tot = 0;
-            for (int64_t r = 0; r < n; ++r) { rp[(size_t)r] = tot; tot += cnt[(size_t)r]; }
-            rp[(size_t)n] = tot;
-            if (tot > th.nnz_cap)
-                SKF_FAIL(SKF_E_INVALID, "constraint on type %d holds %lld non-zeros, more than the bound %lld given in skf_theta_desc.nnz",
-                         th.type, (long long)tot, (long long)th.nnz_cap);
-            th.nnz = tot;
-            SKF_HIP(hipMemcpyAsync(th.Rp.ptr, rp.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-            if (p->f64)
-                hipLaunchKernelGGL((theta_csr_fill_kernel<double>), dim3(grid), dim3(256), 0, st, (const double*)th.data, th.ld, n,
-                                   (const int64_t*)th.Rp.ptr, (int*)th.Ci.ptr, (double*)th.Vv.ptr);
-            else
-                hipLaunchKernelGGL((theta_csr_fill_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)th.data, th.ld, n,
-                                   (const int64_t*)th.Rp.ptr, (int*)th.Ci.ptr, (float*)th.Vv.ptr);
-            check_launch("theta_csr_fill");
-            SKF_HIP(hipStreamSynchronize(st));          // `rp` dies here; bind is not on the hot path
-        }
-        if (!p->thetas.empty()) {
-            // which halves of every constraint's +- split are non-empty (one device pass, read back here:
-            // bind is not on the hot path), and the bf16 engine's copies of the non-empty halves
-            SKF_HIP(hipMemsetAsync(p->theta_flags.ptr, 0, p->theta_flags.bytes, st));
-            for (size_t k = 0; k < p->thetas.size(); ++k) {
-                ThetaState& th = p->thetas[k];
-                if (th.sparse) continue;
-                const int64_t n = p->types[th.type].n;
-                int* fl = (int*)p->theta_flags.ptr + 2 * k;
-                if (p->f64)
-                    hipLaunchKernelGGL((sign_flags_kernel<double>), dim3(elem_grid(n * n)), dim3(256), 0, st,
-                                       (const double*)th.data, th.ld, n, n, fl);
-                else
-                    hipLaunchKernelGGL((sign_flags_kernel<float>), dim3(elem_grid(n * n)), dim3(256), 0, st,
-                                       (const float*)th.data, th.ld, n, n, fl);
-                check_launch("sign_flags");
-            }
-            std::vector<int> flags(p->thetas.size() * 2);
-            SKF_HIP(hipMemcpyAsync(flags.data(), p->theta_flags.ptr, flags.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-            SKF_HIP(hipStreamSynchronize(st));
-            for (size_t k = 0; k < p->thetas.size(); ++k) {
-                ThetaState& th = p->thetas[k];
-                if (th.sparse) continue;
-                th.has_pos = flags[2 * k] != 0;
-                th.has_neg = flags[2 * k + 1] != 0;
-                if (!p->bf16) continue;
-                const int64_t n = p->types[th.type].n;
-                for (int half = 0; half < 2; ++half) {
-                    if (!(half == 0 ? th.has_pos : th.has_neg)) continue;
-                    Slot& dst = half == 0 ? th.Pb : th.Nb;
-                    SKF_HIP(hipMemsetAsync(dst.ptr, 0, dst.bytes, st));
-                    hipLaunchKernelGGL(split_to_bf16_kernel, dim3(elem_grid(n * n)), dim3(256), 0, st, (uint16_t*)dst.ptr,
-                                       th.ldb, (const float*)th.data, th.ld, n, n, half == 0 ? AOP_POS : AOP_NEG);
-                    check_launch("split_to_bf16");
-                }
-            }
-        }
-        if (p->variant != SKF_TRANSFORM) {
-            std::vector<int> n_pad, n_orig;
-            for (TypeState& t : p->types) {
-                n_pad.push_back(t.n_pad);
-                n_orig.push_back(t.c);
-            }
-            SKF_HIP(hipMemcpyAsync(p->eigN.ptr, n_pad.data(), n_pad.size() * sizeof(int), hipMemcpyHostToDevice, st));
-            SKF_HIP(hipMemcpyAsync(p->eigNorig.ptr, n_orig.data(), n_orig.size() * sizeof(int), hipMemcpyHostToDevice, st));
-            SKF_HIP(hipStreamSynchronize(st));     // the host vectors die here; bind is not on the hot path
-        }
-        if (p->small_fused && (p->sw.no_small_fused || p->sw.no_small_chain)) p->small_fused = false;
-        if (p->small_fused) {
-            // job tables and the pointer table of the fused small-graph schedule (skf_small.h)
-            SmTables tb;
-            memset(&tb, 0, sizeof tb);
-            tb.n_types = (int)p->types.size(); tb.n_rels = (int)p->rels.size(); tb.n_thetas = (int)p->thetas.size();
-            tb.nan_upd = 1;                                   // DFMF: nan_to_num on the A / B / C / D terms (_dfmf.py:254-276)
-            tb.wpart = (double*)p->sm_wpart.ptr; tb.gpart = (double*)p->sm_gpart.ptr;
-            tb.tickets = (int*)p->sm_tickets.ptr;
-            SKF_HIP(hipMemsetAsync(p->sm_tickets.ptr, 0, p->sm_tickets.bytes, st));
-            tb.eigA = (double*)p->eigA.ptr; tb.eigV = (double*)p->eigV.ptr; tb.eigOk = (int*)p->eigOk.ptr;
-            tb.eig_stride = p->eig_stride;
-            tb.chol_thr = chol_rel_threshold(p->sw);
-            tb.eig.A = (double*)p->eigA.ptr; tb.eig.V = (double*)p->eigV.ptr; tb.eig.Vs = (double*)p->eigVs.ptr;
-            tb.eig.w = (double*)p->eigW.ptr; tb.eig.stride = p->eig_stride; tb.eig.wstride = p->eig_maxn;
-            tb.eig.n = (const int*)p->eigN.ptr; tb.eig.n_orig = (const int*)p->eigNorig.ptr;
-            tb.eig.chol_ok = (int*)p->eigOk.ptr;
-            tb.eig.max_sweeps = 30;
-            tb.defl_lo = deflation_lo(p->sw); tb.defl_hi = 1e-7;
-            tb.lds_rank = p->eig_maxn < 64 ? p->eig_maxn : 64;          // packed r (r + 1) / 2 doubles inside the staging tiles
-            tb.sweep_single = p->sw.small_sweep1 ? 1 : 0;
-            int64_t goff = 0, woff = 0;
-            for (size_t i = 0; i < p->types.size(); ++i) {
-                TypeState& t = p->types[i];
-                SmType& d = tb.t[i];
-                d.G = t.G.ptr; d.E = t.E.ptr; d.D = t.D.ptr; d.Gram = (double*)t.Gram.ptr; d.K = (double*)t.K.ptr;
-                d.n = t.n; d.c = t.c; d.gpart_off = goff; d.n_gjobs = (int)((t.n + SM_GROWS - 1) / SM_GROWS);
-                goff += (int64_t)align_up((size_t)d.n_gjobs * t.c * t.c, 16);
-                for (const ThetaState& th : p->thetas) d.has_theta = d.has_theta || th.type == (int)i;
-            }
-            for (size_t k = 0; k < p->rels.size(); ++k) {
-                RelState& r = p->rels[k];
-                SmRel& d = tb.r[k];
-                d.R = r.R; d.ldr = r.ldr; d.P = r.P.ptr; d.Q = r.SmQ.ptr; d.n_qparts = r.sm_qparts; d.W = (double*)r.W.ptr; d.S = (double*)r.S.ptr;
-                d.Bp = (double*)r.SmBp.ptr; d.Bn = (double*)r.SmBn.ptr; d.Dp = (double*)r.SmDp.ptr; d.Dn = (double*)r.SmDn.ptr;
-                d.row = r.row; d.col = r.col; d.wpart_off = woff; d.n_pjobs = (int)((p->types[r.row].n + 63) / 64);
-                woff += (int64_t)align_up((size_t)d.n_pjobs * p->types[r.row].c * p->types[r.col].c, 16);
-            }
-            for (size_t k = 0; k < p->thetas.size(); ++k) {
-                ThetaState& th = p->thetas[k];
-                tb.th[k].rp = (const int64_t*)th.Rp.ptr; tb.th[k].ci = (const int*)th.Ci.ptr; tb.th[k].vv = th.Vv.ptr;
-                tb.th[k].type = th.type;
-            }
-            SKF_HIP(hipMemcpyAsync(p->sm_tables.ptr, &tb, sizeof tb, hipMemcpyHostToDevice, st));
-            p->sm_batch_host.assign(1, p->sm_tables.ptr);
-            SKF_HIP(hipMemcpyAsync(p->sm_batch.ptr, p->sm_batch_host.data(), sizeof(void*), hipMemcpyHostToDevice, st));
-            SKF_HIP(hipMemcpyAsync(p->sm_jobs1.ptr, p->sm_j1.data(), p->sm_j1.size() * sizeof(SmJob), hipMemcpyHostToDevice, st));
-            SKF_HIP(hipMemcpyAsync(p->sm_jobs3.ptr, p->sm_j3.data(), p->sm_j3.size() * sizeof(SmJob), hipMemcpyHostToDevice, st));
-            SKF_HIP(hipStreamSynchronize(st));     // (`tb` dies here; bind is not on the hot path)
-        }
-        if (p->owned) {
-            // padded layouts of the exchanges: rows past the objects of a type stay zero for good (they are gathered and
-            // scattered with the rest), the Gram range is summed as a whole
-            for (TypeState& t : p->types) {
-                SKF_HIP(hipMemsetAsync(t.G.ptr, 0, t.G.bytes, st));
-                SKF_HIP(hipMemsetAsync(t.E.ptr, 0, t.E.bytes, st));
-                SKF_HIP(hipMemsetAsync(t.D.ptr, 0, t.D.bytes, st));
-            }
-            for (RelState& r : p->rels) SKF_HIP(hipMemsetAsync(r.Q.ptr, 0, r.Q.bytes, st));
-            SKF_HIP(hipMemsetAsync((char*)ws + p->xg_off, 0, p->xg_bytes, st));
-            SKF_HIP(hipMemsetAsync((char*)ws + p->xw_off, 0, p->xw_bytes, st));
-            if (!p->cs && !p->sw.no_overlap && p->sw.comm_stream)
-                SKF_HIP(hipStreamCreateWithFlags(&p->cs, hipStreamNonBlocking));
-        }
-        p->pipeline = !p->sw.no_pipeline;
-        // (a plan on the three-launch schedule of small graphs issues everything on the caller's stream: no second stream to
-        // create and destroy -- at ten restarts of the README graph the streams of the plans were 4 of 30 ms)
-        if (p->variant != SKF_TRANSFORM && !p->aux && !p->small_fused) {
-            if (!p->sw.no_overlap) {
-                {   // the second stream at the LOWEST priority: its launches fill what the contractions of the main stream
-                    // leave free instead of taking CUs from them (config 5 +0.9 %, config 3 +0.5 % against the default priority)
-                    int lo = 0, hi = 0;
-                    SKF_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-                    // (plans with owned rows, where the second stream carries the critical path of a rank: lowest / default /
-                    // highest priority measured equal -- 2.58 / 2.56 / 2.55 ms for rank 3 of 8 at config 3 --, a running
-                    // contraction workgroup is not preempted; profiles/r04_owned_rank_emulation.txt)
-                    SKF_HIP(hipStreamCreateWithPriority(&p->aux, hipStreamNonBlocking, lo));
-                }
-                SKF_HIP(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
-                SKF_HIP(hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming));
-                p->overlap = true;
-            }
-        }
+        bind_relation_lists(p, st);
+        bind_bf16_copies(p, st);
+        bind_theta_csr(p, st);
+        bind_theta_halves(p, st);
+        bind_pinv_tables(p, st);
+        bind_small_tables(p, st);
+        bind_owned_clears(p, st);
+        bind_streams(p);
         if (p->graph_exec) {
             (void)hipGraphExecDestroy(p->graph_exec);
             p->graph_exec = nullptr;
@@ -1953,17 +1648,7 @@ int skf_complete_topk(int32_t dtype, const void* H, int64_t ldh, int64_t m, cons
             int64_t nnz = -1;
             SKF_HIP(hipMemcpyAsync(&nnz, excl_indptr + m, sizeof nnz, hipMemcpyDeviceToHost, st));
             SKF_HIP(hipStreamSynchronize(st));
-            int bad = nnz < 0 ? 1 : 0;
-            if (!bad) {
-                int* flag = (int*)workspace;
-                SKF_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
-                const int wgrid = (int)((m + 3) / 4 < 2048 ? (m + 3) / 4 : 2048);
-                hipLaunchKernelGGL(known_csr_check_kernel, dim3(wgrid), dim3(256), 0, st, excl_indptr, (const int*)excl_indices, m, n_cols, nnz, flag);
-                check_launch("known_csr_check");
-                SKF_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-                SKF_HIP(hipStreamSynchronize(st));
-            }
-            if (bad)
+            if (nnz < 0 || !csr_is_canonical(excl_indptr, (const int*)excl_indices, m, n_cols, nnz, (int*)workspace, st))
                 SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: the exclusion lists are not canonical for %lld rows x %lld columns (indptr from 0 "
                          "to the count, non-decreasing; indices in range and strictly ascending within a row)", (long long)m, (long long)n_cols);
         }
@@ -1989,14 +1674,13 @@ int skf_complete_entries(int32_t dtype, const void* H, int64_t ldh, int64_t m, c
         hipStream_t st = as_stream(stream);
         // the index check needs one device word and this operator has no workspace: the first word of `out` serves (every
         // out[e] is overwritten by the pass) and gets its old content back when the entries are refused
-        int keep = 0, bad = 0;
+        int keep = 0;
         int* flag = (int*)out;
         SKF_HIP(hipMemcpyAsync(&keep, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-        SKF_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
-        hipLaunchKernelGGL(complete_entries_check_kernel, dim3(elem_grid(n)), dim3(256), 0, st, (const int*)rows, (const int*)cols, n, m, n_cols, flag);
-        check_launch("complete_entries_check");
-        SKF_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-        SKF_HIP(hipStreamSynchronize(st));
+        const int bad = device_flag(flag, st, [&] {
+            hipLaunchKernelGGL(complete_entries_check_kernel, dim3(elem_grid(n)), dim3(256), 0, st, (const int*)rows, (const int*)cols, n, m, n_cols, flag);
+            check_launch("complete_entries_check");
+        });
         if (bad) {
             SKF_HIP(hipMemcpyAsync(flag, &keep, sizeof(int), hipMemcpyHostToDevice, st));
             SKF_HIP(hipStreamSynchronize(st));
@@ -2131,7 +1815,7 @@ int skf_fill_unknown(int32_t dtype, void* data, int64_t ld, int64_t rows, int64_
         if (rows == 0 || cols == 0) return;
         hipStream_t st = as_stream(stream);
         double* stats = (double*)workspace;
-        const int rgrid = (int)((rows + 3) / 4 < 2048 ? ((rows + 3) / 4 > 0 ? (rows + 3) / 4 : 1) : 2048);     // 4 waves per workgroup
+        const int rgrid = wave_grid(rows);
         if (dtype == SKF_F64) {
             double* X = (double*)data;
             if (strategy != FILL_CONST) {

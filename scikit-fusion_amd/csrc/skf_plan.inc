@@ -719,7 +719,7 @@ static void theta_terms_rows(skf_plan* p, int only_type, bool own_rows, hipStrea
         // an all-zero half is skipped
         if (th.sparse) {    // both halves in one pass over the CSR form, master precision
             if (th.nnz == 0) continue;
-            const int grid = (int)((nr + 3) / 4 < 2048 ? (nr + 3) / 4 : 2048);
+            const int grid = wave_grid(nr);
             if (p->f64)
                 hipLaunchKernelGGL((theta_spmm_kernel<double>), dim3(grid), dim3(256), 0, st, (const int64_t*)th.Rp.ptr + r0,
                                    (const int*)th.Ci.ptr, (const double*)th.Vv.ptr, (const double*)t.G.ptr, (double*)Er,

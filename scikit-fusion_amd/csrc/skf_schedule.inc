@@ -1,5 +1,5 @@
 // skf_schedule.inc -- part of the one translation unit skf_api.hip (textually included there, inside its namespaces; not a
-// header of its own): the relation pipeline on two streams, the three-launch iteration of small graphs, hipGraph capture, the fold-in, bind-time list construction.
+// header of its own): the relation pipeline on two streams, the three-launch iteration of small graphs, hipGraph capture, the fold-in.
 // ------------------------------------------------------------------------------------------
 // The same DFMF iteration as stage_contract + stage_backbone + stage_accumulate, scheduled as a pipeline over
 // the relations (whole, unmasked relations; every rank between 65 and 512; MFMA engine): the main stream runs
@@ -480,138 +480,4 @@ static void iterate_transform(skf_plan* p, hipStream_t st) {
     theta_terms(p, st);
     mult_update(p, tt, st);
     if (!p->thetas.empty()) refresh_gt(p, tt, st);      // SKF_BF16: the constraint products read the stored G^T
-}
-
-// The known entries of a masked relation as row lists and column lists (bind time): counts per (row, column part) on the
-// device, prefix sums on the host, fills on the device; the column lists are the transpose of the row lists, every
-// (column, row part) segment sorted by row.  R values come from the caller's relation, which is not referenced afterwards.
-template <typename TR, typename TM>
-static void build_known_lists_t(skf_plan* p, RelState& r, hipStream_t st) {
-    const int64_t rows = r.nr, cols = p->types[r.col].n;
-    const int pc = r.kn_pc, pr = r.kn_pr;
-    const int wgrid = (int)((rows + 3) / 4 < 2048 ? ((rows + 3) / 4 > 0 ? (rows + 3) / 4 : 1) : 2048);
-    int* cnt = (int*)r.KCnt.ptr;
-    hipLaunchKernelGGL(known_row_count_kernel, dim3(wgrid), dim3(256), 0, st, (const uint8_t*)r.Mb.ptr, r.ldmb, rows, cols, pc,
-                       r.kn_pw, cnt);
-    check_launch("known_row_count");
-    const size_t nseg_r = (size_t)rows * pc, nseg_c = (size_t)cols * pr;
-    std::vector<int> hc(std::max(nseg_r, nseg_c));
-    std::vector<int64_t> hp(std::max(nseg_r, nseg_c) + 1);
-    SKF_HIP(hipMemcpyAsync(hc.data(), cnt, nseg_r * 4, hipMemcpyDeviceToHost, st));
-    SKF_HIP(hipStreamSynchronize(st));
-    int64_t tot = 0;
-    for (size_t k = 0; k < nseg_r; ++k) { hp[k] = tot; tot += hc[k]; }
-    hp[nseg_r] = tot;
-    if (tot > r.kn_cap)
-        SKF_FAIL(SKF_E_INVALID, "a masked relation holds %lld known entries, more than the bound %lld given in skf_relation_desc.known_bound",
-                 (long long)tot, (long long)r.kn_cap);
-    r.kn_nnz = tot;
-    SKF_HIP(hipMemcpyAsync(r.KrPtr.ptr, hp.data(), (nseg_r + 1) * 8, hipMemcpyHostToDevice, st));
-    SKF_HIP(hipMemsetAsync(cnt, 0, 2 * nseg_c * 4, st));
-    SKF_HIP(hipStreamSynchronize(st));                      // (`hp` is reused below)
-    int* fillpos = cnt + nseg_c;
-    if (tot > 0) {
-        hipLaunchKernelGGL((known_row_fill_kernel<TR, TM>), dim3(wgrid), dim3(256), 0, st, (const uint8_t*)r.Mb.ptr, r.ldmb, rows, cols,
-                           pc, (const int64_t*)r.KrPtr.ptr, (const TR*)r.R_in, r.ld_in, (int*)r.KrIdx.ptr, (TM*)r.KrVal.ptr);
-        hipLaunchKernelGGL(known_col_count_kernel, dim3(wgrid), dim3(256), 0, st, (const int64_t*)r.KrPtr.ptr, (const int*)r.KrIdx.ptr,
-                           pc, rows, pr, r.kn_ph, cnt);
-        check_launch("known_row_fill");
-    }
-    SKF_HIP(hipMemcpyAsync(hc.data(), cnt, nseg_c * 4, hipMemcpyDeviceToHost, st));
-    SKF_HIP(hipStreamSynchronize(st));
-    int64_t t2 = 0;
-    for (size_t k = 0; k < nseg_c; ++k) { hp[k] = t2; t2 += hc[k]; }
-    hp[nseg_c] = t2;
-    SKF_HIP(hipMemcpyAsync(r.KcPtr.ptr, hp.data(), (nseg_c + 1) * 8, hipMemcpyHostToDevice, st));
-    if (tot > 0) {
-        hipLaunchKernelGGL(known_col_fill_kernel, dim3(wgrid), dim3(256), 0, st, (const int64_t*)r.KrPtr.ptr, (const int*)r.KrIdx.ptr,
-                           pc, rows, pr, r.kn_ph, (const int64_t*)r.KcPtr.ptr, fillpos, (int*)r.KcIdx.ptr);
-        hipLaunchKernelGGL(csc_sort_kernel, dim3(elem_grid((int64_t)nseg_c)), dim3(256), 0, st, (const int64_t*)r.KcPtr.ptr,
-                           (int*)r.KcIdx.ptr, (int64_t)nseg_c);
-        const int cgrid = (int)((cols + 3) / 4 < 2048 ? ((cols + 3) / 4 > 0 ? (cols + 3) / 4 : 1) : 2048);
-        hipLaunchKernelGGL((known_col_values_kernel<TR, TM>), dim3(cgrid), dim3(256), 0, st, (const int64_t*)r.KcPtr.ptr,
-                           (const int*)r.KcIdx.ptr, pr, cols, (const TR*)r.R_in, r.ld_in, (TM*)r.KcVal.ptr);
-        check_launch("known_col_fill");
-        // before the first iteration the completed relation is the known entries and zeros (_dfmc.py:287-292): E = R there
-        SKF_HIP(hipMemcpyAsync(r.KcE.ptr, r.KcVal.ptr, (size_t)tot * sizeof(TM), hipMemcpyDeviceToDevice, st));
-    }
-    SKF_HIP(hipMemsetAsync(r.Sp.ptr, 0, r.Sp.bytes, st));
-    if (r.FiB.bytes) SKF_HIP(hipMemsetAsync(r.FiB.ptr, 0, r.FiB.bytes, st));
-    SKF_HIP(hipStreamSynchronize(st));                      // the host vectors die here; bind is not on the hot path
-    r.R = nullptr;                                          // nothing reads the relation itself after this
-}
-// The same lists from the caller's CSR (SKF_REL_KNOWN_CSR): validated on the device first -- nothing gathers through them
-// before the host has read the verdict --, then the row lists are copies of the CSR with the part split points found by
-// binary search, and the column side is built as above, its values taken from the row lists.  Byte for byte the lists
-// build_known_lists_t makes from a dense relation + mask holding the same entries.  The stored entries of a
-// SKF_REL_SPARSE_CSR relation (unstored = zero) take the same way: same validation, same lists, no residual list.
-template <typename TR, typename TM>
-static void build_known_lists_csr_t(skf_plan* p, RelState& r, hipStream_t st) {
-    const int64_t rows = r.nr, cols = p->types[r.col].n, tot = r.kn_cap;
-    const int pc = r.kn_pc, pr = r.kn_pr;
-    const int wgrid = (int)((rows + 3) / 4 < 2048 ? ((rows + 3) / 4 > 0 ? (rows + 3) / 4 : 1) : 2048);
-    int* cnt = (int*)r.KCnt.ptr;
-    SKF_HIP(hipMemsetAsync(cnt, 0, sizeof(int), st));
-    hipLaunchKernelGGL(known_csr_check_kernel, dim3(wgrid), dim3(256), 0, st, r.csr_ptr, r.csr_idx, rows, cols, tot, cnt);
-    check_launch("known_csr_check");
-    int bad = 0;
-    SKF_HIP(hipMemcpyAsync(&bad, cnt, sizeof(int), hipMemcpyDeviceToHost, st));
-    SKF_HIP(hipStreamSynchronize(st));
-    if (bad)
-        SKF_FAIL(SKF_E_INVALID, "%s: the lists are not a canonical CSR of %lld x %lld with %lld entries (indptr from 0 "
-                 "to the count, non-decreasing; columns in range and strictly ascending within a row)",
-                 r.sp0 ? "SKF_REL_SPARSE_CSR" : "SKF_REL_KNOWN_CSR", (long long)rows, (long long)cols, (long long)tot);
-    r.kn_nnz = tot;
-    hipLaunchKernelGGL(parted_ptr_kernel, dim3(elem_grid(rows * pc + 1)), dim3(256), 0, st, r.csr_ptr, r.csr_idx, rows, pc, r.kn_pw,
-                       (int64_t*)r.KrPtr.ptr);
-    check_launch("known_csr_rows");
-    const size_t nseg_c = (size_t)cols * pr;
-    SKF_HIP(hipMemsetAsync(cnt, 0, 2 * nseg_c * 4, st));
-    int* fillpos = cnt + nseg_c;
-    if (tot > 0) {
-        SKF_HIP(hipMemcpyAsync(r.KrIdx.ptr, r.csr_idx, (size_t)tot * 4, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL((known_csr_values_kernel<TR, TM>), dim3(elem_grid(tot)), dim3(256), 0, st, (const TR*)r.csr_val, tot,
-                           (TM*)r.KrVal.ptr);
-        hipLaunchKernelGGL(known_col_count_kernel, dim3(wgrid), dim3(256), 0, st, (const int64_t*)r.KrPtr.ptr, (const int*)r.KrIdx.ptr,
-                           pc, rows, pr, r.kn_ph, cnt);
-        check_launch("known_csr_fill");
-    }
-    std::vector<int> hc(nseg_c);
-    std::vector<int64_t> hp(nseg_c + 1);
-    SKF_HIP(hipMemcpyAsync(hc.data(), cnt, nseg_c * 4, hipMemcpyDeviceToHost, st));
-    SKF_HIP(hipStreamSynchronize(st));
-    int64_t t2 = 0;
-    for (size_t k = 0; k < nseg_c; ++k) { hp[k] = t2; t2 += hc[k]; }
-    hp[nseg_c] = t2;
-    SKF_HIP(hipMemcpyAsync(r.KcPtr.ptr, hp.data(), (nseg_c + 1) * 8, hipMemcpyHostToDevice, st));
-    if (tot > 0) {
-        hipLaunchKernelGGL(known_col_fill_kernel, dim3(wgrid), dim3(256), 0, st, (const int64_t*)r.KrPtr.ptr, (const int*)r.KrIdx.ptr,
-                           pc, rows, pr, r.kn_ph, (const int64_t*)r.KcPtr.ptr, fillpos, (int*)r.KcIdx.ptr);
-        hipLaunchKernelGGL(csc_sort_kernel, dim3(elem_grid((int64_t)nseg_c)), dim3(256), 0, st, (const int64_t*)r.KcPtr.ptr,
-                           (int*)r.KcIdx.ptr, (int64_t)nseg_c);
-        const int cgrid = (int)((cols + 3) / 4 < 2048 ? ((cols + 3) / 4 > 0 ? (cols + 3) / 4 : 1) : 2048);
-        hipLaunchKernelGGL((known_col_values_csr_kernel<TM>), dim3(cgrid), dim3(256), 0, st, (const int64_t*)r.KcPtr.ptr,
-                           (const int*)r.KcIdx.ptr, pr, cols, (const int64_t*)r.KrPtr.ptr, (const int*)r.KrIdx.ptr, pc,
-                           (const TM*)r.KrVal.ptr, (TM*)r.KcVal.ptr);
-        check_launch("known_csr_cols");
-        // (known entries: E = R before the first iteration; a SKF_REL_SPARSE_CSR relation keeps no residuals)
-        if (r.KcE.ptr) SKF_HIP(hipMemcpyAsync(r.KcE.ptr, r.KcVal.ptr, (size_t)tot * sizeof(TM), hipMemcpyDeviceToDevice, st));
-    }
-    if (r.Sp.ptr) SKF_HIP(hipMemsetAsync(r.Sp.ptr, 0, r.Sp.bytes, st));
-    if (r.FiB.bytes) SKF_HIP(hipMemsetAsync(r.FiB.ptr, 0, r.FiB.bytes, st));
-    SKF_HIP(hipStreamSynchronize(st));                      // the host vectors die here; bind is not on the hot path
-    r.R = nullptr;
-    r.csr_ptr = nullptr; r.csr_idx = nullptr; r.csr_val = nullptr;      // not referenced after bind
-}
-static void build_known_lists_csr(skf_plan* p, RelState& r, hipStream_t st) {
-    // (SKF_REL_SPARSE_CSR hands its values over in the master type -- SKF_BF16: f32, never rounded to bf16)
-    if (p->bf16 && r.sp0) build_known_lists_csr_t<float, float>(p, r, st);
-    else if (p->bf16) build_known_lists_csr_t<uint16_t, float>(p, r, st);
-    else if (p->f64) build_known_lists_csr_t<double, double>(p, r, st);
-    else build_known_lists_csr_t<float, float>(p, r, st);
-}
-static void build_known_lists(skf_plan* p, RelState& r, hipStream_t st) {
-    if (p->bf16) build_known_lists_t<uint16_t, float>(p, r, st);
-    else if (p->f64) build_known_lists_t<double, double>(p, r, st);
-    else build_known_lists_t<float, float>(p, r, st);
 }

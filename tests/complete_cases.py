@@ -311,6 +311,14 @@ def refusals_case(dtype='f64'):
     assert raw.entries([m - 1], [n_cols - 1]).shape == (1,)
 
 
+def refusal_order_case(which, dtype='f64'):
+    """Top-k of 4 rows x 6 columns with defective exclusion lists: refused by the validation kernel alone."""
+    import known_csr_cases as KC
+    G_row, S, G_col = lattice_factors(4, 6, (2, 2))
+    raw = Raw(dtype, np.dot(G_row, S), G_col)
+    KC.refused_after_one_launch(lambda w: raw.topk(2, lists=KC.small_lists(w)), which)
+
+
 # ---- 4. public API ------------------------------------------------------------------------------------------------------------
 def api_case(kind, dtype, monkeypatch):
     """kind 'dfmc-masked': Dfmc on a MaskedArray relation; 'dfmf-csr': Dfmf on a scipy.sparse relation (40 x 30, ranks 5 / 4)."""

@@ -81,3 +81,46 @@ def csr_against_mask(n, ranks, known_share, dtype, parts, monkeypatch, seed=0, e
     assert np.array_equal(Ec, Em), 'squared errors: CSR-fed differs from mask-fed'
     assert wc <= wm - mb_bytes, 'workspace: CSR-fed %d B, mask-fed %d B, packed masks %d B' % (wc, wm, mb_bytes)
     return Gc, Sc, Ec
+
+
+# ---- refusal order: every user of the shared CSR check answers after that one kernel -----------------------------------
+DEFECTS = ('range', 'descending', 'indptr')
+
+
+def small_lists(which):
+    """Six entries of a 4 x 6 relation as CSR: canonical ('ok'), or with a column out of range, a descending pair, or a
+    backward indptr step (the lists of test_invalid_lists_are_refused_before_any_gather)."""
+    indptr = np.array([0, 2, 4, 4, 6], dtype=np.int64)
+    idx = np.array([1, 3, 0, 2, 4, 5], dtype=np.int32)
+    if which == 'range':
+        idx[3] = 6                                      # column 6 of 6
+    elif which == 'descending':
+        idx[2], idx[3] = 2, 0
+    elif which == 'indptr':
+        indptr[2] = 1                                   # 2 -> 1 -> 4: a negative step
+    else:
+        assert which == 'ok'
+    return indptr, idx
+
+
+def small_plan(which, variant, unstored, target=None):
+    """A plan of 4 x 6 objects, ranks 2, whose only relation is small_lists(which), already on the device (no host check)."""
+    from skfusion_amd._engine import DeviceKnownEntries
+    indptr, idx = small_lists(which)
+    mem = nat.get_runtime().mem
+    dev = DeviceKnownEntries(mem.from_host(indptr), mem.from_host(idx), mem.from_host(np.random.RandomState(0).rand(6)), (4, 6), 6,
+                             unstored=unstored)
+    return DevicePlan(['a', 'b'], {'a': 4, 'b': 6}, {'a': 2, 'b': 2}, [('a', 'b', dev, None)], [], variant, target=target)
+
+
+def refused_after_one_launch(call, which):
+    """`call(which)` with defective lists ends in SKF_E_INVALID after exactly one kernel launch -- the validation, nothing
+    that gathers through the lists --, and the same call with the canonical lists succeeds afterwards."""
+    import pytest
+    from skfusion_amd._engine import launch_count
+    before = launch_count()
+    with pytest.raises(nat.SkfNativeError) as err:
+        call(which)
+    assert err.value.code == nat.SKF_E_INVALID
+    assert launch_count() - before == 1
+    call('ok')

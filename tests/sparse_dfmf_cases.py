@@ -352,3 +352,9 @@ def csr_against_oracle(n, ranks, iters, tol, what, seed=0, **kw):
         within(relerr(Ss[k], So[i, j][0]), tol, '%s: CSR-fed f64 engine vs oracle, S_%d' % (what, k))
         want = np.sum((M - Go[i, i] @ So[i, j][0] @ Go[j, j].T) ** 2)
         within(abs(Es[-1][k] - want) / want, tol, '%s: CSR-fed f64 engine vs oracle, squared error of relation %d' % (what, k))
+
+
+def refusal_order_case(which):
+    """A stored-entry relation (SKF_REL_SPARSE_CSR) with defective lists: refused by the validation kernel alone."""
+    import known_csr_cases as KC
+    KC.refused_after_one_launch(lambda w: KC.small_plan(w, nat.SKF_DFMF, 'zero').close(), which)

@@ -356,6 +356,13 @@ def invalid_lists_case(kind, dtype='f64', by_col=False):
         DevicePlan(types, n, ranks, [('a', 'b', good, None)], [], nat.SKF_TRANSFORM, dtype=dtype, target=target).close()
 
 
+def refusal_order_case(which):
+    """A fold-in relation (SKF_REL_FOLD_CSR, lists along the target's 4 objects) with defective lists: refused by the
+    validation kernel alone."""
+    import known_csr_cases as KC
+    KC.refused_after_one_launch(lambda w: KC.small_plan(w, nat.SKF_TRANSFORM, 'zero', target='a').close(), which)
+
+
 # ---- 5. the public API -------------------------------------------------------------------------------------------------
 def fitted(n_u, n_m, n_g, ranks, n_run=1, seed=1):
     """A small fitted model: users x movies and movies x genres, both dense, f64."""

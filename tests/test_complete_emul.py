@@ -44,6 +44,11 @@ def test_refusals():
     CC.refusals_case('f32')
 
 
+@pytest.mark.parametrize('which', ['range', 'descending', 'indptr'])
+def test_invalid_exclusion_lists_are_refused_before_any_gather(which):
+    CC.refusal_order_case(which)
+
+
 def test_refusals_need_no_device():
     """The product library (cross-compiled for gfx950), no device: these checks answer before any HIP call."""
     if not os.path.exists(nat.LIB_PATH):

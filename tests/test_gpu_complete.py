@@ -36,6 +36,11 @@ def test_refusals():
     CC.refusals_case('f32')
 
 
+@pytest.mark.parametrize('which', ['range', 'descending', 'indptr'])
+def test_invalid_exclusion_lists_are_refused_before_any_gather(which):
+    CC.refusal_order_case(which)
+
+
 @pytest.mark.parametrize('dtype', ['f64', 'f32', 'bf16'])
 @pytest.mark.parametrize('kind', ['dfmc-masked', 'dfmf-csr'])
 def test_public_api(kind, dtype, monkeypatch):

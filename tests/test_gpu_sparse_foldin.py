@@ -59,6 +59,11 @@ def test_invalid_lists_are_refused_at_bind(kind, by_col):
     FC.invalid_lists_case(kind, 'bf16', by_col)
 
 
+@pytest.mark.parametrize('which', ['range', 'descending', 'indptr'])
+def test_invalid_fold_lists_are_refused_before_any_gather(which):
+    FC.refusal_order_case(which)
+
+
 def test_api_formats_and_switches(monkeypatch):
     FC.api_formats_case('f64', ('csr', 'csc', 'coo'), monkeypatch)
 

@@ -49,6 +49,11 @@ def test_invalid_lists_are_refused_for_unmasked_dfmc_relations():
     SC.invalid_lists_case('order', 'f32', nat.SKF_DFMC)
 
 
+@pytest.mark.parametrize('which', ['range', 'descending', 'indptr'])
+def test_invalid_stored_entries_are_refused_before_any_gather(which):
+    SC.refusal_order_case(which)
+
+
 def test_flag_combinations():
     SC.invalid_flag_cases()
 

@@ -60,6 +60,11 @@ def test_invalid_lists_are_refused_at_bind(kind, by_col):
     FC.invalid_lists_case(kind, 'f64', by_col)
 
 
+@pytest.mark.parametrize('which', ['range', 'descending', 'indptr'])
+def test_invalid_fold_lists_are_refused_before_any_gather(which):
+    FC.refusal_order_case(which)
+
+
 def test_creation_checks_need_no_device():
     """The product library (cross-compiled for gfx950), no device: the plan-creation checks answer before any HIP call."""
     if not os.path.exists(nat.LIB_PATH):
