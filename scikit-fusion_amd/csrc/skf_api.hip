@@ -1,5 +1,5 @@
 // skf_api.hip -- C ABI (include/skfusion_hip.h) and the host-side plan / launch schedule of the
-// DFMF / DFMC / fold-in iteration.  Kernels: skf_kernels.h.
+// DFMF / DFMC / fold-in iteration.  Kernels: skf_kernels.h; the pseudo-inverse: skf_pinv.h.
 //
 // One iteration (reference _dfmf.py:228-296, 2-GEMM form of SURVEY.md 7.0; everything reads the
 // OLD factors, G is replaced at the very end):
@@ -14,6 +14,7 @@
 //   G_i <- G_i * sqrt(E_i / max(D_i, eps))                                  (:294-296)
 #include "skf_kernels.h"
 #include "skf_known.h"
+#include "skf_pinv.h"
 #include "skf_small.h"
 #include "skf_complete.h"
 // the product build compiles the GEMM-class kernel templates in units of their own, side by side with this file
@@ -115,6 +116,8 @@ static inline int wave_grid(int64_t rows) {
 #include "skf_gemm_launch.inc"
 
 #include "skf_plan.inc"
+
+#include "skf_pinv.inc"
 
 #include "skf_stages.inc"
 
@@ -1695,9 +1698,7 @@ int skf_complete_entries(int32_t dtype, const void* H, int64_t ldh, int64_t m, c
 int skf_pinv_sym_workspace_bytes(int32_t n, size_t* bytes) {
     return guarded([&] {
         if (n <= 0 || n > EIGH_MAXN - 1 || !bytes) SKF_FAIL(SKF_E_INVALID, "bad order");
-        const size_t np = (size_t)(n + 1) / 2 * 2;
-        *bytes = align_up(np * np * 8, 256) * 3 + align_up(np * 8, 256) + 512;
-        if (n > SWEEP_MAXN) *bytes += defl_scratch_bytes(1, (int64_t)np * np) + 256;
+        *bytes = pinv_sym_layout(n).total;
     });
 }
 
@@ -1708,70 +1709,28 @@ int skf_pinv_sym(int32_t dtype, const void* A, int64_t lda, void* K, int64_t ldk
         if (skf_pinv_sym_workspace_bytes(n, &need) != SKF_OK) SKF_FAIL(SKF_E_INVALID, "bad order %d", n);
         if (!A || !K || !ws || ws_bytes < need) SKF_FAIL(SKF_E_WORKSPACE, "pinv workspace too small / null pointer");
         if (dtype != SKF_F64 && dtype != SKF_F32) SKF_FAIL(SKF_E_INVALID, "bad dtype");
-        hipStream_t st = as_stream(stream);
         const int np = (n + 1) / 2 * 2;
-        const size_t mat = align_up((size_t)np * np * 8, 256);
+        const PinvSymLayout l = pinv_sym_layout(n);
         char* base = (char*)ws;
-        double* eA = (double*)base;
-        double* eV = (double*)(base + mat);
-        double* eVs = (double*)(base + 2 * mat);
-        double* eW = (double*)(base + 3 * mat);
-        int* eN = (int*)(base + 3 * mat + align_up((size_t)np * 8, 256));
-        int* eNo = eN + 16;
-        int* eOk = eN + 32;
-        const int total = np * np;
-        if (dtype == SKF_F64)
-            hipLaunchKernelGGL((eigh_pack_kernel<double>), dim3(elem_grid(total)), dim3(256), 0, st, eA, np,
-                               (const double*)A, lda, n, eN, eNo);
-        else
-            hipLaunchKernelGGL((eigh_pack_kernel<float>), dim3(elem_grid(total)), dim3(256), 0, st, eA, np,
-                               (const float*)A, lda, n, eN, eNo);
-        check_launch("eigh_pack");
-        EighArgs e;
-        e.A = eA; e.V = eV; e.Vs = eVs; e.w = eW; e.stride = (int64_t)np * np; e.wstride = np;
-        e.n = eN; e.n_orig = eNo; e.chol_ok = eOk; e.max_sweeps = 30;
-        const int tot2 = n * n;
         const Switches sw = Switches::read();          // stand-alone operator: no plan to hold them
-        // fast path: the blocked sweep for orders 65 .. 256 (writes a contiguous f64 K itself), else Cholesky inverse + unpack
-        const bool sweep = dtype == SKF_F64 && ldk == n && sweep_takes(sw, n);
-        if (sweep) {
-            PinvBatch pb;
-            memset(&pb, 0, sizeof pb);
-            pb.K[0] = (double*)K; pb.c[0] = n; pb.n_pad[0] = np;
-            launch_sweep(sw, e, pb, 1, n, st);
-        } else {
-            launch_chol(sw, e, 1, np, st);
-            if (dtype == SKF_F64)
-                hipLaunchKernelGGL((chol_unpack_kernel<double>), dim3(elem_grid(tot2)), dim3(256), 0, st, (double*)K, ldk,
-                                   eV, np, n, eOk);
-            else
-                hipLaunchKernelGGL((chol_unpack_kernel<float>), dim3(elem_grid(tot2)), dim3(256), 0, st, (float*)K, ldk,
-                                   eV, np, n, eOk);
-            check_launch("chol_unpack");
-        }
-        if (sweep && defl_multi_takes(sw, n)) {      // orders above 256: the deflation over several workgroups first
-            PinvBatch pb;
-            memset(&pb, 0, sizeof pb);
-            pb.K[0] = (double*)K; pb.c[0] = n; pb.n_pad[0] = np;
-            char* scratch = base + align_up(mat * 3 + align_up((size_t)np * 8, 256) + 512, 256);
-            launch_deflation_multi(sw, SKF_ENGINE_MFMA, e, pb, 1, n, scratch, st);
-        }
-        {
-            static DeviceOnce once;
-            allow_dynamic_lds(once, pchol_pinv_kernel, PCHOL_LDS_BYTES);
-        }
-        const int lr = np < PCHOL_LDS_R ? np : PCHOL_LDS_R;
-        hipLaunchKernelGGL(pchol_pinv_kernel, dim3(1), dim3(EIGH_THREADS), (size_t)lr * (lr + 1) / 2 * 8, st, e, deflation_lo(sw), 1e-7, lr);
-        check_launch("pchol_pinv");
-        hipLaunchKernelGGL(jacobi_eigh_kernel, dim3(1), dim3(EIGH_THREADS), 0, st, e);
-        check_launch("jacobi_eigh");
-        if (dtype == SKF_F64)
-            hipLaunchKernelGGL((eigh_unpack_pinv_kernel<double>), dim3(elem_grid(tot2)), dim3(256), 0, st, (double*)K,
-                               ldk, eVs, eV, np, n, eOk);
-        else
-            hipLaunchKernelGGL((eigh_unpack_pinv_kernel<float>), dim3(elem_grid(tot2)), dim3(256), 0, st, (float*)K,
-                               ldk, eVs, eV, np, n, eOk);
-        check_launch("eigh_unpack");
+        PinvBatch pb;
+        memset(&pb, 0, sizeof pb);
+        pb.gram[0] = A; pb.ldg[0] = lda;
+        pb.K[0] = K; pb.ldk[0] = ldk;
+        pb.c[0] = n; pb.n_pad[0] = np;
+        PinvRun r;
+        r.sw = &sw; r.engine = SKF_ENGINE_MFMA;
+        r.e.A = (double*)(base + l.A); r.e.V = (double*)(base + l.V); r.e.Vs = (double*)(base + l.Vs);
+        r.e.w = (double*)(base + l.w); r.e.stride = (int64_t)np * np; r.e.wstride = np;
+        r.e.n = (const int*)(base + l.n); r.e.n_orig = (const int*)(base + l.n_orig); r.e.chol_ok = (int*)(base + l.ok);
+        r.e.max_sweeps = 30;
+        r.pb = &pb; r.nb = 1; r.max_c = n; r.max_pad = np;
+        r.lds_order = np;
+        r.dtype = dtype;
+        r.k_direct = dtype == SKF_F64 && ldk == n;     // else: Cholesky inverse + unpack into the caller's type and stride
+        r.defl_scratch = n > SWEEP_MAXN ? base + l.defl : nullptr;
+        r.write_orders = true;
+        run_pinv(r, as_stream(stream));
     });
 }
 

@@ -1,5 +1,5 @@
 // skf_plan.inc -- part of the one translation unit skf_api.hip (textually included there, inside its namespaces; not a
-// header of its own): the plan: switches, per-type / per-relation state, workspace slots, and the launch helpers of one iteration (Gram, pseudo-inverse routes, constraints, side updates, contractions).
+// header of its own): the plan: switches, per-type / per-relation state, workspace slots, and the launch helpers of one iteration (Gram, constraints, side updates, contractions; the pseudo-inverse: skf_pinv.inc).
 // ------------------------------------------------------------------------------------------
 // plan
 // ------------------------------------------------------------------------------------------
@@ -422,247 +422,6 @@ static void refresh_gt(skf_plan* p, TypeState& t, hipStream_t st) {
     launch_to_bf16<float>((uint16_t*)t.GTb.ptr, t.ldgt, (const float*)t.G.ptr, (int64_t)t.c, t.n, (int64_t)t.c, true, st);
     if (t.Grow.ptr)        // the bf16 rows for the list passes (their all-zero last row is never written)
         launch_to_bf16<float>((uint16_t*)t.Grow.ptr, t.ldrow, (const float*)t.G.ptr, (int64_t)t.c, t.n, (int64_t)t.c, false, st);
-}
-
-// Relative pivot threshold of the Cholesky fast path: below it the Gram matrix goes to the deflation / the
-// eigen-solver.  SKF_PINV_JACOBI=1 forces the eigen path with its exact singular-value cut-off (tests).
-static double chol_rel_threshold(const Switches& sw) { return sw.pinv_jacobi ? 1e300 : 1e-8; }
-// lower edge of the deflation's gap test
-static double deflation_lo(const Switches& sw) { return sw.pinv_jacobi ? 1e300 : 1e-10; }
-
-// Cholesky fast path: the LDS-blocked kernel up to order CHOLB_MAXN, the plain one beyond
-static void launch_chol(const Switches& sw, const EighArgs& e, int batch, int max_order, hipStream_t st) {
-    if (max_order <= CHOLS_MAXN && !sw.chol_no_small && !sw.chol_unblocked) {
-        hipLaunchKernelGGL(chol_inverse_small_kernel, dim3((unsigned)batch), dim3(64), 0, st, e, chol_rel_threshold(sw));
-    } else if (max_order <= CHOLB_MAXN && !sw.chol_unblocked) {
-        size_t wave_tiles = (size_t)(EIGH_THREADS / 64) * CHOLB_NB * (CHOLB_NB + 1);
-        size_t panel = (size_t)CHOLB_NB * max_order;
-        size_t smem = ((size_t)CHOLB_NB * (CHOLB_NB + 1) + (panel > wave_tiles ? panel : wave_tiles)) * sizeof(double);
-        static DeviceOnce once;
-        allow_dynamic_lds(once, chol_inverse_blocked_kernel,
-                          (int)(((size_t)CHOLB_NB * (CHOLB_NB + 1) + (size_t)CHOLB_NB * CHOLB_MAXN) * sizeof(double)));
-        hipLaunchKernelGGL(chol_inverse_blocked_kernel, dim3((unsigned)batch), dim3(EIGH_THREADS), smem, st, e,
-                           chol_rel_threshold(sw));
-    } else {
-        hipLaunchKernelGGL(chol_inverse_kernel, dim3((unsigned)batch), dim3(EIGH_THREADS), 0, st, e, chol_rel_threshold(sw));
-    }
-    check_launch("chol_inverse");
-}
-
-// The blocked sweep of `nb` matrices of order <= max_c: from order sw.sweep_step_min (default: always) one launch per block
-// step with the rank-32 update of the step spread over row slabs -- orders up to SWEEP_MAXN with the panel in LDS, up to
-// EIGH_MAXN with the column operands from memory --, else (orders <= SWEEP_MAXN) one workgroup per matrix in one launch.
-static bool sweep_steps(const Switches& sw, int max_c) { return sw.sweep_step_min > 0 && max_c >= sw.sweep_step_min; }
-static bool sweep_takes(const Switches& sw, int max_c) {
-    if (max_c <= CHOLS_MAXN || sw.no_sweep || sw.chol_unblocked || sw.pinv_jacobi) return false;
-    return max_c <= SWEEP_MAXN || (sweep_steps(sw, max_c) && max_c <= EIGH_MAXN && !sw.no_sweep_big);
-}
-static void launch_sweep(const Switches& sw, const EighArgs& e, const PinvBatch& pb, int nb, int max_c, hipStream_t st) {
-    if (sweep_steps(sw, max_c)) {
-        const bool big = max_c > SWEEP_MAXN;
-        static DeviceOnce once, once_big;
-        if (big) allow_dynamic_lds(once_big, sweep_step_kernel<true>, SWEEP_BIG_LDS_BYTES);
-        else allow_dynamic_lds(once, sweep_step_kernel<false>, SWEEP_LDS_BYTES);
-        const int rs = big ? SWEEP_NB : sw.sweep_rows;
-        const int slabs = (max_c + rs - 1) / rs, steps = (max_c + SWEEP_NB - 1) / SWEEP_NB;
-        for (int step = 0; step < steps; ++step) {
-            if (big)
-                hipLaunchKernelGGL(sweep_step_kernel<true>, dim3((unsigned)nb, (unsigned)slabs), dim3(SWEEP_THREADS), SWEEP_BIG_LDS_BYTES, st,
-                                   e, pb, chol_rel_threshold(sw), step, rs);
-            else
-                hipLaunchKernelGGL(sweep_step_kernel<false>, dim3((unsigned)nb, (unsigned)slabs), dim3(SWEEP_THREADS), SWEEP_LDS_BYTES, st, e,
-                                   pb, chol_rel_threshold(sw), step, rs);
-            check_launch("sweep_step");
-        }
-        return;
-    }
-    static DeviceOnce once;
-    allow_dynamic_lds(once, sweep_inverse_kernel, SWEEP_LDS_BYTES);
-    hipLaunchKernelGGL(sweep_inverse_kernel, dim3((unsigned)nb), dim3(SWEEP_THREADS), SWEEP_LDS_BYTES, st, e, pb, chol_rel_threshold(sw));
-    check_launch("sweep_inverse");
-}
-
-// Rank-revealing deflation over several workgroups (skf_kernels.h, pchol_step_kernel) for the matrices of a batch whose fast
-// path failed, orders above SWEEP_MAXN: every launch is gated on the device (chol_ok, the verdict of the steps, the verdict of
-// the sweep over B), the host issues the sequence blind.  K[b]: c x c f64, ld = c.  `scratch`: defl_scratch_bytes(nb, stride).
-static size_t defl_scratch_bytes(int nb, int64_t stride) {
-    return align_up((size_t)3 * nb * stride * 8, 256) + align_up((size_t)nb * 2 * EIGH_MAXN * 8, 256) +
-           align_up((size_t)nb * 4 * 8, 256) + align_up((size_t)nb * 8 * sizeof(int), 256);
-}
-static bool defl_multi_takes(const Switches& sw, int max_c) {
-    return max_c > SWEEP_MAXN && max_c < EIGH_MAXN && sweep_takes(sw, max_c) && !sw.pinv_jacobi;
-}
-static void launch_deflation_multi(const Switches& sw, int engine, const EighArgs& e, const PinvBatch& pb, int nb, int max_c,
-                                   void* scratch, hipStream_t st) {
-    char* base = (char*)scratch;
-    double* M0 = (double*)base;
-    double* M1 = M0 + (size_t)nb * e.stride;
-    double* Binv = M1 + (size_t)nb * e.stride;
-    base += align_up((size_t)3 * nb * e.stride * 8, 256);
-    DeflArgs da;
-    da.d = (double*)base;
-    base += align_up((size_t)nb * 2 * EIGH_MAXN * 8, 256);
-    da.vals = (double*)base;
-    base += align_up((size_t)nb * 4 * 8, 256);
-    da.state = (int*)base;
-    da.n_defl = da.state + 4 * nb;
-    da.gate = da.n_defl + nb;
-    da.ok2 = da.gate + nb;
-    da.rank = da.ok2 + nb;
-    const int np = max_c + (max_c & 1);
-    hipLaunchKernelGGL(pchol_init_kernel, dim3(elem_grid((int64_t)np * np), (unsigned)nb), dim3(256), 0, st, e, da);
-    check_launch("pchol_init");
-    const int steps = 2 * cdiv(max_c, DEFL_NB) + 1, slabs = cdiv(max_c, DEFL_ROWS);
-    for (int step = 0; step < steps; ++step) {
-        hipLaunchKernelGGL(pchol_step_kernel, dim3((unsigned)nb, (unsigned)slabs), dim3(DEFL_THREADS), 0, st, e, da, deflation_lo(sw), 1e-7,
-                           step);
-        check_launch("pchol_step");
-    }
-    const int fin = steps & 1;
-    hipLaunchKernelGGL(pchol_verdict_kernel, dim3((unsigned)nb), dim3(64), 0, st, e, da, fin);
-    check_launch("pchol_verdict");
-    const GemmTypes f64{SKF_F64, SKF_F64, SKF_F64};
-    for (int b = 0; b < nb; ++b) {                      // B = L^T L  (Lt[k][i] = L[i][k], ld = the padded order)
-        const int c = pb.c[b], ld = pb.n_pad[b];
-        const double* Lt = e.V + (int64_t)b * e.stride;
-        GemmArgs g = gemm_args(Lt, ld, 1, Lt, 1, ld, e.Vs + (int64_t)b * e.stride, ld, c, c, c, EPI_STORE, 0);
-        g.gate = da.gate + b;
-        run_gemm(f64, engine, g, 1, nullptr, 0, st);
-    }
-    hipLaunchKernelGGL(pchol_patch_kernel, dim3((unsigned)nb), dim3(256), 0, st, e, da, fin);
-    check_launch("pchol_patch");
-    {                                                   // B^-1 by the blocked sweep of the fast path (idle where n_defl = 0)
-        EighArgs e2 = e;
-        e2.A = e.Vs; e2.V = M0; e2.Vs = M1;
-        e2.n_orig = da.n_defl;
-        e2.chol_ok = da.ok2;
-        PinvBatch pb2 = pb;
-        for (int b = 0; b < nb; ++b) pb2.K[b] = Binv + (int64_t)b * e.stride;
-        launch_sweep(sw, e2, pb2, nb, max_c, st);
-    }
-    hipLaunchKernelGGL(pchol_gate2_kernel, dim3((unsigned)nb), dim3(64), 0, st, da);
-    check_launch("pchol_gate2");
-    for (int b = 0; b < nb; ++b) {
-        const int c = pb.c[b], ld = pb.n_pad[b];
-        const double* Lt = e.V + (int64_t)b * e.stride;
-        const double* Bi = Binv + (int64_t)b * e.stride;        // (the sweep writes its result with ld = the order)
-        double* Yt = M0 + (int64_t)b * e.stride;
-        GemmArgs g = gemm_args(Bi, c, 1, Lt, ld, 1, Yt, ld, c, c, c, EPI_STORE, 0);         // Y^T = B^-1 L^T
-        g.gate = da.gate + b;
-        run_gemm(f64, engine, g, 1, nullptr, 0, st);
-        g = gemm_args(Yt, 1, ld, Yt, ld, 1, pb.K[b], c, c, c, c, EPI_STORE, 0);             // K = Y Y^T
-        g.gate = da.gate + b;
-        run_gemm(f64, engine, g, 1, nullptr, 0, st);
-    }
-    hipLaunchKernelGGL(pchol_done_kernel, dim3((unsigned)nb), dim3(64), 0, st, e, da);
-    check_launch("pchol_done");
-}
-
-// K_i = pinv(Gram_i) for every type (one workgroup each); `which` = 0..n_types-1, the order
-// of the per-matrix order arrays uploaded once by skf_plan_bind_workspace.
-static void pinv_fallbacks(skf_plan* p, const std::vector<int>& which, const PinvBatch& pb, const EighArgs& e, bool batched, int max_c,
-                           hipStream_t st);
-static void plan_pinv(skf_plan* p, const std::vector<int>& which, hipStream_t st) {
-    if (which.empty()) return;
-    const int64_t stride = p->eig_stride;
-    const int nb = (int)which.size();
-    const bool batched = nb <= PINV_MAXB;       // one launch for all types (pointers travel as kernel arguments)
-    PinvBatch pb;
-    int max_pad = 2, max_c = 1;
-    if (batched) {
-        for (int b = 0; b < nb; ++b) {
-            const TypeState& t = p->types[which[b]];
-            pb.gram[b] = (const double*)t.Gram.ptr;
-            pb.K[b] = (double*)t.K.ptr;
-            pb.c[b] = t.c;
-            pb.n_pad[b] = t.n_pad;
-            if (t.n_pad > max_pad) max_pad = t.n_pad;
-            if (t.c > max_c) max_c = t.c;
-        }
-        hipLaunchKernelGGL(eigh_pack_batched_kernel, dim3(elem_grid((int64_t)max_pad * max_pad), nb), dim3(256), 0, st, pb,
-                           (double*)p->eigA.ptr, stride);
-        check_launch("eigh_pack");
-    } else {
-        for (size_t b = 0; b < which.size(); ++b) {
-            const TypeState& t = p->types[which[b]];
-            double* A = (double*)p->eigA.ptr + (int64_t)b * stride;
-            const int total = t.n_pad * t.n_pad;
-            hipLaunchKernelGGL((eigh_pack_kernel<double>), dim3(elem_grid(total)), dim3(256), 0, st, A, t.n_pad,
-                               (const double*)t.Gram.ptr, (int64_t)t.c, t.c);
-            check_launch("eigh_pack");
-        }
-    }
-    EighArgs e;
-    e.A = (double*)p->eigA.ptr; e.V = (double*)p->eigV.ptr; e.Vs = (double*)p->eigVs.ptr;
-    e.w = (double*)p->eigW.ptr; e.stride = stride; e.wstride = p->eig_maxn;
-    e.n = (const int*)p->eigN.ptr; e.n_orig = (const int*)p->eigNorig.ptr;
-    e.chol_ok = (int*)p->eigOk.ptr;
-    e.max_sweeps = 30;
-    // fast path (Cholesky inverse) with an on-device verdict; the Jacobi eigen-solver only does
-    // work for the matrices the fast path rejected -- no host round trip either way
-    // orders 65 .. 256 (round 4): the blocked sweep operator writes K itself -- one launch instead of the Cholesky inverse and
-    // its unpack (1.15 + 0.09 ms at order 256)
-    const bool sweep = batched && sweep_takes(p->sw, max_c);
-    if (sweep) {
-        launch_sweep(p->sw, e, pb, nb, max_c, st);
-        pinv_fallbacks(p, which, pb, e, batched, max_c, st);
-        return;
-    }
-    launch_chol(p->sw, e, nb, p->eig_maxn, st);
-    if (batched) {
-        hipLaunchKernelGGL(chol_unpack_batched_kernel, dim3(elem_grid((int64_t)max_c * max_c), nb), dim3(256), 0, st, pb,
-                           (const double*)p->eigV.ptr, stride, (const int*)p->eigOk.ptr);
-        check_launch("chol_unpack");
-    } else {
-        for (size_t b = 0; b < which.size(); ++b) {
-            const TypeState& t = p->types[which[b]];
-            const double* X = (const double*)p->eigV.ptr + (int64_t)b * stride;
-            hipLaunchKernelGGL((chol_unpack_kernel<double>), dim3(elem_grid(t.c * t.c)), dim3(256), 0, st,
-                               (double*)t.K.ptr, (int64_t)t.c, X, t.n_pad, t.c, (const int*)p->eigOk.ptr + b);
-            check_launch("chol_unpack");
-        }
-    }
-    pinv_fallbacks(p, which, pb, e, batched, max_c, st);
-}
-
-// the matrices the Cholesky fast path declined (verdicts in eigOk, packed copies in eigA); no-ops for the others
-static void pinv_fallbacks(skf_plan* p, const std::vector<int>& which, const PinvBatch& pb, const EighArgs& e, bool batched, int max_c,
-                           hipStream_t st) {
-    const int64_t stride = p->eig_stride;
-    const int nb = (int)which.size();
-    // orders above 256: the deflation over several workgroups first (round 6); what it declines is still there for the rest
-    if (batched && p->eigX.ptr && p->engine == SKF_ENGINE_MFMA && defl_multi_takes(p->sw, max_c))
-        launch_deflation_multi(p->sw, p->engine, e, pb, nb, max_c, p->eigX.ptr, st);
-    // a rank-deficient Gram matrix with a clear spectral gap: rank-revealing deflation (pchol_pinv_kernel); what it
-    // declines goes to the eigen-solver with the exact singular-value cut-off
-    {
-        static DeviceOnce once;
-        allow_dynamic_lds(once, pchol_pinv_kernel, PCHOL_LDS_BYTES);
-    }
-    {   // dynamic LDS for the packed factor of L^T L, sized by the largest order of this plan (a no-op launch still has
-        // to find a CU with that much LDS free, so small graphs reserve little)
-        const int lr = p->eig_maxn < PCHOL_LDS_R ? p->eig_maxn : PCHOL_LDS_R;
-        hipLaunchKernelGGL(pchol_pinv_kernel, dim3((unsigned)which.size()), dim3(EIGH_THREADS), (size_t)lr * (lr + 1) / 2 * 8, st, e,
-                           deflation_lo(p->sw), 1e-7, lr);
-    }
-    check_launch("pchol_pinv");
-    hipLaunchKernelGGL(jacobi_eigh_kernel, dim3((unsigned)which.size()), dim3(EIGH_THREADS), 0, st, e);
-    check_launch("jacobi_eigh");
-    if (batched) {
-        hipLaunchKernelGGL(eigh_unpack_pinv_batched_kernel, dim3(elem_grid((int64_t)max_c * max_c), nb), dim3(256), 0, st, pb,
-                           (const double*)p->eigVs.ptr, (const double*)p->eigV.ptr, stride, (const int*)p->eigOk.ptr);
-        check_launch("eigh_unpack");
-    } else {
-        for (size_t b = 0; b < which.size(); ++b) {
-            const TypeState& t = p->types[which[b]];
-            const double* Vs = (const double*)p->eigVs.ptr + (int64_t)b * stride;
-            const double* V = (const double*)p->eigV.ptr + (int64_t)b * stride;
-            const int total = t.c * t.c;
-            hipLaunchKernelGGL((eigh_unpack_pinv_kernel<double>), dim3(elem_grid(total)), dim3(256), 0, st,
-                               (double*)t.K.ptr, (int64_t)t.c, Vs, V, t.n_pad, t.c, (const int*)p->eigOk.ptr + b);
-            check_launch("eigh_unpack");
-        }
-    }
 }
 
 static void gram(skf_plan* p, TypeState& t, int nan, hipStream_t st, bool on_aux = false) {

@@ -16,7 +16,7 @@
 // Same arithmetic as the general schedule (f64 c x c algebra, master-type n-sized products, nan_to_num where the
 // reference has it); only the order of the sums differs.
 #pragma once
-#include "skf_kernels.h"
+#include "skf_pinv.h"      // pchol_pinv_body, jacobi_eigh_body, chol_diag_floor, EighArgs: the fall-back of a declined sweep
 
 namespace skf {
 

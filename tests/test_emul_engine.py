@@ -661,6 +661,32 @@ def test_fit_with_a_rank_deficient_gram_above_order_256():
         assert relerr(S[k][0], So[k][0]) < 1e-8, k
 
 
+@pytest.mark.parametrize('dtype', ['f64', 'f32'])
+def test_fit_of_17_types_packs_and_unpacks_in_chunks(dtype, monkeypatch):
+    """A plan of 17 types (tests/pinv_cases.py) is one more than the pack / unpack kernels of the pseudo-inverse take in one
+    launch (PINV_MAXB = 16): the Cholesky fast path, the one-workgroup deflation and the eigen-solver stay one launch over
+    all matrices, pack and the two unpacks go out in two chunks.  The last type (6 objects, rank 8) is declined by the fast
+    path in every iteration, so both unpack kernels run with a verdict pointer offset by 16.  Ten iterations on the general
+    schedule against the oracle: f64 under the bounds of test_rank_deficient_gram (1e-7 on G and S, 1e-6 on the relation
+    errors), f32 under DESIGN section 3 (1e-4 on G, 1e-3 on S, 1e-5 on the relation errors).  Measured on the emulator:
+    f64 6.7e-14 / 1.5e-13 / 5.4e-15, f32 4.6e-7 / 2.0e-6 / 6.5e-8."""
+    import pinv_cases
+    from skfusion_amd._engine import small_graph_limits
+    if len(pinv_cases.chain17_graph()[1]) <= small_graph_limits()['max_types']:
+        monkeypatch.setenv('SKF_NO_SMALL_FUSED', '1')       # (today 17 types are one more than the small-graph schedule takes, too)
+    R, types, rank, G0 = pinv_cases.chain17_graph()
+    Go, So = orc.dfmf(R, {}, types, rank, max_iter=10, G0=G0)
+    G, S = _dfmf.dfmf(R, {}, types, rank, max_iter=10, G0=G0, dtype=dtype)
+    tol_g, tol_s, tol_e = (1e-7, 1e-7, 1e-6) if dtype == 'f64' else (1e-4, 1e-3, 1e-5)
+    for t in types:
+        assert relerr(G[t, t], Go[t, t]) < tol_g, t
+    for k in So:
+        assert relerr(S[k][0], So[k][0]) < tol_s, k
+    e, eo = orc.relation_errors(R, G, S), orc.relation_errors(R, Go, So)
+    for k in e:
+        assert abs(e[k][0] - eo[k][0]) <= tol_e * max(1.0, eo[k][0]), k
+
+
 @pytest.mark.parametrize('dtype', ['f64', 'bf16'])
 def test_round5_schedule_switches_keep_every_bit(dtype, monkeypatch):
     """Round 5: (a) split-K Gram products compute only the tiles on / below the diagonal and the reduce mirrors the rest

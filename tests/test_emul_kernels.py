@@ -523,6 +523,40 @@ def test_pinv_zero_and_diagonal(rt):
     np.testing.assert_allclose(got, np.diag([0.25, 0.5, 0.0, 0.0, 0.2]), atol=1e-15)
 
 
+STRIDED = [(nat.SKF_F64, 33, None, 40, 37), (nat.SKF_F64, 33, 20, 40, 37), (nat.SKF_F32, 33, None, 40, 37),
+           (nat.SKF_F32, 33, 20, 40, 37), (nat.SKF_F64, 70, None, 70, 72)]
+
+
+@pytest.mark.parametrize('dtype,n,rank,lda,ldk', STRIDED)
+def test_pinv_with_leading_dimensions_above_the_order(rt, dtype, n, rank, lda, ldk):
+    """The stand-alone operator on a matrix stored with lda > n into a K with ldk > n, in both element types (pack and both
+    unpack kernels with the caller's strides; tests/pinv_cases.py).  ldk != n rules out the sweep, which writes a dense f64 K
+    itself: the full-rank matrix takes the Cholesky inverse + unpack (verdict 1), the rank-20 one the one-workgroup deflation +
+    eigen unpack (verdict 2).  Order 70 is the smallest at which ldk alone decides: six launches (pack, Cholesky, unpack,
+    deflation, eigen-solver, eigen unpack) with ldk = 72 against the sweep's 4 + ceil(70 / 32) with ldk = 70.  Against
+    scipy.linalg.pinv under the bounds of test_pinv_full_rank_matches_scipy / test_pinv_deflation_matches_scipy_and_the_eigen_path,
+    f32 scaled by eps_f32 / eps_f64 (the inputs are exact in f32; measured on the emulator: f64 3.7e-15 / 1.6e-14 / 9.5e-15,
+    f32 2.6e-8 / 2.6e-8).  Columns n .. ldk - 1 of K keep the bytes they had."""
+    import scipy.linalg as spla
+    import pinv_cases
+    A = pinv_cases.strided_matrix(n, rank)
+    want = spla.pinv(A)
+    got, pad, verdict, launches = pinv_cases.run_pinv_strided(rt, dtype, A, lda, ldk)
+    bound = 1e-9 * max(1.0, np.linalg.cond(A) * 1e-3) if rank is None else 1e-8
+    if dtype == nat.SKF_F32:
+        bound *= float(np.finfo(np.float32).eps) / float(np.finfo(np.float64).eps)
+    err = relerr(got.astype(np.float64), want)
+    print('pinv n=%d rank=%s lda=%d ldk=%d dtype=%d: %.3e (bound %.3e), verdict %d, %d launches' % (n, rank, lda, ldk, dtype, err, bound, verdict, launches))
+    assert err < bound
+    assert (pad == pinv_cases.POISON).all()
+    assert verdict == (1 if rank is None else 2)
+    assert launches == 6
+    if n == 70:
+        dense = pinv_cases.run_pinv_strided(rt, dtype, A, lda, n)
+        assert dense[2] == 1 and dense[3] == 4 + (n + 31) // 32
+        assert relerr(dense[0], want) < bound
+
+
 def test_fill_uniform_matches_oracle_hash(rt):
     from oracle.dfmf_oracle import hash_uniform_matrix
     for dtype, npd in ((nat.SKF_F64, np.float64), (nat.SKF_F32, np.float32)):

@@ -98,6 +98,11 @@ def test_pinv_ambiguous_spectrum_above_order_256(rt):
     K.test_pinv_ambiguous_spectrum_above_order_256_is_left_to_the_exact_cut_off(rt)
 
 
+@pytest.mark.parametrize('dtype,n,rank,lda,ldk', K.STRIDED)
+def test_pinv_with_leading_dimensions_above_the_order(rt, dtype, n, rank, lda, ldk):
+    K.test_pinv_with_leading_dimensions_above_the_order(rt, dtype, n, rank, lda, ldk)
+
+
 def test_fill_uniform(rt):
     K.test_fill_uniform_matches_oracle_hash(rt)
 
@@ -203,6 +208,13 @@ def test_fit_with_a_rank_deficient_gram_above_order_256_on_the_hardware():
     """The multi-workgroup deflation inside a fit (round 6), against the oracle."""
     import test_emul_engine as E
     E.test_fit_with_a_rank_deficient_gram_above_order_256()
+
+
+@pytest.mark.parametrize('dtype', ['f64', 'f32'])
+def test_fit_of_17_types_on_the_hardware(dtype, monkeypatch):
+    """One type more than a pack / unpack launch of the pseudo-inverse holds, the declined matrix in the second chunk."""
+    import test_emul_engine as E
+    E.test_fit_of_17_types_packs_and_unpacks_in_chunks(dtype, monkeypatch)
 
 
 def test_fit_with_every_rank_above_512_on_the_relation_pipeline():
