@@ -152,13 +152,27 @@ enum {
 
 typedef struct {
     int32_t type;     /* constrained object type (Theta[(i,i)][t], dfmf.py:82-85) */
-    const void* data; /* n_i x n_i, engine dtype (SKF_BF16: f32), dense row-major */
+    const void* data; /* n_i x n_i, engine dtype (SKF_BF16: f32), dense row-major.  NULL: the constraint is given as the CSR of
+                         its STORED entries and every other entry is ZERO (what a scipy.sparse matrix means; the reference
+                         multiplies its dense expansion, _dfmf.py:284-292): `nnz` is then the EXACT number of entries (0
+                         allowed: an all-zero constraint), `ld` is ignored and skf_plan_set_constraint_entries hands the lists
+                         over before skf_plan_bind_workspace.  No dense form exists in any type: the constraint is kept as
+                         lists whatever its density, the same lists the dense form of the same matrix is compacted to, and
+                         the workspace grows by nnz * (4 + element size) + (n_i + 1) * 8 + n_i * 4 bytes, never with
+                         n_i * n_i.  SKF_DFMF / SKF_DFMC plans and the target type of SKF_TRANSFORM plans, every engine.  For
+                         the small-graph schedule it counts as sparse under the condition of skf_small_graph_limits
+                         (0 < nnz <= n_i * n_i / 16); otherwise the plan takes the general schedule.  SKF_E_INVALID at
+                         skf_plan_create: plans with row blocks, sliced and SKF_OPT_OWNED_ROWS plans, more than 2e9 entries. */
     int64_t ld;
     int64_t nnz;      /* 0: multiply it as a dense matrix, as the reference does (_dfmf.py:284-292).  > 0: an upper
                          bound on its non-zero entries -- the engine then keeps the constraint as CSR (built on the
                          device at bind time, `data` is not referenced afterwards) and D_i += Theta+ G_i,
                          E_i += Theta- G_i become ONE sparse pass in the master precision.  Accepted up to
-                         n_i * n_i / 16; a bound that turns out too small is an error at bind time. */
+                         n_i * n_i / 16; a bound that turns out too small is an error at bind time.  Either form: a row of
+                         the CSR longer than 4096 entries (SKF_THETA_HUB_ROW=n in the environment of skf_plan_create; 0 =
+                         never) is cut into segments of that length, one wave each, whose partial sums are stored and added
+                         in ascending order -- no atomics: the same bits on every run -- at the price of
+                         (2 nnz / 4096 + 1) * (2 * rank * element size + 32) bytes of workspace. */
 } skf_theta_desc;
 
 typedef struct {
@@ -208,6 +222,16 @@ int skf_plan_workspace_bytes(const skf_plan* plan, size_t* bytes);
  * columns do not ascend strictly is SKF_E_INVALID, as is a SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR relation without this call. */
 int skf_plan_set_known_entries(skf_plan* plan, int32_t rel, const int64_t* indptr, const int32_t* indices,
                                const void* values);
+/* The stored entries of constraint `theta` (the index into the `thetas` of skf_plan_create; one whose skf_theta_desc.data is
+ * NULL, _dfmf.py:284-292 on the dense expansion), as device pointers: indptr[n_i + 1] (int64, indptr[0] = 0,
+ * indptr[n_i] = nnz, non-decreasing), indices[nnz] (int32 columns, strictly ascending within a row: canonical CSR, duplicates
+ * summed beforehand) and values[nnz] in the MASTER type (f64 / f32; SKF_BF16 plans: f32).  Call it between skf_plan_create
+ * and skf_plan_bind_workspace (afterwards: SKF_E_STATE); the buffers are read by skf_plan_bind_workspace and not referenced
+ * afterwards (the contract of `data`).  Bind validates them on the device before anything gathers through them: an indptr
+ * that does not run from 0 to nnz or steps down, an index outside [0, n_i) or a row whose columns do not ascend strictly is
+ * SKF_E_INVALID with a message naming the constraint, as is such a constraint without this call. */
+int skf_plan_set_constraint_entries(skf_plan* plan, int32_t theta, const int64_t* indptr, const int32_t* indices,
+                                    const void* values);
 /* `workspace` must be 256-byte aligned device memory and stay valid for the plan's lifetime.
  * For DFMC the masked relations are copied into the workspace here (the caller's relation
  * data is never written: _dfmc.py:268, tests/test_dfmc.py:62,85). */

@@ -487,7 +487,8 @@ class DevicePlan(object):
     def __init__(self, obj_types, n_obj, rank, relations, thetas, variant, dtype='f64',
                  target=None, engine=None, runtime=None, part=None, stream=None, sparse_known=None, owned=False):
         """relations: list of (row_type, col_type, ndarray, mask-or-None[, block]);
-        thetas: list of (type, ndarray).  `block` (row-block sharding, `_distributed.partition_rows`)
+        thetas: list of (type, ndarray | DeviceMatrix | KnownEntries(unstored='zero') | DeviceKnownEntries -- the last two:
+        the constraint as the CSR of its stored entries, never expanded).  `block` (row-block sharding, `_distributed.partition_rows`)
         = dict(row_begin, n_rows, absent, col_side, masked): data / mask then hold only the local rows
         (None when absent); `part` = (index, count) of this plan among the row-block plans.
         `owned`: the row blocks are the ranges of `owned_rows` (SKF_OPT_OWNED_ROWS: every rank owns the same share of the rows
@@ -606,7 +607,20 @@ class DevicePlan(object):
             if block is not None and block.get('known_lists'):       # (row ownership: decided for all ranks alike by the caller)
                 rdesc[k].flags |= nat.SKF_REL_KNOWN_LISTS
         hdesc = (nat.ThetaDesc * max(len(thetas), 1))()
+        theta_csr = []                                   # (constraint, DeviceKnownEntries): skf_plan_set_constraint_entries
         for k, (t, data) in enumerate(thetas):
+            if isinstance(data, (KnownEntries, DeviceKnownEntries)):
+                # the stored entries of a constraint that is zero elsewhere (skf_theta_desc.data == NULL): no dense form,
+                # always kept as lists; values in the master type
+                if data.unstored != 'zero' or data.by_col:
+                    raise ValueError("constraint on %s: entries need unstored='zero', compressed along the rows" % (t,))
+                if tuple(data.shape) != (n_obj[t], n_obj[t]):
+                    raise ValueError('constraint on %s dimension mismatch' % (t,))
+                dev = data if isinstance(data, DeviceKnownEntries) else upload_known_entries(data, self.dtype, mem)
+                self._keep.append(dev)
+                hdesc[k].type, hdesc[k].data, hdesc[k].ld, hdesc[k].nnz = self.index[t], None, 0, dev.known
+                theta_csr.append((k, dev))
+                continue
             if isinstance(data, DeviceMatrix):           # master dtype, already in HBM
                 if tuple(data.shape) != (n_obj[t], n_obj[t]):
                     raise ValueError('constraint on %s dimension mismatch' % (t,))
@@ -631,6 +645,8 @@ class DevicePlan(object):
                      hdesc, C.byref(opt), C.byref(self.handle))
         for k, dev in csr:
             self.rt.call('skf_plan_set_known_entries', self.handle, k, dev.indptr.ptr, dev.indices.ptr, dev.values.ptr)
+        for k, dev in theta_csr:
+            self.rt.call('skf_plan_set_constraint_entries', self.handle, k, dev.indptr.ptr, dev.indices.ptr, dev.values.ptr)
         nbytes = C.c_size_t()
         self.rt.call('skf_plan_workspace_bytes', self.handle, C.byref(nbytes))
         self.workspace_bytes = nbytes.value
@@ -993,7 +1009,9 @@ def upload_graph(rel_list, theta_list, dtype, runtime=None):
             mask = pack_mask(mask, rt.mem)
         rels.append((i, j, data, mask) + tuple(rel[4:]))
     for t, data in theta_list:
-        if not isinstance(data, DeviceMatrix):
+        if isinstance(data, KnownEntries):               # a constraint as its entries: one upload, master dtype
+            data = upload_known_entries(data, code, rt.mem)
+        if not isinstance(data, (DeviceMatrix, DeviceKnownEntries)):
             arr = np.ascontiguousarray(data, dtype=npd)
             data = DeviceMatrix(rt.mem.from_host(arr), arr.shape)
             data.nnz = int(np.count_nonzero(arr))          # (as DevicePlan counts a host array: the same path either way)

@@ -99,6 +99,7 @@ SIGNATURES = {
     'skf_plan_workspace_bytes': (C.c_int, [_P, C.POINTER(C.c_size_t)]),
     'skf_plan_bind_workspace': (C.c_int, [_P, _P, C.c_size_t, _P]),
     'skf_plan_set_known_entries': (C.c_int, [_P, C.c_int32, _P, _P, _P]),
+    'skf_plan_set_constraint_entries': (C.c_int, [_P, C.c_int32, _P, _P, _P]),
     'skf_set_factor': (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
     'skf_get_factor': (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
     'skf_set_backbone': (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),

@@ -379,8 +379,8 @@ static void plan_decide_lists(skf_plan* p, const skf_relation_desc* relations) {
 static void plan_describe_constraints(skf_plan* p, int32_t n_types, int32_t n_thetas, const skf_theta_desc* thetas) {
     p->thetas.resize(n_thetas);
     for (int t = 0; t < n_thetas; ++t) {
-        if (thetas[t].type < 0 || thetas[t].type >= n_types || !thetas[t].data ||
-            thetas[t].ld < p->types[thetas[t].type].n)
+        if (thetas[t].type < 0 || thetas[t].type >= n_types ||
+            (thetas[t].data && thetas[t].ld < p->types[thetas[t].type].n))
             SKF_FAIL(SKF_E_INVALID, "constraint %d invalid", t);
         if (p->variant == SKF_TRANSFORM && thetas[t].type != p->target)
             SKF_FAIL(SKF_E_INVALID, "constraint %d must be on the target object type", t);
@@ -389,10 +389,28 @@ static void plan_describe_constraints(skf_plan* p, int32_t n_types, int32_t n_th
         p->thetas[t].ld = thetas[t].ld;
         const int64_t nn = p->types[thetas[t].type].n;
         if (thetas[t].nnz < 0) SKF_FAIL(SKF_E_INVALID, "constraint %d: negative non-zero bound", t);
+        if (!thetas[t].data) {      // the CSR of its stored entries (skf_plan_set_constraint_entries): no dense form in any type
+            if (p->sliced)
+                SKF_FAIL(SKF_E_INVALID, "constraint %d: a constraint given as its entries is for plans of whole relations "
+                         "(no row blocks, slices or SKF_OPT_OWNED_ROWS)", t);
+            if (thetas[t].nnz > 2000000000LL)
+                SKF_FAIL(SKF_E_INVALID, "constraint %d: %lld > 2e9 entries", t, (long long)thetas[t].nnz);
+            p->thetas[t].entries = p->thetas[t].sparse = true;
+            p->thetas[t].nnz_cap = thetas[t].nnz;
+            continue;
+        }
         if (thetas[t].nnz > 0 && thetas[t].nnz <= nn * nn / SKF_THETA_SPARSE_DIV) {
             p->thetas[t].sparse = true;
             p->thetas[t].nnz_cap = thetas[t].nnz;
         }
+    }
+    // hub rows of the sparse constraints: the threshold, and a bound on the segments they can be cut into -- a row of L > H
+    // entries gives ceil(L / H) < 2 L / H segments, all hub rows together fewer than 2 nnz / H
+    const int hub_row = Switches::read().theta_hub_row;          // (plan creation: the scratch below is sized from it)
+    for (ThetaState& th : p->thetas) {
+        if (!th.sparse || hub_row <= 0 || th.nnz_cap <= hub_row) continue;
+        th.hub_row = hub_row;
+        th.seg_cap = 2 * th.nnz_cap / hub_row + 1;
     }
     if (p->owned) {
         // SKF_BF16: the other owners' rows of a factor are read as bf16 operands only -- unless a constraint on the type
@@ -418,7 +436,10 @@ static void plan_layout_small_graph(skf_plan* p) {
     // (object counts: the Q shares of the schedule grow with n_i / 256 * n_j * c_i, and from a few thousand objects
     // on the relation contractions are worth the big tiles of the general schedule)
     for (const TypeState& t : p->types) ok = ok && t.c <= SMALLC && t.n <= SM_MAX_OBJECTS;
-    for (const ThetaState& th : p->thetas) ok = ok && th.sparse;
+    // (a constraint given as its entries is kept as lists whatever its density; it rides this schedule under the documented
+    // condition, 0 < nnz <= n * n / SKF_THETA_SPARSE_DIV, like the dense-fed form)
+    for (const ThetaState& th : p->thetas)
+        ok = ok && th.sparse && (!th.entries || (th.nnz_cap > 0 && th.nnz_cap <= p->types[th.type].n * p->types[th.type].n / SKF_THETA_SPARSE_DIV));
     for (const RelState& r : p->rels) ok = ok && !r.absent && !r.masked && !r.sp0;
     p->small_fused = ok;
     if (ok) {
@@ -733,6 +754,12 @@ static void plan_layout(skf_plan* p) {
             add_slot(p, th.Rp, (size_t)(t.n + 1) * sizeof(int64_t));
             add_slot(p, th.Ci, (size_t)th.nnz_cap * sizeof(int));
             add_slot(p, th.Vv, (size_t)th.nnz_cap * es);
+            if (th.seg_cap > 0) {       // hub rows: segment table, row table, the e / d partials of every segment
+                add_slot(p, th.HubSeg, (size_t)th.seg_cap * sizeof(ThetaSeg));
+                add_slot(p, th.HubRows, (size_t)th.seg_cap * sizeof(ThetaHub));
+                add_slot(p, th.HubE, (size_t)th.seg_cap * t.c * es);
+                add_slot(p, th.HubD, (size_t)th.seg_cap * t.c * es);
+            }
             continue;
         }
         if (!p->bf16) want_part(k_plan, t.n, t.c, t.n);                     // dense Theta G
@@ -821,6 +848,20 @@ int skf_plan_set_known_entries(skf_plan* plan, int32_t rel, const int64_t* indpt
         r.csr_ptr = indptr;
         r.csr_idx = (const int*)indices;
         r.csr_val = values;
+    });
+}
+
+int skf_plan_set_constraint_entries(skf_plan* plan, int32_t theta, const int64_t* indptr, const int32_t* indices, const void* values) {
+    return guarded([&] {
+        if (!plan) SKF_FAIL(SKF_E_INVALID, "null argument");
+        if (plan->ws_base) SKF_FAIL(SKF_E_STATE, "skf_plan_set_constraint_entries after skf_plan_bind_workspace");
+        if (theta < 0 || theta >= (int)plan->thetas.size()) SKF_FAIL(SKF_E_INVALID, "constraint %d out of range", theta);
+        ThetaState& th = plan->thetas[theta];
+        if (!th.entries) SKF_FAIL(SKF_E_INVALID, "constraint %d has a dense form (skf_theta_desc.data)", theta);
+        if (!indptr || (th.nnz_cap > 0 && (!indices || !values))) SKF_FAIL(SKF_E_INVALID, "constraint %d: null CSR array", theta);
+        th.csr_ptr = indptr;
+        th.csr_idx = (const int*)indices;
+        th.csr_val = values;
     });
 }
 

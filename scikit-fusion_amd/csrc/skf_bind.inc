@@ -357,13 +357,67 @@ static void bind_bf16_copies(skf_plan* p, hipStream_t st) {
 // ---- constraints -----------------------------------------------------------------------------------------------------------
 
 // Step 3: CSR of every sparse constraint -- per-row counts on the device, prefix sum on the host, fill on the device
+// The hub rows of a sparse constraint from its row pointers on the host (`rp`, n + 1 of them): every row longer than the
+// plan's threshold cut into segments of at most that many entries; the two tables uploaded, host copies kept.
+static void bind_theta_hubs(ThetaState& th, const int64_t* rp, int64_t n, hipStream_t st) {
+    th.n_seg = 0;
+    th.hub_rows.clear();
+    th.hub_first.clear();
+    if (th.hub_row <= 0 || th.seg_cap <= 0) return;
+    std::vector<ThetaSeg> segs;
+    std::vector<ThetaHub> hubs;
+    for (int64_t r = 0; r < n; ++r) {
+        const int64_t a = rp[r], b = rp[r + 1];
+        if (b - a <= th.hub_row) continue;
+        ThetaHub h = {(int32_t)r, (int32_t)segs.size(), 0, 0};
+        for (int64_t q = a; q < b; q += th.hub_row) {
+            segs.push_back(ThetaSeg{q, (int32_t)std::min<int64_t>(th.hub_row, b - q), (int32_t)r});
+            ++h.count;
+        }
+        hubs.push_back(h);
+        th.hub_rows.push_back((int)r);
+        th.hub_first.push_back(h.first);
+    }
+    if ((int64_t)segs.size() > th.seg_cap)
+        SKF_FAIL(SKF_E_STATE, "constraint on type %d: %zu hub segments, more than the %lld the plan sized its scratch for",
+                 th.type, segs.size(), (long long)th.seg_cap);
+    th.n_seg = (int64_t)segs.size();
+    th.hub_first.push_back((int)segs.size());
+    if (segs.empty()) return;
+    SKF_HIP(hipMemcpyAsync(th.HubSeg.ptr, segs.data(), segs.size() * sizeof(ThetaSeg), hipMemcpyHostToDevice, st));
+    SKF_HIP(hipMemcpyAsync(th.HubRows.ptr, hubs.data(), hubs.size() * sizeof(ThetaHub), hipMemcpyHostToDevice, st));
+    SKF_HIP(hipStreamSynchronize(st));          // (the host vectors end here)
+}
+
 template <typename T>
 static void bind_theta_csr_t(skf_plan* p, hipStream_t st) {
     std::vector<int> cnt;
     std::vector<int64_t> rp;
-    for (ThetaState& th : p->thetas) {
+    for (size_t k = 0; k < p->thetas.size(); ++k) {
+        ThetaState& th = p->thetas[k];
         if (!th.sparse) continue;
         const int64_t n = p->types[th.type].n;
+        if (th.entries) {       // the caller's lists, validated on the device before anything gathers through them, then copied as they are
+            if (!th.csr_ptr) SKF_FAIL(SKF_E_INVALID, "constraint %zu is given as its entries (data == NULL) without skf_plan_set_constraint_entries", k);
+            const int64_t tot = th.nnz_cap;
+            if (!csr_is_canonical(th.csr_ptr, th.csr_idx, n, n, tot, (int*)th.Cnt.ptr, st))      // (Cnt: a scratch word)
+                SKF_FAIL(SKF_E_INVALID, "constraint %zu: the lists are not canonical for %lld objects with %lld entries (indptr from 0 "
+                         "to the count, non-decreasing; indices in range and strictly ascending within a row)", k, (long long)n, (long long)tot);
+            th.nnz = tot;
+            SKF_HIP(hipMemcpyAsync(th.Rp.ptr, th.csr_ptr, ((size_t)n + 1) * 8, hipMemcpyDeviceToDevice, st));
+            if (tot > 0) {
+                SKF_HIP(hipMemcpyAsync(th.Ci.ptr, th.csr_idx, (size_t)tot * 4, hipMemcpyDeviceToDevice, st));
+                SKF_HIP(hipMemcpyAsync(th.Vv.ptr, th.csr_val, (size_t)tot * sizeof(T), hipMemcpyDeviceToDevice, st));
+            }
+            th.csr_ptr = nullptr; th.csr_idx = nullptr; th.csr_val = nullptr;      // not referenced after bind
+            if (th.seg_cap > 0 && tot > 0) {        // the row pointers back on the host: which rows are hubs
+                if (rp.size() < (size_t)n + 1) rp.resize((size_t)n + 1);
+                SKF_HIP(hipMemcpyAsync(rp.data(), th.Rp.ptr, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
+                SKF_HIP(hipStreamSynchronize(st));
+                bind_theta_hubs(th, rp.data(), n, st);
+            }
+            continue;
+        }
         const int grid = wave_grid(n);
         hipLaunchKernelGGL((theta_row_count_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)th.data, th.ld, n, (int*)th.Cnt.ptr);
         check_launch("theta_row_count");
@@ -376,6 +430,7 @@ static void bind_theta_csr_t(skf_plan* p, hipStream_t st) {
                            (const int64_t*)th.Rp.ptr, (int*)th.Ci.ptr, (T*)th.Vv.ptr);
         check_launch("theta_csr_fill");
         SKF_HIP(hipStreamSynchronize(st));          // (`rp` is reused by the next constraint)
+        bind_theta_hubs(th, rp.data(), n, st);      // (the row pointers are still on the host)
     }
 }
 static void bind_theta_csr(skf_plan* p, hipStream_t st) {

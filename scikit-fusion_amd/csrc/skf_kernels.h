@@ -2159,7 +2159,8 @@ __global__ __launch_bounds__(256) void fill_apply_kernel(T* __restrict__ X, int6
 // Sparse constraints.  A constraint matrix Theta (n x n) is usually sparse -- lambda I, a handful of must-link /
 // cannot-link pairs per object, dicty's 3 % dense ppi -- while the reference multiplies it as a dense matrix
 // (_dfmf.py:284-292: D_i += Theta+ G_i, E_i += Theta- G_i).  With a non-zero bound from the caller
-// (skf_theta_desc.nnz) the engine keeps it as CSR, built on the device at bind time (count, host prefix sum, fill),
+// (skf_theta_desc.nnz) the engine keeps it as CSR, built on the device at bind time (count, host prefix sum, fill) -- or
+// copied from the caller's own CSR where the constraint has no dense form (skf_plan_set_constraint_entries) --,
 // and the two products become one pass: a wave per row walks the row's non-zeros, gathers the rows of G and adds
 // v G[k] to D (v > 0) or -v G[k] to E (v < 0).  Same arithmetic as the dense split; fixed order within a row.
 // ------------------------------------------------------------------------------------------
@@ -2229,15 +2230,16 @@ __device__ __forceinline__ void theta_row_walk(const int* __restrict__ cols, con
     }
 }
 
+// `hub` > 0: rows longer than that are left to the two hub kernels below (0: every row is walked here).
 template <typename T>
 __global__ __launch_bounds__(256) void theta_spmm_kernel(const int64_t* __restrict__ rowptr, const int* __restrict__ cols,
                                                          const T* __restrict__ vals, const T* __restrict__ G,
-                                                         T* __restrict__ E, T* __restrict__ D, int64_t n, int c) {
+                                                         T* __restrict__ E, T* __restrict__ D, int64_t n, int c, int64_t hub) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     for (int64_t r = wave; r < n; r += nwaves) {
         const int64_t a = rowptr[r], b = rowptr[r + 1];
-        if (a == b) continue;
+        if (a == b || (hub > 0 && b - a > hub)) continue;
         for (int j0 = 0; j0 < c; j0 += 64) {
             const int j = j0 + lane;
             T e = (T)0, d = (T)0;
@@ -2247,6 +2249,57 @@ __global__ __launch_bounds__(256) void theta_spmm_kernel(const int64_t* __restri
                 D[r * c + j] += d;
             }
         }
+    }
+}
+
+// Hub rows.  One wave per row means that a row of 10^5 entries (the hub of a power-law network over a million objects) is
+// walked serially, once per 64 columns of the factor, and sets the time of the whole pass.  Rows longer than the plan's
+// threshold (THETA_HUB_ROW; SKF_THETA_HUB_ROW=n, 0 = never) are therefore cut at bind time into segments of at most that
+// many entries, listed in a table sorted by row, then by position: theta_hub_partial_kernel walks one segment per wave and
+// STORES its two partial sums, theta_hub_combine_kernel adds a row's partials in ascending segment order into E / D.
+// Store and sum: no atomics, no tickets or flags between workgroups -- stream order between the two launches is the only
+// dependency, and the result has the same bits on every run.
+constexpr int THETA_HUB_ROW = 4096;
+struct ThetaSeg { int64_t a; int32_t len, row; };              // entries [a, a + len) of the lists, all of row `row`
+struct ThetaHub { int32_t row, first, count, pad; };           // segments [first, first + count) of the table are row `row`
+
+// one wave per (segment, 64-column group): Pe / Pd [segment][c]
+template <typename T>
+__global__ __launch_bounds__(256) void theta_hub_partial_kernel(const ThetaSeg* __restrict__ segs, int64_t n_seg,
+                                                                const int* __restrict__ cols, const T* __restrict__ vals,
+                                                                const T* __restrict__ G, T* __restrict__ Pe, T* __restrict__ Pd,
+                                                                int c) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t groups = (c + 63) / 64;
+    for (int64_t w = wave; w < n_seg * groups; w += nwaves) {
+        const int64_t s = w / groups;
+        const int j = (int)(w % groups) * 64 + lane;
+        const int64_t a = segs[s].a, b = a + segs[s].len;
+        T e = (T)0, d = (T)0;
+        theta_row_walk<T>(cols, vals, a, b, G, c, j, e, d);
+        if (j < c) {
+            Pe[s * c + j] = e;
+            Pd[s * c + j] = d;
+        }
+    }
+}
+
+// one thread per (hub row, column): the row's partials in ascending segment order, then into E / D
+template <typename T>
+__global__ __launch_bounds__(256) void theta_hub_combine_kernel(const ThetaHub* __restrict__ hubs, int64_t n_hub,
+                                                                const T* __restrict__ Pe, const T* __restrict__ Pd,
+                                                                T* __restrict__ E, T* __restrict__ D, int c) {
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n_hub * c; q += (int64_t)gridDim.x * blockDim.x) {
+        const ThetaHub h = hubs[q / c];
+        const int j = (int)(q % c);
+        T e = (T)0, d = (T)0;
+        for (int64_t s = h.first; s < (int64_t)h.first + h.count; ++s) {
+            e += Pe[s * c + j];
+            d += Pd[s * c + j];
+        }
+        E[(int64_t)h.row * c + j] += e;
+        D[(int64_t)h.row * c + j] += d;
     }
 }
 

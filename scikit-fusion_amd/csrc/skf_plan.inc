@@ -32,6 +32,9 @@ struct Switches {
     bool comm_stream = true;       // SKF_COMM_STREAM=0     plans with owned rows: the exchanges on the main stream (A/B; tests run both)
     bool early_update = true;      // SKF_EARLY_UPDATE=0    pipeline: every type is updated at the end of the iteration (default: a type whose last relation is through
                                    //                       and that nothing reads any more is updated on the second stream, underneath the remaining contractions)
+    int theta_hub_row = THETA_HUB_ROW;   // SKF_THETA_HUB_ROW=n   rows of a sparse constraint longer than n entries are cut into segments of n, a wave
+                                   //                       each (theta_hub_partial_kernel / _combine_kernel); 0 = never.  Read when the plan
+                                   //                       is CREATED (the partial-sum scratch is sized from it), as SKF_DFMC_SPARSE is
     static Switches read() {
         auto on = [](const char* name) { return env_int(name, 0) != 0; };
         auto off = [](const char* name) { return env_int(name, 1) == 0; };         // "=0" switches a default off
@@ -59,6 +62,7 @@ struct Switches {
         { const int kp = env_int("SKF_KNOWN_PARTS", 0); w.known_parts = (kp == 1 || kp == 2 || kp == 4 || kp == 8) ? kp : 0; }
         w.known_parts_forced = env_str("SKF_KNOWN_PARTS") != nullptr;
         w.comm_stream = !off("SKF_COMM_STREAM");
+        { const int hr = env_int("SKF_THETA_HUB_ROW", THETA_HUB_ROW); w.theta_hub_row = hr > 0 ? hr : 0; }
         return w;
     }
 };
@@ -178,6 +182,18 @@ struct ThetaState {
     bool sparse = false;
     int64_t nnz_cap = 0, nnz = 0;
     Slot Rp, Ci, Vv, Cnt;                  // rowptr (n + 1, int64), column indices (int32), values, per-row counts
+    // skf_theta_desc.data == NULL: the CSR comes from the caller (skf_plan_set_constraint_entries; read at bind time only),
+    // nnz_cap is its exact length and no dense form exists in any type -- kept as lists whatever the density
+    bool entries = false;
+    // hub rows (longer than hub_row entries; 0: never split) cut into segments: the table and the rows it covers, sorted by
+    // row, then by position; partial sums e / d per segment in HubE / HubD [n_seg][c], master type.  Host copies of the
+    // rows and of their first segments: plans with owned rows launch the sub-range inside [t0, t0 + tn)
+    int64_t hub_row = 0, seg_cap = 0, n_seg = 0;
+    Slot HubSeg, HubRows, HubE, HubD;
+    std::vector<int> hub_rows, hub_first;
+    const int64_t* csr_ptr = nullptr;
+    const int* csr_idx = nullptr;
+    const void* csr_val = nullptr;
 };
 
 }  // namespace skf
@@ -464,6 +480,26 @@ static void mult_update(skf_plan* p, TypeState& t, hipStream_t st) {
     check_launch("mult_update");
 }
 
+// the hub rows of a sparse constraint inside [r0, r0 + nr): their segments as partial sums, then the sums into E / D.  The
+// table is sorted by row, so the rows of the range are one sub-range of it (found here, on the host).
+template <typename T>
+static void theta_hub_rows_t(ThetaState& th, TypeState& t, int64_t r0, int64_t nr, hipStream_t st) {
+    const size_t h0 = std::lower_bound(th.hub_rows.begin(), th.hub_rows.end(), r0) - th.hub_rows.begin();
+    const size_t h1 = std::lower_bound(th.hub_rows.begin(), th.hub_rows.end(), r0 + nr) - th.hub_rows.begin();
+    if (h1 <= h0) return;
+    const int64_t s0 = th.hub_first[h0], s1 = th.hub_first[h1];       // (hub_first has one entry more than hub_rows: n_seg)
+    const int64_t groups = (t.c + 63) / 64;
+    hipLaunchKernelGGL((theta_hub_partial_kernel<T>), dim3(wave_grid((s1 - s0) * groups)), dim3(256), 0, st,
+                       (const ThetaSeg*)th.HubSeg.ptr + s0, s1 - s0, (const int*)th.Ci.ptr, (const T*)th.Vv.ptr, (const T*)t.G.ptr,
+                       (T*)th.HubE.ptr + s0 * t.c, (T*)th.HubD.ptr + s0 * t.c, t.c);
+    check_launch("theta_hub_partial");
+    // (ThetaHub::first counts from the head of the table, so the partials are addressed from there too; E / D by global row)
+    hipLaunchKernelGGL((theta_hub_combine_kernel<T>), dim3(elem_grid((int64_t)(h1 - h0) * t.c)), dim3(256), 0, st,
+                       (const ThetaHub*)th.HubRows.ptr + h0, (int64_t)(h1 - h0), (const T*)th.HubE.ptr, (const T*)th.HubD.ptr,
+                       (T*)t.E.ptr, (T*)t.D.ptr, t.c);
+    check_launch("theta_hub_combine");
+}
+
 // D_i += Theta+ G_i ; E_i += Theta- G_i   (_dfmf.py:284-292) on the rows [r0, r0 + nr) of the constrained type (all of
 // them, or -- ownership-aligned row blocks -- the rows this plan owns: a row of the product needs the row of Theta and the
 // whole factor).  `only_type` >= 0: the constraints of that type only.
@@ -479,15 +515,20 @@ static void theta_terms_rows(skf_plan* p, int only_type, bool own_rows, hipStrea
         if (th.sparse) {    // both halves in one pass over the CSR form, master precision
             if (th.nnz == 0) continue;
             const int grid = wave_grid(nr);
+            const int64_t hub = th.n_seg > 0 ? th.hub_row : 0;      // (a plan without hub rows launches what it always did)
             if (p->f64)
                 hipLaunchKernelGGL((theta_spmm_kernel<double>), dim3(grid), dim3(256), 0, st, (const int64_t*)th.Rp.ptr + r0,
                                    (const int*)th.Ci.ptr, (const double*)th.Vv.ptr, (const double*)t.G.ptr, (double*)Er,
-                                   (double*)Dr, nr, t.c);
+                                   (double*)Dr, nr, t.c, hub);
             else
                 hipLaunchKernelGGL((theta_spmm_kernel<float>), dim3(grid), dim3(256), 0, st, (const int64_t*)th.Rp.ptr + r0,
                                    (const int*)th.Ci.ptr, (const float*)th.Vv.ptr, (const float*)t.G.ptr, (float*)Er,
-                                   (float*)Dr, nr, t.c);
+                                   (float*)Dr, nr, t.c, hub);
             check_launch("theta_spmm");
+            if (hub > 0) {
+                if (p->f64) theta_hub_rows_t<double>(th, t, r0, nr, st);
+                else theta_hub_rows_t<float>(th, t, r0, nr, st);
+            }
             continue;
         }
         if (p->bf16) {      // bf16 copies of the halves against the stored G^T, f32 accumulate, then added

@@ -4,7 +4,7 @@
 iteration (_dfmc.py:287-292, :319-325).  The relation matrices passed in are never modified
 (the engine completes a device-side copy)."""
 from ... import _native as nat
-from ._dfmf import run_fit, run_fit_sharded, run_fit_rows, run_fit_owned
+from ._dfmf import run_fit, run_fit_sharded, run_fit_rows, run_fit_owned, refuse_constraint_entries
 
 
 def _expand_known_entries(R, M):
@@ -22,8 +22,10 @@ def _expand_known_entries(R, M):
 def dfmc(R, M, Theta, obj_types, obj_type2rank, max_iter=10, init_type="random_vcol",
          stopping=None, stopping_system=None, verbose=0, compute_err=False, callback=None,
          random_state=None, n_jobs=1, dtype='f64', G0=None, engine=None, shard=None):
-    """Data fusion by matrix completion -- drop-in for reference ``dfmc`` (_dfmc.py:181)."""
+    """Data fusion by matrix completion -- drop-in for reference ``dfmc`` (_dfmc.py:181).  Constraints given as their entries:
+    as in ``_dfmf.dfmf`` (shard None / 'runs' only)."""
     if shard in ('relations', 'rows', 'owned'):
+        refuse_constraint_entries(Theta, shard)
         R, M = _expand_known_entries(R, M)      # (the sharded fits take the mask form)
         fit = {'relations': run_fit_sharded, 'rows': run_fit_rows, 'owned': run_fit_owned}[shard]
         return fit(nat.SKF_DFMC, R, M, Theta, obj_types, obj_type2rank, max_iter,

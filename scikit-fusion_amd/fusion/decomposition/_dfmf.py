@@ -356,13 +356,25 @@ def run_fit(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type,
         plan.close()
 
 
+def refuse_constraint_entries(Theta, shard):
+    """The sharded fits take dense constraints: one given as its entries (_engine.KnownEntries) is the caller's mistake --
+    the class layer expands it before it gets here."""
+    from ..._engine import KnownEntries, DeviceKnownEntries
+    for key, mats in (Theta or {}).items():
+        if any(isinstance(m, (KnownEntries, DeviceKnownEntries)) for m in mats):
+            raise ValueError("constraint %r is given as its entries: shard=%r takes dense constraints (shard='runs' or toarray())"
+                             % (key, shard))
+
+
 def dfmf(R, Theta, obj_types, obj_type2rank, max_iter=10, init_type="random_vcol",
          stopping=None, stopping_system=None, verbose=0, compute_err=False, callback=None,
          random_state=None, n_jobs=1, dtype='f64', G0=None, engine=None, shard=None):
     """Data fusion by matrix factorization -- drop-in for reference ``dfmf`` (_dfmf.py:127).
     ``shard='relations'`` (with an initialised torch.distributed group) partitions the relations
-    of this ONE fit over the ranks."""
+    of this ONE fit over the ranks.  A constraint in ``Theta`` may be an ``_engine.KnownEntries(unstored='zero')`` -- its
+    entries as canonical CSR, never expanded -- with shard None / 'runs'; any other shard: ValueError."""
     if shard in ('relations', 'rows', 'owned'):
+        refuse_constraint_entries(Theta, shard)
         logging.basicConfig(format="%(asctime)s %(levelname)s: %(message)s", level=50 - verbose)
         fit = {'relations': run_fit_sharded, 'rows': run_fit_rows, 'owned': run_fit_owned}[shard]
         return fit(nat.SKF_DFMF, R, None, Theta, obj_types, obj_type2rank, max_iter,
@@ -436,7 +448,8 @@ def transform(R_ij, Theta_i, target_obj_type, obj_type2rank, G, S, max_iter=10,
               engine=None):
     """Fold new objects of ``target_obj_type`` into a fitted latent space -- drop-in for
     reference ``transform`` (_dfmf.py:330-458): only the target factor moves, ``G`` of the other
-    types and ``S`` (1-element lists per pair) stay frozen.  callback(G_i, iter)."""
+    types and ``S`` (1-element lists per pair) stay frozen.  callback(G_i, iter).  A constraint on the target may be an
+    ``_engine.KnownEntries(unstored='zero')``: its entries as canonical CSR, never expanded."""
     logging.basicConfig(format="%(asctime)s %(levelname)s: %(message)s", level=50 - verbose)
     t = target_obj_type
     sizes = [R_ij[i, j][0].shape[0 if t == i else 1] for i, j in R_ij]

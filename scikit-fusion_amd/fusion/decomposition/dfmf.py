@@ -65,6 +65,26 @@ def stored_entries_apply(relation, sparse_relations, shard='runs'):
     return cells > 0 and nnz / cells * rank <= SPARSE_RULE
 
 
+def constraint_entries_apply(relation, sparse_constraints, shard='runs'):
+    """Whether a ``scipy.sparse`` constraint (row type == column type) with ``unstored='zero'`` goes to the device as its
+    entries (never expanded): shard='runs', no preprocessor, finite stored values and at most 2e9 of them.
+    `sparse_constraints` True: whenever eligible; False: never (``toarray()``); None: when nnz <= n * n / the library's own
+    divisor (``small_graph_limits()``: up to there the dense-fed form is compacted to the same lists, so nothing changes but
+    the hand-over) -- a denser one is expanded and takes the dense product, the measured path at that density."""
+    if sparse_constraints is False or shard != 'runs':
+        return False
+    if not relation.is_zero_unstored() or relation.preprocessor or relation.row_type != relation.col_type:
+        return False
+    nnz = int(relation.data.nnz)
+    if nnz > 2000000000 or not np.isfinite(relation.data.data).all():      # (a stored NaN / inf is filled: the dense path's job)
+        return False
+    if sparse_constraints:
+        return True
+    from ..._engine import small_graph_limits
+    n = int(relation.data.shape[0])
+    return nnz <= n * n // small_graph_limits()['constraint_nnz_divisor']
+
+
 FOLD_MIN_CELLS = 1 << 20       # fold-ins, default rule: below this many cells the dense upload is free and nothing changes
 
 
@@ -90,7 +110,7 @@ def fold_entries_apply(relation, sparse_relations):
 
 
 def graph_matrices(fusion_graph, with_masks=False, device_dtype=None, known_entries=False, sparse_relations=False,
-                   shard='runs'):
+                   shard='runs', sparse_constraints=False):
     """FusionGraph -> (R, Theta[, M]) dictionaries in the reference's walking order
     (dfmf.py:70-85, dfmc.py:70-93): pairs from product(object_types, repeat=2), each relation
     filled, then preprocessed; relations between two different types go to R, same-type
@@ -101,7 +121,8 @@ def graph_matrices(fusion_graph, with_masks=False, device_dtype=None, known_entr
     ``known_entries`` (Dfmc, shard='runs'): relations given as their known entries enter as ``_engine.KnownEntries`` with
     mask None where ``known_entries_apply`` says so (never filled on the device: nothing unknown is stored).
     ``sparse_relations`` / ``shard``: scipy.sparse relations whose unstored entries are zero enter as their stored entries
-    (``_engine.KnownEntries`` with ``unstored='zero'``, mask None) where ``stored_entries_apply`` says so."""
+    (``_engine.KnownEntries`` with ``unstored='zero'``, mask None) where ``stored_entries_apply`` says so, and
+    ``sparse_constraints``: scipy.sparse constraints as their entries where ``constraint_entries_apply`` says so."""
     R, Theta, M = {}, {}, {}
     for row_type, col_type in product(fusion_graph.object_types, repeat=2):
         for relation in fusion_graph.get_relations(row_type, col_type):
@@ -110,6 +131,8 @@ def graph_matrices(fusion_graph, with_masks=False, device_dtype=None, known_entr
                 data = relation.known_entries()
             elif stored_entries_apply(relation, sparse_relations, shard):
                 data = relation.stored_entries()
+            elif constraint_entries_apply(relation, sparse_constraints, shard):
+                data = relation.constraint_entries()
             elif device_dtype and not relation.preprocessor and relation.row_type != relation.col_type:
                 data, mask = relation.filled_device(device_dtype)
             else:
@@ -190,7 +213,10 @@ def shared_launches(fuser):
         if rel.row_type is rel.col_type:
             n_theta += 1
             n = rel.data.shape[0]
-            nnz = int(np.count_nonzero(np.ma.getdata(rel.dense_data())))
+            if rel.is_zero_unstored():          # counted on the sparse matrix itself, never expanded
+                nnz = int(rel.constraint_entries().known)
+            else:
+                nnz = int(np.count_nonzero(np.ma.getdata(rel.dense_data())))
             if nnz == 0 or nnz > n * n // lim['constraint_nnz_divisor']:
                 return False
         else:
@@ -228,11 +254,16 @@ class Dfmf(FusionFit):
     alone, never expanded, with shard='runs', no preprocessor and two different object types -- None: when
     density * max(rank_row, rank_col) <= 4 and the relation is beyond the small-graph limits (a rank above 64 or more
     than 8192 objects on a side); True: always; False: never (``toarray()``).
+    sparse_constraints=None | True | False: a ``scipy.sparse`` constraint (a relation of a type with itself,
+    ``unstored='zero'``) goes to the device as its entries, never expanded, with shard='runs' and no preprocessor -- None:
+    when nnz <= n * n / 16 (the engine's own bound for the sparse product; a denser one is expanded and multiplied as a
+    dense matrix); True: always; False: never (``toarray()``).  Same factors either way, bit for bit, up to that bound.
     """
 
     def __init__(self, max_iter=100, init_type='random_c', n_run=1, stopping=None,
                  stopping_system=None, verbose=0, compute_err=False, callback=None,
-                 random_state=None, n_jobs=1, dtype='f64', shard='runs', device_fill=False, sparse_relations=None):
+                 random_state=None, n_jobs=1, dtype='f64', shard='runs', device_fill=False, sparse_relations=None,
+                 sparse_constraints=None):
         super(Dfmf, self).__init__()
         self._set_params(vars())
 
@@ -242,7 +273,8 @@ class Dfmf(FusionFit):
         object_types = list(fusion_graph.object_types)
         rank = {ot: int(ot.rank) for ot in object_types}
         R, Theta = graph_matrices(fusion_graph, device_dtype=device_fill_dtype(self),
-                                  sparse_relations=getattr(self, 'sparse_relations', None), shard=self.shard)
+                                  sparse_relations=getattr(self, 'sparse_relations', None), shard=self.shard,
+                                  sparse_constraints=getattr(self, 'sparse_constraints', None))
         G0 = initial_factors(R, object_types, rank, self.init_type, self.random_state, self.n_run)
         kw = dict(R=R, Theta=Theta, obj_types=object_types, obj_type2rank=rank,
                   max_iter=self.max_iter, init_type=self.init_type, stopping=self.stopping,
@@ -283,11 +315,13 @@ class DfmfTransform(FusionTransform):
     has at least 2^20 cells (below that the dense upload is free and results stay bit for bit).  Stored non-finite values
     take `fill_value`, as in the dense path; entries that are not stored are zeros, not unknowns, and never filled.  A
     relation given with ``unstored='unknown'`` is still expanded: the reference's fold-in fills it.
+    sparse_constraints=None | True | False: a ``scipy.sparse`` constraint on the target goes to the device as its entries,
+    under the rule of ``Dfmf``.
     """
 
     def __init__(self, max_iter=100, init_type=None, n_run=1, stopping=None,
                  stopping_system=None, fill_value=0, verbose=0, compute_err=False,
-                 callback=None, random_state=None, n_jobs=1, dtype='f64', sparse_relations=None):
+                 callback=None, random_state=None, n_jobs=1, dtype='f64', sparse_relations=None, sparse_constraints=None):
         super(DfmfTransform, self).__init__()
         self._set_params(vars())
 
@@ -310,6 +344,9 @@ class DfmfTransform(FusionTransform):
                     data = relation.stored_entries(by_col=relation.row_type != target)
                     data.values[~np.isfinite(data.values)] = self.fill_value
                     R.setdefault((relation.row_type, relation.col_type), []).append(data)
+                    continue
+                if relation.row_type == target and constraint_entries_apply(relation, getattr(self, 'sparse_constraints', None)):
+                    Theta.setdefault((relation.row_type, relation.col_type), []).append(relation.constraint_entries())
                     continue
                 data = relation.preprocessor(relation.dense_data()) if relation.preprocessor \
                     else relation.dense_data()

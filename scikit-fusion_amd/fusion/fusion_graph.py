@@ -151,7 +151,8 @@ class Relation(object):
     ``data`` may also be a ``scipy.sparse`` matrix.  ``unstored`` says what its entries that are not stored mean:
     'zero' (default, scipy's own meaning: the result is the one of fusing ``toarray()``; ``Dfmf`` / ``Dfmc`` with
     shard='runs' fit a sparse enough one on its stored entries alone and never expand it, and ``DfmfTransform`` folds new
-    objects in through one the same way -- see their ``sparse_relations`` keyword -- and everything else expands it) or
+    objects in through one the same way -- see their ``sparse_relations`` keyword; a sparse enough CONSTRAINT, row type ==
+    column type, goes to the device as its entries too, see ``sparse_constraints`` -- and everything else expands it) or
     'unknown': the relation is exactly the ``numpy.ma.MaskedArray`` whose stored entries are unmasked and whose unstored
     entries are masked -- every result equals what that MaskedArray gives.  Stored zeros are known zeros; duplicate
     entries are summed (as ``toarray()`` sums them); stored NaN / inf take the fill value and stay known, as in the
@@ -226,6 +227,18 @@ class Relation(object):
             return KnownEntries(csc.indptr, csc.indices, csc.data, csc.shape, unstored='zero', by_col=True)
         csr = scipy.sparse.csr_matrix(self.data, dtype=np.float64, copy=True)
         csr.sum_duplicates()
+        csr.sort_indices()
+        return KnownEntries(csr.indptr, csr.indices, csr.data, csr.shape, unstored='zero')
+
+    def constraint_entries(self):
+        """A constraint (row type == column type, ``unstored='zero'``) as the canonical CSR of its NON-ZERO entries
+        (``_engine.KnownEntries`` with ``unstored='zero'``): duplicates summed, columns sorted, explicit zeros dropped --
+        entry for entry the lists the engine compacts ``toarray()`` to, so both forms give the same bits."""
+        from .._engine import KnownEntries
+        import scipy.sparse
+        csr = scipy.sparse.csr_matrix(self.data, dtype=np.float64, copy=True)
+        csr.sum_duplicates()
+        csr.eliminate_zeros()
         csr.sort_indices()
         return KnownEntries(csr.indptr, csr.indices, csr.data, csr.shape, unstored='zero')
 
