@@ -112,8 +112,16 @@ enum {
                                  lists over before skf_plan_bind_workspace.  Always kept as lists of its known entries (neither
                                  SKF_DFMC_SPARSE nor the share rule applies: there is no dense form to fall back on); the lists
                                  built at bind time are the ones the mask form of the same data builds, byte for byte.
-                                 SKF_E_INVALID: SKF_DFMF / SKF_TRANSFORM plans, row blocks / sliced / SKF_OPT_OWNED_ROWS plans,
-                                 a row type's rank above 1024, more than 2e9 entries. */
+                                 SKF_OPT_OWNED_ROWS plans take the relation as the CSR of the OWNED rows of its row type, over
+                                 all columns: row_begin / n_rows are exactly the range skf_owned_rows names (the rule of dense
+                                 blocks), skf_plan_set_known_entries receives indptr[n_rows + 1] rebased to 0 and known_bound is
+                                 the slice's entry count; a process that owns no row of the row type passes SKF_REL_KNOWN_CSR |
+                                 SKF_REL_ABSENT and hands over no lists.  After bind such a relation is a masked row block
+                                 flagged SKF_REL_KNOWN_LISTS (the absent process adds the dense part of Q on its rows of the
+                                 column type).
+                                 SKF_E_INVALID: SKF_DFMF / SKF_TRANSFORM plans, row blocks / sliced plans without
+                                 SKF_OPT_OWNED_ROWS, a block of an owned plan that is not the owned range, a row type's rank
+                                 above 1024, more than 2e9 entries. */
     SKF_REL_SPARSE_CSR = 128, /* SKF_DFMF plans, and unmasked relations of SKF_DFMC plans: the relation is given as the CSR of its
                                  STORED entries and every other entry is ZERO (what a scipy.sparse matrix means; the reference
                                  multiplies its dense expansion, _dfmf.py:249-276, and forms its error from the dense
@@ -125,9 +133,17 @@ enum {
                                  included), skf_relation_sqerr = tr(S^T Gram_i S Gram_j) + sum over the stored entries of
                                  (r - x)^2 - x^2.  Workspace grows with the number of entries and n * c, never with n_i * n_j.
                                  Such a plan runs the relation pipeline or the staged schedule, never the small-graph one.
-                                 Stored zeros stay entries.  SKF_E_INVALID: SKF_TRANSFORM plans, row blocks / sliced /
-                                 SKF_OPT_OWNED_ROWS plans, a rank above 1024, more than 2e9 entries, a mask, together with
-                                 SKF_REL_KNOWN_CSR. */
+                                 Stored zeros stay entries.  SKF_OPT_OWNED_ROWS plans take the CSR of the OWNED rows of the row
+                                 type, over all columns, under the slice convention of SKF_REL_KNOWN_CSR (row_begin / n_rows =
+                                 the owned range, indptr[n_rows + 1] rebased to 0, known_bound = the slice's entry count,
+                                 SKF_REL_SPARSE_CSR | SKF_REL_ABSENT and no lists where the process owns no row of the row type:
+                                 it still contributes a zero partial Q and receives its scattered rows); the owned schedule runs
+                                 as for a dense block -- P on the local rows, the share of W, the partial Q over all columns --
+                                 and skf_relation_sqerr covers the local rows (the trace term from the Gram of the local rows of
+                                 G_i: the processes' values sum to the relation's).  Nothing of size n_rows x n_j exists.
+                                 SKF_E_INVALID: SKF_TRANSFORM plans, row blocks / sliced plans without SKF_OPT_OWNED_ROWS, a
+                                 block of an owned plan that is not the owned range, a rank above 1024, more than 2e9 entries,
+                                 a mask, together with SKF_REL_KNOWN_CSR. */
     SKF_REL_FOLD_CSR = 256    /* SKF_TRANSFORM plans only: the NEW relation is given as its STORED entries, every other entry ZERO,
                                  compressed along the TARGET's side -- indptr[n_target + 1] (int64), indices (int32, into the
                                  partner type, strictly ascending within a target object) and values in the MASTER type (f64 /
@@ -213,7 +229,8 @@ int skf_plan_destroy(skf_plan* plan);
 int skf_plan_workspace_bytes(const skf_plan* plan, size_t* bytes);
 /* The known entries of relation `rel` (flagged SKF_REL_KNOWN_CSR; or the stored entries of one flagged SKF_REL_SPARSE_CSR
  * or SKF_REL_FOLD_CSR -- the latter compressed along the target's side, see the flag --, whose values are of the master
- * type -- SKF_BF16: f32), as device pointers: indptr[n_row + 1] (int64,
+ * type -- SKF_BF16: f32), as device pointers: indptr[n_row + 1] (int64; n_row = the LOCAL rows: all of them, or the owned
+ * rows of a SKF_OPT_OWNED_ROWS plan, whose slice is rebased to start at 0; a SKF_REL_ABSENT relation takes no call: SKF_E_INVALID;
  * indptr[0] = 0, indptr[n_row] = known_bound, non-decreasing), indices[known_bound] (int32 columns, strictly ascending
  * within a row: canonical CSR, duplicates summed beforehand) and values[known_bound] of the element type of
  * skf_relation_desc.data (SKF_BF16: bf16 bits).  Call it between skf_plan_create and skf_plan_bind_workspace; the buffers
@@ -391,7 +408,9 @@ int skf_get_contraction(const skf_plan* plan, int32_t rel, int32_t which, void* 
  * SKF_REL_SPARSE_CSR relation), for verification: by_col = 0 the row lists (rows -> ascending columns), 1 the column lists
  * (columns -> ascending rows).  `parts` / `n_entries` (host) receive the number of parts the lists are cut into and the
  * number of entries; `ptr` (device, n * parts + 1 int64: the segment pointers, every `parts`-th one opens a list), `idx`
- * (device, n_entries int32) and `values` (device, n_entries of the master type) receive copies.  Null pointers are skipped. */
+ * (device, n_entries int32) and `values` (device, n_entries of the master type) receive copies.  Null pointers are skipped.
+ * SKF_OPT_OWNED_ROWS plans: the lists of the slice -- n = the local rows for the row lists, and the column lists hold LOCAL row
+ * indices (row - row_begin); SKF_E_STATE for a SKF_REL_ABSENT relation. */
 int skf_get_relation_lists(const skf_plan* plan, int32_t rel, int32_t by_col, int32_t* parts, int64_t* n_entries, int64_t* ptr,
                            int32_t* idx, void* values, void* stream);
 

@@ -74,6 +74,15 @@ class KnownEntries(object):
         outer, inner = self.row_of_entries(), self.indices.astype(np.int64)
         return (inner, outer) if self.by_col else (outer, inner)
 
+    def row_slice(self, begin, count):
+        """The entries of rows [begin, begin + count) as a container of their own: slices of `indices` / `values` (views) and
+        `indptr` rebased to 0 -- no dense step.  What a rank of an ownership-sharded fit hands to its plan."""
+        if self.by_col:
+            raise ValueError('lists compressed along the column type have no row slices')
+        lo, hi = int(self.indptr[begin]), int(self.indptr[begin + count])
+        return KnownEntries(self.indptr[begin:begin + count + 1] - lo, self.indices[lo:hi], self.values[lo:hi],
+                            (count, self.shape[1]), fill=self.fill, unstored=self.unstored)
+
     def toarray(self, fill=None):
         """The dense relation of the mask form: the values on the known entries, `fill` (default: self.fill) elsewhere."""
         out = np.full(self.shape, self.fill if fill is None else fill, dtype=np.float64)
@@ -490,7 +499,9 @@ class DevicePlan(object):
         thetas: list of (type, ndarray | DeviceMatrix | KnownEntries(unstored='zero') | DeviceKnownEntries -- the last two:
         the constraint as the CSR of its stored entries, never expanded).  `block` (row-block sharding, `_distributed.partition_rows`)
         = dict(row_begin, n_rows, absent, col_side, masked): data / mask then hold only the local rows
-        (None when absent); `part` = (index, count) of this plan among the row-block plans.
+        (None when absent); `part` = (index, count) of this plan among the row-block plans.  With `owned`, data may be the
+        KnownEntries of the local rows (shape (n_rows, n_col), indptr from 0); an absent block of such a relation says which
+        kind it is with entries='unknown' | 'zero'.
         `owned`: the row blocks are the ranges of `owned_rows` (SKF_OPT_OWNED_ROWS: every rank owns the same share of the rows
         of every type; such a plan iterates through iterate_dist only).
         `sparse_known` (DFMC): None = the engine decides from the number of known entries of every masked relation
@@ -518,18 +529,30 @@ class DevicePlan(object):
             tdesc[k].n_obj, tdesc[k].rank = self.n_obj[k], self.rank[k]
         rdesc = (nat.RelationDesc * max(len(relations), 1))()
         csr = []                                         # (relation, DeviceKnownEntries): skf_plan_set_known_entries
+        self.local_rows = []                             # rows of every relation this plan holds (its block, or all of them)
         for k, rel in enumerate(relations):
             i, j, data, mask = rel[:4]
             block = rel[4] if len(rel) > 4 else None
             rdesc[k].row_type, rdesc[k].col_type = self.index[i], self.index[j]
+            self.local_rows.append(int(block['n_rows']) if block is not None else n_obj[i])
+            if block is not None and block.get('absent') and block.get('entries'):
+                # row ownership, a relation given as its entries, no row of it here: no lists, only the flags
+                if not owned:
+                    raise ValueError('relation (%s,%s): known entries take a row block under row ownership only' % (i, j))
+                rdesc[k].flags = nat.SKF_REL_ABSENT | (nat.SKF_REL_SPARSE_CSR if block['entries'] == 'zero'
+                                                       else nat.SKF_REL_KNOWN_CSR)
+                continue
             if isinstance(data, (KnownEntries, DeviceKnownEntries)):
                 # the known entries only (SKF_REL_KNOWN_CSR), or the stored entries of a relation that is zero elsewhere
-                # (SKF_REL_SPARSE_CSR): no dense form, no mask; always kept as lists
-                if mask is not None or block is not None:
+                # (SKF_REL_SPARSE_CSR): no dense form, no mask; always kept as lists.  Row ownership: the CSR of the owned
+                # rows, indptr rebased to 0, columns over the whole column type
+                if mask is not None or (block is not None and not owned):
                     raise ValueError('relation (%s,%s): known entries take no mask and no row block' % (i, j))
-                if tuple(data.shape) != (n_obj[i], n_obj[j]):
+                if tuple(data.shape) != (self.local_rows[k], n_obj[j]):
                     raise ValueError('relation (%s,%s) dimension mismatch: %r vs object counts (%d,%d)'
-                                     % (i, j, tuple(data.shape), n_obj[i], n_obj[j]))
+                                     % (i, j, tuple(data.shape), self.local_rows[k], n_obj[j]))
+                if block is not None:
+                    rdesc[k].row_begin, rdesc[k].n_rows = int(block['row_begin']), self.local_rows[k]
                 dev = data if isinstance(data, DeviceKnownEntries) else upload_known_entries(data, self.dtype, mem)
                 self._keep_rel.append(dev)
                 if variant == nat.SKF_TRANSFORM and dev.unstored == 'zero':
@@ -764,8 +787,8 @@ class DevicePlan(object):
     def relation_lists(self, rel, by_col=False):
         """(indptr, indices, values) of the entry lists relation `rel` keeps (verification accessor): the row lists, or with
         by_col the column lists -- canonical CSR / CSC whatever the number of parts the engine cut them into."""
-        i, j = self.relations[rel][0], self.relations[rel][1]
-        n_out = self.n_obj[self.index[j if by_col else i]]
+        j = self.relations[rel][1]
+        n_out = self.n_obj[self.index[j]] if by_col else self.local_rows[rel]      # (row ownership: local rows, local indices)
         parts, nnz = C.c_int32(), C.c_int64()
         self.rt.call('skf_get_relation_lists', self.handle, rel, int(bool(by_col)), C.byref(parts), C.byref(nnz), None, None,
                      None, self.stream)

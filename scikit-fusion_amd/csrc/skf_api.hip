@@ -220,7 +220,10 @@ static void plan_describe_relations(skf_plan* p, int32_t n_types, int32_t n_rela
             SKF_FAIL(SKF_E_INVALID, "relation %d: row block [%lld, +%lld) outside the %lld objects of its row type",
                      r, (long long)d.row_begin, (long long)d.n_rows, (long long)n_row_type);
         const bool block = absent || (d.n_rows > 0 && d.n_rows < n_row_type) || (d.flags & SKF_REL_NO_COL_SIDE);
-        if (block && (csr || sp0)) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR relations are whole relations", r);
+        // (SKF_OPT_OWNED_ROWS: the CSR of the owned rows, over all columns -- held to the owned range below, like a dense block)
+        if (block && (csr || sp0) && !p->owned)
+            SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR relations are whole relations "
+                     "(or the owned rows of a SKF_OPT_OWNED_ROWS plan)", r);
         if (block && fold) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR relations are whole relations", r);
         if (block && p->variant == SKF_TRANSFORM)
             SKF_FAIL(SKF_E_INVALID, "relation %d: row blocks are for SKF_DFMF / SKF_DFMC plans", r);
@@ -316,7 +319,8 @@ static void plan_decide_lists(skf_plan* p, const skf_relation_desc* relations) {
             // valued lists whatever the density (the caller chose the form; no dense one to fall back on).  P gathers
             // rank_col-wide rows of G_j through the row lists, Q rank_row-wide rows of G_i through the column lists
             const int cj = p->types[s.col].c;
-            if (p->sliced) SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_SPARSE_CSR is for plans of whole relations", rk);
+            if (p->sliced && !p->owned)
+                SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_SPARSE_CSR is for plans of whole relations or of owned rows", rk);
             if (ci > 64 * SRP_MAXREP || cj > 64 * SRP_MAXREP || s.kn_cap > 2000000000LL)
                 SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_SPARSE_CSR beyond the list limits (a rank above %d or %lld > 2e9 entries)",
                          rk, 64 * SRP_MAXREP, (long long)s.kn_cap);
@@ -326,7 +330,9 @@ static void plan_decide_lists(skf_plan* p, const skf_relation_desc* relations) {
         }
         if (s.kn_csr) {
             // lists whatever the share (no dense form to fall back on); the parts below follow from the exact count
-            if (p->sliced) SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_KNOWN_CSR is for plans of whole relations", rk);
+            // (SKF_OPT_OWNED_ROWS: the slice of the owned rows; from here on a masked row block flagged SKF_REL_KNOWN_LISTS)
+            if (p->sliced && !p->owned)
+                SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_KNOWN_CSR is for plans of whole relations or of owned rows", rk);
             if (ci > 64 * SRP_MAXREP || s.kn_cap > 2000000000LL)
                 SKF_FAIL(SKF_E_INVALID, "relation %zu: SKF_REL_KNOWN_CSR beyond the list limits (rank %d > %d or %lld > 2e9 entries)",
                          rk, ci, 64 * SRP_MAXREP, (long long)s.kn_cap);
@@ -844,6 +850,7 @@ int skf_plan_set_known_entries(skf_plan* plan, int32_t rel, const int64_t* indpt
         RelState& r = plan->rels[rel];
         if (!r.kn_csr && !r.sp0 && !r.fold)
             SKF_FAIL(SKF_E_INVALID, "relation %d is flagged neither SKF_REL_KNOWN_CSR, SKF_REL_SPARSE_CSR nor SKF_REL_FOLD_CSR", rel);
+        if (r.absent) SKF_FAIL(SKF_E_INVALID, "relation %d is SKF_REL_ABSENT here: it takes no lists", rel);
         if (!indptr || (r.kn_cap > 0 && (!indices || !values))) SKF_FAIL(SKF_E_INVALID, "relation %d: null CSR array", rel);
         r.csr_ptr = indptr;
         r.csr_idx = (const int*)indices;
@@ -1351,10 +1358,13 @@ int skf_relation_sqerr(skf_plan* p, int32_t rel, double* out, void* stream) {
             //     |R|^2 - 2 <R, X> = sum over the stored entries of (r - x)^2 - x^2 ,  x = <(G_i S)[row], G_j[col]>
             // -- one pass over the row lists, never the n_i x n_j reconstruction (reference: _dfmf.py:306-316 on the dense form).
             // (slot 0 of the partials collects the trace term, the pass writes behind it)
-            gram_of(ti.G.ptr, ti.G.ptr, r.Xi.ptr, ci, r.nr);
+            // (row ownership: the Gram of the LOCAL rows of G_i -- the trace term is linear in it, so the ranks' values sum to
+            // the relation's error -- and H of those rows)
+            const void* Gi_b = rows_of(p, ti.G, ti, r.r0);
+            gram_of(Gi_b, Gi_b, r.Xi.ptr, ci, r.nr);
             gram_of(tj.G.ptr, tj.G.ptr, r.Xj.ptr, cj, tj.n);
             trace_term(r.Xi.ptr, r.S.ptr, r.Xj.ptr, r.S.ptr, 1.0, true);
-            GemmArgs h = gemm_args(ti.G.ptr, ci, 1, r.S.ptr, cj, 1, r.H.ptr, cj, ni, cj, ci, EPI_STORE, 0);       // H = G_i S
+            GemmArgs h = gemm_args(Gi_b, ci, 1, r.S.ptr, cj, 1, r.H.ptr, cj, ni, cj, ci, EPI_STORE, 0);           // H = G_i S
             mixed_gemm(p, h, st);
             const int waves = sparse_pass(p, r, false, true, nullptr, st, 1);
             hipLaunchKernelGGL((sum_partials_kernel<double>), dim3(1), dim3(256), 0, st, (const double*)p->sqpart.ptr, waves + 1, out);

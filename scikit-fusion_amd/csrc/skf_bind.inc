@@ -230,6 +230,7 @@ static void bind_relation_lists(skf_plan* p, hipStream_t st) {
             copy_fold_lists(p, r, st);
             continue;
         }
+        if ((r.kn_csr || r.sp0) && r.absent) continue;      // (row ownership, no row of the relation here: no lists, only the flag)
         if (r.kn_csr || r.sp0) {               // the caller's CSR, validated, then the same lists the mask form builds
             if (!r.csr_ptr) SKF_FAIL(SKF_E_INVALID, "a SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR relation without skf_plan_set_known_entries");
             build_known_lists_csr(p, r, st);

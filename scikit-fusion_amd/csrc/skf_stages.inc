@@ -146,6 +146,9 @@ static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void
     const int64_t n_out = is_q ? tj.n : r.nr;
     const int parts = is_q ? r.kn_pr : r.kn_pc;
     const int w = tin.c;
+    // Q gathers rows of G_i through column lists whose indices are LOCAL rows: the gathered base is the first row of the
+    // block (row ownership: the owned rows; a whole relation: row 0)
+    const int64_t in0 = is_q ? r.r0 : 0;
     if (err) {
         const int64_t need = ((n_out + 3) / 4 + (8 / parts) - 1) / (8 / parts) * 8 * 4 + sq_first;
         if ((size_t)need > p->sq_elems) SKF_FAIL(SKF_E_STATE, "residual partials: %lld > %zu slots", (long long)need, p->sq_elems);
@@ -166,18 +169,20 @@ static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void
     void* vals = is_q ? r.KcVal.ptr : r.KrVal.ptr;
     if (p->f64) {
         SrpArgs<double, double> a;
-        fill(a, (double*)vals, (const double*)tin.G.ptr, (int64_t)w, (const double*)r.H.ptr, (int64_t)w, (double*)out);
+        fill(a, (double*)vals, (const double*)rows_of(p, tin.G, tin, in0), (int64_t)w, (const double*)r.H.ptr, (int64_t)w, (double*)out);
         waves = launch_srp(a, st, false);
     } else if (p->bf16 && !err) {
         SrpArgs<uint16_t, float> a;
-        fill(a, (float*)vals, (const uint16_t*)tin.Grow.ptr, tin.ldrow, (const uint16_t*)nullptr, tin.ldrow, (float*)out);
-        // slots past the end of a list point at the all-zero row behind the gathered rows (32-bit byte offsets in the v6 kernel)
-        const int64_t zoff = tin.n * tin.ldrow * 2;
+        fill(a, (float*)vals, (const uint16_t*)tin.Grow.ptr + in0 * tin.ldrow, tin.ldrow, (const uint16_t*)nullptr, tin.ldrow, (float*)out);
+        // slots past the end of a list point at the all-zero row behind the gathered rows -- behind ALL rows of the type,
+        // counted from the gathered base (32-bit byte offsets in the v6 kernel; 0 = no such row: launch_srp then takes
+        // srp_bf16_kernel, which needs none -- SrpArgs::zero_off)
+        const int64_t zoff = (tin.n - in0) * tin.ldrow * 2;
         a.zero_off = (zoff + tin.ldrow * 2 < (int64_t)0xffffffffLL) ? (uint32_t)zoff : 0u;
         waves = launch_srp(a, st, false);
     } else {
         SrpArgs<float, float> a;
-        fill(a, (float*)vals, (const float*)tin.G.ptr, (int64_t)w, (const float*)r.H.ptr, (int64_t)w, (float*)out);
+        fill(a, (float*)vals, (const float*)rows_of(p, tin.G, tin, in0), (int64_t)w, (const float*)r.H.ptr, (int64_t)w, (float*)out);
         waves = launch_srp(a, st, false);
     }
     if (parts > 1 && !err) {

@@ -26,7 +26,8 @@ def dfmc(R, M, Theta, obj_types, obj_type2rank, max_iter=10, init_type="random_v
     as in ``_dfmf.dfmf`` (shard None / 'runs' only)."""
     if shard in ('relations', 'rows', 'owned'):
         refuse_constraint_entries(Theta, shard)
-        R, M = _expand_known_entries(R, M)      # (the sharded fits take the mask form)
+        if shard != 'owned':                    # (an ownership-sharded fit slices the entries by rows; the others take the mask form)
+            R, M = _expand_known_entries(R, M)
         fit = {'relations': run_fit_sharded, 'rows': run_fit_rows, 'owned': run_fit_owned}[shard]
         return fit(nat.SKF_DFMC, R, M, Theta, obj_types, obj_type2rank, max_iter,
                    init_type, random_state, dtype, G0, engine, stopping, stopping_system, compute_err, callback)

@@ -119,14 +119,26 @@ def row_block_plan(variant, rel_list, theta_list, obj_types, n_obj, obj_type2ran
 def owned_plan(variant, rel_list, theta_list, obj_types, n_obj, obj_type2rank, dtype, engine, rank, size):
     """The plan of rank `rank` of `size` in a fit sharded by OWNERSHIP (SKF_OPT_OWNED_ROWS): the rank owns the same share
     of the rows of every object type (`_engine.owned_rows`) and holds exactly those rows of every relation whose row type
-    it is -- work is 1 / size of every relation, the row-side terms never leave the rank -- and every constraint."""
-    from ..._engine import is_binary_matrix, owned_rows, known_lists_pay
+    it is -- work is 1 / size of every relation, the row-side terms never leave the rank -- and every constraint.
+    A relation given as its entries (`_engine.KnownEntries`, either kind) is sliced by rows -- `indptr`, `indices` and
+    `values` of the owned rows, no dense step -- and only that slice is uploaded; a rank without rows of its row type marks
+    it absent.  Every process still holds the WHOLE scipy.sparse matrix / KnownEntries on the host: the initialisers read
+    all of it (`_init._KnownView`), only the device sees a slice."""
+    from ..._engine import is_binary_matrix, owned_rows, known_lists_pay, KnownEntries, DeviceKnownEntries
     from ..._distributed import same_on_all_ranks
     local = []
     for (i, j, m, mask) in rel_list:
         begin, count, _ = owned_rows(dtype, n_obj[i], rank, size)
         info = {'masked': mask is not None, 'col_side': True, 'row_begin': begin if count else 0, 'n_rows': count,
                 'absent': count == 0}
+        if isinstance(m, DeviceKnownEntries):
+            raise ValueError("relation (%s,%s): an ownership-sharded fit slices the entries on the host (KnownEntries)" % (i, j))
+        if isinstance(m, KnownEntries):              # the CSR of the owned rows over all columns, never expanded
+            if mask is not None:
+                raise ValueError('relation (%s,%s): known entries take no mask' % (i, j))
+            info['entries'] = m.unstored
+            local.append((i, j, m.row_slice(begin, count) if count else None, None, info))
+            continue
         if mask is not None and variant == nat.SKF_DFMC:      # lists of the known entries: one decision for all ranks
             mk = np.asarray(mask, dtype=bool)
             info['known_lists'] = same_on_all_ranks(known_lists_pay(

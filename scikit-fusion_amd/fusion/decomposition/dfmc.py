@@ -18,7 +18,8 @@ class Dfmc(FusionFit):
     stopping=None, stopping_system=None, verbose=0, compute_err=False, callback=None,
     random_state=None, n_jobs=1.  Addition: dtype='f64' | 'f32'.  A relation given as its known entries
     (``Relation(scipy.sparse matrix, ..., unstored='unknown')``) is fitted on those entries alone with shard='runs'
-    (see ``Relation``); one whose unstored entries are zero on its stored entries (``sparse_relations``, see ``Dfmf``); a
+    (see ``Relation``) and with shard='owned', where every rank uploads the known entries of its owned rows only (the
+    whole matrix stays on every process's host for the initialisers; 'rows' / 'relations' expand it); one whose unstored entries are zero on its stored entries (``sparse_relations``, see ``Dfmf``); a
     ``scipy.sparse`` constraint as its entries (``sparse_constraints``, see ``Dfmf``)."""
 
     def __init__(self, max_iter=100, init_type='random_c', n_run=1, stopping=None,
@@ -34,7 +35,7 @@ class Dfmc(FusionFit):
         object_types = list(fusion_graph.object_types)
         rank = {ot: int(ot.rank) for ot in object_types}
         R, Theta, M = graph_matrices(fusion_graph, with_masks=True, device_dtype=device_fill_dtype(self),
-                                     known_entries=self.shard == 'runs',
+                                     known_entries=self.shard in ('runs', 'owned'),
                                      sparse_relations=getattr(self, 'sparse_relations', None), shard=self.shard,
                                      sparse_constraints=getattr(self, 'sparse_constraints', None))
         G0 = initial_factors(R, object_types, rank, self.init_type, self.random_state, self.n_run)

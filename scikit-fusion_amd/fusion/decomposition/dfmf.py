@@ -28,7 +28,8 @@ def _random_state(obj):
 def known_entries_apply(relation, known_entries):
     """Whether `relation` enters the fit as its known entries only (``Relation(..., unstored='unknown')`` on the list path
     of Dfmc: asked for by the caller, no preprocessor, fill 'mean' or a number, row type rank <= 1024 and at most 2e9
-    entries -- the limits of the library's known-entry lists).  Otherwise such a relation is expanded to its MaskedArray."""
+    entries -- the limits of the library's known-entry lists).  Otherwise such a relation is expanded to its MaskedArray.
+    The answer depends on the whole relation only, so every rank of a shard='owned' fit gives the same one."""
     if not (known_entries and relation.is_known_entries() and not relation.preprocessor):
         return False
     if relation.row_type == relation.col_type or int(relation.row_type.rank) > 1024 or relation.data.nnz > 2000000000:
@@ -41,13 +42,15 @@ SPARSE_RULE = 4.0       # density * max(rank_row, rank_col) at which the entry l
 
 def stored_entries_apply(relation, sparse_relations, shard='runs'):
     """Whether a ``scipy.sparse`` relation with ``unstored='zero'`` enters the fit as its stored entries (never expanded):
-    shard='runs', no preprocessor, row type != column type, ranks <= 1024 and at most 2e9 entries (the limits of the
+    shard='runs' or 'owned' (there every rank uploads the CSR of its owned rows; the decision reads the whole relation's
+    shape, nnz and ranks only, so it is the same on every rank; 'rows' / 'relations' expand), no preprocessor, row type !=
+    column type, ranks <= 1024 and at most 2e9 entries (the limits of the
     library's lists), and sparse enough -- `sparse_relations` None: density * max(rank_row, rank_col) <= 4, the rule of the
     known-entry lists, for relations beyond the limits of the small-graph schedule (a rank above 64 or more than 8192
     objects on a side, ``skf_small_graph_limits``: below them an iteration is bound by its launches, the three-launch
     schedule is the measured path and the lists would take the graph off it); True: whenever eligible; False: never
     (``toarray()``, as before the sparse path existed)."""
-    if sparse_relations is False or shard != 'runs':
+    if sparse_relations is False or shard not in ('runs', 'owned'):
         return False
     if not relation.is_zero_unstored() or relation.preprocessor or relation.row_type == relation.col_type:
         return False
@@ -118,7 +121,7 @@ def graph_matrices(fusion_graph, with_masks=False, device_dtype=None, known_entr
     with ``with_masks``, the mask is kept as the completion mask.
     ``device_dtype``: relations (not constraints) without a preprocessor are filled ON THE DEVICE and enter the
     dictionaries as device-resident matrices of that engine dtype (``Relation.filled_device``).
-    ``known_entries`` (Dfmc, shard='runs'): relations given as their known entries enter as ``_engine.KnownEntries`` with
+    ``known_entries`` (Dfmc, shard='runs' / 'owned'): relations given as their known entries enter as ``_engine.KnownEntries`` with
     mask None where ``known_entries_apply`` says so (never filled on the device: nothing unknown is stored).
     ``sparse_relations`` / ``shard``: scipy.sparse relations whose unstored entries are zero enter as their stored entries
     (``_engine.KnownEntries`` with ``unstored='zero'``, mask None) where ``stored_entries_apply`` says so, and
@@ -251,7 +254,10 @@ class Dfmf(FusionFit):
     every object type with the matching rows of its relations -- a reduce-scatter of each partial Q and an
     all-gather of the updated factor rows, the form with the least exchange).
     sparse_relations=None | True | False: a ``scipy.sparse`` relation (``unstored='zero'``) is fitted on its stored entries
-    alone, never expanded, with shard='runs', no preprocessor and two different object types -- None: when
+    alone, never expanded, with shard='runs' or shard='owned' (every rank then uploads the CSR of its owned rows only and no
+    dense row block exists anywhere; each process still holds the whole scipy.sparse matrix on the host, which the
+    initialisers read; a constraint of an owned fit is still handed over dense), no preprocessor and two different object
+    types -- None: when
     density * max(rank_row, rank_col) <= 4 and the relation is beyond the small-graph limits (a rank above 64 or more
     than 8192 objects on a side); True: always; False: never (``toarray()``).
     sparse_constraints=None | True | False: a ``scipy.sparse`` constraint (a relation of a type with itself,
