@@ -178,7 +178,12 @@ typedef struct {
                          n_i * n_i.  SKF_DFMF / SKF_DFMC plans and the target type of SKF_TRANSFORM plans, every engine.  For
                          the small-graph schedule it counts as sparse under the condition of skf_small_graph_limits
                          (0 < nnz <= n_i * n_i / 16); otherwise the plan takes the general schedule.  SKF_E_INVALID at
-                         skf_plan_create: plans with row blocks, sliced and SKF_OPT_OWNED_ROWS plans, more than 2e9 entries. */
+                         skf_plan_create: plans with row blocks, sliced and SKF_OPT_OWNED_ROWS plans, more than 2e9 entries.
+                         SKF_OPT_OWNED_ROWS plans with SKF_OPT_THETA_OWNED_ROWS take such a constraint as the CSR of the
+                         OWNED rows of its type (skf_owned_rows), over all columns: `nnz` is the exact entry count of that
+                         slice (it differs between the processes; 0 allowed, also where no row is owned) and the workspace
+                         grows by nnz * (4 + element size) + (count + 1) * 8 bytes -- with the slice, never with n_i * n_i
+                         or with the whole constraint. */
     int64_t ld;
     int64_t nnz;      /* 0: multiply it as a dense matrix, as the reference does (_dfmf.py:284-292).  > 0: an upper
                          bound on its non-zero entries -- the engine then keeps the constraint as CSR (built on the
@@ -205,7 +210,7 @@ typedef struct {
 } skf_options;
 
 enum {
-    SKF_OPT_OWNED_ROWS = 1 /* Ownership-aligned row sharding of ONE fit over `part_count` processes (replaces the
+    SKF_OPT_OWNED_ROWS = 1,/* Ownership-aligned row sharding of ONE fit over `part_count` processes (replaces the
                               reference's per-block joblib tasks, _dfmf.py:69-73, _dfmc.py:341-345): process `part_index` OWNS the
                               rows skf_owned_rows() names of EVERY object type -- their factor rows, their E / D accumulators,
                               their update -- and holds exactly those rows of every relation whose row type it is (the
@@ -214,7 +219,18 @@ enum {
                               exchange; per iteration a process sends only: the partial Q = R_blk^T G_i[blk] of every relation
                               (reduce-scatter to the owners of the column type), the updated factor rows (all-gather; SKF_BF16:
                               the bf16 operand copy only, unless a constraint on the type reads the f32 rows), and the c x c
-                              partial Gram / W matrices (all-reduce).  Such a plan iterates through skf_iterate_dist only. */
+                              partial Gram / W matrices (all-reduce).  Such a plan iterates through skf_iterate_dist only.
+                              (Every constraint in full: the dense-fed forms.  One given as its entries is held as the owned
+                              rows only, see SKF_OPT_THETA_OWNED_ROWS.) */
+    SKF_OPT_THETA_OWNED_ROWS = 2 /* only together with SKF_OPT_OWNED_ROWS (otherwise SKF_E_INVALID): a constraint whose
+                              skf_theta_desc.data is NULL is accepted and carries the rows [begin, begin + count) of its type
+                              that this process owns (skf_owned_rows) over ALL columns -- the rows the constraint pass of an
+                              owned plan multiplies; nothing else of Theta is ever read.  skf_theta_desc.nnz is the entry count
+                              of that slice, skf_plan_set_constraint_entries receives indptr[count + 1] rebased to 0; columns
+                              stay global.  The lists are those of the whole-matrix form cut at the row boundaries (hub rows
+                              are segmented per row from the row's first entry), so the fit has the bits of the fit whose
+                              constraint is handed over dense and compacted.  Dense-fed constraints of the same plan are
+                              untouched; without the flag a NULL data pointer stays an error on such a plan. */
 };
 
 /* ---- plan life cycle ------------------------------------------------------------------- */
@@ -242,7 +258,9 @@ int skf_plan_set_known_entries(skf_plan* plan, int32_t rel, const int64_t* indpt
 /* The stored entries of constraint `theta` (the index into the `thetas` of skf_plan_create; one whose skf_theta_desc.data is
  * NULL, _dfmf.py:284-292 on the dense expansion), as device pointers: indptr[n_i + 1] (int64, indptr[0] = 0,
  * indptr[n_i] = nnz, non-decreasing), indices[nnz] (int32 columns, strictly ascending within a row: canonical CSR, duplicates
- * summed beforehand) and values[nnz] in the MASTER type (f64 / f32; SKF_BF16 plans: f32).  Call it between skf_plan_create
+ * summed beforehand) and values[nnz] in the MASTER type (f64 / f32; SKF_BF16 plans: f32).  SKF_OPT_THETA_OWNED_ROWS plans:
+ * the slice of the owned rows -- indptr[count + 1] rebased to 0 (count = 0: the one pointer 0), indptr[count] = nnz, columns
+ * global in [0, n_i); every process makes the call, also one that owns no row.  Call it between skf_plan_create
  * and skf_plan_bind_workspace (afterwards: SKF_E_STATE); the buffers are read by skf_plan_bind_workspace and not referenced
  * afterwards (the contract of `data`).  Bind validates them on the device before anything gathers through them: an indptr
  * that does not run from 0 to nnz or steps down, an index outside [0, n_i) or a row whose columns do not ascend strictly is
@@ -414,6 +432,14 @@ int skf_get_contraction(const skf_plan* plan, int32_t rel, int32_t which, void* 
 int skf_get_relation_lists(const skf_plan* plan, int32_t rel, int32_t by_col, int32_t* parts, int64_t* n_entries, int64_t* ptr,
                            int32_t* idx, void* values, void* stream);
 
+/* The lists a constraint keeps after bind, for verification: one handed over dense and compacted (skf_theta_desc.nnz > 0),
+ * one given as its entries, or the slice of the owned rows of a SKF_OPT_THETA_OWNED_ROWS plan.  `n_rows` / `n_entries` (host)
+ * receive the rows the lists cover (n_i, or the owned rows of the slice) and the number of entries; `indptr` (device,
+ * n_rows + 1 int64), `indices` (device, n_entries int32) and `values` (device, n_entries of the master type) receive copies.
+ * Null pointers are skipped.  SKF_E_INVALID for a constraint kept dense. */
+int skf_get_constraint_lists(const skf_plan* plan, int32_t theta, int64_t* n_rows, int64_t* n_entries, int64_t* indptr,
+                             int32_t* indices, void* values, void* stream);
+
 /* Optional hipEvent timing of the launches that walk a relation (P = R G_j, Q = R^T G_i -- the dominant
  * kernel -- and their sparse counterparts).  get_profile synchronises on the recorded events, returns the summed
  * duration [ms], the number of launches, the flops they EXECUTE (2*M*N*K for a product on the matrix cores, dense or
@@ -566,8 +592,8 @@ const char* skf_version(void);
 /* Layout version of the structs and signatures above (SKF_ABI_VERSION).  A binding built against another version must not
  * call the library: descriptors grew between versions (skf_relation_desc.known_bound: 3, skf_options.flags: 4; version 5
  * adds entry points only -- skf_small_graph_limits, skf_comm_info, skf_launch_count; later: skf_fold_lists and the flag
- * SKF_REL_FOLD_CSR; skf_complete_topk_workspace_bytes, skf_complete_topk, skf_complete_entries and SKF_TOPK_MAX -- the
- * structs are those of version 4). */
+ * SKF_REL_FOLD_CSR; skf_complete_topk_workspace_bytes, skf_complete_topk, skf_complete_entries and SKF_TOPK_MAX;
+ * skf_get_constraint_lists and the flag SKF_OPT_THETA_OWNED_ROWS -- the structs are those of version 4). */
 #define SKF_ABI_VERSION 5
 int skf_abi_version(void);
 

@@ -497,7 +497,8 @@ class DevicePlan(object):
                  target=None, engine=None, runtime=None, part=None, stream=None, sparse_known=None, owned=False):
         """relations: list of (row_type, col_type, ndarray, mask-or-None[, block]);
         thetas: list of (type, ndarray | DeviceMatrix | KnownEntries(unstored='zero') | DeviceKnownEntries -- the last two:
-        the constraint as the CSR of its stored entries, never expanded).  `block` (row-block sharding, `_distributed.partition_rows`)
+        the constraint as the CSR of its stored entries, never expanded; with `owned`: the slice of the rows of the type this
+        part owns, shape (count, n), indptr from 0 -- SKF_OPT_THETA_OWNED_ROWS).  `block` (row-block sharding, `_distributed.partition_rows`)
         = dict(row_begin, n_rows, absent, col_side, masked): data / mask then hold only the local rows
         (None when absent); `part` = (index, count) of this plan among the row-block plans.  With `owned`, data may be the
         KnownEntries of the local rows (shape (n_rows, n_col), indptr from 0); an absent block of such a relation says which
@@ -631,14 +632,19 @@ class DevicePlan(object):
                 rdesc[k].flags |= nat.SKF_REL_KNOWN_LISTS
         hdesc = (nat.ThetaDesc * max(len(thetas), 1))()
         theta_csr = []                                   # (constraint, DeviceKnownEntries): skf_plan_set_constraint_entries
+        self.theta_rows = []                             # rows of every constraint kept here (the owned rows of a slice, or all)
         for k, (t, data) in enumerate(thetas):
+            self.theta_rows.append(int(n_obj[t]))
             if isinstance(data, (KnownEntries, DeviceKnownEntries)):
                 # the stored entries of a constraint that is zero elsewhere (skf_theta_desc.data == NULL): no dense form,
                 # always kept as lists; values in the master type
                 if data.unstored != 'zero' or data.by_col:
                     raise ValueError("constraint on %s: entries need unstored='zero', compressed along the rows" % (t,))
-                if tuple(data.shape) != (n_obj[t], n_obj[t]):
-                    raise ValueError('constraint on %s dimension mismatch' % (t,))
+                if owned:           # the rows [begin, begin + count) this part owns, over all columns
+                    self.theta_rows[k] = owned_rows(self.dtype, n_obj[t], part[0], part[1], self.rt)[1]
+                if tuple(data.shape) != (self.theta_rows[k], n_obj[t]):
+                    raise ValueError('constraint on %s dimension mismatch: %r vs (%d,%d)'
+                                     % (t, tuple(data.shape), self.theta_rows[k], n_obj[t]))
                 dev = data if isinstance(data, DeviceKnownEntries) else upload_known_entries(data, self.dtype, mem)
                 self._keep.append(dev)
                 hdesc[k].type, hdesc[k].data, hdesc[k].ld, hdesc[k].nnz = self.index[t], None, 0, dev.known
@@ -662,7 +668,7 @@ class DevicePlan(object):
         opt = nat.Options(self.dtype, variant, self.index[target] if target is not None else -1,
                           nat.SKF_ENGINE_MFMA if engine is None else engine,
                           part[0] if part else 0, part[1] if part else 0,
-                          nat.SKF_OPT_OWNED_ROWS if owned else 0)
+                          (nat.SKF_OPT_OWNED_ROWS | (nat.SKF_OPT_THETA_OWNED_ROWS if theta_csr else 0)) if owned else 0)
         self.owned = bool(owned)
         self.rt.call('skf_plan_create', len(self.types), tdesc, len(relations), rdesc, len(thetas),
                      hdesc, C.byref(opt), C.byref(self.handle))
@@ -800,6 +806,21 @@ class DevicePlan(object):
         mem.synchronize()
         ptr = mem.to_host(bp, (n_out * parts.value + 1,), np.int64)[::parts.value].copy()
         return (ptr, mem.to_host(bi, (max(nnz.value, 1),), np.int32)[:nnz.value].copy(),
+                mem.to_host(bv, (max(nnz.value, 1),), self.np_dtype)[:nnz.value].copy())
+
+    def constraint_lists(self, k):
+        """(indptr, indices, values) of the lists constraint `k` keeps (verification accessor): one handed over dense and
+        compacted, one given as its entries, or -- row ownership -- the slice of the owned rows (indptr of count + 1 pointers
+        from 0, global columns).  SkfNativeError (SKF_E_INVALID) for a constraint kept dense."""
+        rows, nnz = C.c_int64(), C.c_int64()
+        self.rt.call('skf_get_constraint_lists', self.handle, k, C.byref(rows), C.byref(nnz), None, None, None, self.stream)
+        mem, item = self.rt.mem, np.dtype(self.np_dtype).itemsize
+        bp = mem.empty((rows.value + 1) * 8)
+        bi, bv = mem.empty(max(nnz.value, 1) * 4), mem.empty(max(nnz.value, 1) * item)
+        self.rt.call('skf_get_constraint_lists', self.handle, k, None, None, bp.ptr, bi.ptr, bv.ptr, self.stream)
+        mem.synchronize()
+        return (mem.to_host(bp, (rows.value + 1,), np.int64).copy(),
+                mem.to_host(bi, (max(nnz.value, 1),), np.int32)[:nnz.value].copy(),
                 mem.to_host(bv, (max(nnz.value, 1),), self.np_dtype)[:nnz.value].copy())
 
     def set_graph(self, enable=True):

@@ -73,6 +73,7 @@ class Options(C.Structure):
 
 
 SKF_OPT_OWNED_ROWS = 1
+SKF_OPT_THETA_OWNED_ROWS = 2   # constraints given as their entries: the CSR of the owned rows (needs SKF_OPT_OWNED_ROWS)
 SKF_TOPK_MAX = 64            # include/skfusion_hip.h: longest list skf_complete_topk keeps per row
 SKF_ABI_VERSION = 5          # include/skfusion_hip.h: the struct layouts above belong to this version
 
@@ -133,6 +134,7 @@ SIGNATURES = {
     'skf_relation_sqerr': (C.c_int, [_P, C.c_int32, _P, _P]),
     'skf_get_contraction': (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     'skf_get_relation_lists': (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _P, _P, _P, _P]),
+    'skf_get_constraint_lists': (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, _P, _P, _P]),
     'skf_plan_set_profiling': (C.c_int, [_P, C.c_int32]),
     'skf_plan_get_profile': (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double)]),

@@ -181,6 +181,9 @@ static void plan_describe_types(skf_plan* p, int32_t n_types, const skf_type_des
         }
     }
     if (opt->part_count > 1) p->sliced = true;
+    if ((opt->flags & SKF_OPT_THETA_OWNED_ROWS) && !(opt->flags & SKF_OPT_OWNED_ROWS))
+        SKF_FAIL(SKF_E_INVALID, "SKF_OPT_THETA_OWNED_ROWS needs SKF_OPT_OWNED_ROWS");
+    p->theta_owned = (opt->flags & SKF_OPT_THETA_OWNED_ROWS) != 0;
     if (opt->flags & SKF_OPT_OWNED_ROWS) {
         if (p->variant == SKF_TRANSFORM) SKF_FAIL(SKF_E_INVALID, "SKF_OPT_OWNED_ROWS is for SKF_DFMF / SKF_DFMC plans");
         p->owned = p->sliced = true;
@@ -396,13 +399,18 @@ static void plan_describe_constraints(skf_plan* p, int32_t n_types, int32_t n_th
         const int64_t nn = p->types[thetas[t].type].n;
         if (thetas[t].nnz < 0) SKF_FAIL(SKF_E_INVALID, "constraint %d: negative non-zero bound", t);
         if (!thetas[t].data) {      // the CSR of its stored entries (skf_plan_set_constraint_entries): no dense form in any type
-            if (p->sliced)
+            // (SKF_OPT_THETA_OWNED_ROWS on an owned plan: the CSR of the owned rows of the type, over all columns)
+            const bool local = p->owned && p->theta_owned;
+            if (p->sliced && !local)
                 SKF_FAIL(SKF_E_INVALID, "constraint %d: a constraint given as its entries is for plans of whole relations "
                          "(no row blocks, slices or SKF_OPT_OWNED_ROWS)", t);
             if (thetas[t].nnz > 2000000000LL)
                 SKF_FAIL(SKF_E_INVALID, "constraint %d: %lld > 2e9 entries", t, (long long)thetas[t].nnz);
             p->thetas[t].entries = p->thetas[t].sparse = true;
             p->thetas[t].nnz_cap = thetas[t].nnz;
+            p->thetas[t].local = local;
+            p->thetas[t].l0 = p->types[thetas[t].type].t0;
+            p->thetas[t].ln = p->types[thetas[t].type].tn;
             continue;
         }
         if (thetas[t].nnz > 0 && thetas[t].nnz <= nn * nn / SKF_THETA_SPARSE_DIV) {
@@ -756,8 +764,9 @@ static void plan_layout(skf_plan* p) {
     for (ThetaState& th : p->thetas) {
         TypeState& t = p->types[th.type];
         if (th.sparse) {
-            add_slot(p, th.Cnt, (size_t)t.n * sizeof(int));
-            add_slot(p, th.Rp, (size_t)(t.n + 1) * sizeof(int64_t));
+            // (local rows: everything from the slice -- a scratch word for the validation, count + 1 pointers)
+            add_slot(p, th.Cnt, th.local ? sizeof(int) : (size_t)t.n * sizeof(int));
+            add_slot(p, th.Rp, (size_t)((th.local ? th.ln : t.n) + 1) * sizeof(int64_t));
             add_slot(p, th.Ci, (size_t)th.nnz_cap * sizeof(int));
             add_slot(p, th.Vv, (size_t)th.nnz_cap * es);
             if (th.seg_cap > 0) {       // hub rows: segment table, row table, the e / d partials of every segment
@@ -1473,6 +1482,23 @@ int skf_get_relation_lists(const skf_plan* p, int32_t rel, int32_t by_col, int32
         if (ptr) SKF_HIP(hipMemcpyAsync(ptr, sp.ptr, ((size_t)n_out * pc + 1) * 8, hipMemcpyDeviceToDevice, st));
         if (idx && r.kn_nnz > 0) SKF_HIP(hipMemcpyAsync(idx, si.ptr, (size_t)r.kn_nnz * 4, hipMemcpyDeviceToDevice, st));
         if (values && r.kn_nnz > 0) SKF_HIP(hipMemcpyAsync(values, sv.ptr, (size_t)r.kn_nnz * p->esz, hipMemcpyDeviceToDevice, st));
+    });
+}
+
+int skf_get_constraint_lists(const skf_plan* p, int32_t theta, int64_t* n_rows, int64_t* n_entries, int64_t* indptr, int32_t* indices,
+                             void* values, void* stream) {
+    return guarded([&] {
+        check_bound(p);
+        if (theta < 0 || theta >= (int)p->thetas.size()) SKF_FAIL(SKF_E_INVALID, "constraint %d out of range", theta);
+        const ThetaState& th = p->thetas[theta];
+        if (!th.sparse) SKF_FAIL(SKF_E_INVALID, "constraint %d is kept dense: no lists", theta);
+        const int64_t rows = th.local ? th.ln : p->types[th.type].n;
+        if (n_rows) *n_rows = rows;
+        if (n_entries) *n_entries = th.nnz;
+        hipStream_t st = as_stream(stream);
+        if (indptr) SKF_HIP(hipMemcpyAsync(indptr, th.Rp.ptr, ((size_t)rows + 1) * 8, hipMemcpyDeviceToDevice, st));
+        if (indices && th.nnz > 0) SKF_HIP(hipMemcpyAsync(indices, th.Ci.ptr, (size_t)th.nnz * 4, hipMemcpyDeviceToDevice, st));
+        if (values && th.nnz > 0) SKF_HIP(hipMemcpyAsync(values, th.Vv.ptr, (size_t)th.nnz * p->esz, hipMemcpyDeviceToDevice, st));
     });
 }
 

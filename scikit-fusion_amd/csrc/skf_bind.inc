@@ -401,21 +401,23 @@ static void bind_theta_csr_t(skf_plan* p, hipStream_t st) {
         if (th.entries) {       // the caller's lists, validated on the device before anything gathers through them, then copied as they are
             if (!th.csr_ptr) SKF_FAIL(SKF_E_INVALID, "constraint %zu is given as its entries (data == NULL) without skf_plan_set_constraint_entries", k);
             const int64_t tot = th.nnz_cap;
-            if (!csr_is_canonical(th.csr_ptr, th.csr_idx, n, n, tot, (int*)th.Cnt.ptr, st))      // (Cnt: a scratch word)
-                SKF_FAIL(SKF_E_INVALID, "constraint %zu: the lists are not canonical for %lld objects with %lld entries (indptr from 0 "
-                         "to the count, non-decreasing; indices in range and strictly ascending within a row)", k, (long long)n, (long long)tot);
+            const int64_t rows = th.local ? th.ln : n;       // (local rows: the slice of the owned rows, columns over the whole type)
+            if (!csr_is_canonical(th.csr_ptr, th.csr_idx, rows, n, tot, (int*)th.Cnt.ptr, st))      // (Cnt: a scratch word)
+                SKF_FAIL(SKF_E_INVALID, "constraint %zu: the lists are not canonical for %lld rows of %lld objects with %lld entries (indptr "
+                         "from 0 to the count, non-decreasing; indices in range and strictly ascending within a row)", k, (long long)rows,
+                         (long long)n, (long long)tot);
             th.nnz = tot;
-            SKF_HIP(hipMemcpyAsync(th.Rp.ptr, th.csr_ptr, ((size_t)n + 1) * 8, hipMemcpyDeviceToDevice, st));
+            SKF_HIP(hipMemcpyAsync(th.Rp.ptr, th.csr_ptr, ((size_t)rows + 1) * 8, hipMemcpyDeviceToDevice, st));
             if (tot > 0) {
                 SKF_HIP(hipMemcpyAsync(th.Ci.ptr, th.csr_idx, (size_t)tot * 4, hipMemcpyDeviceToDevice, st));
                 SKF_HIP(hipMemcpyAsync(th.Vv.ptr, th.csr_val, (size_t)tot * sizeof(T), hipMemcpyDeviceToDevice, st));
             }
             th.csr_ptr = nullptr; th.csr_idx = nullptr; th.csr_val = nullptr;      // not referenced after bind
             if (th.seg_cap > 0 && tot > 0) {        // the row pointers back on the host: which rows are hubs
-                if (rp.size() < (size_t)n + 1) rp.resize((size_t)n + 1);
-                SKF_HIP(hipMemcpyAsync(rp.data(), th.Rp.ptr, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
+                if (rp.size() < (size_t)rows + 1) rp.resize((size_t)rows + 1);
+                SKF_HIP(hipMemcpyAsync(rp.data(), th.Rp.ptr, ((size_t)rows + 1) * 8, hipMemcpyDeviceToHost, st));
                 SKF_HIP(hipStreamSynchronize(st));
-                bind_theta_hubs(th, rp.data(), n, st);
+                bind_theta_hubs(th, rp.data(), rows, st);       // (local rows: the tables carry them)
             }
             continue;
         }

@@ -185,6 +185,10 @@ struct ThetaState {
     // skf_theta_desc.data == NULL: the CSR comes from the caller (skf_plan_set_constraint_entries; read at bind time only),
     // nnz_cap is its exact length and no dense form exists in any type -- kept as lists whatever the density
     bool entries = false;
+    // ... and SKF_OPT_THETA_OWNED_ROWS: the caller's CSR is the slice of the OWNED rows [l0, l0 + ln) of the type over all
+    // columns ("local rows"): Rp holds ln + 1 pointers from 0, Ci / Vv the slice, the hub tables carry LOCAL rows
+    bool local = false;
+    int64_t l0 = 0, ln = 0;
     // hub rows (longer than hub_row entries; 0: never split) cut into segments: the table and the rows it covers, sorted by
     // row, then by position; partial sums e / d per segment in HubE / HubD [n_seg][c], master type.  Host copies of the
     // rows and of their first segments: plans with owned rows launch the sub-range inside [t0, t0 + tn)
@@ -233,6 +237,7 @@ struct skf_plan {
     // E, D and G of all types as three regions of identical layout (flat_bytes each, a pad behind every one)
     size_t flat_e_off = 0, flat_d_off = 0, flat_g_off = 0, flat_bytes = 0;
     skf::Slot flat_pad[3];
+    bool theta_owned = false;              // SKF_OPT_THETA_OWNED_ROWS: constraints given as their entries are slices of the owned rows
     skf_comm* comm = nullptr;              // collectives of the distributed iteration (skf_plan_set_comm; not owned)
     // SKF_OPT_OWNED_ROWS: ownership-aligned row blocks (iterate_owned)
     bool owned = false;
@@ -481,9 +486,10 @@ static void mult_update(skf_plan* p, TypeState& t, hipStream_t st) {
 }
 
 // the hub rows of a sparse constraint inside [r0, r0 + nr): their segments as partial sums, then the sums into E / D.  The
-// table is sorted by row, so the rows of the range are one sub-range of it (found here, on the host).
+// table is sorted by row, so the rows of the range are one sub-range of it (found here, on the host).  `E` / `D`: row 0 of
+// the table's row numbering (the whole accumulators; a constraint of local rows: their owned range, r0 = 0, the whole table).
 template <typename T>
-static void theta_hub_rows_t(ThetaState& th, TypeState& t, int64_t r0, int64_t nr, hipStream_t st) {
+static void theta_hub_rows_t(ThetaState& th, TypeState& t, int64_t r0, int64_t nr, T* E, T* D, hipStream_t st) {
     const size_t h0 = std::lower_bound(th.hub_rows.begin(), th.hub_rows.end(), r0) - th.hub_rows.begin();
     const size_t h1 = std::lower_bound(th.hub_rows.begin(), th.hub_rows.end(), r0 + nr) - th.hub_rows.begin();
     if (h1 <= h0) return;
@@ -493,10 +499,10 @@ static void theta_hub_rows_t(ThetaState& th, TypeState& t, int64_t r0, int64_t n
                        (const ThetaSeg*)th.HubSeg.ptr + s0, s1 - s0, (const int*)th.Ci.ptr, (const T*)th.Vv.ptr, (const T*)t.G.ptr,
                        (T*)th.HubE.ptr + s0 * t.c, (T*)th.HubD.ptr + s0 * t.c, t.c);
     check_launch("theta_hub_partial");
-    // (ThetaHub::first counts from the head of the table, so the partials are addressed from there too; E / D by global row)
+    // (ThetaHub::first counts from the head of the table, so the partials are addressed from there too; E / D by the table's row)
     hipLaunchKernelGGL((theta_hub_combine_kernel<T>), dim3(elem_grid((int64_t)(h1 - h0) * t.c)), dim3(256), 0, st,
                        (const ThetaHub*)th.HubRows.ptr + h0, (int64_t)(h1 - h0), (const T*)th.HubE.ptr, (const T*)th.HubD.ptr,
-                       (T*)t.E.ptr, (T*)t.D.ptr, t.c);
+                       E, D, t.c);
     check_launch("theta_hub_combine");
 }
 
@@ -509,6 +515,10 @@ static void theta_terms_rows(skf_plan* p, int only_type, bool own_rows, hipStrea
         TypeState& t = p->types[th.type];
         const int64_t r0 = own_rows ? t.t0 : 0, nr = own_rows ? t.tn : t.n;
         if (nr <= 0) continue;
+        if (th.local && !(own_rows && r0 == th.l0 && nr == th.ln))
+            SKF_FAIL(SKF_E_STATE, "constraint on type %d holds the owned rows only: it runs in the owned schedule (skf_iterate_dist)", th.type);
+        // (the global form shifts its row pointers to the range and finds its hub rows inside it; the local form starts at 0)
+        const int64_t q0 = th.local ? 0 : r0;
         void* Er = (char*)t.E.ptr + (size_t)r0 * t.c * p->esz;
         void* Dr = (char*)t.D.ptr + (size_t)r0 * t.c * p->esz;
         // an all-zero half is skipped
@@ -517,17 +527,19 @@ static void theta_terms_rows(skf_plan* p, int only_type, bool own_rows, hipStrea
             const int grid = wave_grid(nr);
             const int64_t hub = th.n_seg > 0 ? th.hub_row : 0;      // (a plan without hub rows launches what it always did)
             if (p->f64)
-                hipLaunchKernelGGL((theta_spmm_kernel<double>), dim3(grid), dim3(256), 0, st, (const int64_t*)th.Rp.ptr + r0,
+                hipLaunchKernelGGL((theta_spmm_kernel<double>), dim3(grid), dim3(256), 0, st, (const int64_t*)th.Rp.ptr + q0,
                                    (const int*)th.Ci.ptr, (const double*)th.Vv.ptr, (const double*)t.G.ptr, (double*)Er,
                                    (double*)Dr, nr, t.c, hub);
             else
-                hipLaunchKernelGGL((theta_spmm_kernel<float>), dim3(grid), dim3(256), 0, st, (const int64_t*)th.Rp.ptr + r0,
+                hipLaunchKernelGGL((theta_spmm_kernel<float>), dim3(grid), dim3(256), 0, st, (const int64_t*)th.Rp.ptr + q0,
                                    (const int*)th.Ci.ptr, (const float*)th.Vv.ptr, (const float*)t.G.ptr, (float*)Er,
                                    (float*)Dr, nr, t.c, hub);
             check_launch("theta_spmm");
             if (hub > 0) {
-                if (p->f64) theta_hub_rows_t<double>(th, t, r0, nr, st);
-                else theta_hub_rows_t<float>(th, t, r0, nr, st);
+                char* E0 = th.local ? (char*)Er : (char*)t.E.ptr;
+                char* D0 = th.local ? (char*)Dr : (char*)t.D.ptr;
+                if (p->f64) theta_hub_rows_t<double>(th, t, q0, nr, (double*)E0, (double*)D0, st);
+                else theta_hub_rows_t<float>(th, t, q0, nr, (float*)E0, (float*)D0, st);
             }
             continue;
         }

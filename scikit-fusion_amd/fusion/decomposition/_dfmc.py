@@ -21,11 +21,11 @@ def _expand_known_entries(R, M):
 
 def dfmc(R, M, Theta, obj_types, obj_type2rank, max_iter=10, init_type="random_vcol",
          stopping=None, stopping_system=None, verbose=0, compute_err=False, callback=None,
-         random_state=None, n_jobs=1, dtype='f64', G0=None, engine=None, shard=None):
+         random_state=None, n_jobs=1, dtype='f64', G0=None, engine=None, shard=None, sparse_constraints=False):
     """Data fusion by matrix completion -- drop-in for reference ``dfmc`` (_dfmc.py:181).  Constraints given as their entries:
-    as in ``_dfmf.dfmf`` (shard None / 'runs' only)."""
+    as in ``_dfmf.dfmf`` (shard None / 'runs'; shard='owned' with ``sparse_constraints=True``)."""
     if shard in ('relations', 'rows', 'owned'):
-        refuse_constraint_entries(Theta, shard)
+        refuse_constraint_entries(Theta, shard, sparse_constraints)
         if shard != 'owned':                    # (an ownership-sharded fit slices the entries by rows; the others take the mask form)
             R, M = _expand_known_entries(R, M)
         fit = {'relations': run_fit_sharded, 'rows': run_fit_rows, 'owned': run_fit_owned}[shard]

@@ -119,7 +119,10 @@ def row_block_plan(variant, rel_list, theta_list, obj_types, n_obj, obj_type2ran
 def owned_plan(variant, rel_list, theta_list, obj_types, n_obj, obj_type2rank, dtype, engine, rank, size):
     """The plan of rank `rank` of `size` in a fit sharded by OWNERSHIP (SKF_OPT_OWNED_ROWS): the rank owns the same share
     of the rows of every object type (`_engine.owned_rows`) and holds exactly those rows of every relation whose row type
-    it is -- work is 1 / size of every relation, the row-side terms never leave the rank -- and every constraint.
+    it is -- work is 1 / size of every relation, the row-side terms never leave the rank -- and every dense constraint.
+    A constraint given as its entries (`_engine.KnownEntries(unstored='zero')`) is sliced the same way: the rank hands over
+    the CSR of the owned rows of the constrained type over all columns (an empty (0, n) slice where it owns none), the rows
+    its constraint pass multiplies -- never the whole constraint, never a dense form.
     A relation given as its entries (`_engine.KnownEntries`, either kind) is sliced by rows -- `indptr`, `indices` and
     `values` of the owned rows, no dense step -- and only that slice is uploaded; a rank without rows of its row type marks
     it absent.  Every process still holds the WHOLE scipy.sparse matrix / KnownEntries on the host: the initialisers read
@@ -150,7 +153,17 @@ def owned_plan(variant, rel_list, theta_list, obj_types, n_obj, obj_type2rank, d
             continue
         local.append((i, j, np.asarray(m)[begin:begin + count],
                       None if mask is None else np.asarray(mask)[begin:begin + count], info))
-    return DevicePlan(obj_types, n_obj, obj_type2rank, local, list(theta_list), variant, dtype=dtype, engine=engine,
+    thetas = []
+    for (t, th) in theta_list:
+        if isinstance(th, DeviceKnownEntries):
+            raise ValueError("constraint on %s: an ownership-sharded fit slices the entries on the host (KnownEntries)" % (t,))
+        if isinstance(th, KnownEntries):
+            if th.unstored != 'zero' or th.by_col:
+                raise ValueError("constraint on %s: entries need unstored='zero', compressed along the rows" % (t,))
+            begin, count, _ = owned_rows(dtype, n_obj[t], rank, size)
+            th = th.row_slice(begin if count else 0, count)
+        thetas.append((t, th))
+    return DevicePlan(obj_types, n_obj, obj_type2rank, local, thetas, variant, dtype=dtype, engine=engine,
                       part=(rank, size), owned=True)
 
 
@@ -368,10 +381,13 @@ def run_fit(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type,
         plan.close()
 
 
-def refuse_constraint_entries(Theta, shard):
+def refuse_constraint_entries(Theta, shard, sparse_constraints=False):
     """The sharded fits take dense constraints: one given as its entries (_engine.KnownEntries) is the caller's mistake --
-    the class layer expands it before it gets here."""
+    the class layer expands it before it gets here.  `sparse_constraints`: the caller says it means them; shard='owned' then
+    takes them (every rank hands over the slice of its owned rows, `owned_plan`), the other shards still refuse."""
     from ..._engine import KnownEntries, DeviceKnownEntries
+    if sparse_constraints and shard == 'owned':
+        return
     for key, mats in (Theta or {}).items():
         if any(isinstance(m, (KnownEntries, DeviceKnownEntries)) for m in mats):
             raise ValueError("constraint %r is given as its entries: shard=%r takes dense constraints (shard='runs' or toarray())"
@@ -380,13 +396,14 @@ def refuse_constraint_entries(Theta, shard):
 
 def dfmf(R, Theta, obj_types, obj_type2rank, max_iter=10, init_type="random_vcol",
          stopping=None, stopping_system=None, verbose=0, compute_err=False, callback=None,
-         random_state=None, n_jobs=1, dtype='f64', G0=None, engine=None, shard=None):
+         random_state=None, n_jobs=1, dtype='f64', G0=None, engine=None, shard=None, sparse_constraints=False):
     """Data fusion by matrix factorization -- drop-in for reference ``dfmf`` (_dfmf.py:127).
     ``shard='relations'`` (with an initialised torch.distributed group) partitions the relations
     of this ONE fit over the ranks.  A constraint in ``Theta`` may be an ``_engine.KnownEntries(unstored='zero')`` -- its
-    entries as canonical CSR, never expanded -- with shard None / 'runs'; any other shard: ValueError."""
+    entries as canonical CSR, never expanded -- with shard None / 'runs', and with shard='owned' under
+    ``sparse_constraints=True`` (every rank hands over the CSR of its owned rows); any other shard: ValueError."""
     if shard in ('relations', 'rows', 'owned'):
-        refuse_constraint_entries(Theta, shard)
+        refuse_constraint_entries(Theta, shard, sparse_constraints)
         logging.basicConfig(format="%(asctime)s %(levelname)s: %(message)s", level=50 - verbose)
         fit = {'relations': run_fit_sharded, 'rows': run_fit_rows, 'owned': run_fit_owned}[shard]
         return fit(nat.SKF_DFMF, R, None, Theta, obj_types, obj_type2rank, max_iter,

@@ -45,7 +45,8 @@ class Dfmc(FusionFit):
                   compute_err=self.compute_err, callback=self.callback,
                   random_state=self.random_state, n_jobs=self.n_jobs, dtype=self.dtype)
         if self.shard in ('relations', 'rows', 'owned'):
-            store_runs(self, [_dfmc.dfmc(G0=G0[k], shard=self.shard, **kw) for k in range(self.n_run)])
+            store_runs(self, [_dfmc.dfmc(G0=G0[k], shard=self.shard, sparse_constraints=self.shard == 'owned', **kw)
+                              for k in range(self.n_run)])
             return self
         n_streams = concurrent_streams(self)
         if n_streams:                                   # n_jobs restarts side by side on this GPU

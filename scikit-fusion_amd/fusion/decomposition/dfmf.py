@@ -70,11 +70,13 @@ def stored_entries_apply(relation, sparse_relations, shard='runs'):
 
 def constraint_entries_apply(relation, sparse_constraints, shard='runs'):
     """Whether a ``scipy.sparse`` constraint (row type == column type) with ``unstored='zero'`` goes to the device as its
-    entries (never expanded): shard='runs', no preprocessor, finite stored values and at most 2e9 of them.
+    entries (never expanded): shard='runs' or 'owned' (there every rank hands over the CSR of its owned rows; the decision
+    reads the whole constraint's shape and nnz only, so it is the same on every rank; 'rows' / 'relations' expand), no
+    preprocessor, finite stored values and at most 2e9 of them.
     `sparse_constraints` True: whenever eligible; False: never (``toarray()``); None: when nnz <= n * n / the library's own
     divisor (``small_graph_limits()``: up to there the dense-fed form is compacted to the same lists, so nothing changes but
     the hand-over) -- a denser one is expanded and takes the dense product, the measured path at that density."""
-    if sparse_constraints is False or shard != 'runs':
+    if sparse_constraints is False or shard not in ('runs', 'owned'):
         return False
     if not relation.is_zero_unstored() or relation.preprocessor or relation.row_type != relation.col_type:
         return False
@@ -256,12 +258,14 @@ class Dfmf(FusionFit):
     sparse_relations=None | True | False: a ``scipy.sparse`` relation (``unstored='zero'``) is fitted on its stored entries
     alone, never expanded, with shard='runs' or shard='owned' (every rank then uploads the CSR of its owned rows only and no
     dense row block exists anywhere; each process still holds the whole scipy.sparse matrix on the host, which the
-    initialisers read; a constraint of an owned fit is still handed over dense), no preprocessor and two different object
+    initialisers read), no preprocessor and two different object
     types -- None: when
     density * max(rank_row, rank_col) <= 4 and the relation is beyond the small-graph limits (a rank above 64 or more
     than 8192 objects on a side); True: always; False: never (``toarray()``).
     sparse_constraints=None | True | False: a ``scipy.sparse`` constraint (a relation of a type with itself,
-    ``unstored='zero'``) goes to the device as its entries, never expanded, with shard='runs' and no preprocessor -- None:
+    ``unstored='zero'``) goes to the device as its entries, never expanded, with shard='runs' or shard='owned' (every rank
+    then hands over the CSR of its owned rows over all columns; no rank holds the whole constraint on its device) and no
+    preprocessor -- None:
     when nnz <= n * n / 16 (the engine's own bound for the sparse product; a denser one is expanded and multiplied as a
     dense matrix); True: always; False: never (``toarray()``).  Same factors either way, bit for bit, up to that bound.
     """
@@ -288,7 +292,9 @@ class Dfmf(FusionFit):
                   compute_err=self.compute_err, callback=self.callback,
                   random_state=self.random_state, n_jobs=self.n_jobs, dtype=self.dtype)
         if self.shard in ('relations', 'rows', 'owned'):                   # all GPUs cooperate on every restart
-            store_runs(self, [_dfmf.dfmf(G0=G0[k], shard=self.shard, **kw) for k in range(self.n_run)])
+            # (an owned fit takes the constraints graph_matrices left as entries: each rank the slice of its owned rows)
+            store_runs(self, [_dfmf.dfmf(G0=G0[k], shard=self.shard, sparse_constraints=self.shard == 'owned', **kw)
+                              for k in range(self.n_run)])
             return self
         if shared_launches(self):                       # restarts of a SMALL graph share their launches, whatever n_jobs says
             from ... import _native as nat
