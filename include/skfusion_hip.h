@@ -144,6 +144,33 @@ enum {
                                  SKF_E_INVALID: SKF_TRANSFORM plans, row blocks / sliced plans without SKF_OPT_OWNED_ROWS, a
                                  block of an owned plan that is not the owned range, a rank above 1024, more than 2e9 entries,
                                  a mask, together with SKF_REL_KNOWN_CSR. */
+    SKF_REL_FILL_RANK1 = 512, /* only together with SKF_REL_SPARSE_CSR, on SKF_DFMF / SKF_DFMC plans of whole relations: a relation
+                                 with MISSING values whose unknown cells were imputed before the fit (the reference's
+                                 Relation.filled(), fusion_graph.py:464-510).  Every fill strategy writes a rank-one pattern
+                                 into the unknown cells, so the filled matrix is F = a b^T + D with D sparse on the stored pattern,
+                                 d = v - a_r b_c: a constant f: a = f 1, b = 1; 'mean': a = m 1, b = 1; 'row_mean': a = the row
+                                 means, b = 1; 'col_mean': a = 1, b = the column means.  The caller hands over the TRUE stored
+                                 values v (skf_plan_set_known_entries) and the two vectors (skf_plan_set_relation_fill); bind forms
+                                 d = (double)v - (double)a_r (double)b_c, rounded once to the master type, before the column
+                                 lists are built, and skf_get_relation_lists returns d.  Then
+                                     P = F G_j   = D G_j   + a (b^T G_j)
+                                     Q = F^T G_i = D^T G_i + b (a^T G_i)
+                                 -- the list passes of SKF_REL_SPARSE_CSR on d, plus the weighted column sums t = G_j^T b and
+                                 s = G_i^T a (f64, from the rows the list pass gathers: the bf16 rows in the SKF_BF16 engine, so
+                                 that P = sum over the stored of v g^ + a sum over the unstored of b g^ over ONE set of rounded
+                                 rows, as the dense bf16 contraction gives; two stages, a fixed slab of 128 rows per workgroup,
+                                 partials added first to last, no atomics: the same bits on every run and device), added as
+                                 P[r] += a_r t, Q[c] += b_c s in the launch that sums the parts of the lists -- and
+                                     |F - G_i S G_j^T|^2 = tr(S^T Gram_i S Gram_j) + |a|^2 |b|^2 - 2 (a^T G_i) S (G_j^T b)
+                                                           + sum over the stored of (d - x)^2 - x^2 + 2 sum over the stored of d a_r b_c
+                                 (skf_relation_sqerr; the sums over the objects from the masters in every engine, the c_i x c_j
+                                 product in f64, the three constants |a|^2, |b|^2, 2 sum d a b in f64, summed in ascending order
+                                 at bind).  Workspace grows by (n_i + n_j) (element size + 8) + (ceil(n_i / 128) c_i +
+                                 ceil(n_j / 128) c_j + c_i + c_j) 8 bytes, never with n_i * n_j.  A relation without the flag
+                                 issues exactly the launches it issued before the flag existed.
+                                 SKF_E_INVALID at skf_plan_create: without SKF_REL_SPARSE_CSR, SKF_OPT_OWNED_ROWS plans,
+                                 SKF_TRANSFORM plans; at bind: no skf_plan_set_relation_fill, a fill value that is not finite
+                                 (checked with the lists, before anything gathers). */
     SKF_REL_FOLD_CSR = 256    /* SKF_TRANSFORM plans only: the NEW relation is given as its STORED entries, every other entry ZERO,
                                  compressed along the TARGET's side -- indptr[n_target + 1] (int64), indices (int32, into the
                                  partner type, strictly ascending within a target object) and values in the MASTER type (f64 /
@@ -255,6 +282,11 @@ int skf_plan_workspace_bytes(const skf_plan* plan, size_t* bytes);
  * columns do not ascend strictly is SKF_E_INVALID, as is a SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR relation without this call. */
 int skf_plan_set_known_entries(skf_plan* plan, int32_t rel, const int64_t* indptr, const int32_t* indices,
                                const void* values);
+/* The fill vectors of relation `rel` (flagged SKF_REL_FILL_RANK1), as device pointers: row_fill[n_i] = a and col_fill[n_j] = b
+ * in the MASTER type (f64 / f32; SKF_BF16 plans: f32).  Call it between skf_plan_set_known_entries and skf_plan_bind_workspace
+ * (afterwards: SKF_E_STATE); the buffers are read by skf_plan_bind_workspace, on its stream, and not referenced afterwards
+ * (the contract of `data`; `stream` is reserved).  SKF_E_INVALID: a relation without the flag, a null pointer. */
+int skf_plan_set_relation_fill(skf_plan* plan, int32_t rel, const void* row_fill, const void* col_fill, void* stream);
 /* The stored entries of constraint `theta` (the index into the `thetas` of skf_plan_create; one whose skf_theta_desc.data is
  * NULL, _dfmf.py:284-292 on the dense expansion), as device pointers: indptr[n_i + 1] (int64, indptr[0] = 0,
  * indptr[n_i] = nnz, non-decreasing), indices[nnz] (int32 columns, strictly ascending within a row: canonical CSR, duplicates
@@ -427,6 +459,7 @@ int skf_get_contraction(const skf_plan* plan, int32_t rel, int32_t which, void* 
  * (columns -> ascending rows).  `parts` / `n_entries` (host) receive the number of parts the lists are cut into and the
  * number of entries; `ptr` (device, n * parts + 1 int64: the segment pointers, every `parts`-th one opens a list), `idx`
  * (device, n_entries int32) and `values` (device, n_entries of the master type) receive copies.  Null pointers are skipped.
+ * A SKF_REL_FILL_RANK1 relation: `values` are d = v - a_r b_c, what the passes multiply, not the stored values v.
  * SKF_OPT_OWNED_ROWS plans: the lists of the slice -- n = the local rows for the row lists, and the column lists hold LOCAL row
  * indices (row - row_begin); SKF_E_STATE for a SKF_REL_ABSENT relation. */
 int skf_get_relation_lists(const skf_plan* plan, int32_t rel, int32_t by_col, int32_t* parts, int64_t* n_entries, int64_t* ptr,
@@ -446,7 +479,12 @@ int skf_get_constraint_lists(const skf_plan* plan, int32_t theta, int64_t* n_row
  * bitmap; 2 * ones * N for the row gathers of a very sparse 0/1 relation; 2 or 4 * known * c for a pass over the
  * known entries of a masked relation; 2 * stored * N for a pass over a SKF_REL_SPARSE_CSR relation, whose bytes are its
  * index + value lists and the factor rows it gathers) and the relation bytes they read from HBM as stored (bf16 / f32 / f64 entries,
- * 1 bit per entry for a bitmap, index + value lists for the sparse forms) since the last call, and resets the counters. */
+ * 1 bit per entry for a bitmap, index + value lists for the sparse forms) since the last call, and resets the counters.
+ * A SKF_REL_FILL_RANK1 relation adds, per pass, ONE launch (the weighted column sum of the gathered factor with its reduce;
+ * the rank-one term rides the launch that sums the parts), 2 n_in w + 2 n_out w flops (n_in rows of the gathered factor, w its
+ * rank, n_out rows of the output) and n_in (w g + e) + n_out e bytes (g = bytes of a gathered element, e of a master one: the
+ * factor with its weights, the scale vector), plus 2 n_out w e where the lists have one part (the output read and written
+ * once more). */
 int skf_plan_set_profiling(skf_plan* plan, int32_t enable);
 int skf_plan_get_profile(skf_plan* plan, double* total_ms, int64_t* launches, double* flops, double* bytes);
 
@@ -593,7 +631,8 @@ const char* skf_version(void);
  * call the library: descriptors grew between versions (skf_relation_desc.known_bound: 3, skf_options.flags: 4; version 5
  * adds entry points only -- skf_small_graph_limits, skf_comm_info, skf_launch_count; later: skf_fold_lists and the flag
  * SKF_REL_FOLD_CSR; skf_complete_topk_workspace_bytes, skf_complete_topk, skf_complete_entries and SKF_TOPK_MAX;
- * skf_get_constraint_lists and the flag SKF_OPT_THETA_OWNED_ROWS -- the structs are those of version 4). */
+ * skf_get_constraint_lists and the flag SKF_OPT_THETA_OWNED_ROWS; skf_plan_set_relation_fill and the flag SKF_REL_FILL_RANK1 --
+ * the structs are those of version 4). */
 #define SKF_ABI_VERSION 5
 int skf_abi_version(void);
 

@@ -47,13 +47,28 @@ class KnownEntries(object):
     dense relation itself.
     ``by_col=True`` (``unstored='zero'`` only): the lists are compressed along the COLUMN type -- `indptr` has n_col + 1
     entries and `indices` are rows, the canonical CSC -- which is what a fold-in whose target is the relation's column type
-    hands to the library (SKF_REL_FOLD_CSR: lists compressed along the target's side).  `shape` stays the relation's."""
+    hands to the library (SKF_REL_FOLD_CSR: lists compressed along the target's side).  `shape` stays the relation's.
+    ``row_fill=a, col_fill=b`` (``unstored='zero'``, row lists only): a relation with MISSING values after its fill -- the
+    entries not stored hold a_r * b_c, the stored ones their true values (SKF_REL_FILL_RANK1: the filled matrix is
+    a b^T + D with D sparse on the stored pattern; the library forms d = v - a_r b_c itself).  One of the two vectors is
+    all ones for every fill strategy of ``Relation``.  ``expand`` gives the dense filled matrix."""
 
-    def __init__(self, indptr, indices, values, shape, fill=0.0, unstored='unknown', by_col=False):
+    def __init__(self, indptr, indices, values, shape, fill=0.0, unstored='unknown', by_col=False, row_fill=None, col_fill=None):
         if unstored not in ('unknown', 'zero'):
             raise ValueError("unstored must be 'unknown' or 'zero', not %r" % (unstored,))
         if by_col and unstored != 'zero':
             raise ValueError("lists compressed along the column type need unstored='zero'")
+        if (row_fill is None) != (col_fill is None):
+            raise ValueError('row_fill and col_fill come together')
+        if row_fill is not None and (unstored != 'zero' or by_col):
+            raise ValueError("fill vectors need unstored='zero' and lists compressed along the rows")
+        self.row_fill = self.col_fill = None
+        if row_fill is not None:
+            self.row_fill = np.ascontiguousarray(row_fill, dtype=np.float64)
+            self.col_fill = np.ascontiguousarray(col_fill, dtype=np.float64)
+            if self.row_fill.shape != (int(shape[0]),) or self.col_fill.shape != (int(shape[1]),):
+                raise ValueError('fill vectors of %r and %r entries for a %r relation'
+                                 % (self.row_fill.shape, self.col_fill.shape, tuple(shape)))
         self.unstored = unstored
         self.by_col = bool(by_col)
         if unstored == 'zero':
@@ -77,14 +92,25 @@ class KnownEntries(object):
     def row_slice(self, begin, count):
         """The entries of rows [begin, begin + count) as a container of their own: slices of `indices` / `values` (views) and
         `indptr` rebased to 0 -- no dense step.  What a rank of an ownership-sharded fit hands to its plan."""
-        if self.by_col:
-            raise ValueError('lists compressed along the column type have no row slices')
+        if self.by_col or self.row_fill is not None:
+            raise ValueError('lists compressed along the column type and filled relations have no row slices')
         lo, hi = int(self.indptr[begin]), int(self.indptr[begin + count])
         return KnownEntries(self.indptr[begin:begin + count + 1] - lo, self.indices[lo:hi], self.values[lo:hi],
                             (count, self.shape[1]), fill=self.fill, unstored=self.unstored)
 
+    def expand(self):
+        """The dense matrix the container stands for: the stored values on their entries, elsewhere `fill` -- or, with
+        fill vectors, row_fill[r] * col_fill[c] (one factor is 1: the product is the fill value itself, bit for bit)."""
+        if self.row_fill is None:
+            return self.toarray()
+        out = np.multiply.outer(self.row_fill, self.col_fill)
+        out[self.rows_cols()] = self.values
+        return out
+
     def toarray(self, fill=None):
         """The dense relation of the mask form: the values on the known entries, `fill` (default: self.fill) elsewhere."""
+        if self.row_fill is not None and fill is None:
+            return self.expand()
         out = np.full(self.shape, self.fill if fill is None else fill, dtype=np.float64)
         out[self.rows_cols()] = self.values
         return out
@@ -116,13 +142,16 @@ class KnownEntries(object):
                 c1 = min(c0 + chunk, ix.size - 1)
                 if ((ix[c0 + 1:c1 + 1] <= ix[c0:c1]) & ~first[c0 + 1:c1 + 1]).any():
                     raise DataFusionError('known entries: columns not strictly ascending within a row (canonical CSR)')
+        if self.row_fill is not None and not (np.isfinite(self.row_fill).all() and np.isfinite(self.col_fill).all()):
+            raise DataFusionError('known entries: a fill vector holds a value that is not finite')
 
 
 class DeviceKnownEntries(object):
     """KnownEntries uploaded ONCE in the engine's element type (upload_graph: shared by the plans of concurrent restarts)."""
 
-    def __init__(self, indptr, indices, values, shape, known, unstored='unknown', by_col=False):
+    def __init__(self, indptr, indices, values, shape, known, unstored='unknown', by_col=False, row_fill=None, col_fill=None):
         self.indptr, self.indices, self.values = indptr, indices, values
+        self.row_fill, self.col_fill = row_fill, col_fill        # device vectors in the master type (SKF_REL_FILL_RANK1) or None
         self.shape, self.known = tuple(shape), int(known)
         self.unstored = unstored        # 'unknown': SKF_REL_KNOWN_CSR, 'zero': SKF_REL_SPARSE_CSR (fits) / SKF_REL_FOLD_CSR (fold-ins)
         self.by_col = bool(by_col)      # lists compressed along the column type (fold-ins whose target it is)
@@ -138,7 +167,10 @@ def upload_known_entries(ke, dtype, mem):
     if code == nat.SKF_BF16 and ke.unstored != 'zero':
         vals = nat.to_bf16_bits(vals)
     keep = lambda a: mem.from_host(a if a.size else np.zeros(1, dtype=a.dtype))        # (no empty allocations)
-    return DeviceKnownEntries(keep(ke.indptr), keep(ke.indices), keep(vals), ke.shape, ke.known, ke.unstored, ke.by_col)
+    fills = (None, None)
+    if ke.row_fill is not None:         # the fill vectors in the master type, like the values beside them
+        fills = tuple(keep(np.ascontiguousarray(v, dtype=nat.NP_DTYPE[code])) for v in (ke.row_fill, ke.col_fill))
+    return DeviceKnownEntries(keep(ke.indptr), keep(ke.indices), keep(vals), ke.shape, ke.known, ke.unstored, ke.by_col, *fills)
 
 
 def pack_mask(mask, mem):
@@ -558,6 +590,8 @@ class DevicePlan(object):
                 self._keep_rel.append(dev)
                 if variant == nat.SKF_TRANSFORM and dev.unstored == 'zero':
                     # a fold-in: the stored entries compressed along the target's side (SKF_REL_FOLD_CSR)
+                    if dev.row_fill is not None:
+                        raise ValueError('relation (%s,%s): a filled relation with missing values is for fits, not fold-ins' % (i, j))
                     if dev.by_col != (j == target and i != target):
                         raise ValueError('relation (%s,%s): a fold-in takes the lists compressed along the target %s'
                                          % (i, j, target))
@@ -568,6 +602,8 @@ class DevicePlan(object):
                 if dev.by_col:
                     raise ValueError('relation (%s,%s): lists compressed along the column type are for fold-ins' % (i, j))
                 rdesc[k].flags |= nat.SKF_REL_SPARSE_CSR if dev.unstored == 'zero' else nat.SKF_REL_KNOWN_CSR
+                if dev.row_fill is not None:            # a filled relation with missing values: entries plus rank one
+                    rdesc[k].flags |= nat.SKF_REL_FILL_RANK1
                 rdesc[k].known_bound = dev.known
                 csr.append((k, dev))
                 continue
@@ -674,6 +710,8 @@ class DevicePlan(object):
                      hdesc, C.byref(opt), C.byref(self.handle))
         for k, dev in csr:
             self.rt.call('skf_plan_set_known_entries', self.handle, k, dev.indptr.ptr, dev.indices.ptr, dev.values.ptr)
+            if rdesc[k].flags & nat.SKF_REL_FILL_RANK1:
+                self.rt.call('skf_plan_set_relation_fill', self.handle, k, dev.row_fill.ptr, dev.col_fill.ptr, self.stream)
         for k, dev in theta_csr:
             self.rt.call('skf_plan_set_constraint_entries', self.handle, k, dev.indptr.ptr, dev.indices.ptr, dev.values.ptr)
         nbytes = C.c_size_t()
@@ -792,7 +830,9 @@ class DevicePlan(object):
 
     def relation_lists(self, rel, by_col=False):
         """(indptr, indices, values) of the entry lists relation `rel` keeps (verification accessor): the row lists, or with
-        by_col the column lists -- canonical CSR / CSC whatever the number of parts the engine cut them into."""
+        by_col the column lists -- canonical CSR / CSC whatever the number of parts the engine cut them into.  A filled
+        relation with missing values (fill vectors, SKF_REL_FILL_RANK1): the values are d = v - a_r b_c, what the passes
+        multiply, not the stored values."""
         j = self.relations[rel][1]
         n_out = self.n_obj[self.index[j]] if by_col else self.local_rows[rel]      # (row ownership: local rows, local indices)
         parts, nnz = C.c_int32(), C.c_int64()

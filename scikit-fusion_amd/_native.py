@@ -19,6 +19,7 @@ SKF_REL_KNOWN_LISTS = 32
 SKF_REL_KNOWN_CSR = 64
 SKF_REL_SPARSE_CSR = 128
 SKF_REL_FOLD_CSR = 256
+SKF_REL_FILL_RANK1 = 512
 SKF_STAGE_CONTRACT, SKF_STAGE_BACKBONE, SKF_STAGE_ACCUMULATE, SKF_STAGE_UPDATE = 0, 1, 2, 3
 SKF_X_W, SKF_X_Q, SKF_X_QM, SKF_X_ED = 0, 1, 2, 3
 SKF_COMM_SINGLE, SKF_COMM_RCCL, SKF_COMM_CALLBACK, SKF_COMM_NULL = 0, 1, 2, 3
@@ -101,6 +102,7 @@ SIGNATURES = {
     'skf_plan_bind_workspace': (C.c_int, [_P, _P, C.c_size_t, _P]),
     'skf_plan_set_known_entries': (C.c_int, [_P, C.c_int32, _P, _P, _P]),
     'skf_plan_set_constraint_entries': (C.c_int, [_P, C.c_int32, _P, _P, _P]),
+    'skf_plan_set_relation_fill': (C.c_int, [_P, C.c_int32, _P, _P, _P]),
     'skf_set_factor': (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
     'skf_get_factor': (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
     'skf_set_backbone': (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),

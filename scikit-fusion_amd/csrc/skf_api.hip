@@ -213,6 +213,10 @@ static void plan_describe_relations(skf_plan* p, int32_t n_types, int32_t n_rela
         if (fold && p->variant != SKF_TRANSFORM) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR is for SKF_TRANSFORM plans", r);
         if (fold && (csr || sp0))
             SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR excludes SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR", r);
+        const bool fill = (d.flags & SKF_REL_FILL_RANK1) != 0;    // F = a b^T + D: a filled relation with missing values
+        if (fill && (!sp0 || absent || p->owned || p->variant == SKF_TRANSFORM))
+            SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FILL_RANK1 goes with SKF_REL_SPARSE_CSR on SKF_DFMF / SKF_DFMC plans of whole "
+                     "relations (no SKF_OPT_OWNED_ROWS, no fold-in)", r);
         if (fold && (d.data || d.mask || (d.flags & (SKF_REL_MASKED | SKF_REL_MASK_BITS))))
             SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR takes no data / mask", r);
         if (!absent && !csr && !sp0 && !fold && (!d.data || d.ld < p->types[d.col_type].n))
@@ -267,6 +271,7 @@ static void plan_describe_relations(skf_plan* p, int32_t n_types, int32_t n_rela
         }
         if (sp0) {                  // the stored entries as CSR (skf_plan_set_known_entries): no dense form in any type
             s.sp0 = true;
+            s.fill = fill;
             s.binary = false;
             s.R_in = s.R = nullptr;
             s.kn_cap = d.known_bound;
@@ -698,6 +703,17 @@ static void plan_layout(skf_plan* p) {
             want_part(k_mixed, nr, tj.c, ti.c);                             // H = G_i S
             want_part(k_mixed, nr, ti.c, tj.c);                             // side products
             want_part(k_mixed, tj.n, tj.c, ti.c);
+            if (r.fill) {
+                // the fill vectors, the two weighted column sums and their slab partials, the row sums of bind:
+                // (n_i + n_j) (element + 8) + (slabs_i c_i + slabs_j c_j + c_i + c_j) 8 bytes -- O(n_i + n_j + slabs c)
+                add_slot(p, r.Fa, (size_t)nr * es);
+                add_slot(p, r.Fb, (size_t)tj.n * es);
+                add_slot(p, r.Ft, (size_t)tj.c * 8);
+                add_slot(p, r.Fs, (size_t)ti.c * 8);
+                add_slot(p, r.FpartP, (size_t)cdiv(tj.n, COLSUM_ROWS) * tj.c * 8);
+                add_slot(p, r.FpartQ, (size_t)cdiv(nr, COLSUM_ROWS) * ti.c * 8);
+                add_slot(p, r.Frow, (size_t)nr * 8);
+            }
             const size_t waves = (size_t)r.kn_pc * ((size_t)nr + 32) + 64;  // error partials: one per wave of the row pass
             if (waves > sq_elems) sq_elems = waves;
             continue;
@@ -864,6 +880,20 @@ int skf_plan_set_known_entries(skf_plan* plan, int32_t rel, const int64_t* indpt
         r.csr_ptr = indptr;
         r.csr_idx = (const int*)indices;
         r.csr_val = values;
+    });
+}
+
+int skf_plan_set_relation_fill(skf_plan* plan, int32_t rel, const void* row_fill, const void* col_fill, void* stream) {
+    return guarded([&] {
+        (void)stream;       // (the vectors are read by skf_plan_bind_workspace on ITS stream, like the lists)
+        if (!plan) SKF_FAIL(SKF_E_INVALID, "null argument");
+        if (plan->ws_base) SKF_FAIL(SKF_E_STATE, "skf_plan_set_relation_fill after skf_plan_bind_workspace");
+        if (rel < 0 || rel >= (int)plan->rels.size()) SKF_FAIL(SKF_E_INVALID, "relation %d out of range", rel);
+        RelState& r = plan->rels[rel];
+        if (!r.fill) SKF_FAIL(SKF_E_INVALID, "relation %d is not flagged SKF_REL_FILL_RANK1", rel);
+        if (!row_fill || !col_fill) SKF_FAIL(SKF_E_INVALID, "relation %d: null fill vector", rel);
+        r.fill_row = row_fill;
+        r.fill_col = col_fill;
     });
 }
 
@@ -1375,6 +1405,7 @@ int skf_relation_sqerr(skf_plan* p, int32_t rel, double* out, void* stream) {
             trace_term(r.Xi.ptr, r.S.ptr, r.Xj.ptr, r.S.ptr, 1.0, true);
             GemmArgs h = gemm_args(Gi_b, ci, 1, r.S.ptr, cj, 1, r.H.ptr, cj, ni, cj, ci, EPI_STORE, 0);           // H = G_i S
             mixed_gemm(p, h, st);
+            if (r.fill) fill_err_terms(p, r, st);                     // the rank-one terms into slot 0, beside the trace term
             const int waves = sparse_pass(p, r, false, true, nullptr, st, 1);
             hipLaunchKernelGGL((sum_partials_kernel<double>), dim3(1), dim3(256), 0, st, (const double*)p->sqpart.ptr, waves + 1, out);
             check_launch("sum_partials");

@@ -18,12 +18,19 @@ static int device_flag(int* word, hipStream_t st, Launch&& launch) {
 
 // Caller-made CSR lists, checked on the device before anything gathers through them: indptr from 0 to nnz and
 // non-decreasing, indices inside [0, cols) and strictly ascending within a row (known_csr_check_kernel; its only caller).
+// `also` launches further checks that set the same word (the fill vectors of a SKF_REL_FILL_RANK1 relation): one verdict.
+template <class Also>
 static bool csr_is_canonical(const int64_t* indptr, const int* indices, int64_t rows, int64_t cols, int64_t nnz, int* flag_word,
-                             hipStream_t st) {
+                             hipStream_t st, Also&& also) {
     return device_flag(flag_word, st, [&] {
         hipLaunchKernelGGL(known_csr_check_kernel, dim3(wave_grid(rows)), dim3(256), 0, st, indptr, indices, rows, cols, nnz, flag_word);
         check_launch("known_csr_check");
+        also();
     }) == 0;
+}
+static bool csr_is_canonical(const int64_t* indptr, const int* indices, int64_t rows, int64_t cols, int64_t nnz, int* flag_word,
+                             hipStream_t st) {
+    return csr_is_canonical(indptr, indices, rows, cols, nnz, flag_word, st, [] {});
 }
 
 // `n` counts on the device -> their exclusive prefix sum in int64 on the host -> n + 1 pointers uploaded to `dst`; returns
@@ -108,6 +115,32 @@ static void build_known_lists_t(skf_plan* p, RelState& r, hipStream_t st) {
     });
 }
 
+// SKF_REL_FILL_RANK1: copies of the fill vectors a, b; the row lists' values v -> d = v - a_r b_c (once, before the column
+// lists are built from them); the constants of the error formula in f64, every sum in ascending order: |a|^2, |b|^2 on the
+// host from the copies, 2 sum d a_r b_c from the per-row sums of fill_residual_kernel.  The caller's vectors are not
+// referenced afterwards.
+template <typename TM>
+static void bind_relation_fill(skf_plan* p, RelState& r, hipStream_t st) {
+    const int64_t rows = r.nr, cols = p->types[r.col].n;
+    SKF_HIP(hipMemcpyAsync(r.Fa.ptr, r.fill_row, (size_t)rows * sizeof(TM), hipMemcpyDeviceToDevice, st));
+    SKF_HIP(hipMemcpyAsync(r.Fb.ptr, r.fill_col, (size_t)cols * sizeof(TM), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL((fill_residual_kernel<TM>), dim3(elem_grid(rows)), dim3(256), 0, st, (const int64_t*)r.KrPtr.ptr,
+                       (const int*)r.KrIdx.ptr, r.kn_pc, rows, (const TM*)r.Fa.ptr, (const TM*)r.Fb.ptr, (TM*)r.KrVal.ptr,
+                       (double*)r.Frow.ptr);
+    check_launch("fill_residual");
+    std::vector<TM> ha((size_t)rows), hb((size_t)cols);
+    std::vector<double> hs((size_t)rows);
+    SKF_HIP(hipMemcpyAsync(ha.data(), r.Fa.ptr, (size_t)rows * sizeof(TM), hipMemcpyDeviceToHost, st));
+    SKF_HIP(hipMemcpyAsync(hb.data(), r.Fb.ptr, (size_t)cols * sizeof(TM), hipMemcpyDeviceToHost, st));
+    SKF_HIP(hipMemcpyAsync(hs.data(), r.Frow.ptr, (size_t)rows * 8, hipMemcpyDeviceToHost, st));
+    SKF_HIP(hipStreamSynchronize(st));
+    double aa = 0.0, bb = 0.0, dab = 0.0;
+    for (int64_t k = 0; k < rows; ++k) { aa += (double)ha[k] * (double)ha[k]; dab += hs[k]; }
+    for (int64_t k = 0; k < cols; ++k) bb += (double)hb[k] * (double)hb[k];
+    r.fill_aa = aa; r.fill_bb = bb; r.fill_dab = 2.0 * dab;
+    r.fill_row = r.fill_col = nullptr;
+}
+
 // The same lists from the caller's CSR (SKF_REL_KNOWN_CSR): validated on the device first -- nothing gathers through them
 // before the host has read the verdict --, then the row lists are copies of the CSR with the part split points found by
 // binary search, and the column side is built as above, its values taken from the row lists.  Byte for byte the lists
@@ -118,10 +151,19 @@ static void build_known_lists_csr_t(skf_plan* p, RelState& r, hipStream_t st) {
     const int64_t rows = r.nr, cols = p->types[r.col].n, tot = r.kn_cap;
     const int pc = r.kn_pc, pr = r.kn_pr;
     int* cnt = (int*)r.KCnt.ptr;
-    if (!csr_is_canonical(r.csr_ptr, r.csr_idx, rows, cols, tot, cnt, st))
+    if (r.fill && !(r.fill_row && r.fill_col))
+        SKF_FAIL(SKF_E_INVALID, "a SKF_REL_FILL_RANK1 relation without skf_plan_set_relation_fill");
+    const bool lists_ok = csr_is_canonical(r.csr_ptr, r.csr_idx, rows, cols, tot, cnt, st, [&] {
+        if (!r.fill) return;           // the fill vectors, in the validation itself: nothing is formed from a non-finite one
+        hipLaunchKernelGGL((finite_check_kernel<TM>), dim3(elem_grid(rows)), dim3(256), 0, st, (const TM*)r.fill_row, rows, cnt);
+        hipLaunchKernelGGL((finite_check_kernel<TM>), dim3(elem_grid(cols)), dim3(256), 0, st, (const TM*)r.fill_col, cols, cnt);
+        check_launch("fill_check");
+    });
+    if (!lists_ok)
         SKF_FAIL(SKF_E_INVALID, "%s: the lists are not a canonical CSR of %lld x %lld with %lld entries (indptr from 0 "
-                 "to the count, non-decreasing; columns in range and strictly ascending within a row)",
-                 r.sp0 ? "SKF_REL_SPARSE_CSR" : "SKF_REL_KNOWN_CSR", (long long)rows, (long long)cols, (long long)tot);
+                 "to the count, non-decreasing; columns in range and strictly ascending within a row)%s",
+                 r.sp0 ? "SKF_REL_SPARSE_CSR" : "SKF_REL_KNOWN_CSR", (long long)rows, (long long)cols, (long long)tot,
+                 r.fill ? ", or a fill vector of SKF_REL_FILL_RANK1 holds a value that is not finite" : "");
     r.kn_nnz = tot;
     hipLaunchKernelGGL(parted_ptr_kernel, dim3(elem_grid(rows * pc + 1)), dim3(256), 0, st, r.csr_ptr, r.csr_idx, rows, pc, r.kn_pw,
                        (int64_t*)r.KrPtr.ptr);
@@ -135,6 +177,7 @@ static void build_known_lists_csr_t(skf_plan* p, RelState& r, hipStream_t st) {
                            (const int*)r.KrIdx.ptr, pc, rows, pr, r.kn_ph, cnt);
         check_launch("known_csr_fill");
     }
+    if (r.fill) bind_relation_fill<TM>(p, r, st);        // (before the column lists take their values from the row lists)
     std::vector<int> hc;
     std::vector<int64_t> hp;
     build_known_columns<TM>(p, r, hc, hp, "known_csr_cols", st, [&](int cgrid) {      // the values: looked up in the row lists

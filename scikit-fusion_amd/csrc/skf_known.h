@@ -548,6 +548,142 @@ __global__ __launch_bounds__(256) void sum_parts_kernel(T* __restrict__ dst, con
     }
 }
 
+// ---- SKF_REL_FILL_RANK1: a relation F = a b^T + D, D sparse on the stored pattern --------------------------------------
+// The rank-one side of P = F G_j = D G_j + a (b^T G_j) and Q = F^T G_i = D^T G_i + b (a^T G_i): weighted column sums
+// t = G^T w of a factor (c values, f64), formed in two stages without atomics and with a grid fixed by n alone, so two runs
+// and two machines give the same bits, and the term scale[o] * t added in the launch that sums the parts of the list pass.
+
+// sum_parts_kernel with the rank-one term: dst[o][q] = part 0 + part 1 + ... + scale[o] * (T)vec[q]   (o = e / w, q = e % w).
+// nparts == 1 with parts == dst adds the term in place (one read-modify-write of an element by its own thread).
+template <typename T>
+__global__ __launch_bounds__(256) void sum_parts_rank1_kernel(T* dst, const T* parts, int64_t stride, int nparts, int64_t total, int w,
+                                                              const T* __restrict__ scale, const double* __restrict__ vec) {
+    constexpr int VE = 16 / (int)sizeof(T);
+    typedef T vec_t __attribute__((ext_vector_type(VE)));
+    const bool vec_ok = w % VE == 0 && stride % VE == 0 && (((uintptr_t)dst | (uintptr_t)parts) & 15) == 0;
+    if (vec_ok) {
+        const int64_t nv = total / VE, sv = stride / VE;
+        const int wv = w / VE;
+        const vec_t* src = (const vec_t*)parts;
+        for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nv; e += (int64_t)gridDim.x * blockDim.x) {
+            vec_t s = src[e];
+            for (int p = 1; p < nparts; ++p) s += src[(int64_t)p * sv + e];
+            const T sc = scale[e / wv];
+            const int q0 = (int)(e % wv) * VE;
+#pragma unroll
+            for (int k = 0; k < VE; ++k) s[k] += sc * (T)vec[q0 + k];
+            ((vec_t*)dst)[e] = s;
+        }
+        return;
+    }
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+        T s = parts[e];
+        for (int p = 1; p < nparts; ++p) s += parts[(int64_t)p * stride + e];
+        dst[e] = s + scale[e / w] * (T)vec[e % w];
+    }
+}
+
+// Stage 1 of t = G^T w: workgroup b owns the COLSUM_ROWS rows from b * COLSUM_ROWS on and stores its c partial sums in f64,
+// part[b][q] = sum over its rows r (ascending within a thread, the row groups of the workgroup first to last) of
+// (double)w[r] * (double)G[r][q].  VE > 1: 16-byte loads along the row (c, ld multiples of VE, G 16-byte aligned); VE == 1: the
+// scalar path for every other width and leading dimension.  A thread owns one chunk of VE columns and every RG-th row of
+// the slab (RG = 256 / chunks-per-trip); the row groups meet in LDS and are added in ascending order.
+#define COLSUM_ROWS 128
+template <typename TG, typename TW, int VE>
+__global__ __launch_bounds__(256) void colsum_partial_kernel(const TG* __restrict__ G, int64_t ld, int64_t n, int c,
+                                                             const TW* __restrict__ w, double* __restrict__ part) {
+    typedef TG vec_t __attribute__((ext_vector_type(VE)));
+    __shared__ double red[256 * VE];
+    const int nch = c / VE;                              // chunks of a row (VE == 1: columns)
+    int nchp = 1;
+    while (nchp < nch && nchp < 256) nchp *= 2;          // chunks per trip: a power of two, so 256 / nchp row groups
+    const int rg_n = 256 / nchp, rg = (int)threadIdx.x / nchp, cl = (int)threadIdx.x % nchp;
+    const int64_t r0 = (int64_t)blockIdx.x * COLSUM_ROWS;
+    const int64_t r1 = r0 + COLSUM_ROWS < n ? r0 + COLSUM_ROWS : n;
+    for (int cb = 0; cb < nch; cb += nchp) {
+        const int ch = cb + cl;
+        double acc[VE];
+#pragma unroll
+        for (int k = 0; k < VE; ++k) acc[k] = 0.0;
+        if (ch < nch)
+            for (int64_t r = r0 + rg; r < r1; r += rg_n) {
+                const double wr = (double)w[r];
+                if (VE > 1) {
+                    const vec_t g = *(const vec_t*)(G + r * ld + (int64_t)ch * VE);
+#pragma unroll
+                    for (int k = 0; k < VE; ++k) acc[k] += wr * (double)GatherT<TG>::get(g[k]);
+                } else {
+                    acc[0] += wr * (double)GatherT<TG>::get(G[r * ld + ch]);
+                }
+            }
+#pragma unroll
+        for (int k = 0; k < VE; ++k) red[((int)threadIdx.x) * VE + k] = acc[k];
+        __syncthreads();
+        if (rg == 0 && ch < nch) {
+#pragma unroll
+            for (int k = 0; k < VE; ++k) {
+                double s = red[cl * VE + k];
+                for (int g = 1; g < rg_n; ++g) s += red[(g * nchp + cl) * VE + k];
+                part[(int64_t)blockIdx.x * c + (int64_t)ch * VE + k] = s;
+            }
+        }
+        __syncthreads();
+    }
+}
+// Stage 2: out[q] = part[0][q] + part[1][q] + ... (first to last), one thread per column
+static __global__ __launch_bounds__(256) void colsum_final_kernel(const double* __restrict__ part, int64_t slabs, int c,
+                                                                  double* __restrict__ out) {
+    const int q = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (q >= c) return;
+    double s = part[q];
+    for (int64_t b = 1; b < slabs; ++b) s += part[b * c + q];
+    out[q] = s;
+}
+
+// bad[0] = 1 when one of the n values is not finite (the fill vectors of a SKF_REL_FILL_RANK1 relation; part of the
+// validation before anything gathers)
+template <typename T>
+__global__ __launch_bounds__(256) void finite_check_kernel(const T* __restrict__ v, int64_t n, int* __restrict__ bad) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        const T x = v[e];
+        if (!(x - x == (T)0)) *bad = 1;                   // NaN and +-inf: x - x is NaN
+    }
+}
+
+// Bind time: the row lists' values v become d = v - a_r b_c, computed as (double)v - (double)a (double)b and rounded once to
+// the master type; rowsum[r] = sum over the row, in list order, of (double)d (double)a_r (double)b_c -- the host adds the
+// rows in ascending order to the constant 2 sum d a b of the error formula.  One thread per row (bind is not the hot path).
+template <typename T>
+__global__ __launch_bounds__(256) void fill_residual_kernel(const int64_t* __restrict__ rptr, const int* __restrict__ idx, int rparts,
+                                                            int64_t rows, const T* __restrict__ a, const T* __restrict__ b,
+                                                            T* __restrict__ vals, double* __restrict__ rowsum) {
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
+        const double ar = (double)a[r];
+        double s = 0.0;
+        for (int64_t q = rptr[r * rparts]; q < rptr[(r + 1) * rparts]; ++q) {
+            const double bc = (double)b[idx[q]];
+            const T d = (T)((double)vals[q] - ar * bc);
+            vals[q] = d;
+            s += (double)d * ar * bc;
+        }
+        rowsum[r] = s;
+    }
+}
+
+// acc[0] += cst - 2 u^T S v   (u: c_i, v: c_j, S: c_i x c_j, all f64; one workgroup): the rank-one terms of the squared
+// error of a SKF_REL_FILL_RANK1 relation, added to the trace term in slot 0 of the partials
+static __global__ __launch_bounds__(256) void fill_err_terms_kernel(const double* __restrict__ u, const double* __restrict__ S,
+                                                                    const double* __restrict__ v, int ci, int cj, double cst,
+                                                                    double* __restrict__ acc) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (int64_t e = threadIdx.x; e < (int64_t)ci * cj; e += 256) s += u[e / cj] * S[e] * v[e % cj];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) acc[0] += cst - 2.0 * (red[0] + red[1] + red[2] + red[3]);
+}
+
 // E (+)= max(A, 0) ; D (+)= max(-A, 0)      (the +- split of _dfmc.py:141-144 on an already formed product)
 template <typename T>
 __global__ __launch_bounds__(256) void split_accumulate_kernel(T* __restrict__ E, T* __restrict__ D, const T* __restrict__ A,

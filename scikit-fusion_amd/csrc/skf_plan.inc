@@ -157,6 +157,16 @@ struct RelState {
     // values where the known-entry form keeps residuals (sparse_pass), partial outputs of the parts in Apart / Qpart; the error
     // is tr(S^T Gram_i S Gram_j) (Xi, Xj) + one SRP_ERR pass with e = r.  No dense copy in any type.
     bool sp0 = false;
+    // SKF_REL_FILL_RANK1 (with sp0): the relation is F = a b^T + D -- a filled relation with missing values.  The caller's
+    // values are the true stored ones; bind turns the lists' values into d = v - a_r b_c (Fa / Fb: copies of a and b in the
+    // master type).  sparse_pass adds a (b^T G_j) to P and b (a^T G_i) to Q: the weighted column sums Ft (c_j) / Fs (c_i) in
+    // f64 from the slab partials FpartP / FpartQ (P and Q each their own: the relation pipeline runs on two streams).
+    // fill_aa = |a|^2, fill_bb = |b|^2, fill_dab = 2 sum d a_r b_c: the constants of the error formula, f64, fixed order.
+    bool fill = false;
+    const void* fill_row = nullptr;        // the caller's a / b (skf_plan_set_relation_fill; read at bind time only)
+    const void* fill_col = nullptr;
+    Slot Fa, Fb, Ft, Fs, FpartP, FpartQ, Frow;
+    double fill_aa = 0.0, fill_bb = 0.0, fill_dab = 0.0;
     // SKF_REL_FOLD_CSR (SKF_TRANSFORM): the new relation as ONE set of lists compressed along the target's side, copied into
     // KrPtr / KrIdx / KrVal at bind time (master type); Tm = G_p S^T (row side) / G_p S (column side), n_partner x c_target;
     // H = G_t S / G_t S^T (n_target x c_partner) and Xi / Xj / T1 for skf_relation_sqerr.  No P, no Q, no parts.

@@ -128,6 +128,39 @@ static int known_pass(skf_plan* p, RelState& r, bool by_col, int mode, hipStream
     return waves;
 }
 
+// t = G^T w for SKF_REL_FILL_RANK1 (colsum_partial_kernel / colsum_final_kernel): `part` holds cdiv(n, COLSUM_ROWS) x c
+// doubles, `out` c doubles.  The grid follows from n alone; 16-byte loads where width, leading dimension and base allow.
+template <typename TG, typename TW>
+static void launch_colsum(const TG* G, int64_t ld, int64_t n, int c, const TW* w, double* part, double* out, hipStream_t st) {
+    constexpr int VE = 16 / (int)sizeof(TG);
+    const int slabs = cdiv(n, COLSUM_ROWS);
+    const bool vec = c % VE == 0 && ld % VE == 0 && (((uintptr_t)G) & 15) == 0;
+    if (vec) hipLaunchKernelGGL((colsum_partial_kernel<TG, TW, VE>), dim3(slabs), dim3(256), 0, st, G, ld, n, c, w, part);
+    else hipLaunchKernelGGL((colsum_partial_kernel<TG, TW, 1>), dim3(slabs), dim3(256), 0, st, G, ld, n, c, w, part);
+    hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(c, 256)), dim3(256), 0, st, (const double*)part, (int64_t)slabs, c, out);
+    check_launch("colsum");
+}
+
+// The rank-one terms of the squared error of a SKF_REL_FILL_RANK1 relation, added into slot 0 of p->sqpart (which holds the
+// trace term): |a|^2 |b|^2 + 2 sum d a_r b_c - 2 (a^T G_i) S (G_j^T b).  The two sums over the objects read the MASTERS in
+// every engine (the reason sparse_pass gives for its error pass); the c_i x c_j product against S is f64.
+static void fill_err_terms(skf_plan* p, const RelState& r, hipStream_t st) {
+    const TypeState& ti = p->types[r.row];
+    const TypeState& tj = p->types[r.col];
+    double* u = (double*)r.Fs.ptr;
+    double* v = (double*)r.Ft.ptr;
+    if (p->f64) {
+        launch_colsum((const double*)ti.G.ptr, (int64_t)ti.c, ti.n, ti.c, (const double*)r.Fa.ptr, (double*)r.FpartQ.ptr, u, st);
+        launch_colsum((const double*)tj.G.ptr, (int64_t)tj.c, tj.n, tj.c, (const double*)r.Fb.ptr, (double*)r.FpartP.ptr, v, st);
+    } else {
+        launch_colsum((const float*)ti.G.ptr, (int64_t)ti.c, ti.n, ti.c, (const float*)r.Fa.ptr, (double*)r.FpartQ.ptr, u, st);
+        launch_colsum((const float*)tj.G.ptr, (int64_t)tj.c, tj.n, tj.c, (const float*)r.Fb.ptr, (double*)r.FpartP.ptr, v, st);
+    }
+    hipLaunchKernelGGL(fill_err_terms_kernel, dim3(1), dim3(256), 0, st, (const double*)u, (const double*)r.S.ptr, (const double*)v,
+                       ti.c, tj.c, r.fill_aa * r.fill_bb + r.fill_dab, (double*)p->sqpart.ptr);
+    check_launch("fill_err_terms");
+}
+
 // One pass over the stored entries of a SKF_REL_SPARSE_CSR relation (every entry not stored is zero; reference: the dense
 // products of _dfmf.py:249-276 and the error of _dfmf.py:306-316):
 //   err == false, is_q == false   P = R G_j    over the row lists, gathering rows of G_j   (SRP_APPLY, e = the stored value)
@@ -167,6 +200,17 @@ static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void
         a.sq = (double*)p->sqpart.ptr + sq_first;
     };
     void* vals = is_q ? r.KcVal.ptr : r.KrVal.ptr;
+    // SKF_REL_FILL_RANK1: the weighted column sum of the gathered factor -- t = G_j^T b for P, s = G_i^T a for Q -- over the
+    // rows the list pass gathers, before the lists are walked, on this stream; the term is added where the parts are summed
+    const bool rank1 = r.fill && !err;
+    double* tvec = (double*)(is_q ? r.Fs.ptr : r.Ft.ptr);
+    if (rank1) {
+        double* part = (double*)(is_q ? r.FpartQ.ptr : r.FpartP.ptr);
+        const void* wts = is_q ? r.Fa.ptr : r.Fb.ptr;
+        if (p->f64) launch_colsum((const double*)tin.G.ptr, (int64_t)w, tin.n, w, (const double*)wts, part, tvec, st);
+        else if (p->bf16) launch_colsum((const uint16_t*)tin.Grow.ptr, tin.ldrow, tin.n, w, (const float*)wts, part, tvec, st);
+        else launch_colsum((const float*)tin.G.ptr, (int64_t)w, tin.n, w, (const float*)wts, part, tvec, st);
+    }
     if (p->f64) {
         SrpArgs<double, double> a;
         fill(a, (double*)vals, (const double*)rows_of(p, tin.G, tin, in0), (int64_t)w, (const double*)r.H.ptr, (int64_t)w, (double*)out);
@@ -185,7 +229,18 @@ static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void
         fill(a, (float*)vals, (const float*)rows_of(p, tin.G, tin, in0), (int64_t)w, (const float*)r.H.ptr, (int64_t)w, (float*)out);
         waves = launch_srp(a, st, false);
     }
-    if (parts > 1 && !err) {
+    if (rank1) {
+        // P[r] += a_r t / Q[c] += b_c s in the launch that sums the parts (one part: one pass over the output, in place)
+        const int64_t total = n_out * w;
+        const void* scale = is_q ? r.Fb.ptr : r.Fa.ptr;
+        if (p->f64)
+            hipLaunchKernelGGL((sum_parts_rank1_kernel<double>), dim3(elem_grid(total)), dim3(256), 0, st, (double*)dst, (const double*)out,
+                               total, parts, total, w, (const double*)scale, (const double*)tvec);
+        else
+            hipLaunchKernelGGL((sum_parts_rank1_kernel<float>), dim3(elem_grid(total)), dim3(256), 0, st, (float*)dst, (const float*)out,
+                               total, parts, total, w, (const float*)scale, (const double*)tvec);
+        check_launch("sum_parts_rank1");
+    } else if (parts > 1 && !err) {
         const int64_t total = n_out * w;
         if (p->f64)
             hipLaunchKernelGGL((sum_parts_kernel<double>), dim3(elem_grid(total)), dim3(256), 0, st, (double*)dst, (const double*)out,
@@ -201,6 +256,15 @@ static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void
         p->prof_flops += 2.0 * (double)r.kn_nnz * w;
         p->prof_bytes += (double)r.kn_nnz * (4.0 + (double)p->esz + (double)w * (p->bf16 ? 2.0 : (double)p->esz));
         p->prof_launches += 1;
+        if (rank1) {
+            // the rank-one side (one more counted launch: the column sum with its reduce): 2 n_in w flops for the sum, 2 n_out w
+            // for the term; the gathered factor and its weights once, the scale vector once, and -- lists in one part -- the
+            // output read and written once more
+            p->prof_flops += 2.0 * (double)tin.n * w + 2.0 * (double)n_out * w;
+            p->prof_bytes += (double)tin.n * ((double)w * (p->bf16 ? 2.0 : (double)p->esz) + (double)p->esz) + (double)n_out * (double)p->esz +
+                             (parts > 1 ? 0.0 : 2.0 * (double)n_out * w * (double)p->esz);
+            p->prof_launches += 1;
+        }
     }
     return waves;
 }

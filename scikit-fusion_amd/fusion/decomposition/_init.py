@@ -33,6 +33,12 @@ class _KnownView(object):
         self.shape = ke.shape[::-1] if transposed else ke.shape
         self.values, self.fill = ke.values, ke.fill
         self.zeros = getattr(ke, 'unstored', 'unknown') == 'zero'      # the entries not stored ARE zeros (a scipy.sparse relation)
+        # a per-line fill (a filled relation with missing values): an entry not stored holds a[row] * b[column] in the
+        # view's orientation; one of the two is all ones, so the product is the dense fill value bit for bit
+        self.a = self.b = None
+        if getattr(ke, 'row_fill', None) is not None:
+            self.a, self.b = (ke.col_fill, ke.row_fill) if transposed else (ke.row_fill, ke.col_fill)
+            self.zeros = False
 
     def row_means(self, columns):
         if self.zeros:
@@ -51,6 +57,9 @@ class _KnownView(object):
         known = np.bincount(self.rows[hit], weights=self.values[hit], minlength=self.shape[0])
         count = np.bincount(self.rows[hit], minlength=self.shape[0])
         take = len(columns)
+        if self.a is not None:      # (known + a_r (sum of b over the chosen columns - sum of b over the stored chosen ones)) / take
+            b_stored = np.bincount(self.rows[hit], weights=self.b[self.cols[hit]], minlength=self.shape[0])
+            return (known + self.a * (self.b[columns].sum() - b_stored)) / take
         return (known + (take - count) * self.fill) / take
 
     def column_norms(self):
@@ -61,7 +70,7 @@ class _KnownView(object):
         col = np.empty(self.shape[0]) if self.transposed else np.empty((self.shape[0], 2))[:, 0]
         norms = []
         for k in range(self.shape[1]):
-            col[:] = self.fill
+            col[:] = self.fill if self.a is None else self.a * self.b[k]
             col[rows[ptr[k]:ptr[k + 1]]] = vals[ptr[k]:ptr[k + 1]]
             norms.append(np.linalg.norm(col, 2))
         return norms

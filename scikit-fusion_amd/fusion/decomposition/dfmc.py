@@ -19,7 +19,9 @@ class Dfmc(FusionFit):
     random_state=None, n_jobs=1.  Addition: dtype='f64' | 'f32'.  A relation given as its known entries
     (``Relation(scipy.sparse matrix, ..., unstored='unknown')``) is fitted on those entries alone with shard='runs'
     (see ``Relation``) and with shard='owned', where every rank uploads the known entries of its owned rows only (the
-    whole matrix stays on every process's host for the initialisers; 'rows' / 'relations' expand it); one whose unstored entries are zero on its stored entries (``sparse_relations``, see ``Dfmf``); a
+    whole matrix stays on every process's host for the initialisers; 'rows' / 'relations' expand it); such a relation with
+    fill_value 'row_mean' / 'col_mean' (no mask is left) as entries plus rank one with shard='runs' (``sparse_relations``,
+    ``filled_entries_apply``); one whose unstored entries are zero on its stored entries (``sparse_relations``, see ``Dfmf``); a
     ``scipy.sparse`` constraint as its entries (``sparse_constraints``, see ``Dfmf``)."""
 
     def __init__(self, max_iter=100, init_type='random_c', n_run=1, stopping=None,
@@ -37,7 +39,7 @@ class Dfmc(FusionFit):
         R, Theta, M = graph_matrices(fusion_graph, with_masks=True, device_dtype=device_fill_dtype(self),
                                      known_entries=self.shard in ('runs', 'owned'),
                                      sparse_relations=getattr(self, 'sparse_relations', None), shard=self.shard,
-                                     sparse_constraints=getattr(self, 'sparse_constraints', None))
+                                     sparse_constraints=getattr(self, 'sparse_constraints', None), variant='dfmc')
         G0 = initial_factors(R, object_types, rank, self.init_type, self.random_state, self.n_run)
         kw = dict(R=R, M=M, Theta=Theta, obj_types=object_types, obj_type2rank=rank,
                   max_iter=self.max_iter, init_type=self.init_type, stopping=self.stopping,

@@ -68,6 +68,43 @@ def stored_entries_apply(relation, sparse_relations, shard='runs'):
     return cells > 0 and nnz / cells * rank <= SPARSE_RULE
 
 
+def filled_entries_apply(relation, sparse_relations, shard='runs', variant='dfmf'):
+    """Whether a ``scipy.sparse`` relation with ``unstored='unknown'`` enters the fit as entries plus rank one
+    (``Relation.filled_entries``: the filled matrix is a b^T + D, never expanded): shard='runs', no preprocessor, two
+    different object types, every stored value finite (a stored NaN / inf takes part in the fill: the dense path's job),
+    at least one entry NOT stored (a MaskedArray that masks nothing follows numpy.ma's other rules, ``_fill_lines``), ranks
+    <= 1024 and at most 2e9 entries.  `variant` 'dfmf': every fill value; 'dfmc': 'row_mean' / 'col_mean' only -- they leave
+    no mask, so the relation is an unmasked one of the DFMC plan ('mean' and numbers keep their mask and go to
+    ``known_entries_apply``).  `sparse_relations` follows the rule of ``stored_entries_apply``: None: density *
+    max(rank_row, rank_col) <= 4 beyond the small-graph limits; True: whenever eligible; False: never."""
+    if sparse_relations is False or shard != 'runs':
+        return False
+    if not relation.is_known_entries() or relation.preprocessor or relation.row_type == relation.col_type:
+        return False
+    if isinstance(relation.fill_value, Number) or relation.fill_value == 'mean':
+        if variant != 'dfmf':
+            return False
+    elif relation.fill_value not in ('row_mean', 'col_mean'):
+        return False
+    rank = max(int(relation.row_type.rank), int(relation.col_type.rank))
+    cells = float(relation.data.shape[0]) * float(relation.data.shape[1])
+    if rank > 1024 or int(relation.data.nnz) > 2000000000 or cells <= 0:
+        return False
+    import scipy.sparse
+    csr = scipy.sparse.csr_matrix(relation.data, copy=True)
+    csr.sum_duplicates()                                # (the stored pattern: duplicates are one entry)
+    nnz = int(csr.indices.size)
+    if nnz >= cells or not np.isfinite(csr.data).all():
+        return False
+    if sparse_relations:
+        return True
+    from ..._engine import small_graph_limits
+    lim = small_graph_limits()
+    if rank <= lim['max_rank'] and max(relation.data.shape) <= lim['max_objects']:
+        return False
+    return nnz / cells * rank <= SPARSE_RULE
+
+
 def constraint_entries_apply(relation, sparse_constraints, shard='runs'):
     """Whether a ``scipy.sparse`` constraint (row type == column type) with ``unstored='zero'`` goes to the device as its
     entries (never expanded): shard='runs' or 'owned' (there every rank hands over the CSR of its owned rows; the decision
@@ -115,7 +152,7 @@ def fold_entries_apply(relation, sparse_relations):
 
 
 def graph_matrices(fusion_graph, with_masks=False, device_dtype=None, known_entries=False, sparse_relations=False,
-                   shard='runs', sparse_constraints=False):
+                   shard='runs', sparse_constraints=False, variant='dfmf'):
     """FusionGraph -> (R, Theta[, M]) dictionaries in the reference's walking order
     (dfmf.py:70-85, dfmc.py:70-93): pairs from product(object_types, repeat=2), each relation
     filled, then preprocessed; relations between two different types go to R, same-type
@@ -127,7 +164,9 @@ def graph_matrices(fusion_graph, with_masks=False, device_dtype=None, known_entr
     mask None where ``known_entries_apply`` says so (never filled on the device: nothing unknown is stored).
     ``sparse_relations`` / ``shard``: scipy.sparse relations whose unstored entries are zero enter as their stored entries
     (``_engine.KnownEntries`` with ``unstored='zero'``, mask None) where ``stored_entries_apply`` says so, and
-    ``sparse_constraints``: scipy.sparse constraints as their entries where ``constraint_entries_apply`` says so."""
+    ``sparse_constraints``: scipy.sparse constraints as their entries where ``constraint_entries_apply`` says so.
+    scipy.sparse relations whose unstored entries are UNKNOWN enter as entries plus rank one (``Relation.filled_entries``,
+    mask None) where ``filled_entries_apply`` says so for `variant` ('dfmf' | 'dfmc'), ahead of the dense ``filled()``."""
     R, Theta, M = {}, {}, {}
     for row_type, col_type in product(fusion_graph.object_types, repeat=2):
         for relation in fusion_graph.get_relations(row_type, col_type):
@@ -138,6 +177,8 @@ def graph_matrices(fusion_graph, with_masks=False, device_dtype=None, known_entr
                 data = relation.stored_entries()
             elif constraint_entries_apply(relation, sparse_constraints, shard):
                 data = relation.constraint_entries()
+            elif filled_entries_apply(relation, sparse_relations, shard, variant):
+                data = relation.filled_entries()
             elif device_dtype and not relation.preprocessor and relation.row_type != relation.col_type:
                 data, mask = relation.filled_device(device_dtype)
             else:
@@ -268,6 +309,10 @@ class Dfmf(FusionFit):
     preprocessor -- None:
     when nnz <= n * n / 16 (the engine's own bound for the sparse product; a denser one is expanded and multiplied as a
     dense matrix); True: always; False: never (``toarray()``).  Same factors either way, bit for bit, up to that bound.
+    A ``scipy.sparse`` relation with MISSING values (``Relation(..., unstored='unknown')``, any ``fill_value``) is fitted
+    as entries plus rank one under the same ``sparse_relations`` rule with shard='runs' and never expanded either: every
+    fill writes a rank-one pattern a b^T into the unknown cells, so the filled matrix is a b^T + D with D sparse on the
+    stored pattern (``Relation.filled_entries``; see ``filled_entries_apply`` for what is still expanded).
     """
 
     def __init__(self, max_iter=100, init_type='random_c', n_run=1, stopping=None,

@@ -157,9 +157,13 @@ class Relation(object):
     entries are masked -- every result equals what that MaskedArray gives.  Stored zeros are known zeros; duplicate
     entries are summed (as ``toarray()`` sums them); stored NaN / inf take the fill value and stay known, as in the
     MaskedArray.  ``Dfmc`` (shard='runs', no preprocessor, fill_value 'mean' or a number, row type rank <= 1024, at most
-    2e9 stored entries) fits such a relation on its known entries alone and never forms the dense matrix; every other
-    use -- ``Dfmf`` / ``DfmfTransform``, a preprocessor, 'row_mean' / 'col_mean' (under numpy.ma they leave every entry
-    known), the other shard modes, larger ranks -- expands it on the host to that MaskedArray and runs unchanged.  The
+    2e9 stored entries) fits such a relation on its known entries alone and never forms the dense matrix.  ``Dfmf`` (every
+    fill value) and ``Dfmc`` with 'row_mean' / 'col_mean' (under numpy.ma they leave every entry known) fit it as entries
+    plus rank one -- the filled matrix is a b^T + D with D sparse on the stored pattern, ``filled_entries()`` -- and never
+    form the dense matrix either: shard='runs', no preprocessor, finite stored values, at least one entry not stored,
+    ranks <= 1024, sparse enough (see ``sparse_relations`` of ``Dfmf``).  Every other use -- ``DfmfTransform``, a
+    preprocessor, stored NaN / inf, the other shard modes, larger ranks, small graphs under the default rule -- expands it
+    on the host to that MaskedArray and runs unchanged.  The
     column initialisers read their statistics from the entries; with fill_value='mean' the mean is summed over the
     entries, not in NumPy's order over the dense matrix, so `random_c` may rank two near-equal columns the other way.
     """
@@ -209,6 +213,44 @@ class Relation(object):
             raise ValueError("known entries are filled with 'mean' or a number, not %r" % (self.fill_value,))
         vals[~np.isfinite(vals)] = fill
         return KnownEntries(csr.indptr, csr.indices, vals, csr.shape, fill=fill)
+
+    def filled_entries(self):
+        """An ``unstored='unknown'`` relation after its fill as entries plus rank one (``_engine.KnownEntries`` with
+        ``unstored='zero'`` and fill vectors): the canonical CSR of the stored entries as ``known_entries()`` builds it
+        (duplicates summed, columns sorted, stored zeros kept) and the vectors a, b whose product a_r * b_c is what
+        ``filled()`` writes into every entry not stored -- a number f: a = f, b = 1; 'mean': a = m, b = 1; 'row_mean':
+        a = the row means of the stored values (a row without entries: m), b = 1; 'col_mean': a = 1, b = the column
+        means (a column without entries: m); m = data.sum() / nnz.  Never a ``toarray()``: what ``Dfmf`` (and ``Dfmc`` for
+        'row_mean' / 'col_mean') fits without the dense matrix.  For finite stored values (``filled_entries_apply``
+        expands everything else): the means are sums over the entries in list order."""
+        from .._engine import KnownEntries
+        import scipy.sparse
+        csr = scipy.sparse.csr_matrix(self.data, dtype=np.float64, copy=True)
+        csr.sum_duplicates()
+        csr.sort_indices()
+        n_r, n_c = csr.shape
+        vals, nnz = csr.data, csr.indices.size
+        with np.errstate(invalid='ignore', divide='ignore'):
+            m = float(np.true_divide(vals.sum(), nnz))
+        a, b = np.ones(n_r), np.ones(n_c)
+        if isinstance(self.fill_value, Number):
+            a[:] = float(self.fill_value)
+        elif self.fill_value == 'mean':
+            a[:] = m
+        elif self.fill_value in ('row_mean', 'col_mean'):
+            by_row = self.fill_value == 'row_mean'
+            line = np.repeat(np.arange(n_r), np.diff(csr.indptr)) if by_row else csr.indices
+            n_line = n_r if by_row else n_c
+            total = np.bincount(line, weights=vals, minlength=n_line)
+            count = np.bincount(line, minlength=n_line)
+            mean = np.where(count > 0, total / np.maximum(count, 1), m)
+            if by_row:
+                a = mean
+            else:
+                b = mean
+        else:
+            raise KeyError(self.fill_value)
+        return KnownEntries(csr.indptr, csr.indices, vals, csr.shape, unstored='zero', row_fill=a, col_fill=b)
 
     def is_zero_unstored(self):
         """True for a scipy.sparse relation whose unstored entries are zero (``unstored='zero'``, the default)."""
