@@ -591,7 +591,9 @@ static void plan_layout(skf_plan* p) {
             add_slot(p, t.Bn_tot, (size_t)t.c * t.c * 8);
         }
     }
+    // slot 0 of the error partials collects the trace term; an error pass over lists writes one partial per wave behind it
     size_t sq_elems = 1;
+    auto want_partials = [&](int64_t n_out, int parts) { sq_elems = std::max(sq_elems, (size_t)(1 + srp_partials(n_out, parts))); };
     if (p->variant != SKF_TRANSFORM) {
         // the per-type sums of B+ / B- form one range: one memset per iteration clears them all
         p->btot_off = p->ws_bytes;
@@ -643,8 +645,7 @@ static void plan_layout(skf_plan* p) {
             want_part(k_wide, tj.c, tj.c, tj.n);
             want_part(k_mixed, tp.n, tt.c, tp.c);                           // T = G_p S'
             want_part(k_mixed, tt.n, tp.c, tt.c);                           // H = G_t S / G_t S^T
-            const size_t waves = ((size_t)tt.n + 3) / 4 + 8;                // error partials: one per wave of the pass
-            if (waves * 4 + 64 > sq_elems) sq_elems = waves * 4 + 64;
+            want_partials(tt.n, 1);                                         // fold_err_pass
             continue;
         }
         if (nr > 0 && !r.kn) add_slot(p, r.H, (size_t)nr * tj.c * es);
@@ -685,8 +686,7 @@ static void plan_layout(skf_plan* p) {
             want_part(k_wide, tj.c, tj.c, tj.n);                            // G_j^T G_j'
             want_part(k_mixed, tj.n, ti.c, tj.c);                           // T = G_j S^T ; Q += G_j (S^T Gram_i)
             want_part(k_mixed, nr, ti.c, ti.c);                             // A += G_i (S Gram_j S^T)
-            const size_t waves = (size_t)r.kn_pr * ((size_t)tj.n + 32) + 64;   // error partials: one per wave of the column pass
-            if (waves > sq_elems) sq_elems = waves;
+            want_partials(tj.n, r.kn_pr);                                   // the error pass walks the column lists
             continue;
         }
         if (r.sp0) {
@@ -714,8 +714,7 @@ static void plan_layout(skf_plan* p) {
                 add_slot(p, r.FpartQ, (size_t)cdiv(nr, COLSUM_ROWS) * ti.c * 8);
                 add_slot(p, r.Frow, (size_t)nr * 8);
             }
-            const size_t waves = (size_t)r.kn_pc * ((size_t)nr + 32) + 64;  // error partials: one per wave of the row pass
-            if (waves > sq_elems) sq_elems = waves;
+            want_partials(nr, r.kn_pc);                                     // the error pass walks the row lists
             continue;
         }
         if (r.mask && !p->bf16) add_slot(p, r.Rw, (size_t)nr * tj.n * es);
@@ -1373,6 +1372,12 @@ int skf_relation_sqerr(skf_plan* p, int32_t rel, double* out, void* stream) {
                                (int64_t)ci * cj, scale, acc, first ? 0 : 1);
             check_launch("dot_small");
         };
+        // the ending of the list forms: an error pass has written `waves` partials behind slot 0 (capacity checked before it
+        // launched); out = slot 0 + all of them
+        auto list_total = [&](int waves) {
+            hipLaunchKernelGGL((sum_partials_kernel<double>), dim3(1), dim3(256), 0, st, (const double*)acc, waves + 1, out);
+            check_launch("sum_partials");
+        };
         auto gram_of = [&](const void* A, const void* B, void* C, int c, int64_t n) {                      // C = A^T B (c x c)
             GemmArgs h = gemm_args(A, 1, c, B, c, 1, C, c, c, c, (int)n, EPI_STORE, 0);
             wide_gemm(p, h, st);
@@ -1386,9 +1391,7 @@ int skf_relation_sqerr(skf_plan* p, int32_t rel, double* out, void* stream) {
             GemmArgs h = r.row == p->target ? gemm_args(ti.G.ptr, ci, 1, r.S.ptr, cj, 1, r.H.ptr, cj, (int)ti.n, cj, ci, EPI_STORE, 0)
                                             : gemm_args(tj.G.ptr, cj, 1, r.S.ptr, 1, cj, r.H.ptr, ci, nj, ci, cj, EPI_STORE, 0);
             mixed_gemm(p, h, st);
-            const int waves = fold_err_pass(p, r, st, 1);
-            hipLaunchKernelGGL((sum_partials_kernel<double>), dim3(1), dim3(256), 0, st, (const double*)p->sqpart.ptr, waves + 1, out);
-            check_launch("sum_partials");
+            list_total(fold_err_pass(p, r, st, 1));
             return;
         }
         if (r.sp0) {
@@ -1406,9 +1409,7 @@ int skf_relation_sqerr(skf_plan* p, int32_t rel, double* out, void* stream) {
             GemmArgs h = gemm_args(Gi_b, ci, 1, r.S.ptr, cj, 1, r.H.ptr, cj, ni, cj, ci, EPI_STORE, 0);           // H = G_i S
             mixed_gemm(p, h, st);
             if (r.fill) fill_err_terms(p, r, st);                     // the rank-one terms into slot 0, beside the trace term
-            const int waves = sparse_pass(p, r, false, true, nullptr, st, 1);
-            hipLaunchKernelGGL((sum_partials_kernel<double>), dim3(1), dim3(256), 0, st, (const double*)p->sqpart.ptr, waves + 1, out);
-            check_launch("sum_partials");
+            list_total(sparse_pass(p, r, false, true, nullptr, st, 1));
             return;
         }
         if (r.kn) {
@@ -1433,10 +1434,7 @@ int skf_relation_sqerr(skf_plan* p, int32_t rel, double* out, void* stream) {
             GemmArgs g2 = gemm_args(tj.G.ptr, cj, 1, r.S.ptr, 1, cj, r.Tm.ptr, ci, nj, ci, cj, EPI_STORE, 0);  // T = G_j S^T
             mixed_gemm(p, g2, st);
             if (p->bf16) launch_to_bf16<float>((uint16_t*)r.FiB.ptr, r.kn_ldf, (const float*)r.Tm.ptr, (int64_t)ci, tj.n, ci, false, st);
-            const int waves = known_pass(p, r, true, SRP_ERR, st, 1);       // the pass writes its partials behind slot 0
-                                                                            // (capacity checked before it launches)
-            hipLaunchKernelGGL((sum_partials_kernel<double>), dim3(1), dim3(256), 0, st, (const double*)p->sqpart.ptr, waves + 1, out);
-            check_launch("sum_partials");
+            list_total(known_pass(p, r, true, SRP_ERR, st, 1));
             return;
         }
         GemmArgs g = gemm_args(rows_of(p, ti.G, ti, r.r0), ci, 1, r.S.ptr, cj, 1, r.H.ptr, cj, ni, cj, ci, EPI_STORE, 0);
@@ -1481,13 +1479,8 @@ int skf_get_contraction(const skf_plan* p, int32_t rel, int32_t which, void* dst
         const int64_t rows = which == 1 ? tj.n : r.nr, cols = which == 0 ? tj.c : ti.c;
         if (p->small_fused && which == 1 && r.Q.ptr) {       // the fused small-graph schedule keeps Q as shares: sum them first
             const int64_t total = rows * cols;
-            if (p->f64)
-                hipLaunchKernelGGL((sum_parts_kernel<double>), dim3(elem_grid(total)), dim3(256), 0, as_stream(stream), (double*)r.Q.ptr,
-                                   (const double*)r.SmQ.ptr, total, r.sm_qparts, total);
-            else
-                hipLaunchKernelGGL((sum_parts_kernel<float>), dim3(elem_grid(total)), dim3(256), 0, as_stream(stream), (float*)r.Q.ptr,
-                                   (const float*)r.SmQ.ptr, total, r.sm_qparts, total);
-            check_launch("sum_parts");
+            if (p->f64) launch_sum_parts<double>(r.Q.ptr, r.SmQ.ptr, total, r.sm_qparts, as_stream(stream));
+            else launch_sum_parts<float>(r.Q.ptr, r.SmQ.ptr, total, r.sm_qparts, as_stream(stream));
         }
         if (!src.ptr || rows <= 0) SKF_FAIL(SKF_E_STATE, "relation %d keeps no %s here", rel, which == 0 ? "P" : "Q");
         if (ld < cols) SKF_FAIL(SKF_E_INVALID, "ld too small");

@@ -46,6 +46,16 @@ struct SrpArgs {
     uint32_t zero_off;          // srp_bf16_v6_kernel: byte offset of an all-zero row behind Fi (0 = none: srp_bf16_kernel runs)
 };
 
+// Workgroups of a pass over n_out outer objects whose lists are cut into `parts` parts (1, 2, 4 or 8): 4 outer objects per
+// workgroup (one per wave), workgroups in groups of 8, 8 / parts of a group per part.  The ONE host-side place that knows
+// this mapping -- the launch, the capacity check of an error pass and the sizing of its partials all ask here; srp_segment
+// below is the device-side counterpart.  An SRP_ERR pass writes one f64 partial per wave.
+constexpr int64_t srp_grid(int64_t n_out, int parts) {
+    const int64_t per = 8 / parts;
+    return ((n_out + 3) / 4 + per - 1) / per * 8;
+}
+constexpr int64_t srp_partials(int64_t n_out, int parts) { return srp_grid(n_out, parts) * 4; }
+
 template <typename TG> struct GatherT;
 template <> struct GatherT<uint16_t> {          // bf16 bit patterns
     typedef float acc;
@@ -60,7 +70,8 @@ template <> struct GatherT<double> {
     static __device__ __forceinline__ double get(double v) { return v; }
 };
 
-// workgroup -> (part, outer object of wave 0): blocks b, b + 8, ... share an XCD; part = (b % 8) % parts
+// workgroup -> (part, outer object of wave 0): blocks b, b + 8, ... share an XCD; part = (b % 8) % parts.  The device-side
+// counterpart of srp_grid above: the grid that function returns is the one this mapping covers n_out objects with.
 __device__ __forceinline__ void srp_segment(int parts, int& part, int64_t& first) {
     const int xcd = blockIdx.x & 7;
     const int lg = parts >= 8 ? 3 : parts >= 4 ? 2 : parts >= 2 ? 1 : 0;      // parts is 1, 2, 4 or 8

@@ -366,51 +366,22 @@ static hipEvent_t next_event(skf_plan* p) {
 
 // one of the two contractions that stream a relation matrix: P = R G_j or Q = R^T G_i
 static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void* dst, hipStream_t st, int sq_first = 0);
+static void ones_pass(skf_plan* p, const RelState& r, bool is_q, void* dst, int64_t ld_out, int64_t n_out, int w, hipStream_t st);
 static void relation_gemm(skf_plan* p, GemmArgs g, hipStream_t st, const RelState* r = nullptr, bool is_q = false) {
     if (r && r->sp0) {             // the stored entries as valued lists (every engine): no matrix to stream
         if (g.ldc != g.N) SKF_FAIL(SKF_E_STATE, "SKF_REL_SPARSE_CSR relation: strided contraction output");
         sparse_pass(p, *r, is_q, false, g.C, st);
         return;
     }
+    if (r && p->bf16 && r->sparse && r->sp_gather) {       // the ones as lists over the bf16 rows of the factor
+        ones_pass(p, *r, is_q, g.C, g.ldc, g.M, g.N, st);
+        return;
+    }
     if (p->profiling) SKF_HIP(hipEventRecord(next_event(p), st));
     if (p->bf16) {
         const TypeState& ti = p->types[r->row];
         const TypeState& tj = p->types[r->col];
-        if (r->sparse && r->sp_gather) {       // the ones as lists over the bf16 rows of the factor, every entry counting 1
-            const TypeState& tin = is_q ? ti : tj;           // the gathered factor: Q = R^T G_i sums rows of G_i, P = R G_j rows of G_j
-            const int parts = is_q ? r->sp_pr : r->sp_pc;
-            const int64_t in0 = is_q ? r->r0 : 0, n_in = tin.n - in0;
-            SrpArgs<uint16_t, float> a;
-            memset(&a, 0, sizeof a);
-            a.ptr = (const int64_t*)(parts > 1 ? (is_q ? r->SpCpP.ptr : r->SpRpP.ptr) : (is_q ? r->SpCp.ptr : r->SpRp.ptr));
-            a.idx = (const int*)(is_q ? r->SpRi.ptr : r->SpCi.ptr);
-            a.Fi = (const uint16_t*)tin.Grow.ptr + in0 * tin.ldrow;
-            a.ldi = tin.ldrow; a.ldo = tin.ldrow;
-            a.n_out = g.M; a.w = g.N; a.parts = parts; a.mode = SRP_ONES;
-            a.ld_out = parts > 1 ? g.N : g.ldc;
-            a.part_stride = (int64_t)g.M * g.N;
-            a.out = parts > 1 ? (float*)p->sp_part.ptr : (float*)g.C;
-            a.zero_off = (uint32_t)(n_in * tin.ldrow * 2);
-            if (((int64_t)(n_in + 1) * tin.ldrow * 2) >= (int64_t)0xffffffffLL || tin.ldrow != g.N)
-                SKF_FAIL(SKF_E_STATE, "sparse 0/1 relation: the gathered factor does not fit the list kernel");
-            const int per = 8 / parts;
-            const int64_t wgs = ((int64_t)g.M + 3) / 4;
-            const int grid = (int)((wgs + per - 1) / per * 8);
-            if (g.N == 64) hipLaunchKernelGGL((srp_bf16_v6_kernel<1, SRP_ONES, 2>), dim3(grid), dim3(256), 0, st, a);
-            else if (g.N == 128) hipLaunchKernelGGL((srp_bf16_v6_kernel<1, SRP_ONES, 4>), dim3(grid), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((srp_bf16_v6_kernel<2, SRP_ONES, 4>), dim3(grid), dim3(256), 0, st, a);
-            check_launch("sparse 0/1 relation (lists)");
-            if (parts > 1) {
-                if (g.ldc == g.N) {
-                    const int64_t total = (int64_t)g.M * g.N;
-                    hipLaunchKernelGGL((sum_parts_kernel<float>), dim3(elem_grid(total)), dim3(256), 0, st, (float*)g.C,
-                                       (const float*)p->sp_part.ptr, total, parts, total);
-                    check_launch("sum_parts");
-                } else {
-                    SKF_FAIL(SKF_E_STATE, "sparse 0/1 relation: strided output with parted lists");
-                }
-            }
-        } else if (r->sparse) {        // a handful of ones per row / column: gather the factor's f32 rows (binary_spmm_kernel)
+        if (r->sparse) {               // a handful of ones per row / column: gather the factor's f32 rows (binary_spmm_kernel)
             const int wgrid = (int)(((int64_t)g.M + 3) / 4 < 4096 ? ((int64_t)g.M + 3) / 4 : 4096);
             hipLaunchKernelGGL(binary_spmm_kernel, dim3(wgrid), dim3(256), 0, st,
                                (const int64_t*)(is_q ? r->SpCp.ptr : r->SpRp.ptr), (const int*)(is_q ? r->SpRi.ptr : r->SpCi.ptr),

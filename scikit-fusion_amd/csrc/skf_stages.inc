@@ -3,17 +3,57 @@
 // ------------------------------------------------------------------------------------------
 // DFMC on the known entries only (skf_known.h): launches of the list passes and the c x c / n x c x c algebra around them
 // ------------------------------------------------------------------------------------------
+// dst = part 0 + part 1 + ... of `total` elements each (sum_parts_kernel)
+template <typename T>
+static void launch_sum_parts(void* dst, const void* parts, int64_t total, int nparts, hipStream_t st) {
+    hipLaunchKernelGGL((sum_parts_kernel<T>), dim3(elem_grid(total)), dim3(256), 0, st, (T*)dst, (const T*)parts, total, nparts, total);
+    check_launch("sum_parts");
+}
+
+// A pass over entry lists as its call site describes it: plain pointers, typed once in srp_pass below.  Every form the engine
+// walks as lists -- known entries (from a mask or CSR), stored entries with or without a rank-one fill, fold-in lists, 0/1
+// relations over bf16 rows -- is one of these.
+struct SrpPass {
+    const void* ptr;            // segment table (int64, [n_out * parts + 1]) and inner index (int) of every entry
+    const void* idx;
+    const void* rvals;          // value and residual lists in the list type (see bf16_rows), or none
+    void* evals;
+    const void* Fi;             // gathered matrix: n_in rows of leading dimension ldi
+    int64_t ldi, n_in;
+    const void* Fo;             // vectors of the outer objects (leading dimension ldo), or none
+    int64_t ldo;
+    bool bf16_rows;             // Fi / Fo are bf16 rows with an all-zero row behind row n_in of Fi, lists and sums f32;
+                                // otherwise everything is of the plan's master type
+    bool need_v6;               // bf16_rows: srp_bf16_kernel is no fallback when the zero row is out of the v6 kernel's reach
+    void* dst;                  // [n_out][ld_out], the result (SRP_ERR: none)
+    void* part;                 // [parts][n_out][w], the outputs of the parts (parts > 1)
+    int64_t n_out, ld_out;
+    int parts, w, mode;
+    int sq_first;               // SRP_ERR: the partials go to p->sqpart from this slot on
+    const void* r1_scale;       // rank-one term dst[o] += r1_scale[o] * r1_vec, added where the parts are summed, or none
+    const double* r1_vec;
+    int launches;               // profiling: counted launches (0: the pass is not profiled), with the caller's flop and byte
+    double flops, bytes;        // formulas; prof_open: the caller recorded the opening event ahead of a step of its own
+    bool prof_open;
+};
+
+// the kernel of a pass: 16-byte chunks where width, leading dimensions and bases allow, srp_any_kernel otherwise
 template <typename TG, typename TM>
-static int launch_srp(const SrpArgs<TG, TM>& a, hipStream_t st, bool generic) {
-    const int per = 8 / a.parts;
-    const int64_t wgs = (a.n_out + 3) / 4;
-    const int grid = (int)((wgs + per - 1) / per * 8);
+static void launch_srp(const SrpArgs<TG, TM>& a, hipStream_t st) {
+    const int grid = (int)srp_grid(a.n_out, a.parts);
     constexpr int VE = 16 / (int)sizeof(TG);
     auto al = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
     const bool vec = a.w % VE == 0 && a.ldi % VE == 0 && al(a.Fi) && (a.mode == SRP_APPLY || (a.ldo % VE == 0 && al(a.Fo)));
-    const int gl = (vec && !generic) ? a.w / VE : 0;
+    const int gl = vec ? a.w / VE : 0;
     bool done = false;
     if constexpr (std::is_same<TG, uint16_t>::value) {
+        if (a.mode == SRP_ONES) {          // 0/1 relations as lists: w = 64 (8-byte chunks), 128 or 256
+            if (a.w == 64) hipLaunchKernelGGL((srp_bf16_v6_kernel<1, SRP_ONES, 2>), dim3(grid), dim3(256), 0, st, a);
+            else if (a.w == 128) hipLaunchKernelGGL((srp_bf16_v6_kernel<1, SRP_ONES, 4>), dim3(grid), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((srp_bf16_v6_kernel<2, SRP_ONES, 4>), dim3(grid), dim3(256), 0, st, a);
+            check_launch("sparse 0/1 relation (lists)");
+            return;
+        }
         // srp_bf16_v6_kernel: a row of 16 lanes per gathered vector, w = 128 (both modes) or 256 (SRP_APPLY: measured, the
         // residual pass at w = 256 is faster with two rows per vector), 32-bit byte offsets, an all-zero row behind Fi
         if (a.zero_off != 0 && a.mode != SRP_ERR && (gl == 16 || (gl == 32 && a.mode == SRP_APPLY))) {
@@ -21,7 +61,7 @@ static int launch_srp(const SrpArgs<TG, TM>& a, hipStream_t st, bool generic) {
             else if (gl == 16) hipLaunchKernelGGL((srp_bf16_v6_kernel<1, SRP_APPLY>), dim3(grid), dim3(256), 0, st, a);
             else hipLaunchKernelGGL((srp_bf16_v6_kernel<2, SRP_APPLY>), dim3(grid), dim3(256), 0, st, a);
             check_launch("known-entry pass (v6)");
-            return grid * 4;
+            return;
         }
         done = true;
 #define SKF_SRP_BF16(GL_)                                                                                                   \
@@ -44,7 +84,62 @@ static int launch_srp(const SrpArgs<TG, TM>& a, hipStream_t st, bool generic) {
         else hipLaunchKernelGGL((srp_any_kernel<TG, TM>), dim3(grid), dim3(256), 0, st, a);
     }
     check_launch("known-entry pass");
-    return grid * 4;                 // waves = error partials of an SRP_ERR pass
+}
+
+// the typed half of srp_pass: SrpArgs from the description, the kernel, then the tail that sums the parts
+template <typename TG, typename TM>
+static void srp_pass_typed(skf_plan* p, const SrpPass& d, uint32_t zero_off, hipStream_t st) {
+    const bool parted = d.parts > 1 && d.mode != SRP_ERR;
+    SrpArgs<TG, TM> a;
+    memset(&a, 0, sizeof a);
+    a.ptr = (const int64_t*)d.ptr; a.idx = (const int*)d.idx;
+    a.rvals = (const TM*)d.rvals; a.evals = (TM*)d.evals;
+    a.Fo = (const TG*)d.Fo; a.ldo = d.ldo; a.Fi = (const TG*)d.Fi; a.ldi = d.ldi;
+    a.out = (TM*)(parted ? d.part : d.dst);
+    a.ld_out = parted ? d.w : d.ld_out; a.part_stride = d.n_out * d.w; a.n_out = d.n_out;
+    a.w = d.w; a.parts = d.parts; a.mode = d.mode;
+    a.sq = (double*)p->sqpart.ptr + d.sq_first;
+    a.zero_off = zero_off;
+    launch_srp(a, st);
+    if (d.mode == SRP_ERR) return;
+    const int64_t total = d.n_out * d.w;
+    if (d.r1_vec) {         // (one part: one pass over the output, in place)
+        hipLaunchKernelGGL((sum_parts_rank1_kernel<TM>), dim3(elem_grid(total)), dim3(256), 0, st, (TM*)d.dst, (const TM*)a.out, total,
+                           d.parts, total, d.w, (const TM*)d.r1_scale, d.r1_vec);
+        check_launch("sum_parts_rank1");
+    } else if (parted) {
+        launch_sum_parts<TM>(d.dst, d.part, total, d.parts, st);
+    }
+}
+
+// THE launcher of every list pass: capacity check of an error pass, the all-zero row of the v6 kernel, the one split over the
+// gathered / list types, kernel and tail (srp_pass_typed), the profiling bracket.  Returns the waves of the pass = the error
+// partials an SRP_ERR pass has written from slot d.sq_first of p->sqpart on.
+static int srp_pass(skf_plan* p, const SrpPass& d, hipStream_t st) {
+    const int64_t waves = srp_partials(d.n_out, d.parts);
+    if (d.mode == SRP_ERR && (size_t)(waves + d.sq_first) > p->sq_elems)
+        SKF_FAIL(SKF_E_STATE, "residual partials: %lld > %zu slots", (long long)(waves + d.sq_first), p->sq_elems);
+    if (d.parts > 1 && d.mode != SRP_ERR && d.ld_out != d.w) SKF_FAIL(SKF_E_STATE, "list pass: strided output with parted lists");
+    // slots past the end of a list point at the all-zero row behind the n_in gathered rows; byte offsets into the matrix are
+    // 32 bits wide in the v6 kernel (0 = no such row within reach: srp_bf16_kernel, which needs none, or no pass at all)
+    uint32_t zero_off = 0;
+    if (d.bf16_rows) {
+        const int64_t zoff = d.n_in * d.ldi * 2;
+        if (zoff + d.ldi * 2 < (int64_t)0xffffffffLL) zero_off = (uint32_t)zoff;
+        else if (d.need_v6) SKF_FAIL(SKF_E_STATE, "list pass: the gathered factor does not fit the list kernel");
+    }
+    const bool prof = p->profiling && d.launches > 0;
+    if (prof && !d.prof_open) SKF_HIP(hipEventRecord(next_event(p), st));
+    if (d.bf16_rows) srp_pass_typed<uint16_t, float>(p, d, zero_off, st);
+    else if (p->f64) srp_pass_typed<double, double>(p, d, zero_off, st);
+    else srp_pass_typed<float, float>(p, d, zero_off, st);
+    if (prof) {
+        SKF_HIP(hipEventRecord(next_event(p), st));
+        p->prof_flops += d.flops;
+        p->prof_bytes += d.bytes;
+        p->prof_launches += d.launches;
+    }
+    return (int)waves;
 }
 
 // One pass over the known entries of relation r: by_col == false walks the row lists (outer = rows, gathers the rows of
@@ -54,78 +149,29 @@ static int known_pass(skf_plan* p, RelState& r, bool by_col, int mode, hipStream
     TypeState& ti = p->types[r.row];
     TypeState& tj = p->types[r.col];
     const int ci = ti.c;
-    const int64_t n_out = by_col ? tj.n : r.nr;
-    const int parts = by_col ? r.kn_pr : r.kn_pc;
-    if (mode == SRP_ERR) {          // one error partial per wave, written from slot `sq_first` of p->sqpart on: room for all of them?
-        const int64_t need = ((n_out + 3) / 4 + (8 / parts) - 1) / (8 / parts) * 8 * 4 + sq_first;
-        if ((size_t)need > p->sq_elems) SKF_FAIL(SKF_E_STATE, "residual partials: %lld > %zu slots", (long long)need, p->sq_elems);
-    }
-    void* final_out = by_col ? r.Q.ptr : r.A.ptr;
-    void* out = parts > 1 ? (by_col ? r.Qpart.ptr : r.Apart.ptr) : final_out;
     // vectors of the row objects of the block (bf16: kept in step with G^T); rows [r0, r0 + nr) of the type under row ownership
     const void* Gi = p->bf16 ? (const void*)((const char*)ti.Grow.ptr + (size_t)r.r0 * ti.ldrow * 2)
                              : (const void*)((const char*)ti.G.ptr + (size_t)r.r0 * ci * p->esz);
     const void* Tj = p->bf16 ? r.FiB.ptr : r.Tm.ptr;          // vectors of the column objects
     const int64_t ldv = p->bf16 ? r.kn_ldf : ci;
-    if (p->profiling) SKF_HIP(hipEventRecord(next_event(p), st));
-    int waves = 0;
-    auto fill = [&](auto& a) {
-        memset(&a, 0, sizeof a);
-        a.ptr = (const int64_t*)(by_col ? r.KcPtr.ptr : r.KrPtr.ptr);
-        a.idx = (const int*)(by_col ? r.KcIdx.ptr : r.KrIdx.ptr);
-        a.ldo = ldv; a.ldi = ldv; a.ld_out = ci; a.part_stride = n_out * ci; a.n_out = n_out;
-        a.w = ci; a.parts = parts; a.mode = mode;
-        a.sq = (double*)p->sqpart.ptr + sq_first;
-    };
-    if (p->f64) {
-        SrpArgs<double, double> a;
-        fill(a);
-        a.rvals = (const double*)(by_col ? r.KcVal.ptr : r.KrVal.ptr);
-        a.evals = by_col ? (double*)r.KcE.ptr : nullptr;
-        a.Fo = (const double*)(by_col ? Tj : Gi); a.Fi = (const double*)(by_col ? Gi : Tj);
-        a.out = (double*)out;
-        waves = launch_srp(a, st, false);
-    } else if (p->bf16) {
-        SrpArgs<uint16_t, float> a;
-        fill(a);
-        a.rvals = (const float*)(by_col ? r.KcVal.ptr : r.KrVal.ptr);
-        a.evals = by_col ? (float*)r.KcE.ptr : nullptr;
-        a.Fo = (const uint16_t*)(by_col ? Tj : Gi); a.Fi = (const uint16_t*)(by_col ? Gi : Tj);
-        a.out = (float*)out;
-        // the all-zero row behind the gathered matrix (TypeState::Grow / FiB hold one row more than the factor): slots past the end of
-        // a list point there.  Byte offsets into the matrix are 32 bits wide in the v6 kernel.
-        const int64_t n_in = by_col ? ti.n - r.r0 : tj.n;          // (the zero row of Grow sits behind ALL rows of the type)
-        const int64_t zoff = n_in * ldv * 2;
-        a.zero_off = (zoff + ldv * 2 < (int64_t)0xffffffffLL) ? (uint32_t)zoff : 0u;
-        waves = launch_srp(a, st, false);
-    } else {
-        SrpArgs<float, float> a;
-        fill(a);
-        a.rvals = (const float*)(by_col ? r.KcVal.ptr : r.KrVal.ptr);
-        a.evals = by_col ? (float*)r.KcE.ptr : nullptr;
-        a.Fo = (const float*)(by_col ? Tj : Gi); a.Fi = (const float*)(by_col ? Gi : Tj);
-        a.out = (float*)out;
-        waves = launch_srp(a, st, false);
-    }
-    if (parts > 1 && mode != SRP_ERR) {
-        const int64_t total = n_out * ci;
-        if (p->f64)
-            hipLaunchKernelGGL((sum_parts_kernel<double>), dim3(elem_grid(total)), dim3(256), 0, st, (double*)final_out,
-                               (const double*)out, total, parts, total);
-        else
-            hipLaunchKernelGGL((sum_parts_kernel<float>), dim3(elem_grid(total)), dim3(256), 0, st, (float*)final_out,
-                               (const float*)out, total, parts, total);
-        check_launch("sum_parts");
-    }
-    if (p->profiling) {
-        SKF_HIP(hipEventRecord(next_event(p), st));
-        const size_t gsz = p->bf16 ? 2 : p->esz;
-        p->prof_flops += (mode == SRP_APPLY ? 2.0 : 4.0) * (double)r.kn_nnz * ci;
-        p->prof_bytes += (double)r.kn_nnz * (4.0 + 2.0 * p->esz);          // index + value (+ residual) lists
-        (void)gsz;
-        p->prof_launches += 1;
-    }
-    return waves;
+    SrpPass d = {};
+    d.ptr = by_col ? r.KcPtr.ptr : r.KrPtr.ptr;
+    d.idx = by_col ? r.KcIdx.ptr : r.KrIdx.ptr;
+    d.rvals = by_col ? r.KcVal.ptr : r.KrVal.ptr;
+    d.evals = by_col ? r.KcE.ptr : nullptr;
+    d.Fi = by_col ? Gi : Tj; d.ldi = ldv;
+    d.n_in = by_col ? ti.n - r.r0 : tj.n;          // (the zero row of Grow sits behind ALL rows of the type, FiB's behind T)
+    d.Fo = by_col ? Tj : Gi; d.ldo = ldv;
+    d.bf16_rows = p->bf16;
+    d.dst = by_col ? r.Q.ptr : r.A.ptr;
+    d.part = by_col ? r.Qpart.ptr : r.Apart.ptr;
+    d.n_out = by_col ? tj.n : r.nr; d.ld_out = ci;
+    d.parts = by_col ? r.kn_pr : r.kn_pc; d.w = ci; d.mode = mode;
+    d.sq_first = sq_first;
+    d.launches = 1;
+    d.flops = (mode == SRP_APPLY ? 2.0 : 4.0) * (double)r.kn_nnz * ci;
+    d.bytes = (double)r.kn_nnz * (4.0 + 2.0 * p->esz);          // index + value (+ residual) lists
+    return srp_pass(p, d, st);
 }
 
 // t = G^T w for SKF_REL_FILL_RANK1 (colsum_partial_kernel / colsum_final_kernel): `part` holds cdiv(n, COLSUM_ROWS) x c
@@ -182,91 +228,70 @@ static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void
     // Q gathers rows of G_i through column lists whose indices are LOCAL rows: the gathered base is the first row of the
     // block (row ownership: the owned rows; a whole relation: row 0)
     const int64_t in0 = is_q ? r.r0 : 0;
-    if (err) {
-        const int64_t need = ((n_out + 3) / 4 + (8 / parts) - 1) / (8 / parts) * 8 * 4 + sq_first;
-        if ((size_t)need > p->sq_elems) SKF_FAIL(SKF_E_STATE, "residual partials: %lld > %zu slots", (long long)need, p->sq_elems);
-    }
-    void* out = (parts > 1 && !err) ? (is_q ? r.Qpart.ptr : r.Apart.ptr) : dst;
-    if (p->profiling) SKF_HIP(hipEventRecord(next_event(p), st));
-    int waves = 0;
-    auto fill = [&](auto& a, auto* vals, auto* Fi, int64_t ldi, auto* Fo, int64_t ldo, auto* o) {
-        memset(&a, 0, sizeof a);
-        a.ptr = (const int64_t*)(is_q ? r.KcPtr.ptr : r.KrPtr.ptr);
-        a.idx = (const int*)(is_q ? r.KcIdx.ptr : r.KrIdx.ptr);
-        a.rvals = vals; a.evals = vals;                      // (never written: SRP_APPLY / SRP_ERR only read the residual list)
-        a.Fi = Fi; a.ldi = ldi; a.Fo = Fo; a.ldo = ldo; a.out = o;
-        a.ld_out = w; a.part_stride = n_out * w; a.n_out = n_out;
-        a.w = w; a.parts = parts; a.mode = err ? SRP_ERR : SRP_APPLY;
-        a.sq = (double*)p->sqpart.ptr + sq_first;
-    };
-    void* vals = is_q ? r.KcVal.ptr : r.KrVal.ptr;
+    const bool bf16_rows = p->bf16 && !err;
+    SrpPass d = {};
+    d.ptr = is_q ? r.KcPtr.ptr : r.KrPtr.ptr;
+    d.idx = is_q ? r.KcIdx.ptr : r.KrIdx.ptr;
+    d.rvals = is_q ? r.KcVal.ptr : r.KrVal.ptr;
+    d.evals = const_cast<void*>(d.rvals);                    // (never written: SRP_APPLY / SRP_ERR only read the residual list)
+    // the all-zero row of the bf16 rows sits behind ALL rows of the type, counted from the gathered base
+    d.Fi = bf16_rows ? (const void*)((const uint16_t*)tin.Grow.ptr + in0 * tin.ldrow) : rows_of(p, tin.G, tin, in0);
+    d.ldi = bf16_rows ? tin.ldrow : w; d.n_in = tin.n - in0;
+    d.Fo = bf16_rows ? nullptr : r.H.ptr; d.ldo = d.ldi;
+    d.bf16_rows = bf16_rows;
+    d.dst = dst;
+    d.part = is_q ? r.Qpart.ptr : r.Apart.ptr;
+    d.n_out = n_out; d.ld_out = w;
+    d.parts = parts; d.w = w; d.mode = err ? SRP_ERR : SRP_APPLY;
+    d.sq_first = sq_first;
+    // what the pass executes and reads: index + value lists, one gathered factor row per entry (include/skfusion_hip.h)
+    d.launches = 1;
+    d.flops = 2.0 * (double)r.kn_nnz * w;
+    d.bytes = (double)r.kn_nnz * (4.0 + (double)p->esz + (double)w * (p->bf16 ? 2.0 : (double)p->esz));
     // SKF_REL_FILL_RANK1: the weighted column sum of the gathered factor -- t = G_j^T b for P, s = G_i^T a for Q -- over the
-    // rows the list pass gathers, before the lists are walked, on this stream; the term is added where the parts are summed
-    const bool rank1 = r.fill && !err;
-    double* tvec = (double*)(is_q ? r.Fs.ptr : r.Ft.ptr);
-    if (rank1) {
+    // rows the list pass gathers, before the lists are walked, on this stream; P[r] += a_r t / Q[c] += b_c s is added where
+    // the parts are summed
+    if (r.fill && !err) {
+        double* tvec = (double*)(is_q ? r.Fs.ptr : r.Ft.ptr);
         double* part = (double*)(is_q ? r.FpartQ.ptr : r.FpartP.ptr);
         const void* wts = is_q ? r.Fa.ptr : r.Fb.ptr;
+        if (p->profiling) SKF_HIP(hipEventRecord(next_event(p), st));
         if (p->f64) launch_colsum((const double*)tin.G.ptr, (int64_t)w, tin.n, w, (const double*)wts, part, tvec, st);
         else if (p->bf16) launch_colsum((const uint16_t*)tin.Grow.ptr, tin.ldrow, tin.n, w, (const float*)wts, part, tvec, st);
         else launch_colsum((const float*)tin.G.ptr, (int64_t)w, tin.n, w, (const float*)wts, part, tvec, st);
+        d.r1_scale = is_q ? r.Fb.ptr : r.Fa.ptr;
+        d.r1_vec = tvec;
+        // the rank-one side (one more counted launch: the column sum with its reduce): 2 n_in w flops for the sum, 2 n_out w
+        // for the term; the gathered factor and its weights once, the scale vector once, and -- lists in one part -- the
+        // output read and written once more
+        d.prof_open = true;
+        d.launches = 2;
+        d.flops += 2.0 * (double)tin.n * w + 2.0 * (double)n_out * w;
+        d.bytes += (double)tin.n * ((double)w * (p->bf16 ? 2.0 : (double)p->esz) + (double)p->esz) + (double)n_out * (double)p->esz +
+                   (parts > 1 ? 0.0 : 2.0 * (double)n_out * w * (double)p->esz);
     }
-    if (p->f64) {
-        SrpArgs<double, double> a;
-        fill(a, (double*)vals, (const double*)rows_of(p, tin.G, tin, in0), (int64_t)w, (const double*)r.H.ptr, (int64_t)w, (double*)out);
-        waves = launch_srp(a, st, false);
-    } else if (p->bf16 && !err) {
-        SrpArgs<uint16_t, float> a;
-        fill(a, (float*)vals, (const uint16_t*)tin.Grow.ptr + in0 * tin.ldrow, tin.ldrow, (const uint16_t*)nullptr, tin.ldrow, (float*)out);
-        // slots past the end of a list point at the all-zero row behind the gathered rows -- behind ALL rows of the type,
-        // counted from the gathered base (32-bit byte offsets in the v6 kernel; 0 = no such row: launch_srp then takes
-        // srp_bf16_kernel, which needs none -- SrpArgs::zero_off)
-        const int64_t zoff = (tin.n - in0) * tin.ldrow * 2;
-        a.zero_off = (zoff + tin.ldrow * 2 < (int64_t)0xffffffffLL) ? (uint32_t)zoff : 0u;
-        waves = launch_srp(a, st, false);
-    } else {
-        SrpArgs<float, float> a;
-        fill(a, (float*)vals, (const float*)rows_of(p, tin.G, tin, in0), (int64_t)w, (const float*)r.H.ptr, (int64_t)w, (float*)out);
-        waves = launch_srp(a, st, false);
-    }
-    if (rank1) {
-        // P[r] += a_r t / Q[c] += b_c s in the launch that sums the parts (one part: one pass over the output, in place)
-        const int64_t total = n_out * w;
-        const void* scale = is_q ? r.Fb.ptr : r.Fa.ptr;
-        if (p->f64)
-            hipLaunchKernelGGL((sum_parts_rank1_kernel<double>), dim3(elem_grid(total)), dim3(256), 0, st, (double*)dst, (const double*)out,
-                               total, parts, total, w, (const double*)scale, (const double*)tvec);
-        else
-            hipLaunchKernelGGL((sum_parts_rank1_kernel<float>), dim3(elem_grid(total)), dim3(256), 0, st, (float*)dst, (const float*)out,
-                               total, parts, total, w, (const float*)scale, (const double*)tvec);
-        check_launch("sum_parts_rank1");
-    } else if (parts > 1 && !err) {
-        const int64_t total = n_out * w;
-        if (p->f64)
-            hipLaunchKernelGGL((sum_parts_kernel<double>), dim3(elem_grid(total)), dim3(256), 0, st, (double*)dst, (const double*)out,
-                               total, parts, total);
-        else
-            hipLaunchKernelGGL((sum_parts_kernel<float>), dim3(elem_grid(total)), dim3(256), 0, st, (float*)dst, (const float*)out,
-                               total, parts, total);
-        check_launch("sum_parts");
-    }
-    if (p->profiling) {
-        SKF_HIP(hipEventRecord(next_event(p), st));
-        // what the pass executes and reads: index + value lists, one gathered factor row per entry (include/skfusion_hip.h)
-        p->prof_flops += 2.0 * (double)r.kn_nnz * w;
-        p->prof_bytes += (double)r.kn_nnz * (4.0 + (double)p->esz + (double)w * (p->bf16 ? 2.0 : (double)p->esz));
-        p->prof_launches += 1;
-        if (rank1) {
-            // the rank-one side (one more counted launch: the column sum with its reduce): 2 n_in w flops for the sum, 2 n_out w
-            // for the term; the gathered factor and its weights once, the scale vector once, and -- lists in one part -- the
-            // output read and written once more
-            p->prof_flops += 2.0 * (double)tin.n * w + 2.0 * (double)n_out * w;
-            p->prof_bytes += (double)tin.n * ((double)w * (p->bf16 ? 2.0 : (double)p->esz) + (double)p->esz) + (double)n_out * (double)p->esz +
-                             (parts > 1 ? 0.0 : 2.0 * (double)n_out * w * (double)p->esz);
-            p->prof_launches += 1;
-        }
-    }
-    return waves;
+    return srp_pass(p, d, st);
+}
+
+// P = R G_j / Q = R^T G_i of a sparse 0/1 relation of SKF_BF16 kept as lists (RelState::sp_gather): the ones as lists over
+// the bf16 rows of the gathered factor, every entry counting 1 (SRP_ONES); dst is n_out x w with leading dimension ld_out
+static void ones_pass(skf_plan* p, const RelState& r, bool is_q, void* dst, int64_t ld_out, int64_t n_out, int w, hipStream_t st) {
+    const TypeState& tin = p->types[is_q ? r.row : r.col];           // Q = R^T G_i sums rows of G_i, P = R G_j rows of G_j
+    const int64_t in0 = is_q ? r.r0 : 0;
+    if (tin.ldrow != w) SKF_FAIL(SKF_E_STATE, "sparse 0/1 relation: the gathered factor does not fit the list kernel");
+    SrpPass d = {};
+    d.parts = is_q ? r.sp_pr : r.sp_pc;
+    d.ptr = d.parts > 1 ? (is_q ? r.SpCpP.ptr : r.SpRpP.ptr) : (is_q ? r.SpCp.ptr : r.SpRp.ptr);
+    d.idx = is_q ? r.SpRi.ptr : r.SpCi.ptr;
+    d.Fi = (const uint16_t*)tin.Grow.ptr + in0 * tin.ldrow; d.ldi = tin.ldrow; d.n_in = tin.n - in0;
+    d.ldo = tin.ldrow;
+    d.bf16_rows = true; d.need_v6 = true;
+    d.dst = dst; d.part = p->sp_part.ptr;
+    d.n_out = n_out; d.ld_out = ld_out; d.w = w; d.mode = SRP_ONES;
+    d.launches = 1;
+    d.flops = 2.0 * (double)r.sp_nnz * (double)w;
+    d.bytes = 4.0 * (double)r.sp_nnz;
+    srp_pass(p, d, st);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -317,28 +342,15 @@ static void fold_prepare(skf_plan* p, RelState& r, hipStream_t st) {
 static int fold_err_pass(skf_plan* p, const RelState& r, hipStream_t st, int sq_first) {
     const bool row_side = r.row == p->target;
     const TypeState& tp = p->types[row_side ? r.col : r.row];          // the partner: its factor rows are gathered
-    const int64_t n_out = p->types[p->target].n;
-    const int w = tp.c;
-    const int64_t need = ((n_out + 3) / 4 + 7) / 8 * 8 * 4 + sq_first;
-    if ((size_t)need > p->sq_elems) SKF_FAIL(SKF_E_STATE, "residual partials: %lld > %zu slots", (long long)need, p->sq_elems);
-    auto fill = [&](auto& a, auto* vals, auto* Fi, auto* Fo) {
-        memset(&a, 0, sizeof a);
-        a.ptr = (const int64_t*)r.KrPtr.ptr;
-        a.idx = (const int*)r.KrIdx.ptr;
-        a.rvals = vals; a.evals = vals;                      // (never written: SRP_ERR only reads the residual list)
-        a.Fi = Fi; a.ldi = w; a.Fo = Fo; a.ldo = w;
-        a.ld_out = w; a.part_stride = n_out * w; a.n_out = n_out;
-        a.w = w; a.parts = 1; a.mode = SRP_ERR;
-        a.sq = (double*)p->sqpart.ptr + sq_first;
-    };
-    if (p->f64) {
-        SrpArgs<double, double> a;
-        fill(a, (double*)r.KrVal.ptr, (const double*)tp.G.ptr, (const double*)r.H.ptr);
-        return launch_srp(a, st, false);
-    }
-    SrpArgs<float, float> a;
-    fill(a, (float*)r.KrVal.ptr, (const float*)tp.G.ptr, (const float*)r.H.ptr);
-    return launch_srp(a, st, false);
+    SrpPass d = {};
+    d.ptr = r.KrPtr.ptr; d.idx = r.KrIdx.ptr;
+    d.rvals = r.KrVal.ptr; d.evals = r.KrVal.ptr;            // (never written: SRP_ERR only reads the residual list)
+    d.Fi = tp.G.ptr; d.ldi = tp.c; d.n_in = tp.n;
+    d.Fo = r.H.ptr; d.ldo = tp.c;
+    d.n_out = p->types[p->target].n; d.ld_out = tp.c;
+    d.parts = 1; d.w = tp.c; d.mode = SRP_ERR;
+    d.sq_first = sq_first;
+    return srp_pass(p, d, st);
 }
 
 // W = G_i^T R_c G_j for the backbone (_dfmc.py:311-314) with R_c = G_i,prev S_prev G_j,prev^T + E_prev:
