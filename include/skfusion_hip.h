@@ -582,6 +582,34 @@ int skf_complete_topk(int32_t dtype, const void* H, int64_t ldh, int64_t m, cons
 int skf_complete_entries(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols,
                          int32_t c, const int32_t* rows, const int32_t* cols, int64_t n, void* out, void* stream);
 
+/* The rank of given (row, column) pairs in X = H Gc^T (H, Gc as for skf_complete_topk) without X: the one number per
+ * held-out pair that Recall@k, MRR, NDCG and AUC need of the array the reference's users rank
+ * (examples/movielens_completion.py:121-126).  For a target (r, j) with s = score(r, j):
+ *     rank(r, j) = #{ j' in [0, n_cols), j' != j, j' not in row r's exclusion list, score(r, j') not NaN,
+ *                     score(r, j') > s  or  (score(r, j') == s and j' < j) }
+ *   -- the 0-based position of j in the total order of skf_complete_topk: higher score first, equal scores by lower column,
+ *   NaN never.  A target with a NaN score gets -1.  A target that is itself in the exclusion list is still ranked: exclusion
+ *   removes competitors only.  score(r, j) is the same chain of matrix instructions as in skf_complete_topk, hence
+ *   P1: if (r, j) is not excluded and rank(r, j) = p < k <= 64, skf_complete_topk on the same inputs returns
+ *     out_idx[r][p] == j and out_val[r][p] with the bits of out_val[e]; if p >= k, j is not in row r's list -- for every
+ *     col_splits of either operator.
+ *   Targets: CSR over the m rows, tgt_indptr[m + 1] (int64, from 0, non-decreasing, tgt_indptr[m] == n_targets),
+ *     tgt_indices (int32 columns, in range, strictly ascending within a row).  Exclusion: as for skf_complete_topk (both
+ *     pointers NULL = none).  Both lists are validated on the device before anything gathers through them; an invalid list
+ *     gives SKF_E_INVALID and leaves out_rank and out_val as they were.
+ *   Output: out_rank[e] (int32) and, unless NULL, out_val[e] = score of target e (dtype), e < n_targets in list order.
+ *   Counts are integers added with integer atomics: the result does not depend on col_splits (0 = the library chooses, at
+ *     most 32) or the launch geometry.  skf_complete_ranks_workspace_bytes sizes the workspace (256-byte aligned): flag
+ *     words and n_targets scores, nothing that grows with m x n_cols.  n_targets == 0 succeeds without a launch.
+ *   dtype SKF_F64 / SKF_F32; 1 <= c <= 1024; m and n_cols < 2^31. */
+int skf_complete_ranks_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int64_t n_targets, int32_t col_splits,
+                                       size_t* bytes);
+int skf_complete_ranks(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols,
+                       int32_t c, const int64_t* tgt_indptr, const int32_t* tgt_indices, int64_t n_targets,
+                       const int64_t* excl_indptr, const int32_t* excl_indices, int32_t* out_rank,
+                       void* out_val /* dtype, may be NULL */, int32_t col_splits /* 0 = choose */, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* K = pinv(A) for symmetric A (n x n): f64 Jacobi eigen-decomposition + the singular-value
  * cut-off of scipy.linalg.pinv (reference _dfmf.py:232, _dfmc.py:307). */
 int skf_pinv_sym_workspace_bytes(int32_t n, size_t* bytes);
@@ -631,8 +659,8 @@ const char* skf_version(void);
  * call the library: descriptors grew between versions (skf_relation_desc.known_bound: 3, skf_options.flags: 4; version 5
  * adds entry points only -- skf_small_graph_limits, skf_comm_info, skf_launch_count; later: skf_fold_lists and the flag
  * SKF_REL_FOLD_CSR; skf_complete_topk_workspace_bytes, skf_complete_topk, skf_complete_entries and SKF_TOPK_MAX;
- * skf_get_constraint_lists and the flag SKF_OPT_THETA_OWNED_ROWS; skf_plan_set_relation_fill and the flag SKF_REL_FILL_RANK1 --
- * the structs are those of version 4). */
+ * skf_get_constraint_lists and the flag SKF_OPT_THETA_OWNED_ROWS; skf_plan_set_relation_fill and the flag SKF_REL_FILL_RANK1;
+ * skf_complete_ranks_workspace_bytes and skf_complete_ranks -- the structs are those of version 4). */
 #define SKF_ABI_VERSION 5
 int skf_abi_version(void);
 

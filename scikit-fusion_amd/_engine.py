@@ -1273,8 +1273,8 @@ def device_reconstruct(G_row_block, S, G_col, dtype='f64', runtime=None):
 
 class DeviceCompleter(object):
     """The consuming side of a completion model without the dense reconstruction: for ``X = G_row S G_col^T`` the ``k`` best
-    columns of every row (``topk``) and the predictions at given pairs (``entries``), both on the device
-    (csrc/skf_complete.h).  The reference forms ``X`` on the host (fusion/base/base.py ``complete``) and its users rank or
+    columns of every row (``topk``), the predictions at given pairs (``entries``) and the position of given pairs in
+    their row's ranking (``ranks``), all on the device (csrc/skf_complete.h).  The reference forms ``X`` on the host (fusion/base/base.py ``complete``) and its users rank or
     index that array (examples/movielens_completion.py:121-126).  ``S`` and ``G_col`` are uploaded ONCE and stay resident
     across blocks (the contract of ``DeviceReconstructor``); per block only ``H = G_row[block] S`` (``skf_gemm``), the
     block's exclusion lists, its outputs and the partial lists of the column splits live in HBM -- never anything of size
@@ -1373,6 +1373,50 @@ class DeviceCompleter(object):
             return mem.to_host(oi, (m, k), np.int32), mem.to_host(ov, (m, k), self.npd).astype(np.float64)
         finally:
             del a, xp, xi
+            self._transient = 0
+
+    def ranks(self, G_row_block, targets, exclude=None, col_splits=0):
+        """``(rank int32 [n], val float64 [n])`` for the ``n`` target pairs of the block, in list order: ``rank`` is the
+        number of admissible columns of the pair's row that come before the pair's column in the order of ``topk`` -- a
+        higher score, or an equal score and a lower column; NaN scores, the column itself and the row's excluded columns
+        are no competitors -- i.e. the pair's 0-based position in that order, and -1 where the pair's own score is NaN;
+        ``val`` is that score.  An excluded pair is still ranked.  ``targets = (indptr, indices)`` and ``exclude =
+        (indptr, indices)``: CSR over the rows of THIS block (columns strictly ascending within a row), validated on the
+        device.  ``col_splits`` 0 lets the library choose; the result does not depend on it.  Only the block's H, its
+        lists and one rank and score per pair live in HBM."""
+        A = self._rows_of(G_row_block)
+        m = A.shape[0]
+        rt, mem = self.rt, self.rt.mem
+        keep = [np.ascontiguousarray(targets[0], dtype=np.int64), np.ascontiguousarray(targets[1], dtype=np.int32)]
+        if keep[0].shape != (m + 1,):
+            raise ValueError('targets: indptr must have one entry per row of the block, plus one')
+        n = int(keep[1].size)
+        if exclude is not None:
+            keep += [np.ascontiguousarray(exclude[0], dtype=np.int64), np.ascontiguousarray(exclude[1], dtype=np.int32)]
+            if keep[2].shape != (m + 1,):
+                raise ValueError('exclude: indptr must have one entry per row of the block, plus one')
+        need = C.c_size_t()
+        rt.call('skf_complete_ranks_workspace_bytes', self.code, m, self.nj, n, int(col_splits), C.byref(need))
+        if n == 0:
+            return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float64)
+        h, a = self._h(A)
+        held = self._transient
+        bufs = self._upload(keep)
+        self._transient += held
+        tp, ti = bufs[0], bufs[1]
+        xp, xi = (bufs[2], bufs[3]) if exclude is not None else (None, None)
+        ws = self._scratch('ws', need.value)
+        orank = self._scratch('rank', n * 4)
+        oval = self._scratch('rank_val', n * self.es)
+        self.peak_bytes = max(self.peak_bytes, self.device_bytes)
+        try:
+            rt.call('skf_complete_ranks', self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, tp.ptr, ti.ptr, n,
+                    xp.ptr if xp else None, xi.ptr if xi else None, orank.ptr, oval.ptr, int(col_splits), ws.ptr, ws.nbytes,
+                    mem.stream)
+            mem.synchronize()
+            return mem.to_host(orank, (n,), np.int32), mem.to_host(oval, (n,), self.npd).astype(np.float64)
+        finally:
+            del a, bufs, tp, ti, xp, xi
             self._transient = 0
 
     def entries(self, G_row, rows, cols):

@@ -1718,6 +1718,45 @@ static void launch_complete_entries(const void* H, int64_t ldh, const void* Gc, 
     check_launch("complete_entries");
 }
 
+// ranks of given pairs.  Workspace: [0, 256) the flag word of the list checks; [256, 512) the RANK_MAX_PARTS partial maxima
+// of rank_longest_row_kernel; then the scores of the targets, used when the caller keeps none (out_val NULL) -- the query
+// cannot know and sizes for them.  Nothing here grows with m x n_cols.  The column splits are topk_col_splits': one
+// decision for both operators.
+static size_t ranks_workspace(size_t esz, int64_t n_targets) { return 512 + align_up((size_t)n_targets * esz, 256); }
+
+static void ranks_check_shape(int32_t dtype, int64_t m, int64_t n_cols, int64_t n_targets, int32_t col_splits) {
+    if (dtype != SKF_F64 && dtype != SKF_F32) SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: dtype must be SKF_F64 / SKF_F32");
+    if (m < 0 || m >= (1LL << 31) || n_cols < 0 || n_cols >= (1LL << 31))
+        SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: m = %lld / n_cols = %lld outside 0 .. 2^31 - 1", (long long)m, (long long)n_cols);
+    if (n_targets < 0) SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: n_targets = %lld is negative", (long long)n_targets);
+    if (col_splits < 0 || col_splits > TOPK_MAX_SPLITS)
+        SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: col_splits = %d outside 0 .. %d", col_splits, TOPK_MAX_SPLITS);
+}
+
+template <typename T>
+static void launch_complete_ranks(const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int c,
+                                  const int64_t* tptr, const int* tidx, const int64_t* xptr, const int* xidx, int* out_rank, void* val,
+                                  int splits, int64_t longest, hipStream_t st) {
+    RankArgs<T> a;
+    a.H = (const T*)H; a.ldh = ldh; a.m = m;
+    a.Gc = (const T*)Gc; a.ldg = ldg; a.n_cols = n_cols;
+    a.c = c;
+    a.tptr = tptr; a.tidx = tidx; a.xptr = xptr; a.xidx = xidx;
+    const int64_t ntiles = (n_cols + TOPK_BN - 1) / TOPK_BN;
+    a.tiles_per_split = (int)std::max<int64_t>(1, (ntiles + splits - 1) / splits);
+    a.out_rank = out_rank; a.val = (T*)val;
+    const int row_tiles = cdiv(m, TOPK_BM);
+    hipLaunchKernelGGL((complete_rank_scores_kernel<T>), dim3(row_tiles), dim3(TOPK_THREADS), 0, st, a);
+    check_launch("complete_rank_scores");
+    // one workgroup per chunk of the longest row (a workgroup strides over the chunks beyond what one grid dimension holds)
+    const int64_t chunks = (longest + RANK_CHUNK - 1) / RANK_CHUNK;
+    a.chunk_groups = (int)std::max<int64_t>(1, std::min<int64_t>(chunks, 0x7fffffff / row_tiles));
+    static DeviceOnce once;
+    allow_dynamic_lds(once, complete_rank_count_kernel<T>, (int)rank_chunk_bytes(sizeof(T)));
+    hipLaunchKernelGGL((complete_rank_count_kernel<T>), dim3((unsigned)a.chunk_groups * row_tiles, splits), dim3(TOPK_THREADS), rank_chunk_bytes(sizeof(T)), st, a);
+    check_launch("complete_rank_count");
+}
+
 extern "C" {
 
 int skf_complete_topk_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int32_t k, int32_t col_splits, size_t* bytes) {
@@ -1793,6 +1832,68 @@ int skf_complete_entries(int32_t dtype, const void* H, int64_t ldh, int64_t m, c
         }
         if (dtype == SKF_F64) launch_complete_entries<double>(H, ldh, Gc, ldg, c, (const int*)rows, (const int*)cols, n, out, st);
         else launch_complete_entries<float>(H, ldh, Gc, ldg, c, (const int*)rows, (const int*)cols, n, out, st);
+    });
+}
+
+int skf_complete_ranks_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int64_t n_targets, int32_t col_splits, size_t* bytes) {
+    return guarded([&] {
+        if (!bytes) SKF_FAIL(SKF_E_INVALID, "null argument");
+        ranks_check_shape(dtype, m, n_cols, n_targets, col_splits);
+        *bytes = ranks_workspace(dtype == SKF_F64 ? 8 : 4, n_targets);
+    });
+}
+
+int skf_complete_ranks(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int32_t c,
+                       const int64_t* tgt_indptr, const int32_t* tgt_indices, int64_t n_targets, const int64_t* excl_indptr,
+                       const int32_t* excl_indices, int32_t* out_rank, void* out_val, int32_t col_splits, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    return guarded([&] {
+        ranks_check_shape(dtype, m, n_cols, n_targets, col_splits);
+        if (c < 1 || c > 1024) SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: width c = %d outside 1 .. 1024", c);
+        if (!H || !Gc || !out_rank || !tgt_indptr || !tgt_indices) SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: null argument");
+        if ((excl_indptr == nullptr) != (excl_indices == nullptr))
+            SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: excl_indptr and excl_indices come together (both NULL: no exclusion)");
+        if (ldh < c || ldg < c) SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: ld too small");
+        const size_t esz = dtype == SKF_F64 ? 8 : 4;
+        const size_t need = ranks_workspace(esz, n_targets);
+        if (!workspace || workspace_bytes < need)
+            SKF_FAIL(SKF_E_WORKSPACE, "skf_complete_ranks: workspace %zu B < required %zu B (or null)", workspace ? workspace_bytes : (size_t)0, need);
+        if (((uintptr_t)workspace & 255) != 0) SKF_FAIL(SKF_E_WORKSPACE, "skf_complete_ranks: workspace must be 256-byte aligned");
+        if (n_targets == 0) return;
+        hipStream_t st = as_stream(stream);
+        char* ws = (char*)workspace;
+        // the target lists against the caller's count (tgt_indptr[m] == n_targets is part of the check), and in the same
+        // round trip the longest row, which sizes the chunk grid (read only once the lists have passed)
+        int* parts = (int*)(ws + 256);
+        const int nparts = (int)std::max<int64_t>(1, std::min<int64_t>(RANK_MAX_PARTS, (m + 255) / 256));
+        SKF_HIP(hipMemsetAsync(parts, 0, RANK_MAX_PARTS * sizeof(int), st));
+        if (!csr_is_canonical(tgt_indptr, (const int*)tgt_indices, m, n_cols, n_targets, (int*)ws, st, [&] {
+                hipLaunchKernelGGL(rank_longest_row_kernel, dim3(nparts), dim3(256), 0, st, tgt_indptr, m, parts);
+                check_launch("rank_longest_row");
+            }))
+            SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: the target lists are not canonical for %lld rows x %lld columns and %lld targets "
+                     "(indptr from 0 to the count, non-decreasing; indices in range and strictly ascending within a row)",
+                     (long long)m, (long long)n_cols, (long long)n_targets);
+        if (excl_indptr) {
+            int64_t nnz = -1;
+            SKF_HIP(hipMemcpyAsync(&nnz, excl_indptr + m, sizeof nnz, hipMemcpyDeviceToHost, st));
+            SKF_HIP(hipStreamSynchronize(st));
+            if (nnz < 0 || !csr_is_canonical(excl_indptr, (const int*)excl_indices, m, n_cols, nnz, (int*)ws, st))
+                SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: the exclusion lists are not canonical for %lld rows x %lld columns (indptr from 0 "
+                         "to the count, non-decreasing; indices in range and strictly ascending within a row)", (long long)m, (long long)n_cols);
+        }
+        int longest[RANK_MAX_PARTS];
+        SKF_HIP(hipMemcpyAsync(longest, parts, sizeof longest, hipMemcpyDeviceToHost, st));
+        SKF_HIP(hipStreamSynchronize(st));
+        const int64_t longest_row = *std::max_element(longest, longest + RANK_MAX_PARTS);
+        const int splits = topk_col_splits(m, n_cols, col_splits);
+        void* val = out_val ? out_val : (void*)(ws + 512);
+        if (dtype == SKF_F64)
+            launch_complete_ranks<double>(H, ldh, m, Gc, ldg, n_cols, c, tgt_indptr, (const int*)tgt_indices, excl_indptr,
+                                          (const int*)excl_indices, out_rank, val, splits, longest_row, st);
+        else
+            launch_complete_ranks<float>(H, ldh, m, Gc, ldg, n_cols, c, tgt_indptr, (const int*)tgt_indices, excl_indptr,
+                                         (const int*)excl_indices, out_rank, val, splits, longest_row, st);
     });
 }
 

@@ -17,6 +17,17 @@
 // than the current k-th best (an equal score further right loses the tie), and is inserted behind every entry that is
 // greater or equal.  The splits cover ascending, disjoint column ranges: the merge takes the heads in split order with a
 // strict comparison, which is the same rule.  No float atomics anywhere.
+//
+// RANKS of held-out pairs (what Recall@k, MRR, NDCG and AUC need of the array the reference's users rank,
+// examples/movielens_completion.py:121-126).  For a target (r, j) with s = score(r, j):
+//     rank(r, j) = #{ j' in [0, n_cols), j' != j, j' not in row r's exclusion list, score(r, j') not NaN,
+//                     score(r, j') > s  or  (score(r, j') == s and j' < j) }
+// -- the 0-based position of j in the total order above.  A target with a NaN score gets -1; a target that is itself in the
+// exclusion list is still ranked (exclusion removes competitors only).  score(r, j) is formed by topk_score_tile, the one
+// product every pass here shares, hence
+//   P1: if (r, j) is not excluded and rank(r, j) = p < k <= 64, complete_topk on the same inputs returns out_idx[r][p] == j
+//       and out_val[r][p] with the bits of the rank pass's out_val; if p >= k, j is not in row r's list
+// for every col_splits of either operator.
 #pragma once
 #include "skf_kernels.h"
 
@@ -61,12 +72,80 @@ struct TopkArgs {
     int* part_idx; T* part_val;
 };
 
+// The 64 x 64 score tile of rows row0 .. row0 + 63 of H against 64 rows of Gc, into sc = buf as [64][TOPK_SLD]: the K loop
+// over c in chunks of TOPK_KC (both operands staged per chunk into buf as [64][TOPK_LD] each), the four chains of 16x16x4
+// matrix instructions of every wave (2 x 2 waves, 32 x 32 scores each) and the hand-over of the accumulators, with a
+// barrier on either side of it.  `col_of(r)`, r < 64, names the row of Gc that is column r of the tile, or -1 for none (its
+// scores are 0): a contiguous tile and a gathered one run the SAME instructions on the same operands, so score(r, j) has the
+// same bits wherever column j sits in whichever tile.  Every thread of the workgroup calls it; `buf` may still be read by
+// the previous user on entry (the first barrier waits for it) and holds the finished tile, visible to all, on return.  What
+// `col_of` reads must be in place before the call: it is asked ahead of that barrier.
+template <typename T, class ColOf>
+__device__ __forceinline__ void topk_score_tile(const T* __restrict__ H, int64_t ldh, int64_t m, int64_t row0, const T* __restrict__ Gc,
+                                                int64_t ldg, int c, ColOf col_of, T* buf) {
+    typedef TopkMma<T> M;
+    T* sH = buf;
+    T* sG = buf + TOPK_BM * TOPK_LD;
+    T* sc = buf;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wr = wave >> 1, wc = wave & 1;            // 2 x 2 waves, 32 x 32 scores each (2 x 2 instruction tiles)
+    typename M::acc_t acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = typename M::acc_t{0, 0, 0, 0};
+    int gcol[8];                                         // the rows of Gc this thread stages (the same for every chunk)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) gcol[i] = col_of((t + TOPK_THREADS * i) >> 5);
+
+    for (int k0 = 0; k0 < c; k0 += TOPK_KC) {
+        __syncthreads();                                 // the previous chunk / the previous user has left `buf`
+        // element e = t + 256 i: 32 adjacent lanes read 32 adjacent k of one row (whole 128 / 256 B segments) and write
+        // 32 adjacent LDS words; rows / columns past the end and the K tail are zero
+        T hv[8], gv[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int e = t + TOPK_THREADS * i, r = e >> 5, kk = e & 31;
+            const bool kin = k0 + kk < c;
+            hv[i] = (kin && row0 + r < m) ? H[(row0 + r) * ldh + k0 + kk] : (T)0;
+            gv[i] = (kin && gcol[i] >= 0) ? Gc[(int64_t)gcol[i] * ldg + k0 + kk] : (T)0;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int e = t + TOPK_THREADS * i, r = e >> 5, kk = e & 31;
+            sH[r * TOPK_LD + kk] = hv[i];
+            sG[r * TOPK_LD + kk] = gv[i];
+        }
+        __syncthreads();
+        const int left = c - k0;
+        const int kend = left >= TOPK_KC ? TOPK_KC : (left + 3) / 4 * 4;
+        const T* pa = sH + (wr * 32 + (lane & 15)) * TOPK_LD + (lane >> 4);
+        const T* pb = sG + (wc * 32 + (lane & 15)) * TOPK_LD + (lane >> 4);
+        for (int kk = 0; kk < kend; kk += 4) {
+            const T a0 = pa[kk], a1 = pa[16 * TOPK_LD + kk];
+            const T b0 = pb[kk], b1 = pb[16 * TOPK_LD + kk];
+            acc[0][0] = M::mma(a0, b0, acc[0][0]);
+            acc[0][1] = M::mma(a0, b1, acc[0][1]);
+            acc[1][0] = M::mma(a1, b0, acc[1][0]);
+            acc[1][1] = M::mma(a1, b1, acc[1][1]);
+        }
+    }
+    __syncthreads();                                     // every wave is through with the operand tiles
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                sc[(wr * 32 + 16 * i + M::d_row(lane, r)) * TOPK_SLD + wc * 32 + 16 * j + (lane & 15)] = acc[i][j][r];
+    __syncthreads();
+}
+
 // bytes of dynamic LDS: the 64 running lists (values, then indices)
 static inline size_t topk_list_bytes(int k, size_t esz) { return (size_t)TOPK_BM * k * (esz + sizeof(int)); }
 
 template <typename T>
 __global__ __launch_bounds__(TOPK_THREADS) void complete_topk_kernel(TopkArgs<T> a) {
-    typedef TopkMma<T> M;
     // the operand tiles of a K chunk and the finished score tile share one buffer (a barrier on either side of the hand-over)
     constexpr int OPER = 2 * TOPK_BM * TOPK_LD, TILE = TOPK_BM * TOPK_SLD;
     __shared__ T buf[OPER > TILE ? OPER : TILE];
@@ -75,12 +154,9 @@ __global__ __launch_bounds__(TOPK_THREADS) void complete_topk_kernel(TopkArgs<T>
     HIP_DYNAMIC_SHARED(double, dyn)                     // lv[64][k] (T), then li[64][k] (int)
     T* lv = (T*)dyn;
     int* li = (int*)(lv + (size_t)TOPK_BM * a.k);
-    T* sH = buf;
-    T* sG = buf + TOPK_BM * TOPK_LD;
     T* sc = buf;
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wr = wave >> 1, wc = wave & 1;            // 2 x 2 waves, 32 x 32 scores each (2 x 2 instruction tiles)
     const int k = a.k, c = a.c;
     const int64_t row0 = (int64_t)blockIdx.x * TOPK_BM;
     const int64_t ntiles = (a.n_cols + TOPK_BN - 1) / TOPK_BN;
@@ -109,53 +185,8 @@ __global__ __launch_bounds__(TOPK_THREADS) void complete_topk_kernel(TopkArgs<T>
 
     for (int64_t tile = tile_lo; tile < tile_hi; ++tile) {
         const int64_t col0 = tile * TOPK_BN;
-        typename M::acc_t acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = typename M::acc_t{0, 0, 0, 0};
-
-        for (int k0 = 0; k0 < c; k0 += TOPK_KC) {
-            __syncthreads();                             // the previous chunk / the previous tile's selection has left `buf`
-            // element e = t + 256 i: 32 adjacent lanes read 32 adjacent k of one row (whole 128 / 256 B segments) and write
-            // 32 adjacent LDS words; rows / columns past the end and the K tail are zero
-            T hv[8], gv[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int e = t + TOPK_THREADS * i, r = e >> 5, kk = e & 31;
-                const bool kin = k0 + kk < c;
-                hv[i] = (kin && row0 + r < a.m) ? a.H[(row0 + r) * a.ldh + k0 + kk] : (T)0;
-                gv[i] = (kin && col0 + r < a.n_cols) ? a.Gc[(col0 + r) * a.ldg + k0 + kk] : (T)0;
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int e = t + TOPK_THREADS * i, r = e >> 5, kk = e & 31;
-                sH[r * TOPK_LD + kk] = hv[i];
-                sG[r * TOPK_LD + kk] = gv[i];
-            }
-            __syncthreads();
-            const int left = c - k0;
-            const int kend = left >= TOPK_KC ? TOPK_KC : (left + 3) / 4 * 4;
-            const T* pa = sH + (wr * 32 + (lane & 15)) * TOPK_LD + (lane >> 4);
-            const T* pb = sG + (wc * 32 + (lane & 15)) * TOPK_LD + (lane >> 4);
-            for (int kk = 0; kk < kend; kk += 4) {
-                const T a0 = pa[kk], a1 = pa[16 * TOPK_LD + kk];
-                const T b0 = pb[kk], b1 = pb[16 * TOPK_LD + kk];
-                acc[0][0] = M::mma(a0, b0, acc[0][0]);
-                acc[0][1] = M::mma(a0, b1, acc[0][1]);
-                acc[1][0] = M::mma(a1, b0, acc[1][0]);
-                acc[1][1] = M::mma(a1, b1, acc[1][1]);
-            }
-        }
-        __syncthreads();                                 // every wave is through with the operand tiles
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    sc[(wr * 32 + 16 * i + M::d_row(lane, r)) * TOPK_SLD + wc * 32 + 16 * j + (lane & 15)] = acc[i][j][r];
-        __syncthreads();
+        topk_score_tile<T>(a.H, a.ldh, a.m, row0, a.Gc, a.ldg, c,
+                           [&](int r) { return col0 + r < a.n_cols ? (int)(col0 + r) : -1; }, buf);
 
         // all 256 threads: 16 scores of one row each against the row's threshold as it stands (it only rises: the owner
         // looks again before it inserts)
@@ -292,6 +323,198 @@ __global__ __launch_bounds__(256) void complete_entries_kernel(const T* __restri
 #pragma unroll
         for (int off = ENTRY_LANES / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, ENTRY_LANES);
         if (e < n && g == 0) out[e] = sum;
+    }
+}
+
+// ---- ranks of given (row, column) pairs -------------------------------------------------------------------------------------
+// rank(r, j) of the header comment is a COUNT, so it needs no list: the score pass writes score(r, j) of every target
+// (the shared score tile on 64 gathered columns: the same chain as anywhere else) and the count pass walks the columns as
+// the top-k pass does and counts, per target, the admissible columns that come before it in the total order.  Counts are
+// integers: LDS counters per workgroup, one integer atomicAdd per (target, split) at the end -- the sum does not depend on
+// the splits, the chunk grid or the order of arrival.
+constexpr int RANK_CHUNK = 32;                 // targets of one row a workgroup of the count pass holds
+// chunk arrays [64][33]: the compare loop reads entry i of row (lane & 63) in all lanes at once -- 33 r + i (words) and
+// 66 r + 2 i (f64, ds_read_b64: 64 banks) are distinct banks over a group of 32 lanes
+constexpr int RANK_CLD = RANK_CHUNK + 1;
+constexpr int RANK_MAX_PARTS = 64;             // workgroups (and result words) of rank_longest_row_kernel
+
+// part[b] = the longest row (indptr[r + 1] - indptr[r], capped to int) among the rows workgroup b strides over.  Plain
+// loads of the m + 1 pointers: it may run on lists the check has not passed yet (the result is then not used).
+static __global__ __launch_bounds__(256) void rank_longest_row_kernel(const int64_t* __restrict__ indptr, int64_t rows, int* __restrict__ part) {
+    __shared__ int red[256];
+    const int t = threadIdx.x;
+    int64_t best = 0;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + t; r < rows; r += (int64_t)gridDim.x * 256) {
+        const int64_t d = indptr[r + 1] - indptr[r];
+        if (d > best) best = d;
+    }
+    red[t] = best > 0x7fffffff ? 0x7fffffff : (int)best;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s && red[t + s] > red[t]) red[t] = red[t + s];
+        __syncthreads();
+    }
+    if (t == 0) part[blockIdx.x] = red[0];
+}
+
+template <typename T>
+struct RankArgs {
+    const T* H;  int64_t ldh;  int64_t m;           // [m][c]
+    const T* Gc; int64_t ldg;  int64_t n_cols;      // [n_cols][c]
+    int c;
+    const int64_t* tptr; const int* tidx;           // target CSR over the m rows (validated by the caller)
+    const int64_t* xptr; const int* xidx;           // exclusion CSR over the m rows (validated by the caller), or both null
+    int tiles_per_split;                            // column tiles (of TOPK_BN) a split walks
+    int chunk_groups;                               // workgroups per (row tile, split): chunk z, z + chunk_groups, ... each
+    int* out_rank;                                  // [n_targets]
+    T* val;                                         // [n_targets]: score of every target (the caller's out_val, or workspace)
+};
+
+// bytes of dynamic LDS of the count pass: the chunk's scores, columns and counters.  With the operand / score buffer the
+// f64 kernel holds 69 KB of LDS, the f32 kernel 43 KB.
+static inline size_t rank_chunk_bytes(size_t esz) { return (size_t)TOPK_BM * RANK_CLD * (esz + 2 * sizeof(int)); }
+
+// A workgroup owns 64 rows; their targets are the contiguous entries tptr[row0] .. tptr[row0 + 64].  64 consecutive
+// entries at a time are the 64 gathered columns of a score tile; entry e of row r reads sc[r - row0][e - e0].
+template <typename T>
+__global__ __launch_bounds__(TOPK_THREADS) void complete_rank_scores_kernel(RankArgs<T> a) {
+    constexpr int OPER = 2 * TOPK_BM * TOPK_LD, TILE = TOPK_BM * TOPK_SLD;
+    __shared__ T buf[OPER > TILE ? OPER : TILE];
+    __shared__ int64_t tp[TOPK_BM + 1];                  // the target pointers of the 64 rows (rows past m: empty)
+    __shared__ int gc[TOPK_BN];                          // the gathered columns of the tile, -1: none
+    const int t = threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * TOPK_BM;
+    if (t <= TOPK_BM) tp[t] = a.tptr[row0 + t < a.m ? row0 + t : a.m];
+    __syncthreads();
+    const int64_t e_hi = tp[TOPK_BM];
+    for (int64_t e0 = tp[0]; e0 < e_hi; e0 += TOPK_BN) {
+        // (a thread that writes gc here has passed the barriers of the previous tile, which every thread passes after
+        // it has asked col_of)
+        if (t < TOPK_BN) gc[t] = e0 + t < e_hi ? a.tidx[e0 + t] : -1;
+        __syncthreads();
+        topk_score_tile<T>(a.H, a.ldh, a.m, row0, a.Gc, a.ldg, a.c, [&](int r) { return gc[r]; }, buf);
+        if (t < TOPK_BN && e0 + t < e_hi) {
+            const int64_t e = e0 + t;
+            int lo = 0, hi = TOPK_BM;                    // the row of entry e: tp[lo] <= e < tp[hi], rows may be empty
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (tp[mid] <= e) lo = mid; else hi = mid;
+            }
+            const T s = buf[lo * TOPK_SLD + t];
+            a.val[e] = s;
+            a.out_rank[e] = s == s ? 0 : -1;
+        }
+    }
+}
+
+// grid (target chunk within 64-row tile, column split): chunk z holds targets 32 z .. 32 z + 31 of each of its rows -- scores,
+// columns and counters in LDS -- and walks its split's column tiles in ascending order.  Per tile the owner lane of a row
+// (as in the top-k pass) advances the row's exclusion cursor over the tile's columns and publishes them as a 64-bit mask;
+// then thread (row = t & 63, quarter = t >> 6) holds its 16 scores -- NaN where the column is past the end or excluded,
+// so that it compares false like a NaN score does -- and runs over the row's chunk targets with the predicate of the
+// definition.  (Column j itself has the target's own bits and fails both halves of it.)
+template <typename T>
+__global__ __launch_bounds__(TOPK_THREADS) void complete_rank_count_kernel(RankArgs<T> a) {
+    constexpr int OPER = 2 * TOPK_BM * TOPK_LD, TILE = TOPK_BM * TOPK_SLD;
+    __shared__ T buf[OPER > TILE ? OPER : TILE];
+    HIP_DYNAMIC_SHARED(double, dyn)                      // the chunk (rank_chunk_bytes): score (T),
+    T* ts = (T*)dyn;
+    int* tc = (int*)(ts + TOPK_BM * RANK_CLD);           // column
+    int* tn = tc + TOPK_BM * RANK_CLD;                   // and count so far of target i of row r at [r][i]
+    __shared__ unsigned long long xmask[TOPK_BM];        // the excluded columns of the tile, per row
+    __shared__ int64_t tp[TOPK_BM + 1];
+    __shared__ int nt[TOPK_BM];                          // targets of the row in this chunk
+    const T* sc = buf;
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    // blockIdx.x = chunk group + chunk_groups * row tile: the chunks of one long row are consecutive workgroups, which the
+    // hardware hands round its dies in turn; as a slower grid dimension they would lie a whole number of row tiles apart
+    const int64_t row0 = (int64_t)(blockIdx.x / a.chunk_groups) * TOPK_BM;
+    const int64_t ch0 = blockIdx.x % a.chunk_groups;
+    const int64_t ntiles = (a.n_cols + TOPK_BN - 1) / TOPK_BN;
+    const int64_t tile_lo = (int64_t)blockIdx.y * a.tiles_per_split;
+    const int64_t tile_hi = tile_lo + a.tiles_per_split < ntiles ? tile_lo + a.tiles_per_split : ntiles;
+
+    // the chunks this row tile needs: those of its longest row.  A workgroup beyond them leaves before it touches a list.
+    if (t <= TOPK_BM) tp[t] = a.tptr[row0 + t < a.m ? row0 + t : a.m];
+    __syncthreads();
+    int64_t longest = 0;
+    for (int r = 0; r < TOPK_BM; ++r) longest = tp[r + 1] - tp[r] > longest ? tp[r + 1] - tp[r] : longest;
+    const int64_t chunks = (longest + RANK_CHUNK - 1) / RANK_CHUNK;
+    if (ch0 >= chunks) return;
+
+    const bool owner = lane < 16;                        // of row wave * 16 + lane of the tile
+    const int orow = wave * 16 + lane;
+    int64_t xp0 = 0, xe = 0;                             // the row's exclusion list from the split's first column on
+    if (owner && row0 + orow < a.m && a.xptr) {
+        xp0 = a.xptr[row0 + orow];
+        xe = a.xptr[row0 + orow + 1];
+        const int64_t first = tile_lo * TOPK_BN;
+        if (first > 0) {
+            int64_t lo = xp0, hi = xe;
+            while (lo < hi) {
+                const int64_t mid = lo + ((hi - lo) >> 1);
+                if ((int64_t)a.xidx[mid] < first) lo = mid + 1; else hi = mid;
+            }
+            xp0 = lo;
+        }
+    }
+
+    for (int64_t ch = ch0; ch < chunks; ch += a.chunk_groups) {
+        __syncthreads();                                 // the previous chunk's flush has left nt / tn
+        if (t < TOPK_BM) {
+            int64_t n = tp[t + 1] - tp[t] - ch * RANK_CHUNK;
+            nt[t] = (int)(n < 0 ? 0 : (n > RANK_CHUNK ? RANK_CHUNK : n));
+        }
+        __syncthreads();
+        for (int i = t; i < TOPK_BM * RANK_CHUNK; i += TOPK_THREADS) {
+            const int r = i / RANK_CHUNK, q = i % RANK_CHUNK;
+            if (q < nt[r]) {
+                const int64_t e = tp[r] + ch * RANK_CHUNK + q;
+                ts[r * RANK_CLD + q] = a.val[e];
+                tc[r * RANK_CLD + q] = a.tidx[e];
+                tn[r * RANK_CLD + q] = 0;
+            }
+        }
+        int64_t xp = xp0;
+        for (int64_t tile = tile_lo; tile < tile_hi; ++tile) {
+            const int64_t col0 = tile * TOPK_BN;
+            topk_score_tile<T>(a.H, a.ldh, a.m, row0, a.Gc, a.ldg, a.c,
+                               [&](int r) { return col0 + r < a.n_cols ? (int)(col0 + r) : -1; }, buf);
+            if (owner) {
+                unsigned long long mk = 0;
+                while (xp < xe && (int64_t)a.xidx[xp] < col0 + TOPK_BN) {
+                    mk |= 1ull << ((int64_t)a.xidx[xp] - col0);
+                    ++xp;
+                }
+                xmask[orow] = mk;
+            }
+            __syncthreads();                             // (covers the chunk arrays too, on the first tile)
+            const int r = t & 63, q = t >> 6, n = nt[r];
+            if (n > 0) {
+                const unsigned xm = (unsigned)(xmask[r] >> (16 * q)) & 0xffffu;
+                const int64_t cb = col0 + 16 * q;
+                T sv[16];
+#pragma unroll
+                for (int b = 0; b < 16; ++b)
+                    sv[b] = (cb + b < a.n_cols && !((xm >> b) & 1u)) ? sc[r * TOPK_SLD + 16 * q + b] : (T)NAN;
+                for (int i = 0; i < n; ++i) {
+                    const T s = ts[r * RANK_CLD + i];
+                    const int64_t d = (int64_t)tc[r * RANK_CLD + i] - cb;
+                    const int jb = d < 0 ? 0 : (d > 16 ? 16 : (int)d);      // columns cb + b with b < jb lie left of the target
+                    int cn = 0;
+#pragma unroll
+                    for (int b = 0; b < 16; ++b) cn += (int)((sv[b] > s) | ((sv[b] == s) & (b < jb)));
+                    if (cn) atomicAdd(&tn[r * RANK_CLD + i], cn);
+                }
+            }
+            // (the first barrier of the next tile's product separates this compare from the next tile and mask)
+        }
+        __syncthreads();
+        for (int i = t; i < TOPK_BM * RANK_CHUNK; i += TOPK_THREADS) {
+            const int r = i / RANK_CHUNK, q = i % RANK_CHUNK;
+            if (q < nt[r] && tn[r * RANK_CLD + q] != 0) atomicAdd(&a.out_rank[tp[r] + ch * RANK_CHUNK + q], tn[r * RANK_CLD + q]);
+        }
     }
 }
 

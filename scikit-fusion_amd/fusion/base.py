@@ -338,6 +338,47 @@ class FusionFit(FusionBase):
             return (one(r) for r in range(self.n_run))
         return one(0 if run is None else run)
 
+    def complete_ranks(self, relation, rows, cols, exclude=None, run=None, dtype='f64', block_rows=8192):
+        """``int64 [n]``: for every pair ``(rows[e], cols[e])`` its 0-based position in the ranking of its row's columns
+        by the model -- the number of columns with a higher score, or an equal score and a lower index, in the order of
+        ``complete_topk`` -- which is what Recall@k, MRR, NDCG and AUC of held-out pairs need; ``-1`` where the pair's
+        score is NaN.  ``exclude`` (as for ``complete_topk``: None, ``'known'`` or a scipy.sparse matrix of the relation's
+        shape) removes COMPETITORS only: a pair that is itself excluded is still ranked.  Pairs may come in any order and
+        with duplicates.  The counts are taken on the device over score tiles, ``block_rows`` distinct rows at a time;
+        nothing of size ``n_i x n_j`` is formed.  A relation with a postprocessor is refused, as in ``complete_topk``.
+        ``n_run > 1`` and ``run=None``: a generator over the runs.  Extension of the reference API."""
+        self._check_relation_types(relation)
+        if relation.postprocessor:
+            raise DataFusionError("complete_ranks ranks raw device scores; relation %s -> %s has a "
+                                  "postprocessor (rank complete_blocks(device=False) yourself)"
+                                  % (relation.row_type.name, relation.col_type.name))
+        rows = np.asarray(rows).reshape(-1)
+        cols = np.asarray(cols).reshape(-1)
+        if rows.shape != cols.shape or rows.dtype.kind not in 'iu' or cols.dtype.kind not in 'iu':
+            raise DataFusionError("rows and cols must be integer arrays of one length")
+        n_i, n_j = np.shape(self.factor(relation.row_type, 0))[0], np.shape(self.factor(relation.col_type, 0))[0]
+        if rows.size and (rows.min() < 0 or rows.max() >= n_i or cols.min() < 0 or cols.max() >= n_j):
+            raise DataFusionError("A pair lies outside the %d x %d relation" % (n_i, n_j))
+        lists = self._exclusion_lists(relation, exclude, (n_i, n_j))
+        step = max(1, int(block_rows))
+        # the distinct pairs in (row, column) order are the target CSR over the distinct rows; `back` leads home
+        key, back = np.unique(rows.astype(np.int64) * n_j + cols.astype(np.int64), return_inverse=True)
+        prow, pcol = key // max(n_j, 1), (key % max(n_j, 1)).astype(np.int32)
+        urows, first = np.unique(prow, return_index=True)
+        ptr = np.append(first, key.size).astype(np.int64)
+
+        def one(r):
+            G1, comp = self._completer(relation, r, dtype)
+            out = np.empty(key.size, dtype=np.int64)
+            for b0 in range(0, urows.size, step):
+                blk = urows[b0:b0 + step]
+                p = ptr[b0:b0 + blk.size + 1]
+                out[p[0]:p[-1]] = comp.ranks(G1[blk], (p - p[0], pcol[p[0]:p[-1]]), exclude=lists(blk) if lists else None)[0]
+            return out[back.reshape(-1)]
+        if self.n_run > 1 and run is None:
+            return (one(r) for r in range(self.n_run))
+        return one(0 if run is None else run)
+
 
 # ---- persistence of a fitted model (SURVEY.md 8 f4; the reference has none: its accessors base.py:35-56,
 # 169-189 are the only consumers of factors_ / backbones_) ----------------------------------------------
