@@ -610,6 +610,36 @@ int skf_complete_ranks(int32_t dtype, const void* H, int64_t ldh, int64_t m, con
                        void* out_val /* dtype, may be NULL */, int32_t col_splits /* 0 = choose */, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* Every pair of X = H Gc^T (H, Gc as for skf_complete_topk) that scores at or above a per-row threshold, as a sparse matrix
+ * and without X: link prediction reads the reference's dense product (fusion/base/base.py `complete`: np.dot(G1, np.dot(S,
+ * G2.T))) against a cut-off; here nothing of size m x n_cols is written anywhere.  For row r with threshold thr[r]:
+ *     above(r) = { j in [0, n_cols) : j not in row r's exclusion list, score(r, j) >= thr[r] }
+ *   score(r, j) is the same chain of matrix instructions as in skf_complete_topk and >= is the IEEE comparison: a NaN score
+ *   or a NaN threshold selects nothing, -inf selects every admissible column whose score is not NaN, +inf only +inf scores.
+ *   Output: canonical CSR over the m rows -- out_indptr[m + 1] (int64, from 0), out_indices (int32, strictly ascending within
+ *     a row) and, unless NULL, out_values (dtype, the scores).  The pass runs twice over the tiles (count, integer scan,
+ *     fill); the position of every entry is a function of the inputs alone, so the bytes are the same for every col_splits
+ *     (0 = the library chooses, at most 32) and every run.  No atomics on positions, no float atomics.
+ *   capacity: entries out_indices (and out_values) can hold.  *n_found (host) is the number of entries found.
+ *     out_indices == NULL (out_values then NULL too): count only -- out_indptr and *n_found are written.
+ *     *n_found > capacity: SKF_E_WORKSPACE, the message names both numbers; out_indptr and *n_found are written, out_indices
+ *       and out_values are not touched -- call again with that capacity.
+ *     otherwise: everything is written and the memory behind entry *n_found is not touched.
+ *     m == 0 or n_cols == 0: success without a product launch, out_indptr all zero, *n_found = 0.
+ *   Exclusion: as for skf_complete_topk (both pointers NULL = none), validated on the device before anything gathers
+ *     through the lists.  Every refusal (SKF_E_INVALID; SKF_E_WORKSPACE for a workspace that is NULL, too small or not
+ *     256-byte aligned) leaves every output as it was.  skf_complete_above_workspace_bytes sizes the workspace: flag words,
+ *     the words of the scan and one int64 per (column split, row), nothing that grows with m x n_cols.
+ *   dtype SKF_F64 / SKF_F32 (the type of H, Gc, thr and out_values); 1 <= c <= 1024; m and n_cols < 2^31. */
+int skf_complete_above_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int32_t col_splits, size_t* bytes);
+int skf_complete_above(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols,
+                       int32_t c, const void* thr /* dtype [m], device */,
+                       const int64_t* excl_indptr, const int32_t* excl_indices,
+                       int64_t capacity, int64_t* out_indptr /* [m + 1], device */,
+                       int32_t* out_indices /* [capacity] or NULL */, void* out_values /* dtype [capacity] or NULL */,
+                       int64_t* n_found /* host */, int32_t col_splits /* 0 = choose */,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* K = pinv(A) for symmetric A (n x n): f64 Jacobi eigen-decomposition + the singular-value
  * cut-off of scipy.linalg.pinv (reference _dfmf.py:232, _dfmc.py:307). */
 int skf_pinv_sym_workspace_bytes(int32_t n, size_t* bytes);
@@ -660,7 +690,8 @@ const char* skf_version(void);
  * adds entry points only -- skf_small_graph_limits, skf_comm_info, skf_launch_count; later: skf_fold_lists and the flag
  * SKF_REL_FOLD_CSR; skf_complete_topk_workspace_bytes, skf_complete_topk, skf_complete_entries and SKF_TOPK_MAX;
  * skf_get_constraint_lists and the flag SKF_OPT_THETA_OWNED_ROWS; skf_plan_set_relation_fill and the flag SKF_REL_FILL_RANK1;
- * skf_complete_ranks_workspace_bytes and skf_complete_ranks -- the structs are those of version 4). */
+ * skf_complete_ranks_workspace_bytes and skf_complete_ranks; skf_complete_above_workspace_bytes and skf_complete_above -- the
+ * structs are those of version 4). */
 #define SKF_ABI_VERSION 5
 int skf_abi_version(void);
 

@@ -1271,10 +1271,18 @@ def device_reconstruct(G_row_block, S, G_col, dtype='f64', runtime=None):
     return DeviceReconstructor(S, G_col, dtype, runtime).block(G_row_block)
 
 
+class AboveLimit(ValueError):
+    """``DeviceCompleter.above`` found more entries than the caller's ``max_entries`` allows; ``found`` is the count."""
+
+    def __init__(self, found):
+        ValueError.__init__(self, '%d entries at or above the threshold' % found)
+        self.found = found
+
+
 class DeviceCompleter(object):
     """The consuming side of a completion model without the dense reconstruction: for ``X = G_row S G_col^T`` the ``k`` best
-    columns of every row (``topk``), the predictions at given pairs (``entries``) and the position of given pairs in
-    their row's ranking (``ranks``), all on the device (csrc/skf_complete.h).  The reference forms ``X`` on the host (fusion/base/base.py ``complete``) and its users rank or
+    columns of every row (``topk``), the predictions at given pairs (``entries``), the position of given pairs in
+    their row's ranking (``ranks``) and every pair at or above a threshold as CSR (``above``), all on the device (csrc/skf_complete.h).  The reference forms ``X`` on the host (fusion/base/base.py ``complete``) and its users rank or
     index that array (examples/movielens_completion.py:121-126).  ``S`` and ``G_col`` are uploaded ONCE and stay resident
     across blocks (the contract of ``DeviceReconstructor``); per block only ``H = G_row[block] S`` (``skf_gemm``), the
     block's exclusion lists, its outputs and the partial lists of the column splits live in HBM -- never anything of size
@@ -1417,6 +1425,68 @@ class DeviceCompleter(object):
             return mem.to_host(orank, (n,), np.int32), mem.to_host(oval, (n,), self.npd).astype(np.float64)
         finally:
             del a, bufs, tp, ti, xp, xi
+            self._transient = 0
+
+    ABOVE_PER_ROW = 64                   # entries per row the first call of `above` makes room for
+
+    def above(self, G_row_block, thr, exclude=None, col_splits=0, capacity=None, max_entries=None):
+        """``(indptr int64 [m + 1], indices int32 [n], values float64 [n])``: canonical CSR over the rows of the block of
+        every column whose score is at or above the row's threshold -- ``score >= thr`` in the SCORING type (``thr``, a
+        scalar or one value per row, is cast to it first), IEEE: a NaN score or threshold selects nothing, ``-inf``
+        every admissible column whose score is not NaN.  Columns ascend within a row; ``values`` are the scores, with the
+        bits ``topk`` and ``ranks`` give.  ``exclude = (indptr, indices)`` as for ``topk``.  The device counts, scans and
+        fills; the first call makes room for ``capacity`` entries (default: ``ABOVE_PER_ROW`` per row, or what an earlier
+        block needed) and is repeated ONCE with the exact count when they do not suffice -- the arrays are the same either
+        way.  ``max_entries``: a count beyond it raises ``AboveLimit`` before anything of that size is allocated.
+        ``col_splits`` 0 lets the library choose; the result does not depend on it."""
+        A = self._rows_of(G_row_block)
+        m = A.shape[0]
+        rt, mem = self.rt, self.rt.mem
+        t = np.asarray(thr, dtype=np.float64)
+        if t.ndim > 1 or (t.ndim == 1 and t.shape != (m,)):
+            raise ValueError('thr: a scalar or one value per row of the block')
+        keep = [np.ascontiguousarray(np.broadcast_to(t.astype(self.npd), (m,)))]
+        if exclude is not None:
+            keep += [np.ascontiguousarray(exclude[0], dtype=np.int64), np.ascontiguousarray(exclude[1], dtype=np.int32)]
+            if keep[1].shape != (m + 1,):
+                raise ValueError('exclude: indptr must have one entry per row of the block, plus one')
+        need = C.c_size_t()
+        rt.call('skf_complete_above_workspace_bytes', self.code, m, self.nj, int(col_splits), C.byref(need))
+        if m == 0:
+            return np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float64)
+        h, a = self._h(A)
+        held = self._transient
+        bufs = self._upload(keep)
+        self._transient += held
+        bt = bufs[0]
+        xp, xi = (bufs[1], bufs[2]) if exclude is not None else (None, None)
+        ws = self._scratch('ws', need.value)
+        op = self._scratch('above_ptr', (m + 1) * 8)
+        if capacity is None:
+            have = self._bufs.get('above_idx')
+            cap = min(m * self.nj, max(self.ABOVE_PER_ROW * m, have.nbytes // 4 if have else 0))
+        else:
+            cap = int(capacity)
+        found = C.c_int64(-1)
+        try:
+            for attempt in (0, 1):
+                oi = self._scratch('above_idx', max(cap, 1) * 4)
+                ov = self._scratch('above_val', max(cap, 1) * self.es)
+                self.peak_bytes = max(self.peak_bytes, self.device_bytes)
+                rc = rt.lib.skf_complete_above(self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, bt.ptr,
+                                               xp.ptr if xp else None, xi.ptr if xi else None, cap, op.ptr, oi.ptr, ov.ptr,
+                                               C.byref(found), int(col_splits), ws.ptr, ws.nbytes, mem.stream)
+                mem.synchronize()
+                n = found.value
+                if max_entries is not None and n > max_entries:
+                    raise AboveLimit(n)
+                if rc != nat.SKF_E_WORKSPACE or attempt or n <= cap:
+                    rt.check(rc)
+                    break
+                cap = n                  # the count pass has said how many there are: once more, with room for them
+            return mem.to_host(op, (m + 1,), np.int64), mem.to_host(oi, (n,), np.int32), mem.to_host(ov, (n,), self.npd).astype(np.float64)
+        finally:
+            del a, bufs, bt, xp, xi
             self._transient = 0
 
     def entries(self, G_row, rows, cols):

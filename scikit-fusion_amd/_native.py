@@ -157,6 +157,9 @@ SIGNATURES = {
     'skf_complete_ranks_workspace_bytes': (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
     'skf_complete_ranks': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int64,
                                      _P, _P, _P, _P, C.c_int32, _P, C.c_size_t, _P]),
+    'skf_complete_above_workspace_bytes': (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    'skf_complete_above': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, C.c_int64,
+                                     _P, _P, _P, C.POINTER(C.c_int64), C.c_int32, _P, C.c_size_t, _P]),
     'skf_pinv_sym_workspace_bytes': (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
     'skf_pinv_sym': (C.c_int, [C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_size_t, _P]),
     'skf_fill_uniform': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, C.c_int64, C.c_uint64,

@@ -1757,6 +1757,81 @@ static void launch_complete_ranks(const void* H, int64_t ldh, int64_t m, const v
     check_launch("complete_rank_count");
 }
 
+// every pair at or above a threshold.  Workspace: [0, 256) the flag word of the exclusion check; then the ABOVE_SCAN_PARTS
+// chunk sums of the scan; then one int64 per (split, row): the counts of the count pass, turned into the starts of the fill
+// pass in place.  Nothing here grows with m x n_cols.  The column splits are topk_col_splits'.
+static size_t above_workspace(int64_t m, int splits) {
+    return 256 + ABOVE_SCAN_PARTS * sizeof(int64_t) + align_up((size_t)splits * (size_t)m * sizeof(int64_t), 256);
+}
+
+static void above_check_shape(int32_t dtype, int64_t m, int64_t n_cols, int32_t col_splits) {
+    if (dtype != SKF_F64 && dtype != SKF_F32) SKF_FAIL(SKF_E_INVALID, "skf_complete_above: dtype must be SKF_F64 / SKF_F32");
+    if (m < 0 || m >= (1LL << 31) || n_cols < 0 || n_cols >= (1LL << 31))
+        SKF_FAIL(SKF_E_INVALID, "skf_complete_above: m = %lld / n_cols = %lld outside 0 .. 2^31 - 1", (long long)m, (long long)n_cols);
+    if (col_splits < 0 || col_splits > TOPK_MAX_SPLITS)
+        SKF_FAIL(SKF_E_INVALID, "skf_complete_above: col_splits = %d outside 0 .. %d", col_splits, TOPK_MAX_SPLITS);
+}
+
+template <typename T>
+static AboveArgs<T> above_args(const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int c, const void* thr,
+                               const int64_t* xptr, const int* xidx, int splits, char* ws, const int64_t* indptr, int* out_indices,
+                               void* out_values) {
+    AboveArgs<T> a;
+    a.H = (const T*)H; a.ldh = ldh; a.m = m;
+    a.Gc = (const T*)Gc; a.ldg = ldg; a.n_cols = n_cols;
+    a.c = c;
+    a.thr = (const T*)thr;
+    a.xptr = xptr; a.xidx = xidx;
+    const int64_t ntiles = (n_cols + TOPK_BN - 1) / TOPK_BN;
+    a.tiles_per_split = (int)std::max<int64_t>(1, (ntiles + splits - 1) / splits);
+    a.work = (int64_t*)(ws + 256 + ABOVE_SCAN_PARTS * sizeof(int64_t));
+    a.indptr = indptr;
+    a.out_indices = out_indices; a.out_values = (T*)out_values;
+    return a;
+}
+
+// the count pass and the scan: out_indptr (the total at [m]) and the (row, split) starts in the workspace
+template <typename T>
+static void launch_above_count(const AboveArgs<T>& a, int splits, char* ws, int64_t* out_indptr, hipStream_t st) {
+    const int row_tiles = cdiv(a.m, TOPK_BM);
+    hipLaunchKernelGGL((complete_above_kernel<T, false>), dim3(row_tiles, splits), dim3(TOPK_THREADS), 0, st, a);
+    check_launch("complete_above_count");
+    int64_t* parts = (int64_t*)(ws + 256);
+    const int64_t want = std::min<int64_t>(ABOVE_SCAN_PARTS, (a.m + 255) / 256);
+    const int64_t chunk = ((a.m + want - 1) / want + 255) / 256 * 256;           // rows per workgroup: a multiple of 256
+    const int nparts = (int)((a.m + chunk - 1) / chunk);
+    hipLaunchKernelGGL(above_chunk_sums_kernel, dim3(nparts), dim3(256), 0, st, (const int64_t*)a.work, a.m, splits, chunk, parts);
+    check_launch("above_chunk_sums");
+    hipLaunchKernelGGL(above_chunk_starts_kernel, dim3(1), dim3(256), 0, st, parts, nparts, a.m, out_indptr);
+    check_launch("above_chunk_starts");
+    hipLaunchKernelGGL(above_offsets_kernel, dim3(nparts), dim3(256), 0, st, a.work, a.m, splits, chunk, (const int64_t*)parts, out_indptr);
+    check_launch("above_offsets");
+}
+
+template <typename T>
+static void launch_above_fill(const AboveArgs<T>& a, int splits, hipStream_t st) {
+    hipLaunchKernelGGL((complete_above_kernel<T, true>), dim3(cdiv(a.m, TOPK_BM), splits), dim3(TOPK_THREADS), 0, st, a);
+    check_launch("complete_above_fill");
+}
+
+// count, scan, ONE read-back of the total, then -- unless the caller asked for the count alone or has too little room -- fill
+template <typename T>
+static void run_complete_above(const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int c, const void* thr,
+                               const int64_t* xptr, const int* xidx, int64_t capacity, int64_t* out_indptr, int* out_indices,
+                               void* out_values, int64_t* n_found, int splits, char* ws, hipStream_t st) {
+    const AboveArgs<T> a = above_args<T>(H, ldh, m, Gc, ldg, n_cols, c, thr, xptr, xidx, splits, ws, out_indptr, out_indices, out_values);
+    launch_above_count<T>(a, splits, ws, out_indptr, st);
+    int64_t total = -1;
+    SKF_HIP(hipMemcpyAsync(&total, out_indptr + m, sizeof total, hipMemcpyDeviceToHost, st));
+    SKF_HIP(hipStreamSynchronize(st));
+    *n_found = total;
+    if (!out_indices) return;                           // count only
+    if (total > capacity)
+        SKF_FAIL(SKF_E_WORKSPACE, "skf_complete_above: %lld entries found, capacity %lld (out_indptr and *n_found are written: "
+                 "call again with that capacity)", (long long)total, (long long)capacity);
+    if (total > 0) launch_above_fill<T>(a, splits, st);
+}
+
 extern "C" {
 
 int skf_complete_topk_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int32_t k, int32_t col_splits, size_t* bytes) {
@@ -1894,6 +1969,57 @@ int skf_complete_ranks(int32_t dtype, const void* H, int64_t ldh, int64_t m, con
         else
             launch_complete_ranks<float>(H, ldh, m, Gc, ldg, n_cols, c, tgt_indptr, (const int*)tgt_indices, excl_indptr,
                                          (const int*)excl_indices, out_rank, val, splits, longest_row, st);
+    });
+}
+
+int skf_complete_above_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int32_t col_splits, size_t* bytes) {
+    return guarded([&] {
+        if (!bytes) SKF_FAIL(SKF_E_INVALID, "null argument");
+        above_check_shape(dtype, m, n_cols, col_splits);
+        *bytes = above_workspace(m, topk_col_splits(m, n_cols, col_splits));
+    });
+}
+
+int skf_complete_above(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int32_t c,
+                       const void* thr, const int64_t* excl_indptr, const int32_t* excl_indices, int64_t capacity, int64_t* out_indptr,
+                       int32_t* out_indices, void* out_values, int64_t* n_found, int32_t col_splits, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    return guarded([&] {
+        above_check_shape(dtype, m, n_cols, col_splits);
+        if (c < 1 || c > 1024) SKF_FAIL(SKF_E_INVALID, "skf_complete_above: width c = %d outside 1 .. 1024", c);
+        if (!H || !Gc || !thr || !out_indptr || !n_found) SKF_FAIL(SKF_E_INVALID, "skf_complete_above: null argument");
+        if (out_values && !out_indices) SKF_FAIL(SKF_E_INVALID, "skf_complete_above: out_values without out_indices");
+        if ((excl_indptr == nullptr) != (excl_indices == nullptr))
+            SKF_FAIL(SKF_E_INVALID, "skf_complete_above: excl_indptr and excl_indices come together (both NULL: no exclusion)");
+        if (ldh < c || ldg < c) SKF_FAIL(SKF_E_INVALID, "skf_complete_above: ld too small");
+        if (capacity < 0) SKF_FAIL(SKF_E_INVALID, "skf_complete_above: capacity = %lld is negative", (long long)capacity);
+        const int splits = topk_col_splits(m, n_cols, col_splits);
+        const size_t need = above_workspace(m, splits);
+        if (!workspace || workspace_bytes < need)
+            SKF_FAIL(SKF_E_WORKSPACE, "skf_complete_above: workspace %zu B < required %zu B (or null)", workspace ? workspace_bytes : (size_t)0, need);
+        if (((uintptr_t)workspace & 255) != 0) SKF_FAIL(SKF_E_WORKSPACE, "skf_complete_above: workspace must be 256-byte aligned");
+        hipStream_t st = as_stream(stream);
+        char* ws = (char*)workspace;
+        if (m > 0 && excl_indptr) {
+            int64_t nnz = -1;
+            SKF_HIP(hipMemcpyAsync(&nnz, excl_indptr + m, sizeof nnz, hipMemcpyDeviceToHost, st));
+            SKF_HIP(hipStreamSynchronize(st));
+            if (nnz < 0 || !csr_is_canonical(excl_indptr, (const int*)excl_indices, m, n_cols, nnz, (int*)ws, st))
+                SKF_FAIL(SKF_E_INVALID, "skf_complete_above: the exclusion lists are not canonical for %lld rows x %lld columns (indptr from 0 "
+                         "to the count, non-decreasing; indices in range and strictly ascending within a row)", (long long)m, (long long)n_cols);
+        }
+        if (m == 0 || n_cols == 0) {                    // nothing to score: every row is empty
+            SKF_HIP(hipMemsetAsync(out_indptr, 0, (size_t)(m + 1) * sizeof(int64_t), st));
+            SKF_HIP(hipStreamSynchronize(st));
+            *n_found = 0;
+            return;
+        }
+        if (dtype == SKF_F64)
+            run_complete_above<double>(H, ldh, m, Gc, ldg, n_cols, c, thr, excl_indptr, (const int*)excl_indices, capacity, out_indptr,
+                                       out_indices, out_values, n_found, splits, ws, st);
+        else
+            run_complete_above<float>(H, ldh, m, Gc, ldg, n_cols, c, thr, excl_indptr, (const int*)excl_indices, capacity, out_indptr,
+                                      out_indices, out_values, n_found, splits, ws, st);
     });
 }
 

@@ -28,6 +28,13 @@
 //   P1: if (r, j) is not excluded and rank(r, j) = p < k <= 64, complete_topk on the same inputs returns out_idx[r][p] == j
 //       and out_val[r][p] with the bits of the rank pass's out_val; if p >= k, j is not in row r's list
 // for every col_splits of either operator.
+//
+// ABOVE a threshold (link prediction: every pair the reference's dense product, fusion/base/base.py `complete`, holds at or
+// above a cut-off).  For row r with threshold thr[r]:
+//     above(r) = { j in [0, n_cols) : j not in row r's exclusion list, score(r, j) >= thr[r] }
+// with the IEEE comparison (a NaN score or threshold selects nothing), as canonical CSR.  Same product, hence
+//   P2: with thr[r] = the k-th value of complete_topk on the same inputs, row r's entries ordered by (value descending,
+//       column ascending) begin with top-k's list, bit for bit, and every further entry equals thr[r].
 #pragma once
 #include "skf_kernels.h"
 
@@ -515,6 +522,227 @@ __global__ __launch_bounds__(TOPK_THREADS) void complete_rank_count_kernel(RankA
             const int r = i / RANK_CHUNK, q = i % RANK_CHUNK;
             if (q < nt[r] && tn[r * RANK_CLD + q] != 0) atomicAdd(&a.out_rank[tp[r] + ch * RANK_CHUNK + q], tn[r * RANK_CLD + q]);
         }
+    }
+}
+
+// ---- every pair at or above a per-row threshold, as CSR -------------------------------------------------------------------------
+// above(r) of the header comment has no size known in advance, so the pass runs twice over the same tiles: the count pass
+// leaves one integer per (split, row), the scan turns them into out_indptr and into the start of every (row, split) run --
+// row r's entries are those of split 0, then split 1, ..., each in ascending columns, i.e. ascending columns altogether
+// whatever the split count -- and the fill pass walks the tiles again and writes every selected (column, score) to
+//     start(r, split) + #{ selected columns of row r in this split left of it }.
+// Positions are functions of the inputs alone: no atomics on them, the same bytes for every col_splits and every run.
+template <typename T>
+struct AboveArgs {
+    const T* H;  int64_t ldh;  int64_t m;           // [m][c]
+    const T* Gc; int64_t ldg;  int64_t n_cols;      // [n_cols][c]
+    int c;
+    const T* thr;                                   // [m]
+    const int64_t* xptr; const int* xidx;           // exclusion CSR over the m rows (validated by the caller), or both null
+    int tiles_per_split;                            // column tiles (of TOPK_BN) a split walks
+    int64_t* work;                                  // [splits][m]: the counts (count pass writes), then the starts (fill pass reads)
+    const int64_t* indptr;                          // [m + 1]: out_indptr (fill pass: where row r's last split ends)
+    int* out_indices; T* out_values;                // fill pass; out_values may be null
+};
+
+// THE predicate, for thread (row r, quarter q) of a finished score tile: bit b of the result says that column
+// col0 + 16 q + b is in above(r) -- inside the relation, not in the row's exclusion mask `xm` (bit b: that column) and
+// with a score >= thr under the IEEE comparison, which is false for a NaN on either side.
+template <typename T>
+__device__ __forceinline__ unsigned above_quarter_mask(const T* sc, int r, int q, int64_t col0, int64_t n_cols, unsigned xm, T thr) {
+    unsigned mk = 0;
+#pragma unroll
+    for (int b = 0; b < 16; ++b) {
+        const T s = sc[r * TOPK_SLD + 16 * q + b];
+        if (col0 + 16 * q + b < n_cols && !((xm >> b) & 1u) && s >= thr) mk |= 1u << b;
+    }
+    return mk;
+}
+
+// grid (64-row tile, column split) as complete_topk_kernel.  Per tile the owner lane of a row publishes the excluded columns
+// of the tile as a 64-bit mask (as complete_rank_count_kernel does); thread (row = t & 63, quarter = t >> 6) then holds the
+// 16-bit mask of above_quarter_mask.  FILL = false adds its popcount to a register and the four quarters meet in LDS at the
+// end; FILL = true publishes the four masks of a row, so that every thread of the row knows the selected columns left of
+// its own, and keeps the row's write cursor in a register (all four advance it by the same total).
+template <typename T, bool FILL>
+__global__ __launch_bounds__(TOPK_THREADS) void complete_above_kernel(AboveArgs<T> a) {
+    constexpr int OPER = 2 * TOPK_BM * TOPK_LD, TILE = TOPK_BM * TOPK_SLD;
+    __shared__ T buf[OPER > TILE ? OPER : TILE];
+    __shared__ unsigned long long xmask[TOPK_BM];        // the excluded columns of the tile, per row
+    __shared__ unsigned short qmask[4 * TOPK_BM];        // FILL: [quarter][row] the selected columns of the tile
+    __shared__ int qcnt[4 * TOPK_BM];                    // count: [quarter][row] at the end; FILL: word 0 = any row has entries
+    const T* sc = buf;
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r = t & 63, q = t >> 6;
+    const int64_t row0 = (int64_t)blockIdx.x * TOPK_BM;
+    const int64_t ntiles = (a.n_cols + TOPK_BN - 1) / TOPK_BN;
+    const int64_t tile_lo = (int64_t)blockIdx.y * a.tiles_per_split;
+    const int64_t tile_hi = tile_lo + a.tiles_per_split < ntiles ? tile_lo + a.tiles_per_split : ntiles;
+    const bool rin = row0 + r < a.m;
+
+    int64_t pos = 0, end = 0;                            // FILL: where the row's next entry goes, and where its run ends
+    if (FILL) {
+        // the run of (row, split) ends where the next split's starts, the last one where the row ends
+        if (rin) {
+            pos = a.work[(int64_t)blockIdx.y * a.m + row0 + r];
+            end = blockIdx.y + 1 < gridDim.y ? a.work[(int64_t)(blockIdx.y + 1) * a.m + row0 + r] : a.indptr[row0 + r + 1];
+        }
+        if (t == 0) qcnt[0] = 0;
+        __syncthreads();
+        if (q == 0 && end > pos) qcnt[0] = 1;
+        __syncthreads();
+        if (!qcnt[0]) return;                            // nothing of these 64 rows lies in this split: no product
+    }
+
+    const bool owner = lane < 16;                        // of row wave * 16 + lane of the tile
+    const int orow = wave * 16 + lane;
+    int64_t xp = 0, xe = 0;                              // the row's exclusion list from the split's first column on
+    if (owner && row0 + orow < a.m && a.xptr) {
+        xp = a.xptr[row0 + orow];
+        xe = a.xptr[row0 + orow + 1];
+        const int64_t first = tile_lo * TOPK_BN;
+        if (first > 0) {
+            int64_t lo = xp, hi = xe;
+            while (lo < hi) {
+                const int64_t mid = lo + ((hi - lo) >> 1);
+                if ((int64_t)a.xidx[mid] < first) lo = mid + 1; else hi = mid;
+            }
+            xp = lo;
+        }
+    }
+    const T thr = rin ? a.thr[row0 + r] : (T)NAN;        // (a row past the end selects nothing)
+    int cnt = 0;
+
+    for (int64_t tile = tile_lo; tile < tile_hi; ++tile) {
+        const int64_t col0 = tile * TOPK_BN;
+        topk_score_tile<T>(a.H, a.ldh, a.m, row0, a.Gc, a.ldg, a.c,
+                           [&](int rr) { return col0 + rr < a.n_cols ? (int)(col0 + rr) : -1; }, buf);
+        if (owner) {
+            unsigned long long mk = 0;
+            while (xp < xe && (int64_t)a.xidx[xp] < col0 + TOPK_BN) {
+                mk |= 1ull << ((int64_t)a.xidx[xp] - col0);
+                ++xp;
+            }
+            xmask[orow] = mk;
+        }
+        __syncthreads();
+        const unsigned xm = (unsigned)(xmask[r] >> (16 * q)) & 0xffffu;
+        const unsigned mk = above_quarter_mask<T>(sc, r, q, col0, a.n_cols, xm, thr);
+        if (!FILL) {
+            cnt += __popc(mk);
+        } else {
+            qmask[q * TOPK_BM + r] = (unsigned short)mk;
+            __syncthreads();
+            int before = 0, all = 0;
+#pragma unroll
+            for (int qq = 0; qq < 4; ++qq) {
+                const int n = __popc((unsigned)qmask[qq * TOPK_BM + r]);
+                all += n;
+                if (qq < q) before += n;
+            }
+            int64_t at = pos + before;
+            unsigned left = mk;
+            while (left) {
+                const int b = __ffs((int)left) - 1;
+                left &= left - 1;
+                if (at < end) {                          // (always, the count pass ran the same predicate: a guard, not a rule)
+                    a.out_indices[at] = (int)(col0 + 16 * q + b);
+                    if (a.out_values) a.out_values[at] = sc[r * TOPK_SLD + 16 * q + b];
+                }
+                ++at;
+            }
+            pos += all;
+        }
+        // (the first barrier of the next tile's product separates these reads from the next tile and masks)
+    }
+    if (!FILL) {
+        qcnt[q * TOPK_BM + r] = cnt;
+        __syncthreads();
+        if (q == 0 && rin)
+            a.work[(int64_t)blockIdx.y * a.m + row0 + r] =
+                (int64_t)qcnt[r] + qcnt[TOPK_BM + r] + qcnt[2 * TOPK_BM + r] + qcnt[3 * TOPK_BM + r];
+    }
+}
+
+// The scan over the rows, in integers, three launches: every workgroup adds up the row totals of its chunk of rows
+// (a multiple of 256, at most ABOVE_SCAN_PARTS chunks); one workgroup turns the chunk sums into chunk starts; every
+// workgroup walks its chunk again, 256 rows at a time, and writes out_indptr[row] and, in place of the counts, the start of
+// every (row, split) run.  out_indptr[m] is the total.
+constexpr int ABOVE_SCAN_PARTS = 1024;
+
+// all 256 threads: the sum of v over the workgroup's threads before this one (exclusive) and over all of them (`total`)
+static __device__ __forceinline__ int64_t above_block_scan(int64_t v, int64_t* red, int64_t* total) {
+    const int t = threadIdx.x;
+    red[t] = v;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int64_t add = t >= off ? red[t - off] : 0;
+        __syncthreads();
+        red[t] += add;
+        __syncthreads();
+    }
+    const int64_t incl = red[t];
+    *total = red[255];
+    __syncthreads();                                     // `red` is free again
+    return incl - v;
+}
+
+static __global__ __launch_bounds__(256) void above_chunk_sums_kernel(const int64_t* __restrict__ work, int64_t m, int splits, int64_t chunk,
+                                                                      int64_t* __restrict__ parts) {
+    __shared__ int64_t red[256];
+    const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < m ? lo + chunk : m;
+    int64_t sum = 0;
+    for (int64_t row = lo + threadIdx.x; row < hi; row += 256)
+        for (int s = 0; s < splits; ++s) sum += work[(int64_t)s * m + row];
+    int64_t total;
+    above_block_scan(sum, red, &total);
+    if (threadIdx.x == 0) parts[blockIdx.x] = total;
+}
+
+// one workgroup: parts[b] becomes the entries of the chunks before b; out_indptr[m] the total
+static __global__ __launch_bounds__(256) void above_chunk_starts_kernel(int64_t* __restrict__ parts, int nparts, int64_t m,
+                                                                        int64_t* __restrict__ out_indptr) {
+    __shared__ int64_t red[256];
+    constexpr int PER = ABOVE_SCAN_PARTS / 256;          // consecutive chunks of one thread
+    const int t = threadIdx.x;
+    int64_t v[PER], sum = 0;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        v[i] = t * PER + i < nparts ? parts[t * PER + i] : 0;
+        sum += v[i];
+    }
+    int64_t total;
+    int64_t run = above_block_scan(sum, red, &total);
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        if (t * PER + i < nparts) parts[t * PER + i] = run;
+        run += v[i];
+    }
+    if (t == 0) out_indptr[m] = total;
+}
+
+static __global__ __launch_bounds__(256) void above_offsets_kernel(int64_t* __restrict__ work, int64_t m, int splits, int64_t chunk,
+                                                                   const int64_t* __restrict__ parts, int64_t* __restrict__ out_indptr) {
+    __shared__ int64_t red[256];
+    const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < m ? lo + chunk : m;
+    int64_t base = parts[blockIdx.x];
+    for (int64_t row0 = lo; row0 < hi; row0 += 256) {    // (chunk is a multiple of 256: the trip count is the workgroup's)
+        const int64_t row = row0 + threadIdx.x;
+        int64_t sum = 0;
+        if (row < hi)
+            for (int s = 0; s < splits; ++s) sum += work[(int64_t)s * m + row];
+        int64_t total;
+        int64_t at = base + above_block_scan(sum, red, &total);
+        if (row < hi) {
+            out_indptr[row] = at;
+            for (int s = 0; s < splits; ++s) {
+                const int64_t n = work[(int64_t)s * m + row];
+                work[(int64_t)s * m + row] = at;
+                at += n;
+            }
+        }
+        base += total;
     }
 }
 

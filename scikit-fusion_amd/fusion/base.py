@@ -379,6 +379,66 @@ class FusionFit(FusionBase):
             return (one(r) for r in range(self.n_run))
         return one(0 if run is None else run)
 
+    def complete_above(self, relation, threshold, rows=None, exclude=None, run=None, dtype='f64', block_rows=8192,
+                       max_entries=2 ** 28):
+        """``scipy.sparse.csr_matrix`` of shape ``(len(rows), n_j)``, float64, sorted indices: for each of ``rows``
+        (default: every row object; otherwise an integer array in any order, duplicates allowed, results in that order)
+        every column the model scores at or above ``threshold``, with its score -- what link prediction asks of
+        ``complete(relation) >= threshold`` without forming it.  ``threshold`` is a scalar or one value per row; it is
+        CAST TO THE SCORING TYPE of ``dtype`` ('f64' | 'f32' | 'bf16' -> f32) and the comparison ``score >= threshold``
+        is made in that type, under IEEE rules: a NaN score or threshold selects nothing, ``-inf`` selects every
+        admissible column.  ``exclude`` as for ``complete_topk`` (None, ``'known'`` or a scipy.sparse matrix of the
+        relation's shape): an excluded pair is never returned.  The device counts, scans and fills ``block_rows`` rows at
+        a time; nothing of size ``n_i x n_j`` is formed.  The size of the result depends on the data: once more than
+        ``max_entries`` entries are found a ``DataFusionError`` is raised, before any array of that size is allocated.  A
+        relation with a postprocessor is refused, as in ``complete_topk``.  ``n_run > 1`` and ``run=None``: a generator
+        over the runs.  Extension of the reference API."""
+        self._check_relation_types(relation)
+        if relation.postprocessor:
+            raise DataFusionError("complete_above ranks raw device scores; relation %s -> %s has a "
+                                  "postprocessor (rank complete_blocks(device=False) yourself)"
+                                  % (relation.row_type.name, relation.col_type.name))
+        import scipy.sparse
+        from .._engine import AboveLimit
+        n_i, n_j = np.shape(self.factor(relation.row_type, 0))[0], np.shape(self.factor(relation.col_type, 0))[0]
+        if rows is None:
+            rows = np.arange(n_i)
+        rows = np.asarray(rows).reshape(-1)
+        if rows.dtype.kind not in 'iu' or (rows.size and (rows.min() < 0 or rows.max() >= n_i)):
+            raise DataFusionError("rows must be integers in 0 .. %d" % (n_i - 1))
+        thr = np.asarray(threshold, dtype=np.float64)
+        if thr.ndim > 1 or (thr.ndim == 1 and thr.shape != rows.shape):
+            raise DataFusionError("threshold must be a scalar or one value per row (%d), not of shape %r"
+                                  % (rows.size, tuple(thr.shape)))
+        lists = self._exclusion_lists(relation, exclude, (n_i, n_j))
+        step = max(1, int(block_rows))
+        limit = int(max_entries)
+
+        def one(r):
+            G1, comp = self._completer(relation, r, dtype)
+            indptr = np.zeros(rows.size + 1, dtype=np.int64)
+            idx, val, found = [], [], 0
+            for b0 in range(0, rows.size, step):
+                blk = rows[b0:b0 + step]
+                try:
+                    p, i, v = comp.above(G1[blk], thr[b0:b0 + step] if thr.ndim else thr, exclude=lists(blk) if lists else None,
+                                         max_entries=limit - found)
+                except AboveLimit as over:
+                    raise DataFusionError("complete_above: %d entries at or above the threshold in the first %d rows, "
+                                          "max_entries = %d (raise the threshold or max_entries)"
+                                          % (found + over.found, b0 + blk.size, limit))
+                indptr[b0 + 1:b0 + blk.size + 1] = found + p[1:]
+                found += int(p[-1])
+                idx.append(i)
+                val.append(v)
+            out = scipy.sparse.csr_matrix((np.concatenate(val) if val else np.zeros(0), np.concatenate(idx) if idx else
+                                           np.zeros(0, dtype=np.int32), indptr), shape=(rows.size, n_j))
+            out.has_sorted_indices = True      # (ascending within a row by construction)
+            return out
+        if self.n_run > 1 and run is None:
+            return (one(r) for r in range(self.n_run))
+        return one(0 if run is None else run)
+
 
 # ---- persistence of a fitted model (SURVEY.md 8 f4; the reference has none: its accessors base.py:35-56,
 # 169-189 are the only consumers of factors_ / backbones_) ----------------------------------------------
