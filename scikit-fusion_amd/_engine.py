@@ -4,6 +4,7 @@
 _dfmf.py:330), keeps every matrix resident in HBM for the whole ``max_iter`` loop and copies
 ``G`` / ``S`` back once at the end (or per iteration when a callback is installed).
 """
+import contextlib
 import os
 import ctypes as C
 
@@ -1343,6 +1344,35 @@ class DeviceCompleter(object):
             raise ValueError('shape mismatch in completion')
         return A
 
+    @staticmethod
+    def _exclusion(exclude, m):
+        """[] or ``[indptr int64, indices int32]`` of the block's exclusion lists, checked against its ``m`` rows (host work
+        only: a shape error costs no upload)."""
+        if exclude is None:
+            return []
+        xl = [np.ascontiguousarray(exclude[0], dtype=np.int64), np.ascontiguousarray(exclude[1], dtype=np.int32)]
+        if xl[0].shape != (m + 1,):
+            raise ValueError('exclude: indptr must have one entry per row of the block, plus one')
+        return xl
+
+    @contextlib.contextmanager
+    def _on_device(self, A, own, xl):
+        """What ``topk``, ``ranks`` and ``above`` hold on the device for one block: ``H = A S`` and the uploads of the
+        method's ``own`` host arrays and of the exclusion lists ``xl``, all accounted in ``_transient`` and released on
+        the way out, whatever happened.  Yields ``(h, pointers of own, excl_indptr, excl_indices)``, the last two None
+        without lists."""
+        h, a = self._h(A)
+        held = self._transient
+        bufs = []
+        if own or xl:
+            bufs = self._upload(list(own) + xl)
+            self._transient += held
+        try:
+            yield h, [b.ptr for b in bufs[:len(own)]], bufs[-2].ptr if xl else None, bufs[-1].ptr if xl else None
+        finally:
+            del a, bufs
+            self._transient = 0
+
     def topk(self, G_row_block, k, exclude=None, col_splits=0):
         """``(idx int32 [m, k], val float64 [m, k])``: per row of the block the ``k`` best columns, best first -- higher
         score first, equal scores by lower column, NaN never; slots no candidate fills hold ``-1`` / ``-inf``.
@@ -1356,32 +1386,15 @@ class DeviceCompleter(object):
         rt.call('skf_complete_topk_workspace_bytes', self.code, m, self.nj, k, int(col_splits), C.byref(need))
         if m == 0:
             return np.zeros((0, k), dtype=np.int32), np.zeros((0, k), dtype=np.float64)
-        xp = xi = None
-        keep = []
-        if exclude is not None:
-            indptr = np.ascontiguousarray(exclude[0], dtype=np.int64)
-            indices = np.ascontiguousarray(exclude[1], dtype=np.int32)
-            if indptr.shape != (m + 1,):
-                raise ValueError('exclude: indptr must have one entry per row of the block, plus one')
-            keep = [indptr, indices]
-        h, a = self._h(A)
-        held = self._transient
-        if keep:
-            xp, xi = self._upload(keep)
-            self._transient += held
-        ws = self._scratch('ws', need.value)
-        oi = self._scratch('idx', m * k * 4)
-        ov = self._scratch('val', m * k * self.es)
-        self.peak_bytes = max(self.peak_bytes, self.device_bytes)
-        try:
-            rt.call('skf_complete_topk', self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, k,
-                    xp.ptr if xp else None, xi.ptr if xi else None, oi.ptr, k, ov.ptr, k, int(col_splits), ws.ptr, ws.nbytes,
-                    mem.stream)
+        with self._on_device(A, [], self._exclusion(exclude, m)) as (h, _, xp, xi):
+            ws = self._scratch('ws', need.value)
+            oi = self._scratch('idx', m * k * 4)
+            ov = self._scratch('val', m * k * self.es)
+            self.peak_bytes = max(self.peak_bytes, self.device_bytes)
+            rt.call('skf_complete_topk', self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, k, xp, xi,
+                    oi.ptr, k, ov.ptr, k, int(col_splits), ws.ptr, ws.nbytes, mem.stream)
             mem.synchronize()
             return mem.to_host(oi, (m, k), np.int32), mem.to_host(ov, (m, k), self.npd).astype(np.float64)
-        finally:
-            del a, xp, xi
-            self._transient = 0
 
     def ranks(self, G_row_block, targets, exclude=None, col_splits=0):
         """``(rank int32 [n], val float64 [n])`` for the ``n`` target pairs of the block, in list order: ``rank`` is the
@@ -1395,37 +1408,24 @@ class DeviceCompleter(object):
         A = self._rows_of(G_row_block)
         m = A.shape[0]
         rt, mem = self.rt, self.rt.mem
-        keep = [np.ascontiguousarray(targets[0], dtype=np.int64), np.ascontiguousarray(targets[1], dtype=np.int32)]
-        if keep[0].shape != (m + 1,):
+        tgt = [np.ascontiguousarray(targets[0], dtype=np.int64), np.ascontiguousarray(targets[1], dtype=np.int32)]
+        if tgt[0].shape != (m + 1,):
             raise ValueError('targets: indptr must have one entry per row of the block, plus one')
-        n = int(keep[1].size)
-        if exclude is not None:
-            keep += [np.ascontiguousarray(exclude[0], dtype=np.int64), np.ascontiguousarray(exclude[1], dtype=np.int32)]
-            if keep[2].shape != (m + 1,):
-                raise ValueError('exclude: indptr must have one entry per row of the block, plus one')
+        n = int(tgt[1].size)
+        xl = self._exclusion(exclude, m)
         need = C.c_size_t()
         rt.call('skf_complete_ranks_workspace_bytes', self.code, m, self.nj, n, int(col_splits), C.byref(need))
         if n == 0:
             return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float64)
-        h, a = self._h(A)
-        held = self._transient
-        bufs = self._upload(keep)
-        self._transient += held
-        tp, ti = bufs[0], bufs[1]
-        xp, xi = (bufs[2], bufs[3]) if exclude is not None else (None, None)
-        ws = self._scratch('ws', need.value)
-        orank = self._scratch('rank', n * 4)
-        oval = self._scratch('rank_val', n * self.es)
-        self.peak_bytes = max(self.peak_bytes, self.device_bytes)
-        try:
-            rt.call('skf_complete_ranks', self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, tp.ptr, ti.ptr, n,
-                    xp.ptr if xp else None, xi.ptr if xi else None, orank.ptr, oval.ptr, int(col_splits), ws.ptr, ws.nbytes,
-                    mem.stream)
+        with self._on_device(A, tgt, xl) as (h, (tp, ti), xp, xi):
+            ws = self._scratch('ws', need.value)
+            orank = self._scratch('rank', n * 4)
+            oval = self._scratch('rank_val', n * self.es)
+            self.peak_bytes = max(self.peak_bytes, self.device_bytes)
+            rt.call('skf_complete_ranks', self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, tp, ti, n, xp, xi,
+                    orank.ptr, oval.ptr, int(col_splits), ws.ptr, ws.nbytes, mem.stream)
             mem.synchronize()
             return mem.to_host(orank, (n,), np.int32), mem.to_host(oval, (n,), self.npd).astype(np.float64)
-        finally:
-            del a, bufs, tp, ti, xp, xi
-            self._transient = 0
 
     ABOVE_PER_ROW = 64                   # entries per row the first call of `above` makes room for
 
@@ -1445,37 +1445,27 @@ class DeviceCompleter(object):
         t = np.asarray(thr, dtype=np.float64)
         if t.ndim > 1 or (t.ndim == 1 and t.shape != (m,)):
             raise ValueError('thr: a scalar or one value per row of the block')
-        keep = [np.ascontiguousarray(np.broadcast_to(t.astype(self.npd), (m,)))]
-        if exclude is not None:
-            keep += [np.ascontiguousarray(exclude[0], dtype=np.int64), np.ascontiguousarray(exclude[1], dtype=np.int32)]
-            if keep[1].shape != (m + 1,):
-                raise ValueError('exclude: indptr must have one entry per row of the block, plus one')
+        own = [np.ascontiguousarray(np.broadcast_to(t.astype(self.npd), (m,)))]
+        xl = self._exclusion(exclude, m)
         need = C.c_size_t()
         rt.call('skf_complete_above_workspace_bytes', self.code, m, self.nj, int(col_splits), C.byref(need))
         if m == 0:
             return np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float64)
-        h, a = self._h(A)
-        held = self._transient
-        bufs = self._upload(keep)
-        self._transient += held
-        bt = bufs[0]
-        xp, xi = (bufs[1], bufs[2]) if exclude is not None else (None, None)
-        ws = self._scratch('ws', need.value)
-        op = self._scratch('above_ptr', (m + 1) * 8)
-        if capacity is None:
-            have = self._bufs.get('above_idx')
-            cap = min(m * self.nj, max(self.ABOVE_PER_ROW * m, have.nbytes // 4 if have else 0))
-        else:
-            cap = int(capacity)
-        found = C.c_int64(-1)
-        try:
+        with self._on_device(A, own, xl) as (h, (bt,), xp, xi):
+            ws = self._scratch('ws', need.value)
+            op = self._scratch('above_ptr', (m + 1) * 8)
+            if capacity is None:
+                have = self._bufs.get('above_idx')
+                cap = min(m * self.nj, max(self.ABOVE_PER_ROW * m, have.nbytes // 4 if have else 0))
+            else:
+                cap = int(capacity)
+            found = C.c_int64(-1)
             for attempt in (0, 1):
                 oi = self._scratch('above_idx', max(cap, 1) * 4)
                 ov = self._scratch('above_val', max(cap, 1) * self.es)
                 self.peak_bytes = max(self.peak_bytes, self.device_bytes)
-                rc = rt.lib.skf_complete_above(self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, bt.ptr,
-                                               xp.ptr if xp else None, xi.ptr if xi else None, cap, op.ptr, oi.ptr, ov.ptr,
-                                               C.byref(found), int(col_splits), ws.ptr, ws.nbytes, mem.stream)
+                rc = rt.lib.skf_complete_above(self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, bt, xp, xi, cap,
+                                               op.ptr, oi.ptr, ov.ptr, C.byref(found), int(col_splits), ws.ptr, ws.nbytes, mem.stream)
                 mem.synchronize()
                 n = found.value
                 if max_entries is not None and n > max_entries:
@@ -1485,9 +1475,6 @@ class DeviceCompleter(object):
                     break
                 cap = n                  # the count pass has said how many there are: once more, with room for them
             return mem.to_host(op, (m + 1,), np.int64), mem.to_host(oi, (n,), np.int32), mem.to_host(ov, (n,), self.npd).astype(np.float64)
-        finally:
-            del a, bufs, bt, xp, xi
-            self._transient = 0
 
     def entries(self, G_row, rows, cols):
         """``float64 [n]``: ``X[rows[e], cols[e]]``.  Only the DISTINCT rows of ``G_row`` that ``rows`` names are uploaded

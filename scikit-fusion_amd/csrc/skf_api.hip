@@ -1,5 +1,6 @@
 // skf_api.hip -- C ABI (include/skfusion_hip.h) and the host-side plan / launch schedule of the
-// DFMF / DFMC / fold-in iteration.  Kernels: skf_kernels.h; the pseudo-inverse: skf_pinv.h.
+// DFMF / DFMC / fold-in iteration.  Kernels: skf_kernels.h; the pseudo-inverse: skf_pinv.h; the completion operators
+// (skf_complete_*): kernels skf_complete.h, host side and entry points skf_complete.inc.
 //
 // One iteration (reference _dfmf.py:228-296, 2-GEMM form of SURVEY.md 7.0; everything reads the
 // OLD factors, G is replaced at the very end):
@@ -126,6 +127,8 @@ static inline int wave_grid(int64_t rows) {
 #include "skf_schedule.inc"
 
 #include "skf_bind.inc"
+
+#include "skf_complete.inc"
 
 }  // namespace skf
 
@@ -1642,384 +1645,6 @@ int skf_fold_lists(int32_t dtype, const int64_t* indptr, const int32_t* indices,
             launch_fold_lists<double>(indptr, (const int*)indices, values, n_out, T, ldt, c, Ec, lde, Dc, ldd, as_stream(stream));
         else
             launch_fold_lists<float>(indptr, (const int*)indices, values, n_out, T, ldt, c, Ec, lde, Dc, ldd, as_stream(stream));
-    });
-}
-
-}  // extern "C"
-
-// ---- top-k completion and entry predictions (skf_complete.h) ---------------------------------------------------------
-static_assert(SKF_TOPK_MAX == SKF_TOPK_MAX_K, "include/skfusion_hip.h and skf_complete.h disagree on the list length");
-
-// The ONE place the column splits of a top-k launch are decided: the workspace query and the launch both call it, so a
-// query with col_splits = 0 sizes for what the launch will choose.  A split is a whole number of 64-column tiles; a chosen
-// count aims at two workgroups per compute unit (256 CUs) and keeps at least four tiles per split, so that the partial
-// lists and their merge stay small next to the pass; a requested count is only clamped to what exists.
-static int topk_col_splits(int64_t m, int64_t n_cols, int want) {
-    const int64_t ntiles = std::max<int64_t>(1, (n_cols + TOPK_BN - 1) / TOPK_BN);
-    const int64_t row_tiles = std::max<int64_t>(1, (m + TOPK_BM - 1) / TOPK_BM);
-    int64_t s = want;
-    if (want <= 0) {
-        s = (512 + row_tiles - 1) / row_tiles;
-        s = std::min<int64_t>(s, std::max<int64_t>(1, ntiles / 4));
-    }
-    s = std::min<int64_t>(std::min<int64_t>(s, TOPK_MAX_SPLITS), ntiles);
-    return (int)std::max<int64_t>(1, s);
-}
-
-// [0, 256): the flag of the exclusion check; then, for more than one split, the partial lists: values [splits][m][k],
-// indices [splits][m][k]
-static size_t topk_workspace(size_t esz, int64_t m, int k, int splits) {
-    size_t b = 256;
-    if (splits > 1) b += align_up((size_t)splits * m * k * esz, 256) + align_up((size_t)splits * m * k * sizeof(int), 256);
-    return b;
-}
-
-static void topk_check_shape(int32_t dtype, int64_t m, int64_t n_cols, int32_t k, int32_t col_splits) {
-    if (dtype != SKF_F64 && dtype != SKF_F32) SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: dtype must be SKF_F64 / SKF_F32");
-    if (k < 1 || k > SKF_TOPK_MAX) SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: k = %d outside 1 .. %d", k, SKF_TOPK_MAX);
-    if (m < 0 || m >= (1LL << 31) || n_cols < 0 || n_cols >= (1LL << 31))
-        SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: m = %lld / n_cols = %lld outside 0 .. 2^31 - 1", (long long)m, (long long)n_cols);
-    if (col_splits < 0) SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: col_splits = %d is negative", col_splits);
-}
-
-template <typename T>
-static void launch_complete_topk(const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int c, int k,
-                                 const int64_t* xptr, const int* xidx, int* out_idx, int64_t ld_idx, void* out_val, int64_t ld_val,
-                                 int splits, char* ws, hipStream_t st) {
-    TopkArgs<T> a;
-    a.H = (const T*)H; a.ldh = ldh; a.m = m;
-    a.Gc = (const T*)Gc; a.ldg = ldg; a.n_cols = n_cols;
-    a.c = c; a.k = k;
-    a.xptr = xptr; a.xidx = xidx;
-    const int64_t ntiles = (n_cols + TOPK_BN - 1) / TOPK_BN;
-    a.tiles_per_split = (int)std::max<int64_t>(1, (ntiles + splits - 1) / splits);
-    a.out_idx = out_idx; a.ld_idx = ld_idx; a.out_val = (T*)out_val; a.ld_val = ld_val;
-    a.part_val = (T*)(ws + 256);
-    a.part_idx = (int*)(ws + 256 + align_up((size_t)splits * m * k * sizeof(T), 256));
-    static DeviceOnce once;
-    allow_dynamic_lds(once, complete_topk_kernel<T>, (int)topk_list_bytes(SKF_TOPK_MAX, sizeof(T)));
-    const int row_tiles = cdiv(m, TOPK_BM);
-    hipLaunchKernelGGL((complete_topk_kernel<T>), dim3(row_tiles, splits), dim3(TOPK_THREADS), topk_list_bytes(k, sizeof(T)), st, a);
-    check_launch("complete_topk");
-    if (splits > 1) {
-        hipLaunchKernelGGL((complete_topk_merge_kernel<T>), dim3(elem_grid(m)), dim3(256), 0, st, a.part_idx, a.part_val, m, k, splits,
-                           out_idx, ld_idx, (T*)out_val, ld_val);
-        check_launch("complete_topk_merge");
-    }
-}
-
-template <typename T>
-static void launch_complete_entries(const void* H, int64_t ldh, const void* Gc, int64_t ldg, int c, const int* rows, const int* cols,
-                                    int64_t n, void* out, hipStream_t st) {
-    const int64_t waves = (n + 3) / 4;                      // four entries per wave and step
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, 4096));
-    hipLaunchKernelGGL((complete_entries_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)H, ldh, (const T*)Gc, ldg, c, rows, cols, n,
-                       (T*)out);
-    check_launch("complete_entries");
-}
-
-// ranks of given pairs.  Workspace: [0, 256) the flag word of the list checks; [256, 512) the RANK_MAX_PARTS partial maxima
-// of rank_longest_row_kernel; then the scores of the targets, used when the caller keeps none (out_val NULL) -- the query
-// cannot know and sizes for them.  Nothing here grows with m x n_cols.  The column splits are topk_col_splits': one
-// decision for both operators.
-static size_t ranks_workspace(size_t esz, int64_t n_targets) { return 512 + align_up((size_t)n_targets * esz, 256); }
-
-static void ranks_check_shape(int32_t dtype, int64_t m, int64_t n_cols, int64_t n_targets, int32_t col_splits) {
-    if (dtype != SKF_F64 && dtype != SKF_F32) SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: dtype must be SKF_F64 / SKF_F32");
-    if (m < 0 || m >= (1LL << 31) || n_cols < 0 || n_cols >= (1LL << 31))
-        SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: m = %lld / n_cols = %lld outside 0 .. 2^31 - 1", (long long)m, (long long)n_cols);
-    if (n_targets < 0) SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: n_targets = %lld is negative", (long long)n_targets);
-    if (col_splits < 0 || col_splits > TOPK_MAX_SPLITS)
-        SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: col_splits = %d outside 0 .. %d", col_splits, TOPK_MAX_SPLITS);
-}
-
-template <typename T>
-static void launch_complete_ranks(const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int c,
-                                  const int64_t* tptr, const int* tidx, const int64_t* xptr, const int* xidx, int* out_rank, void* val,
-                                  int splits, int64_t longest, hipStream_t st) {
-    RankArgs<T> a;
-    a.H = (const T*)H; a.ldh = ldh; a.m = m;
-    a.Gc = (const T*)Gc; a.ldg = ldg; a.n_cols = n_cols;
-    a.c = c;
-    a.tptr = tptr; a.tidx = tidx; a.xptr = xptr; a.xidx = xidx;
-    const int64_t ntiles = (n_cols + TOPK_BN - 1) / TOPK_BN;
-    a.tiles_per_split = (int)std::max<int64_t>(1, (ntiles + splits - 1) / splits);
-    a.out_rank = out_rank; a.val = (T*)val;
-    const int row_tiles = cdiv(m, TOPK_BM);
-    hipLaunchKernelGGL((complete_rank_scores_kernel<T>), dim3(row_tiles), dim3(TOPK_THREADS), 0, st, a);
-    check_launch("complete_rank_scores");
-    // one workgroup per chunk of the longest row (a workgroup strides over the chunks beyond what one grid dimension holds)
-    const int64_t chunks = (longest + RANK_CHUNK - 1) / RANK_CHUNK;
-    a.chunk_groups = (int)std::max<int64_t>(1, std::min<int64_t>(chunks, 0x7fffffff / row_tiles));
-    static DeviceOnce once;
-    allow_dynamic_lds(once, complete_rank_count_kernel<T>, (int)rank_chunk_bytes(sizeof(T)));
-    hipLaunchKernelGGL((complete_rank_count_kernel<T>), dim3((unsigned)a.chunk_groups * row_tiles, splits), dim3(TOPK_THREADS), rank_chunk_bytes(sizeof(T)), st, a);
-    check_launch("complete_rank_count");
-}
-
-// every pair at or above a threshold.  Workspace: [0, 256) the flag word of the exclusion check; then the ABOVE_SCAN_PARTS
-// chunk sums of the scan; then one int64 per (split, row): the counts of the count pass, turned into the starts of the fill
-// pass in place.  Nothing here grows with m x n_cols.  The column splits are topk_col_splits'.
-static size_t above_workspace(int64_t m, int splits) {
-    return 256 + ABOVE_SCAN_PARTS * sizeof(int64_t) + align_up((size_t)splits * (size_t)m * sizeof(int64_t), 256);
-}
-
-static void above_check_shape(int32_t dtype, int64_t m, int64_t n_cols, int32_t col_splits) {
-    if (dtype != SKF_F64 && dtype != SKF_F32) SKF_FAIL(SKF_E_INVALID, "skf_complete_above: dtype must be SKF_F64 / SKF_F32");
-    if (m < 0 || m >= (1LL << 31) || n_cols < 0 || n_cols >= (1LL << 31))
-        SKF_FAIL(SKF_E_INVALID, "skf_complete_above: m = %lld / n_cols = %lld outside 0 .. 2^31 - 1", (long long)m, (long long)n_cols);
-    if (col_splits < 0 || col_splits > TOPK_MAX_SPLITS)
-        SKF_FAIL(SKF_E_INVALID, "skf_complete_above: col_splits = %d outside 0 .. %d", col_splits, TOPK_MAX_SPLITS);
-}
-
-template <typename T>
-static AboveArgs<T> above_args(const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int c, const void* thr,
-                               const int64_t* xptr, const int* xidx, int splits, char* ws, const int64_t* indptr, int* out_indices,
-                               void* out_values) {
-    AboveArgs<T> a;
-    a.H = (const T*)H; a.ldh = ldh; a.m = m;
-    a.Gc = (const T*)Gc; a.ldg = ldg; a.n_cols = n_cols;
-    a.c = c;
-    a.thr = (const T*)thr;
-    a.xptr = xptr; a.xidx = xidx;
-    const int64_t ntiles = (n_cols + TOPK_BN - 1) / TOPK_BN;
-    a.tiles_per_split = (int)std::max<int64_t>(1, (ntiles + splits - 1) / splits);
-    a.work = (int64_t*)(ws + 256 + ABOVE_SCAN_PARTS * sizeof(int64_t));
-    a.indptr = indptr;
-    a.out_indices = out_indices; a.out_values = (T*)out_values;
-    return a;
-}
-
-// the count pass and the scan: out_indptr (the total at [m]) and the (row, split) starts in the workspace
-template <typename T>
-static void launch_above_count(const AboveArgs<T>& a, int splits, char* ws, int64_t* out_indptr, hipStream_t st) {
-    const int row_tiles = cdiv(a.m, TOPK_BM);
-    hipLaunchKernelGGL((complete_above_kernel<T, false>), dim3(row_tiles, splits), dim3(TOPK_THREADS), 0, st, a);
-    check_launch("complete_above_count");
-    int64_t* parts = (int64_t*)(ws + 256);
-    const int64_t want = std::min<int64_t>(ABOVE_SCAN_PARTS, (a.m + 255) / 256);
-    const int64_t chunk = ((a.m + want - 1) / want + 255) / 256 * 256;           // rows per workgroup: a multiple of 256
-    const int nparts = (int)((a.m + chunk - 1) / chunk);
-    hipLaunchKernelGGL(above_chunk_sums_kernel, dim3(nparts), dim3(256), 0, st, (const int64_t*)a.work, a.m, splits, chunk, parts);
-    check_launch("above_chunk_sums");
-    hipLaunchKernelGGL(above_chunk_starts_kernel, dim3(1), dim3(256), 0, st, parts, nparts, a.m, out_indptr);
-    check_launch("above_chunk_starts");
-    hipLaunchKernelGGL(above_offsets_kernel, dim3(nparts), dim3(256), 0, st, a.work, a.m, splits, chunk, (const int64_t*)parts, out_indptr);
-    check_launch("above_offsets");
-}
-
-template <typename T>
-static void launch_above_fill(const AboveArgs<T>& a, int splits, hipStream_t st) {
-    hipLaunchKernelGGL((complete_above_kernel<T, true>), dim3(cdiv(a.m, TOPK_BM), splits), dim3(TOPK_THREADS), 0, st, a);
-    check_launch("complete_above_fill");
-}
-
-// count, scan, ONE read-back of the total, then -- unless the caller asked for the count alone or has too little room -- fill
-template <typename T>
-static void run_complete_above(const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int c, const void* thr,
-                               const int64_t* xptr, const int* xidx, int64_t capacity, int64_t* out_indptr, int* out_indices,
-                               void* out_values, int64_t* n_found, int splits, char* ws, hipStream_t st) {
-    const AboveArgs<T> a = above_args<T>(H, ldh, m, Gc, ldg, n_cols, c, thr, xptr, xidx, splits, ws, out_indptr, out_indices, out_values);
-    launch_above_count<T>(a, splits, ws, out_indptr, st);
-    int64_t total = -1;
-    SKF_HIP(hipMemcpyAsync(&total, out_indptr + m, sizeof total, hipMemcpyDeviceToHost, st));
-    SKF_HIP(hipStreamSynchronize(st));
-    *n_found = total;
-    if (!out_indices) return;                           // count only
-    if (total > capacity)
-        SKF_FAIL(SKF_E_WORKSPACE, "skf_complete_above: %lld entries found, capacity %lld (out_indptr and *n_found are written: "
-                 "call again with that capacity)", (long long)total, (long long)capacity);
-    if (total > 0) launch_above_fill<T>(a, splits, st);
-}
-
-extern "C" {
-
-int skf_complete_topk_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int32_t k, int32_t col_splits, size_t* bytes) {
-    return guarded([&] {
-        if (!bytes) SKF_FAIL(SKF_E_INVALID, "null argument");
-        topk_check_shape(dtype, m, n_cols, k, col_splits);
-        *bytes = topk_workspace(dtype == SKF_F64 ? 8 : 4, m, k, topk_col_splits(m, n_cols, col_splits));
-    });
-}
-
-int skf_complete_topk(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int32_t c,
-                      int32_t k, const int64_t* excl_indptr, const int32_t* excl_indices, int32_t* out_idx, int64_t ld_idx,
-                      void* out_val, int64_t ld_val, int32_t col_splits, void* workspace, size_t workspace_bytes, void* stream) {
-    return guarded([&] {
-        topk_check_shape(dtype, m, n_cols, k, col_splits);
-        if (c < 1 || c > 1024) SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: width c = %d outside 1 .. 1024", c);
-        if (!H || !Gc || !out_idx || !out_val) SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: null argument");
-        if ((excl_indptr == nullptr) != (excl_indices == nullptr))
-            SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: excl_indptr and excl_indices come together (both NULL: no exclusion)");
-        if (ldh < c || ldg < c || ld_idx < k || ld_val < k) SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: ld too small");
-        const size_t esz = dtype == SKF_F64 ? 8 : 4;
-        const int splits = topk_col_splits(m, n_cols, col_splits);
-        const size_t need = topk_workspace(esz, m, k, splits);
-        if (!workspace || workspace_bytes < need)
-            SKF_FAIL(SKF_E_WORKSPACE, "skf_complete_topk: workspace %zu B < required %zu B (or null)", workspace ? workspace_bytes : (size_t)0, need);
-        if (((uintptr_t)workspace & 255) != 0) SKF_FAIL(SKF_E_WORKSPACE, "skf_complete_topk: workspace must be 256-byte aligned");
-        if (m == 0) return;
-        hipStream_t st = as_stream(stream);
-        if (excl_indptr) {
-            // the number of entries is the list's own last pointer; everything else is checked against it on the device
-            // before anything walks the lists
-            int64_t nnz = -1;
-            SKF_HIP(hipMemcpyAsync(&nnz, excl_indptr + m, sizeof nnz, hipMemcpyDeviceToHost, st));
-            SKF_HIP(hipStreamSynchronize(st));
-            if (nnz < 0 || !csr_is_canonical(excl_indptr, (const int*)excl_indices, m, n_cols, nnz, (int*)workspace, st))
-                SKF_FAIL(SKF_E_INVALID, "skf_complete_topk: the exclusion lists are not canonical for %lld rows x %lld columns (indptr from 0 "
-                         "to the count, non-decreasing; indices in range and strictly ascending within a row)", (long long)m, (long long)n_cols);
-        }
-        if (dtype == SKF_F64)
-            launch_complete_topk<double>(H, ldh, m, Gc, ldg, n_cols, c, k, excl_indptr, (const int*)excl_indices, out_idx, ld_idx, out_val,
-                                         ld_val, splits, (char*)workspace, st);
-        else
-            launch_complete_topk<float>(H, ldh, m, Gc, ldg, n_cols, c, k, excl_indptr, (const int*)excl_indices, out_idx, ld_idx, out_val,
-                                        ld_val, splits, (char*)workspace, st);
-    });
-}
-
-int skf_complete_entries(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int32_t c,
-                         const int32_t* rows, const int32_t* cols, int64_t n, void* out, void* stream) {
-    return guarded([&] {
-        if (dtype != SKF_F64 && dtype != SKF_F32) SKF_FAIL(SKF_E_INVALID, "skf_complete_entries: dtype must be SKF_F64 / SKF_F32");
-        if (c < 1 || c > 1024) SKF_FAIL(SKF_E_INVALID, "skf_complete_entries: width c = %d outside 1 .. 1024", c);
-        if (m < 0 || m >= (1LL << 31) || n_cols < 0 || n_cols >= (1LL << 31) || n < 0)
-            SKF_FAIL(SKF_E_INVALID, "skf_complete_entries: m = %lld / n_cols = %lld / n = %lld", (long long)m, (long long)n_cols, (long long)n);
-        if (!H || !Gc || !rows || !cols || !out) SKF_FAIL(SKF_E_INVALID, "skf_complete_entries: null argument");
-        if (ldh < c || ldg < c) SKF_FAIL(SKF_E_INVALID, "skf_complete_entries: ld too small");
-        if (n == 0) return;
-        hipStream_t st = as_stream(stream);
-        // the index check needs one device word and this operator has no workspace: the first word of `out` serves (every
-        // out[e] is overwritten by the pass) and gets its old content back when the entries are refused
-        int keep = 0;
-        int* flag = (int*)out;
-        SKF_HIP(hipMemcpyAsync(&keep, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-        const int bad = device_flag(flag, st, [&] {
-            hipLaunchKernelGGL(complete_entries_check_kernel, dim3(elem_grid(n)), dim3(256), 0, st, (const int*)rows, (const int*)cols, n, m, n_cols, flag);
-            check_launch("complete_entries_check");
-        });
-        if (bad) {
-            SKF_HIP(hipMemcpyAsync(flag, &keep, sizeof(int), hipMemcpyHostToDevice, st));
-            SKF_HIP(hipStreamSynchronize(st));
-            SKF_FAIL(SKF_E_INVALID, "skf_complete_entries: an entry names a row outside 0 .. %lld or a column outside 0 .. %lld",
-                     (long long)m - 1, (long long)n_cols - 1);
-        }
-        if (dtype == SKF_F64) launch_complete_entries<double>(H, ldh, Gc, ldg, c, (const int*)rows, (const int*)cols, n, out, st);
-        else launch_complete_entries<float>(H, ldh, Gc, ldg, c, (const int*)rows, (const int*)cols, n, out, st);
-    });
-}
-
-int skf_complete_ranks_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int64_t n_targets, int32_t col_splits, size_t* bytes) {
-    return guarded([&] {
-        if (!bytes) SKF_FAIL(SKF_E_INVALID, "null argument");
-        ranks_check_shape(dtype, m, n_cols, n_targets, col_splits);
-        *bytes = ranks_workspace(dtype == SKF_F64 ? 8 : 4, n_targets);
-    });
-}
-
-int skf_complete_ranks(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int32_t c,
-                       const int64_t* tgt_indptr, const int32_t* tgt_indices, int64_t n_targets, const int64_t* excl_indptr,
-                       const int32_t* excl_indices, int32_t* out_rank, void* out_val, int32_t col_splits, void* workspace,
-                       size_t workspace_bytes, void* stream) {
-    return guarded([&] {
-        ranks_check_shape(dtype, m, n_cols, n_targets, col_splits);
-        if (c < 1 || c > 1024) SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: width c = %d outside 1 .. 1024", c);
-        if (!H || !Gc || !out_rank || !tgt_indptr || !tgt_indices) SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: null argument");
-        if ((excl_indptr == nullptr) != (excl_indices == nullptr))
-            SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: excl_indptr and excl_indices come together (both NULL: no exclusion)");
-        if (ldh < c || ldg < c) SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: ld too small");
-        const size_t esz = dtype == SKF_F64 ? 8 : 4;
-        const size_t need = ranks_workspace(esz, n_targets);
-        if (!workspace || workspace_bytes < need)
-            SKF_FAIL(SKF_E_WORKSPACE, "skf_complete_ranks: workspace %zu B < required %zu B (or null)", workspace ? workspace_bytes : (size_t)0, need);
-        if (((uintptr_t)workspace & 255) != 0) SKF_FAIL(SKF_E_WORKSPACE, "skf_complete_ranks: workspace must be 256-byte aligned");
-        if (n_targets == 0) return;
-        hipStream_t st = as_stream(stream);
-        char* ws = (char*)workspace;
-        // the target lists against the caller's count (tgt_indptr[m] == n_targets is part of the check), and in the same
-        // round trip the longest row, which sizes the chunk grid (read only once the lists have passed)
-        int* parts = (int*)(ws + 256);
-        const int nparts = (int)std::max<int64_t>(1, std::min<int64_t>(RANK_MAX_PARTS, (m + 255) / 256));
-        SKF_HIP(hipMemsetAsync(parts, 0, RANK_MAX_PARTS * sizeof(int), st));
-        if (!csr_is_canonical(tgt_indptr, (const int*)tgt_indices, m, n_cols, n_targets, (int*)ws, st, [&] {
-                hipLaunchKernelGGL(rank_longest_row_kernel, dim3(nparts), dim3(256), 0, st, tgt_indptr, m, parts);
-                check_launch("rank_longest_row");
-            }))
-            SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: the target lists are not canonical for %lld rows x %lld columns and %lld targets "
-                     "(indptr from 0 to the count, non-decreasing; indices in range and strictly ascending within a row)",
-                     (long long)m, (long long)n_cols, (long long)n_targets);
-        if (excl_indptr) {
-            int64_t nnz = -1;
-            SKF_HIP(hipMemcpyAsync(&nnz, excl_indptr + m, sizeof nnz, hipMemcpyDeviceToHost, st));
-            SKF_HIP(hipStreamSynchronize(st));
-            if (nnz < 0 || !csr_is_canonical(excl_indptr, (const int*)excl_indices, m, n_cols, nnz, (int*)ws, st))
-                SKF_FAIL(SKF_E_INVALID, "skf_complete_ranks: the exclusion lists are not canonical for %lld rows x %lld columns (indptr from 0 "
-                         "to the count, non-decreasing; indices in range and strictly ascending within a row)", (long long)m, (long long)n_cols);
-        }
-        int longest[RANK_MAX_PARTS];
-        SKF_HIP(hipMemcpyAsync(longest, parts, sizeof longest, hipMemcpyDeviceToHost, st));
-        SKF_HIP(hipStreamSynchronize(st));
-        const int64_t longest_row = *std::max_element(longest, longest + RANK_MAX_PARTS);
-        const int splits = topk_col_splits(m, n_cols, col_splits);
-        void* val = out_val ? out_val : (void*)(ws + 512);
-        if (dtype == SKF_F64)
-            launch_complete_ranks<double>(H, ldh, m, Gc, ldg, n_cols, c, tgt_indptr, (const int*)tgt_indices, excl_indptr,
-                                          (const int*)excl_indices, out_rank, val, splits, longest_row, st);
-        else
-            launch_complete_ranks<float>(H, ldh, m, Gc, ldg, n_cols, c, tgt_indptr, (const int*)tgt_indices, excl_indptr,
-                                         (const int*)excl_indices, out_rank, val, splits, longest_row, st);
-    });
-}
-
-int skf_complete_above_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int32_t col_splits, size_t* bytes) {
-    return guarded([&] {
-        if (!bytes) SKF_FAIL(SKF_E_INVALID, "null argument");
-        above_check_shape(dtype, m, n_cols, col_splits);
-        *bytes = above_workspace(m, topk_col_splits(m, n_cols, col_splits));
-    });
-}
-
-int skf_complete_above(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int32_t c,
-                       const void* thr, const int64_t* excl_indptr, const int32_t* excl_indices, int64_t capacity, int64_t* out_indptr,
-                       int32_t* out_indices, void* out_values, int64_t* n_found, int32_t col_splits, void* workspace,
-                       size_t workspace_bytes, void* stream) {
-    return guarded([&] {
-        above_check_shape(dtype, m, n_cols, col_splits);
-        if (c < 1 || c > 1024) SKF_FAIL(SKF_E_INVALID, "skf_complete_above: width c = %d outside 1 .. 1024", c);
-        if (!H || !Gc || !thr || !out_indptr || !n_found) SKF_FAIL(SKF_E_INVALID, "skf_complete_above: null argument");
-        if (out_values && !out_indices) SKF_FAIL(SKF_E_INVALID, "skf_complete_above: out_values without out_indices");
-        if ((excl_indptr == nullptr) != (excl_indices == nullptr))
-            SKF_FAIL(SKF_E_INVALID, "skf_complete_above: excl_indptr and excl_indices come together (both NULL: no exclusion)");
-        if (ldh < c || ldg < c) SKF_FAIL(SKF_E_INVALID, "skf_complete_above: ld too small");
-        if (capacity < 0) SKF_FAIL(SKF_E_INVALID, "skf_complete_above: capacity = %lld is negative", (long long)capacity);
-        const int splits = topk_col_splits(m, n_cols, col_splits);
-        const size_t need = above_workspace(m, splits);
-        if (!workspace || workspace_bytes < need)
-            SKF_FAIL(SKF_E_WORKSPACE, "skf_complete_above: workspace %zu B < required %zu B (or null)", workspace ? workspace_bytes : (size_t)0, need);
-        if (((uintptr_t)workspace & 255) != 0) SKF_FAIL(SKF_E_WORKSPACE, "skf_complete_above: workspace must be 256-byte aligned");
-        hipStream_t st = as_stream(stream);
-        char* ws = (char*)workspace;
-        if (m > 0 && excl_indptr) {
-            int64_t nnz = -1;
-            SKF_HIP(hipMemcpyAsync(&nnz, excl_indptr + m, sizeof nnz, hipMemcpyDeviceToHost, st));
-            SKF_HIP(hipStreamSynchronize(st));
-            if (nnz < 0 || !csr_is_canonical(excl_indptr, (const int*)excl_indices, m, n_cols, nnz, (int*)ws, st))
-                SKF_FAIL(SKF_E_INVALID, "skf_complete_above: the exclusion lists are not canonical for %lld rows x %lld columns (indptr from 0 "
-                         "to the count, non-decreasing; indices in range and strictly ascending within a row)", (long long)m, (long long)n_cols);
-        }
-        if (m == 0 || n_cols == 0) {                    // nothing to score: every row is empty
-            SKF_HIP(hipMemsetAsync(out_indptr, 0, (size_t)(m + 1) * sizeof(int64_t), st));
-            SKF_HIP(hipStreamSynchronize(st));
-            *n_found = 0;
-            return;
-        }
-        if (dtype == SKF_F64)
-            run_complete_above<double>(H, ldh, m, Gc, ldg, n_cols, c, thr, excl_indptr, (const int*)excl_indices, capacity, out_indptr,
-                                       out_indices, out_values, n_found, splits, ws, st);
-        else
-            run_complete_above<float>(H, ldh, m, Gc, ldg, n_cols, c, thr, excl_indptr, (const int*)excl_indices, capacity, out_indptr,
-                                      out_indices, out_values, n_found, splits, ws, st);
     });
 }
 

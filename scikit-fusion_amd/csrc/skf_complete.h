@@ -4,7 +4,10 @@
 // The reference materialises X on the host (fusion/base/base.py `complete`: np.dot(G1, np.dot(S, G2.T))) and its users index or
 // rank that array (examples/movielens_completion.py:121-126 evaluates R12_pred[hidden]).  Both kernels here work on
 //     H = G_row[rows] S        (m x c, formed by the caller with skf_gemm)      and      Gc = G_col   (n_cols x c)
-// and never write a score tile to HBM.
+// and never write a score tile to HBM.  Host side (every check, the split decision, the launches, the C entry points):
+// skf_complete.inc.  What the passes over the score tiles share lives here once: the
+// product (topk_score_tile), a split's tile range (split_tiles), the owner lane's exclusion cursor and its lower bound
+// (excl_seek) and the 64-bit exclusion mask of a tile (excl_tile_mask).
 //
 // complete_topk_kernel: a workgroup owns 64 rows and a contiguous range of columns (blockIdx.y = the column split), walks the
 // range in 64-column tiles in increasing order, forms each 64 x 64 score tile on the matrix cores (K loop over c in chunks of
@@ -42,7 +45,7 @@
 
 namespace skf {
 
-constexpr int SKF_TOPK_MAX_K = 64;         // == SKF_TOPK_MAX of include/skfusion_hip.h (checked in skf_api.hip)
+constexpr int SKF_TOPK_MAX_K = 64;         // == SKF_TOPK_MAX of include/skfusion_hip.h (checked in skf_complete.inc)
 constexpr int TOPK_MAX_SPLITS = 32;        // column splits of one launch (the merge keeps one cursor per split in registers)
 constexpr int TOPK_BM = 64, TOPK_BN = 64;  // score tile
 constexpr int TOPK_KC = 32;                // K chunk staged per step
@@ -67,6 +70,49 @@ template <> struct TopkMma<double> {
     static __device__ __forceinline__ acc_t mma(double a, double b, acc_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
 };
 
+// ---- the walk over a split's column tiles, shared by the top-k, rank-count and above passes --------------------------------
+// Values and references to the callers' own variables in and out, never the argument block, and `col_of` of a contiguous
+// tile stays a lambda at its three calls: in these forms every kernel compiles to the instruction stream of the separate
+// copies (a struct for the cursor, a named functor for `col_of`, by value or by reference, each changed all eight:
+// profiles/r21_complete_refactor.txt).
+// the column tiles [lo, hi) of split blockIdx.y
+struct TileRange { int64_t lo, hi; };
+static __device__ __forceinline__ TileRange split_tiles(int64_t n_cols, int tiles_per_split) {
+    const int64_t ntiles = (n_cols + TOPK_BN - 1) / TOPK_BN;
+    const int64_t lo = (int64_t)blockIdx.y * tiles_per_split;
+    return TileRange{lo, lo + tiles_per_split < ntiles ? lo + tiles_per_split : ntiles};
+}
+
+// The owner lane's cursor into its row's exclusion list (ascending, as the tiles are): positions [at, end) of xidx, placed
+// at the first entry >= `first`, the split's first column (a later split starts inside the list: lower bound).  The caller
+// asks only for a live row of given lists; otherwise its cursor stays empty (0, 0).
+static __device__ __forceinline__ void excl_seek(const int64_t* xptr, const int* xidx, int64_t row, int64_t first, int64_t& at, int64_t& end) {
+    at = xptr[row];
+    end = xptr[row + 1];
+    if (first > 0) {
+        int64_t lo = at, hi = end;
+        while (lo < hi) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if ((int64_t)xidx[mid] < first) lo = mid + 1; else hi = mid;
+        }
+        at = lo;
+    }
+}
+
+// bit b: column col0 + b of the tile is in the row's list; the cursor moves past the tile
+static __device__ __forceinline__ unsigned long long excl_tile_mask(const int* xidx, int64_t& at, int64_t end, int64_t col0) {
+    unsigned long long mk = 0;
+    while (at < end && (int64_t)xidx[at] < col0 + TOPK_BN) {
+        mk |= 1ull << ((int64_t)xidx[at] - col0);
+        ++at;
+    }
+    return mk;
+}
+
+// The argument blocks of the three passes over the score tiles begin with the same operands under the same names -- H, ldh,
+// m, Gc, ldg, n_cols, c, xptr, xidx, tiles_per_split -- which the host fills in ONE place (skf_complete.inc, fill_operands).
+// They stay three flat structs: a shared base moves the pass's own fields behind the operands, and with the kernel
+// arguments laid out differently the kernels no longer compile to the instruction stream they had.
 template <typename T>
 struct TopkArgs {
     const T* H;  int64_t ldh;  int64_t m;           // [m][c]
@@ -166,31 +212,17 @@ __global__ __launch_bounds__(TOPK_THREADS) void complete_topk_kernel(TopkArgs<T>
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int k = a.k, c = a.c;
     const int64_t row0 = (int64_t)blockIdx.x * TOPK_BM;
-    const int64_t ntiles = (a.n_cols + TOPK_BN - 1) / TOPK_BN;
-    const int64_t tile_lo = (int64_t)blockIdx.y * a.tiles_per_split;
-    const int64_t tile_hi = tile_lo + a.tiles_per_split < ntiles ? tile_lo + a.tiles_per_split : ntiles;
+    const TileRange tiles = split_tiles(a.n_cols, a.tiles_per_split);
 
     // the owner of row r of the tile is lane (r & 15) of wave (r >> 4): the insertions of a tile run on all four SIMDs
     const bool owner = lane < 16;
     const int orow = wave * 16 + lane;
     const bool live = owner && row0 + orow < a.m;
-    int64_t xp = 0, xe = 0;                              // cursor into the row's exclusion list (ascending, as the tiles are)
-    if (live && a.xptr) {
-        xp = a.xptr[row0 + orow];
-        xe = a.xptr[row0 + orow + 1];
-        const int64_t first = tile_lo * TOPK_BN;
-        if (first > 0) {                                 // a later split starts at its first column: lower bound
-            int64_t lo = xp, hi = xe;
-            while (lo < hi) {
-                const int64_t mid = lo + ((hi - lo) >> 1);
-                if ((int64_t)a.xidx[mid] < first) lo = mid + 1; else hi = mid;
-            }
-            xp = lo;
-        }
-    }
+    int64_t xp = 0, xe = 0;                              // cursor into the row's exclusion list
+    if (live && a.xptr) excl_seek(a.xptr, a.xidx, row0 + orow, tiles.lo * TOPK_BN, xp, xe);
     if (t < TOPK_BM) cnt[t] = 0;
 
-    for (int64_t tile = tile_lo; tile < tile_hi; ++tile) {
+    for (int64_t tile = tiles.lo; tile < tiles.hi; ++tile) {
         const int64_t col0 = tile * TOPK_BN;
         topk_score_tile<T>(a.H, a.ldh, a.m, row0, a.Gc, a.ldg, c,
                            [&](int r) { return col0 + r < a.n_cols ? (int)(col0 + r) : -1; }, buf);
@@ -438,9 +470,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void complete_rank_count_kernel(RankA
     // hardware hands round its dies in turn; as a slower grid dimension they would lie a whole number of row tiles apart
     const int64_t row0 = (int64_t)(blockIdx.x / a.chunk_groups) * TOPK_BM;
     const int64_t ch0 = blockIdx.x % a.chunk_groups;
-    const int64_t ntiles = (a.n_cols + TOPK_BN - 1) / TOPK_BN;
-    const int64_t tile_lo = (int64_t)blockIdx.y * a.tiles_per_split;
-    const int64_t tile_hi = tile_lo + a.tiles_per_split < ntiles ? tile_lo + a.tiles_per_split : ntiles;
+    const TileRange tiles = split_tiles(a.n_cols, a.tiles_per_split);
 
     // the chunks this row tile needs: those of its longest row.  A workgroup beyond them leaves before it touches a list.
     if (t <= TOPK_BM) tp[t] = a.tptr[row0 + t < a.m ? row0 + t : a.m];
@@ -453,19 +483,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void complete_rank_count_kernel(RankA
     const bool owner = lane < 16;                        // of row wave * 16 + lane of the tile
     const int orow = wave * 16 + lane;
     int64_t xp0 = 0, xe = 0;                             // the row's exclusion list from the split's first column on
-    if (owner && row0 + orow < a.m && a.xptr) {
-        xp0 = a.xptr[row0 + orow];
-        xe = a.xptr[row0 + orow + 1];
-        const int64_t first = tile_lo * TOPK_BN;
-        if (first > 0) {
-            int64_t lo = xp0, hi = xe;
-            while (lo < hi) {
-                const int64_t mid = lo + ((hi - lo) >> 1);
-                if ((int64_t)a.xidx[mid] < first) lo = mid + 1; else hi = mid;
-            }
-            xp0 = lo;
-        }
-    }
+    if (owner && row0 + orow < a.m && a.xptr) excl_seek(a.xptr, a.xidx, row0 + orow, tiles.lo * TOPK_BN, xp0, xe);
 
     for (int64_t ch = ch0; ch < chunks; ch += a.chunk_groups) {
         __syncthreads();                                 // the previous chunk's flush has left nt / tn
@@ -484,18 +502,11 @@ __global__ __launch_bounds__(TOPK_THREADS) void complete_rank_count_kernel(RankA
             }
         }
         int64_t xp = xp0;
-        for (int64_t tile = tile_lo; tile < tile_hi; ++tile) {
+        for (int64_t tile = tiles.lo; tile < tiles.hi; ++tile) {
             const int64_t col0 = tile * TOPK_BN;
             topk_score_tile<T>(a.H, a.ldh, a.m, row0, a.Gc, a.ldg, a.c,
                                [&](int r) { return col0 + r < a.n_cols ? (int)(col0 + r) : -1; }, buf);
-            if (owner) {
-                unsigned long long mk = 0;
-                while (xp < xe && (int64_t)a.xidx[xp] < col0 + TOPK_BN) {
-                    mk |= 1ull << ((int64_t)a.xidx[xp] - col0);
-                    ++xp;
-                }
-                xmask[orow] = mk;
-            }
+            if (owner) xmask[orow] = excl_tile_mask(a.xidx, xp, xe, col0);
             __syncthreads();                             // (covers the chunk arrays too, on the first tile)
             const int r = t & 63, q = t >> 6, n = nt[r];
             if (n > 0) {
@@ -576,9 +587,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void complete_above_kernel(AboveArgs<
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int r = t & 63, q = t >> 6;
     const int64_t row0 = (int64_t)blockIdx.x * TOPK_BM;
-    const int64_t ntiles = (a.n_cols + TOPK_BN - 1) / TOPK_BN;
-    const int64_t tile_lo = (int64_t)blockIdx.y * a.tiles_per_split;
-    const int64_t tile_hi = tile_lo + a.tiles_per_split < ntiles ? tile_lo + a.tiles_per_split : ntiles;
+    const TileRange tiles = split_tiles(a.n_cols, a.tiles_per_split);
     const bool rin = row0 + r < a.m;
 
     int64_t pos = 0, end = 0;                            // FILL: where the row's next entry goes, and where its run ends
@@ -598,34 +607,15 @@ __global__ __launch_bounds__(TOPK_THREADS) void complete_above_kernel(AboveArgs<
     const bool owner = lane < 16;                        // of row wave * 16 + lane of the tile
     const int orow = wave * 16 + lane;
     int64_t xp = 0, xe = 0;                              // the row's exclusion list from the split's first column on
-    if (owner && row0 + orow < a.m && a.xptr) {
-        xp = a.xptr[row0 + orow];
-        xe = a.xptr[row0 + orow + 1];
-        const int64_t first = tile_lo * TOPK_BN;
-        if (first > 0) {
-            int64_t lo = xp, hi = xe;
-            while (lo < hi) {
-                const int64_t mid = lo + ((hi - lo) >> 1);
-                if ((int64_t)a.xidx[mid] < first) lo = mid + 1; else hi = mid;
-            }
-            xp = lo;
-        }
-    }
+    if (owner && row0 + orow < a.m && a.xptr) excl_seek(a.xptr, a.xidx, row0 + orow, tiles.lo * TOPK_BN, xp, xe);
     const T thr = rin ? a.thr[row0 + r] : (T)NAN;        // (a row past the end selects nothing)
     int cnt = 0;
 
-    for (int64_t tile = tile_lo; tile < tile_hi; ++tile) {
+    for (int64_t tile = tiles.lo; tile < tiles.hi; ++tile) {
         const int64_t col0 = tile * TOPK_BN;
         topk_score_tile<T>(a.H, a.ldh, a.m, row0, a.Gc, a.ldg, a.c,
                            [&](int rr) { return col0 + rr < a.n_cols ? (int)(col0 + rr) : -1; }, buf);
-        if (owner) {
-            unsigned long long mk = 0;
-            while (xp < xe && (int64_t)a.xidx[xp] < col0 + TOPK_BN) {
-                mk |= 1ull << ((int64_t)a.xidx[xp] - col0);
-                ++xp;
-            }
-            xmask[orow] = mk;
-        }
+        if (owner) xmask[orow] = excl_tile_mask(a.xidx, xp, xe, col0);
         __syncthreads();
         const unsigned xm = (unsigned)(xmask[r] >> (16 * q)) & 0xffffu;
         const unsigned mk = above_quarter_mask<T>(sc, r, q, col0, a.n_cols, xm, thr);

@@ -229,6 +229,42 @@ class FusionFit(FusionBase):
             raise DataFusionError("Object type %s or %s are not included in the fusion scheme"
                                   % (relation.row_type.name, relation.col_type.name))
 
+    def _check_raw_scores(self, relation, method):
+        """The preamble of the operators that rank or compare raw device scores (``method``: the caller's own name)."""
+        self._check_relation_types(relation)
+        if relation.postprocessor:
+            raise DataFusionError("%s ranks raw device scores; relation %s -> %s has a "
+                                  "postprocessor (rank complete_blocks(device=False) yourself)"
+                                  % (method, relation.row_type.name, relation.col_type.name))
+
+    def _relation_shape(self, relation):
+        return np.shape(self.factor(relation.row_type, 0))[0], np.shape(self.factor(relation.col_type, 0))[0]
+
+    @staticmethod
+    def _row_vector(rows, n_i):
+        """``rows`` as a flat integer array inside the relation; None: every row object."""
+        rows = np.arange(n_i) if rows is None else np.asarray(rows).reshape(-1)
+        if rows.dtype.kind not in 'iu' or (rows.size and (rows.min() < 0 or rows.max() >= n_i)):
+            raise DataFusionError("rows must be integers in 0 .. %d" % (n_i - 1))
+        return rows
+
+    def _pair_vectors(self, relation, rows, cols):
+        """``rows`` / ``cols`` as flat integer arrays of one length inside the relation, and the relation's shape."""
+        rows = np.asarray(rows).reshape(-1)
+        cols = np.asarray(cols).reshape(-1)
+        if rows.shape != cols.shape or rows.dtype.kind not in 'iu' or cols.dtype.kind not in 'iu':
+            raise DataFusionError("rows and cols must be integer arrays of one length")
+        n_i, n_j = self._relation_shape(relation)
+        if rows.size and (rows.min() < 0 or rows.max() >= n_i or cols.min() < 0 or cols.max() >= n_j):
+            raise DataFusionError("A pair lies outside the %d x %d relation" % (n_i, n_j))
+        return rows, cols, n_i, n_j
+
+    # one(run) for the one run asked for; several runs and no explicit run -> a generator over the runs (as `_select`)
+    def _per_run(self, one, run):
+        if self.n_run > 1 and run is None:
+            return (one(r) for r in range(self.n_run))
+        return one(0 if run is None else run)
+
     def _completer(self, relation, run, dtype):
         from .._engine import DeviceCompleter
         return (np.asarray(self.factor(relation.row_type, run)),
@@ -241,21 +277,13 @@ class FusionFit(FusionBase):
         products run in the master type of ``dtype`` ('f64' | 'f32' | 'bf16' -> f32).  ``n_run > 1`` and ``run=None``: a
         generator over the runs.  Extension of the reference API."""
         self._check_relation_types(relation)
-        rows = np.asarray(rows).reshape(-1)
-        cols = np.asarray(cols).reshape(-1)
-        if rows.shape != cols.shape or rows.dtype.kind not in 'iu' or cols.dtype.kind not in 'iu':
-            raise DataFusionError("rows and cols must be integer arrays of one length")
-        n_i, n_j = np.shape(self.factor(relation.row_type, 0))[0], np.shape(self.factor(relation.col_type, 0))[0]
-        if rows.size and (rows.min() < 0 or rows.max() >= n_i or cols.min() < 0 or cols.max() >= n_j):
-            raise DataFusionError("A pair lies outside the %d x %d relation" % (n_i, n_j))
+        rows, cols, _, _ = self._pair_vectors(relation, rows, cols)
 
         def one(k):
             G1, comp = self._completer(relation, k, dtype)
             out = comp.entries(G1, rows, cols)
             return relation.postprocessor(out) if relation.postprocessor else out
-        if self.n_run > 1 and run is None:
-            return (one(k) for k in range(self.n_run))
-        return one(0 if run is None else run)
+        return self._per_run(one, run)
 
     def _exclusion_lists(self, relation, exclude, shape):
         """None, or a function ``rows -> (indptr int64, indices int32)``: the excluded columns of the given rows as CSR
@@ -308,21 +336,13 @@ class FusionFit(FusionBase):
         blocks.  A relation with a postprocessor is refused: the ranking is that of the raw scores and a ranking of
         post-processed values cannot be promised (``complete_blocks(device=True)`` refuses for the same reason).
         ``1 <= k <= 64``.  ``n_run > 1`` and ``run=None``: a generator over the runs.  Extension of the reference API."""
-        self._check_relation_types(relation)
-        if relation.postprocessor:
-            raise DataFusionError("complete_topk ranks raw device scores; relation %s -> %s has a "
-                                  "postprocessor (rank complete_blocks(device=False) yourself)"
-                                  % (relation.row_type.name, relation.col_type.name))
+        self._check_raw_scores(relation, 'complete_topk')
         from .._native import SKF_TOPK_MAX
         k = int(k)
         if not 1 <= k <= SKF_TOPK_MAX:
             raise DataFusionError("k = %d outside 1 .. %d" % (k, SKF_TOPK_MAX))
-        n_i, n_j = np.shape(self.factor(relation.row_type, 0))[0], np.shape(self.factor(relation.col_type, 0))[0]
-        if rows is None:
-            rows = np.arange(n_i)
-        rows = np.asarray(rows).reshape(-1)
-        if rows.dtype.kind not in 'iu' or (rows.size and (rows.min() < 0 or rows.max() >= n_i)):
-            raise DataFusionError("rows must be integers in 0 .. %d" % (n_i - 1))
+        n_i, n_j = self._relation_shape(relation)
+        rows = self._row_vector(rows, n_i)
         lists = self._exclusion_lists(relation, exclude, (n_i, n_j))
         step = max(1, int(block_rows))
 
@@ -334,9 +354,7 @@ class FusionFit(FusionBase):
                 blk = rows[b0:b0 + step]
                 idx[b0:b0 + step], val[b0:b0 + step] = comp.topk(G1[blk], k, exclude=lists(blk) if lists else None)
             return idx, val
-        if self.n_run > 1 and run is None:
-            return (one(r) for r in range(self.n_run))
-        return one(0 if run is None else run)
+        return self._per_run(one, run)
 
     def complete_ranks(self, relation, rows, cols, exclude=None, run=None, dtype='f64', block_rows=8192):
         """``int64 [n]``: for every pair ``(rows[e], cols[e])`` its 0-based position in the ranking of its row's columns
@@ -347,18 +365,8 @@ class FusionFit(FusionBase):
         with duplicates.  The counts are taken on the device over score tiles, ``block_rows`` distinct rows at a time;
         nothing of size ``n_i x n_j`` is formed.  A relation with a postprocessor is refused, as in ``complete_topk``.
         ``n_run > 1`` and ``run=None``: a generator over the runs.  Extension of the reference API."""
-        self._check_relation_types(relation)
-        if relation.postprocessor:
-            raise DataFusionError("complete_ranks ranks raw device scores; relation %s -> %s has a "
-                                  "postprocessor (rank complete_blocks(device=False) yourself)"
-                                  % (relation.row_type.name, relation.col_type.name))
-        rows = np.asarray(rows).reshape(-1)
-        cols = np.asarray(cols).reshape(-1)
-        if rows.shape != cols.shape or rows.dtype.kind not in 'iu' or cols.dtype.kind not in 'iu':
-            raise DataFusionError("rows and cols must be integer arrays of one length")
-        n_i, n_j = np.shape(self.factor(relation.row_type, 0))[0], np.shape(self.factor(relation.col_type, 0))[0]
-        if rows.size and (rows.min() < 0 or rows.max() >= n_i or cols.min() < 0 or cols.max() >= n_j):
-            raise DataFusionError("A pair lies outside the %d x %d relation" % (n_i, n_j))
+        self._check_raw_scores(relation, 'complete_ranks')
+        rows, cols, n_i, n_j = self._pair_vectors(relation, rows, cols)
         lists = self._exclusion_lists(relation, exclude, (n_i, n_j))
         step = max(1, int(block_rows))
         # the distinct pairs in (row, column) order are the target CSR over the distinct rows; `back` leads home
@@ -375,9 +383,7 @@ class FusionFit(FusionBase):
                 p = ptr[b0:b0 + blk.size + 1]
                 out[p[0]:p[-1]] = comp.ranks(G1[blk], (p - p[0], pcol[p[0]:p[-1]]), exclude=lists(blk) if lists else None)[0]
             return out[back.reshape(-1)]
-        if self.n_run > 1 and run is None:
-            return (one(r) for r in range(self.n_run))
-        return one(0 if run is None else run)
+        return self._per_run(one, run)
 
     def complete_above(self, relation, threshold, rows=None, exclude=None, run=None, dtype='f64', block_rows=8192,
                        max_entries=2 ** 28):
@@ -393,19 +399,11 @@ class FusionFit(FusionBase):
         ``max_entries`` entries are found a ``DataFusionError`` is raised, before any array of that size is allocated.  A
         relation with a postprocessor is refused, as in ``complete_topk``.  ``n_run > 1`` and ``run=None``: a generator
         over the runs.  Extension of the reference API."""
-        self._check_relation_types(relation)
-        if relation.postprocessor:
-            raise DataFusionError("complete_above ranks raw device scores; relation %s -> %s has a "
-                                  "postprocessor (rank complete_blocks(device=False) yourself)"
-                                  % (relation.row_type.name, relation.col_type.name))
+        self._check_raw_scores(relation, 'complete_above')
         import scipy.sparse
         from .._engine import AboveLimit
-        n_i, n_j = np.shape(self.factor(relation.row_type, 0))[0], np.shape(self.factor(relation.col_type, 0))[0]
-        if rows is None:
-            rows = np.arange(n_i)
-        rows = np.asarray(rows).reshape(-1)
-        if rows.dtype.kind not in 'iu' or (rows.size and (rows.min() < 0 or rows.max() >= n_i)):
-            raise DataFusionError("rows must be integers in 0 .. %d" % (n_i - 1))
+        n_i, n_j = self._relation_shape(relation)
+        rows = self._row_vector(rows, n_i)
         thr = np.asarray(threshold, dtype=np.float64)
         if thr.ndim > 1 or (thr.ndim == 1 and thr.shape != rows.shape):
             raise DataFusionError("threshold must be a scalar or one value per row (%d), not of shape %r"
@@ -435,9 +433,7 @@ class FusionFit(FusionBase):
                                            np.zeros(0, dtype=np.int32), indptr), shape=(rows.size, n_j))
             out.has_sorted_indices = True      # (ascending within a row by construction)
             return out
-        if self.n_run > 1 and run is None:
-            return (one(r) for r in range(self.n_run))
-        return one(0 if run is None else run)
+        return self._per_run(one, run)
 
 
 # ---- persistence of a fitted model (the reference has none: its accessors base.py:35-56,

@@ -23,7 +23,7 @@ import pytest
 import skfusion_amd._native as nat
 from skfusion_amd._engine import DeviceCompleter
 from complete_cases import Raw, bound, exclusion_mask, host_topk, lattice_factors, lists_of, random_factors
-from ranks_cases import raw_ranks, rows_of, target_mask
+from ranks_cases import host_ranks, raw_ranks, rows_of, target_mask
 
 SPLITS = (0, 1, 2, 3, 32)
 PAD = 5                                          # sentinel entries behind every output
@@ -204,6 +204,70 @@ def scan_case(dtype, m, n_cols=70, ranks=(5, 1), col_splits=2):
     xl = lists_of(ex)
     same(raw_above(raw, thr, xlists=xl, col_splits=col_splits, capacity=int(want[0][-1])), want,
          'above scan %s m %d splits %d' % (dtype, m, col_splits))
+
+
+def seam_mask(m, n_cols, seam, seed=0):
+    """Excluded pairs around `seam`, the first column of a later split: row r lists columns seam - 1 and seam (r % 4 == 0),
+    only seam - 1 (1), only seam (2) or neither (3), over a thin random pattern elsewhere, so that the lower bound of the
+    later split lands inside a list; row 5's list begins at seam - 1 and row 8's ends at seam."""
+    ex = np.random.RandomState(seed + 13).rand(m, n_cols) < 0.0625
+    r = np.arange(m)
+    ex[:, seam - 1] = r % 4 <= 1
+    ex[:, seam] = r % 2 == 0
+    ex[5 % m, :seam - 1] = False
+    ex[8 % m, seam + 1:] = False
+    return ex
+
+
+def seam_case(dtype, m=67, n_cols=203, ranks=(5, 7), k=10):
+    """The first column of the second of two splits (four column tiles, two per split: column 128) against exclusion lists
+    that hold columns 127 and 128, one of them or neither, the last (partial) row tile included: top-k, ranks and above bit
+    for bit against the host and against the same call with one split."""
+    seam = 2 * 64
+    assert 3 * 64 < n_cols <= 4 * 64 and m > 64
+    # seed 1: columns 127 and 128 are among the ten best of 39 rows on the host (seed 0: of none), so that an entry lost at
+    # the seam shows in top-k too; the three asserts on `open_seam` below hold every operator to that
+    G_row, S, G_col = lattice_factors(m, n_cols, ranks, seed=1)
+    H = np.dot(G_row, S)
+    X = np.dot(H, G_col.T)
+    assert X.max() * 512 < 2 ** 23 and np.array_equal(X.astype(np.float32).astype(np.float64), X)      # exact in f32
+    raw = Raw(dtype, H, G_col)
+    ex = seam_mask(m, n_cols, seam)
+    pairs = set(map(tuple, ex[:, seam - 1:seam + 1].tolist()))
+    assert pairs == {(True, True), (True, False), (False, True), (False, False)} and ex[64:, seam - 1:seam + 1].any()
+    assert ex[m - 1, seam] and not ex[5, :seam - 1].any() and ex[5, seam - 1] and not ex[8, seam + 1:].any() and ex[8, seam]
+    open_seam = ex.copy()
+    open_seam[:, seam - 1:seam + 1] = False                          # what a cursor that loses the seam's entries would see
+    what = 'seam %s m %d n %d ranks %r' % (dtype, m, n_cols, ranks)
+
+    hi, hv = host_topk(X, k, ex)
+    assert not np.array_equal(hi, host_topk(X, k, open_seam)[0]), 'top-k does not depend on the seam entries'
+    got = [raw.topk(k, ex, col_splits=s) for s in (2, 1)]
+    for (gi, gv), s in zip(got, (2, 1)):
+        assert np.array_equal(gi, hi), '%s top-k splits %d: indices differ from the host order' % (what, s)
+        assert np.array_equal(gv.astype(np.float64), hv), '%s top-k splits %d: values differ from the host scores' % (what, s)
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(*got)), what + ' top-k: two splits and one differ'
+
+    tg = target_mask(m, n_cols)
+    tg[::3, seam - 1:seam + 1] = True                                # targets ON the seam, excluded ones among them
+    tl = lists_of(tg)
+    rows = rows_of(tl)
+    assert ex[rows, tl[1]].any() and tg[m - 1, seam - 1:seam + 1].all()
+    want = host_ranks(X, tl, ex)
+    assert not np.array_equal(want, host_ranks(X, tl, open_seam)), 'the ranks do not depend on the seam entries'
+    got = [raw_ranks(raw, tl, ex, col_splits=s) for s in (2, 1)]
+    for (gr, gv), s in zip(got, (2, 1)):
+        assert np.array_equal(gr, want), '%s ranks splits %d: ranks differ from the host count' % (what, s)
+        assert np.array_equal(gv.astype(np.float64), X[rows, tl[1]]), '%s ranks splits %d: values differ from the host scores' % (what, s)
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(*got)), what + ' ranks: two splits and one differ'
+
+    thr = own_thresholds(X)
+    want = host_above(X, thr, ex)
+    assert not np.array_equal(want[0], host_above(X, thr, open_seam)[0]), 'above does not depend on the seam entries'
+    got = [raw_above(raw, thr, ex, col_splits=s) for s in (2, 1)]
+    for g, s in zip(got, (2, 1)):
+        same(g, want, '%s above splits %d' % (what, s))
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(*got)), what + ' above: two splits and one differ'
 
 
 # ---- 2. agreement with top-k and ranks -------------------------------------------------------------------------------------

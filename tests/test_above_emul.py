@@ -34,6 +34,11 @@ def test_exact_three_row_tiles_and_many_column_tiles(dtype):
 
 
 @pytest.mark.parametrize('dtype', ['f64', 'f32'])
+def test_exclusion_entries_on_either_side_of_a_split_boundary(dtype):
+    AC.seam_case(dtype)
+
+
+@pytest.mark.parametrize('dtype', ['f64', 'f32'])
 def test_scan_over_several_chunks_of_rows(dtype):
     AC.scan_case(dtype, 600)
 

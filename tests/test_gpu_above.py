@@ -20,6 +20,11 @@ def test_exact_index_for_index_bit_for_bit(dtype, n_cols, ranks):
         AC.exact_case(dtype, m, n_cols, ranks)
 
 
+@pytest.mark.parametrize('dtype', ['f64', 'f32'])
+def test_exclusion_entries_on_either_side_of_a_split_boundary(dtype):
+    AC.seam_case(dtype)
+
+
 @pytest.mark.parametrize('m', [600, 262144 + 300])
 def test_scan_over_several_chunks_of_rows(m):
     """600 rows: three workgroups of the scan; 262 444 rows: 513 workgroups that walk 512 rows each in two steps."""
