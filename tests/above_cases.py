@@ -73,7 +73,7 @@ def call_above(raw, thr_host, xlists=None, col_splits=0, capacity=None, **over):
     optr = mem.from_host(np.full(m + 1 + PAD, -7, dtype=np.int64))
     oidx = mem.from_host(np.full(cap + PAD, -7, dtype=np.int32))
     oval = mem.from_host(np.full(cap + PAD, -7.0, dtype=raw.T))
-    ws = mem.empty(raw_workspace(raw, col_splits) + 256)
+    ws = mem.empty(raw_workspace(raw, col_splits))      # exactly what the query asks for
     xp = xi = None
     if xlists is not None:
         xp = mem.from_host(np.asarray(xlists[0], dtype=np.int64))
@@ -81,7 +81,7 @@ def call_above(raw, thr_host, xlists=None, col_splits=0, capacity=None, **over):
     found = C.c_int64(-7)
     a = dict(dtype=raw.code, H=raw.h.ptr, ldh=raw.ldh, m=m, Gc=raw.g.ptr, ldg=raw.ldg, n_cols=raw.n_cols, c=raw.c, thr=bt.ptr,
              xp=xp.ptr if xp else None, xi=xi.ptr if xi else None, cap=cap, optr=optr.ptr, oidx=oidx.ptr, oval=oval.ptr,
-             found=C.byref(found), splits=col_splits, ws=ws.ptr, ws_bytes=ws.nbytes - 256)
+             found=C.byref(found), splits=col_splits, ws=ws.ptr, ws_bytes=ws.nbytes)
     assert set(over) <= set(a), over
     a.update(over)
     rc = rt.lib.skf_complete_above(a['dtype'], a['H'], a['ldh'], a['m'], a['Gc'], a['ldg'], a['n_cols'], a['c'], a['thr'], a['xp'],

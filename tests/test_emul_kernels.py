@@ -8,7 +8,7 @@ import pytest
 
 import skfusion_amd._native as nat
 from emul.runtime import emulated_runtime
-from helpers import relerr
+from helpers import relerr, within
 
 
 @pytest.fixture(scope='module')
@@ -16,34 +16,88 @@ def rt():
     return emulated_runtime()
 
 
+class Stored(object):
+    """A row-major matrix X inside a larger upload: `off` elements, then the rows of X `X.shape[1] + pad` elements apart
+    (the last row without its pad).  Every element of the upload outside X holds `fill` (NaN for floats, 0xFF for bytes):
+    .ptr is the device address of X[0, 0], .ld the leading dimension; .download() returns the matrix and asserts that the
+    upload around it came back bit for bit."""
+
+    def __init__(self, mem, X, pad=0, off=0, fill=None):
+        X = np.ascontiguousarray(X)
+        rows, cols = X.shape
+        self.mem, self.shape, self.ld, self.off = mem, (rows, cols), cols + pad, off
+        if fill is None:
+            fill = 0xFF if X.dtype.kind in 'ui' else np.nan
+        self.host = np.full(off + (rows - 1) * self.ld + cols, fill, X.dtype)
+        self.inside = np.zeros(self.host.shape, bool)
+        self._view(self.host)[...] = X
+        self._view(self.inside)[...] = True
+        self.buf = mem.from_host(self.host)
+        self.ptr = self.buf.ptr + off * X.dtype.itemsize
+
+    def _view(self, flat):
+        rows, cols = self.shape
+        return np.lib.stride_tricks.as_strided(flat[self.off:], (rows, cols), (self.ld * flat.itemsize, flat.itemsize))
+
+    def download(self):
+        got = self.mem.to_host(self.buf, self.host.shape, self.host.dtype)
+        bits = 'u%d' % got.itemsize
+        np.testing.assert_array_equal(got.view(bits)[~self.inside], self.host.view(bits)[~self.inside],
+                                      err_msg='elements around the matrix (pad columns, lead-in) changed')
+        return self._view(got).copy()
+
+
+def elementwise(got, want, bound, what):
+    """max over the elements of |got - want| / bound, held below 1 (recorded with helpers.within); an element whose bound
+    is 0 must be exact."""
+    err = np.abs(np.asarray(got).astype(np.longdouble) - want)
+    assert np.isfinite(err).all(), '%s: non-finite result' % what
+    bound = np.asarray(bound, dtype=np.longdouble)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        ratio = np.where(err == 0, 0.0, err / bound)
+    return within(float(ratio.max()) if ratio.size else 0.0, 1.0, '%s, |got - want| / bound' % what)
+
+
 def run_gemm(rt, dtype, engine, A, B, transA=False, transB=False, aop=0, epi=0, C0=None, C20=None,
-             mask=None, nan=0, splits=0, a_dtype=-1, b_dtype=-1):
-    """C = epi(aop(op(A)) @ op(B)) through skf_gemm; A/B given as stored (row-major)."""
+             mask=None, nan=0, splits=0, a_dtype=-1, b_dtype=-1, pad_a=0, pad_b=0, pad_c=0, off_a=0, off_b=0, off_c=0,
+             ws_bytes=None, info=None):
+    """C = epi(aop(op(A)) @ op(B)) through skf_gemm; A/B given as stored (row-major).  pad_* : extra elements per row of the
+    stored operand / result, off_* : elements by which its pointer is advanced into a larger upload (the pads of C, C2 and
+    the mask hold NaN / 0xFF and must come back bit for bit).  `info` (a dict) receives the product of the operands as stored
+    in extended precision ('P') and of their magnitudes ('absP'), for the elementwise bound (K + s) u |A| |B|."""
     npd = nat.NP_DTYPE[dtype]
     A = np.ascontiguousarray(A, dtype=npd if a_dtype < 0 else nat.NP_DTYPE[a_dtype])
     B = np.ascontiguousarray(B, dtype=npd if b_dtype < 0 else nat.NP_DTYPE[b_dtype])
     M, K = (A.shape[1], A.shape[0]) if transA else A.shape
     N = B.shape[0] if transB else B.shape[1]
     mem = rt.mem
-    a, b = mem.from_host(A), mem.from_host(B)
+    a, b = Stored(mem, A, pad_a, off_a), Stored(mem, B, pad_b, off_b)
     Cm = np.zeros((M, N), npd) if C0 is None else np.array(C0, dtype=npd)
     C2m = np.zeros((M, N), npd) if C20 is None else np.array(C20, dtype=npd)
-    c, c2 = mem.from_host(Cm), mem.from_host(C2m)
+    c, c2 = Stored(mem, Cm, pad_c, off_c), Stored(mem, C2m, pad_c, off_c)
     d = nat.GemmDesc()
     d.A, d.B, d.C, d.C2 = a.ptr, b.ptr, c.ptr, c2.ptr
-    d.sa_m, d.sa_k = (1, A.shape[1]) if transA else (A.shape[1], 1)
-    d.sb_k, d.sb_n = (1, B.shape[1]) if transB else (B.shape[1], 1)
-    d.ldc = d.ldc2 = N
+    d.sa_m, d.sa_k = (1, a.ld) if transA else (a.ld, 1)
+    d.sb_k, d.sb_n = (1, b.ld) if transB else (b.ld, 1)
+    d.ldc = d.ldc2 = c.ld
     d.M, d.N, d.K = M, N, K
     d.aop, d.epi, d.nan_to_num, d.splits = aop, epi, nan, splits
     d.a_dtype, d.b_dtype = a_dtype, b_dtype
     keep = None
     if mask is not None:                    # the stand-alone operator takes one byte per entry
-        keep = mem.from_host(np.ascontiguousarray(mask, dtype=np.uint8))
-        d.mask, d.ldmask = keep.ptr, N
-    ws = mem.empty(64 * M * N * 8 + 256)
+        keep = Stored(mem, np.ascontiguousarray(mask, dtype=np.uint8), pad_c, off_c)
+        d.mask, d.ldmask = keep.ptr, keep.ld
+    ws = mem.empty(64 * M * N * 8 + 256 if ws_bytes is None else ws_bytes)
     rt.call('skf_gemm', dtype, engine, C.byref(d), ws.ptr, ws.nbytes, None)
-    return mem.to_host(c, (M, N), npd), mem.to_host(c2, (M, N), npd)
+    if keep is not None:
+        keep.download()
+    if info is not None:
+        wide = np.longdouble if dtype == nat.SKF_F64 else np.float64
+        Aw, Bw = (A.T if transA else A).astype(wide), (B.T if transB else B).astype(wide)
+        with np.errstate(invalid='ignore', over='ignore'):
+            info['P'], info['absP'] = Aw @ Bw, np.abs(Aw) @ np.abs(Bw)
+        info['u'] = 2.0 ** -53 if dtype == nat.SKF_F64 else 2.0 ** -24
+    return c.download(), c2.download()
 
 
 SHAPES = [(1, 1, 1), (5, 3, 7), (50, 10, 100), (64, 64, 32), (70, 130, 33), (129, 200, 65),
@@ -133,21 +187,37 @@ def test_gemm_mixed_operand_types(rt, engine):
     assert lib.skf_gemm(nat.SKF_F32, engine, C.byref(d), None, 0, None) == -1
 
 
-def run_gemm_bf16(rt, A, B, splits=0):
-    """C = A @ B with bf16 operands through skf_gemm_bf16 (A: M x K, B: K x N given as floats)."""
+def bf16_result(rt, M, N, ldc_pad):
+    """The f32 result of a bf16 operator: M rows N + ldc_pad apart, every element NaN before the call."""
+    return Stored(rt.mem, np.full((M, N), np.nan, np.float32), ldc_pad)
+
+
+def bf16_check(got, Ar, Br, K, splits, what):
+    """|got - want| <= 2 (K + s) 2^-24 (|A| |B|)_ij against the f64 product of the operands as stored (exact bf16 products,
+    f32 accumulation in any order, the slice sum; the factor 2: the matrix core's alignment of a 32-term step)."""
+    want, absP = Ar @ Br, np.abs(Ar) @ np.abs(Br)
+    elementwise(got, want, 2.0 * (K + max(splits, 1)) * 2.0 ** -24 * absP, what)
+    return want
+
+
+def run_gemm_bf16(rt, A, B, splits=0, ldc_pad=0, lda_pad=0, ws_bytes=None, check=None):
+    """C = A @ B with bf16 operands through skf_gemm_bf16 (A: M x K, B: K x N given as floats).  ldc_pad: extra elements per
+    row of C (NaN before and after), lda_pad: extra (zero) elements per row of A, a multiple of 8; `check`: a label -- hold
+    the result to the elementwise bound of bf16_check."""
     M, K = A.shape
     N = B.shape[1]
     Kp = (K + 63) // 64 * 64
-    Ab = np.zeros((M, Kp), np.uint16)
+    Ab = np.zeros((M, Kp + lda_pad), np.uint16)
     Ab[:, :K] = nat.to_bf16_bits(A)
     Bb = np.zeros((N, Kp), np.uint16)
     Bb[:, :K] = nat.to_bf16_bits(B.T)
     a, b = rt.mem.from_host(Ab), rt.mem.from_host(Bb)
-    c = rt.mem.empty(M * N * 4)
-    ws = rt.mem.empty(40 * M * N * 4 + 256)
-    rt.call('skf_gemm_bf16', a.ptr, Kp, b.ptr, Kp, c.ptr, N, M, N, Kp, splits, ws.ptr, ws.nbytes, None)
-    got = rt.mem.to_host(c, (M, N), np.float32)
-    want = nat.from_bf16_bits(Ab[:, :K]).astype(np.float64) @ nat.from_bf16_bits(Bb[:, :K]).astype(np.float64).T
+    c = bf16_result(rt, M, N, ldc_pad)
+    ws = rt.mem.empty(40 * M * N * 4 + 256 if ws_bytes is None else ws_bytes)
+    rt.call('skf_gemm_bf16', a.ptr, Kp + lda_pad, b.ptr, Kp, c.ptr, c.ld, M, N, Kp, splits, ws.ptr, ws.nbytes, None)
+    got = c.download()
+    Ar, Br = nat.from_bf16_bits(Ab[:, :K]).astype(np.float64), nat.from_bf16_bits(Bb[:, :K]).astype(np.float64).T
+    want = Ar @ Br if check is None else bf16_check(got, Ar, Br, K, splits, check)
     return got, want
 
 
@@ -165,23 +235,24 @@ def test_gemm_bf16_contraction(rt, shape):
         assert relerr(got, want) < 2e-6, splits     # exact products, f32 accumulation
 
 
-def run_gemm_bf16_tn(rt, R, G, splits=0):
+def run_gemm_bf16_tn(rt, R, G, splits=0, ldc_pad=0, lda_pad=0, ws_bytes=None, check=None):
     """Q = R^T @ G through skf_gemm_bf16_tn: R (K x M, row-major, the relation as stored) is read
     transposed out of LDS; G (K x N) is passed as the stored transpose G^T."""
     K, M = R.shape
     N = G.shape[1]
     Kp = (K + 63) // 64 * 64
-    lda = (M + 63) // 64 * 64
+    lda = (M + 63) // 64 * 64 + lda_pad
     Rb = np.zeros((Kp, lda), np.uint16)
     Rb[:K, :M] = nat.to_bf16_bits(R)
     Gt = np.zeros((N, Kp), np.uint16)
     Gt[:, :K] = nat.to_bf16_bits(G.T)
     a, b = rt.mem.from_host(Rb), rt.mem.from_host(Gt)
-    c = rt.mem.empty(M * N * 4)
-    ws = rt.mem.empty(40 * M * N * 4 + 256)
-    rt.call('skf_gemm_bf16_tn', a.ptr, lda, b.ptr, Kp, c.ptr, N, M, N, Kp, splits, ws.ptr, ws.nbytes, None)
-    got = rt.mem.to_host(c, (M, N), np.float32)
-    want = nat.from_bf16_bits(Rb[:K, :M]).astype(np.float64).T @ nat.from_bf16_bits(Gt[:, :K]).astype(np.float64).T
+    c = bf16_result(rt, M, N, ldc_pad)
+    ws = rt.mem.empty(40 * M * N * 4 + 256 if ws_bytes is None else ws_bytes)
+    rt.call('skf_gemm_bf16_tn', a.ptr, lda, b.ptr, Kp, c.ptr, c.ld, M, N, Kp, splits, ws.ptr, ws.nbytes, None)
+    got = c.download()
+    Ar, Br = nat.from_bf16_bits(Rb[:K, :M]).astype(np.float64).T, nat.from_bf16_bits(Gt[:, :K]).astype(np.float64).T
+    want = Ar @ Br if check is None else bf16_check(got, Ar, Br, K, splits, check)
     return got, want
 
 
@@ -198,7 +269,7 @@ def test_gemm_bf16_transposed_a(rt, shape):
         assert relerr(got, want) < 2e-6, splits
 
 
-def run_gemm_bits(rt, Rb, G, transposed, splits=0):
+def run_gemm_bits(rt, Rb, G, transposed, splits=0, ldc_pad=0, ws_bytes=None, check=None):
     """Binary relation Rb (0 / 1) as a bitmap through skf_gemm_bits: P = Rb @ G (transposed=0, Rb is M x K) or
     Q = Rb^T @ G (transposed=1, Rb is K x M)."""
     rows, cols = Rb.shape
@@ -216,13 +287,13 @@ def run_gemm_bits(rt, Rb, G, transposed, splits=0):
     Gt = np.zeros((N, Kp), np.uint16)
     Gt[:, :K] = nat.to_bf16_bits(G.T)
     a, b = rt.mem.from_host(bits), rt.mem.from_host(Gt)
-    c = rt.mem.empty(M * N * 4)
-    ws = rt.mem.empty(40 * M * N * 4 + 256)
-    rt.call('skf_gemm_bits', a.ptr, ldb_bytes, b.ptr, Kp, c.ptr, N, M, N, Kp, 1 if transposed else 0, splits,
+    c = bf16_result(rt, M, N, ldc_pad)
+    ws = rt.mem.empty(40 * M * N * 4 + 256 if ws_bytes is None else ws_bytes)
+    rt.call('skf_gemm_bits', a.ptr, ldb_bytes, b.ptr, Kp, c.ptr, c.ld, M, N, Kp, 1 if transposed else 0, splits,
             ws.ptr, ws.nbytes, None)
-    got = rt.mem.to_host(c, (M, N), np.float32)
-    Gr = nat.from_bf16_bits(Gt[:, :K]).astype(np.float64).T
-    want = (Rb.T if transposed else Rb).astype(np.float64) @ Gr
+    got = c.download()
+    Ar, Br = (Rb.T if transposed else Rb).astype(np.float64), nat.from_bf16_bits(Gt[:, :K]).astype(np.float64).T
+    want = Ar @ Br if check is None else bf16_check(got, Ar, Br, K, splits, check)
     return got, want
 
 
@@ -583,3 +654,206 @@ def test_errors_are_reported_not_thrown(rt):
     t[0].n_obj, t[0].rank = 5, 0
     opt = nat.Options(nat.SKF_F64, nat.SKF_DFMF, -1, 0)
     assert lib.skf_plan_create(1, t, 0, None, 0, None, C.byref(opt), C.byref(out)) == -1
+
+
+# ---- the stand-alone operators at the layouts the ABI promises: unpacked strides, misaligned bases, sub-matrix views, exact
+# scratch, many slices (the GPU twins: tests/test_gpu_parity.py).  Reference and bound of every check below: the product of
+# the operands AS STORED (rounded to f32 / bf16 first) in f64 (np.longdouble for the f64 engine), elementwise
+#     |got - want| <= (K + s) u (|A| |B|)_ij          f32 / f64 products, u = 2^-24 / 2^-53, s the slice count
+#     |got - want| <= 2 (K + s) 2^-24 (|A| |B|)_ij    bf16 products
+# -- the first-order bound of a length-K sum in any order plus the sum of the slices; the factor 2 of the bf16 form covers the
+# matrix core's internal alignment of a 32-term step (a derived allowance, not a measured one).
+def slices_of(K, splits, bk):
+    """The K slices a request for `splits` becomes (fit_slices of skf_gemm_launch.inc: whole K tiles of `bk` per slice)."""
+    ktiles = -(-K // bk)
+    chunk = -(-ktiles // max(min(splits, ktiles), 1)) * bk
+    return -(-K // chunk)
+
+
+def gemm_check(rt, dtype, engine, A, B, what, splits=0, epi=0, ones=False, mask=None, nan=0, skip_rows=(), s=None, **kw):
+    """One skf_gemm call held to the elementwise bound (plain store; epi 3 on ones; epi 4 through a mask); `s`: the slices
+    that run where they differ from the `splits` asked for."""
+    M = A.shape[1] if kw.get('transA') else A.shape[0]
+    N = B.shape[0] if kw.get('transB') else B.shape[1]
+    info = {}
+    C0 = np.ones((M, N)) if ones else (np.full((M, N), 0.25) if mask is not None else None)
+    g1, g2 = run_gemm(rt, dtype, engine, A, B, epi=epi, C0=C0, C20=C0 if ones else None, mask=mask, nan=nan, splits=splits,
+                      info=info, **kw)
+    K = A.shape[0] if kw.get('transA') else A.shape[1]
+    P, u = info['P'], info['u']
+    bound = (K + max(splits if s is None else s, 1)) * u * info['absP']
+    keep = np.setdiff1d(np.arange(M), skip_rows)
+    if epi == 3:
+        w1, w2 = 1 + np.maximum(P, 0), 1 + np.maximum(-P, 0)
+        elementwise(g1[keep], w1[keep], bound[keep], what + ' C')
+        elementwise(g2[keep], w2[keep], bound[keep], what + ' C2')
+    elif epi == 4:
+        elementwise(g1[keep], np.where(mask, P, 0.25)[keep], np.where(mask, bound, 0.0)[keep], what)
+    else:
+        elementwise(g1[keep], P[keep], bound[keep], what)
+    return g1
+
+
+def layouts(V):
+    """(pad, off) of A, of B, pad and off of C: every operand layout with its like, and the pairs that differ in kind."""
+    packed, unpacked, scalar, misaligned, view = (0, 0), (V, 0), (1, 0), (0, 1), (V, V)
+    pairs = [(packed, packed), (unpacked, unpacked), (scalar, scalar), (misaligned, misaligned), (view, view),
+             (unpacked, scalar), (scalar, unpacked), (misaligned, packed), (packed, misaligned), (view, unpacked)]
+    return [(a, b, (0, 1, 3)[q % 3], (0, 0, 0, 1, V)[q % 5]) for q, (a, b) in enumerate(pairs)]
+
+
+@pytest.mark.parametrize('dtype', [nat.SKF_F64, nat.SKF_F32])
+@pytest.mark.parametrize('engine', [nat.SKF_ENGINE_MFMA, nat.SKF_ENGINE_VALU])
+def test_gemm_strides_and_alignment(rt, dtype, engine):
+    """stage_mode (device) and host_stage_mode (host, which also decides the big tile) see strides, lengths and base
+    alignment that do not coincide: V = 16 bytes of elements; operands packed, with V or 1 pad elements per row, one element
+    off a 16-byte base, and as an aligned view into a wider matrix.  Pads of C hold NaN and come back bit for bit.
+
+    Which tile a shape runs on (pick_tile, gemm_tile; matrix-core engine):
+      K = 64, 64 + V   f32: (70, 40, .) the small tile (64 x 64 x 32, run-time modes), (130, 132, .) and (128 + V, 132, .) the
+                       big tile (128 x 128 x 32, compile-time modes) where the layout pair has an instantiation.  f64: every
+                       all-f64 product with 64 <= K <= 1024 takes the DEEP tile (32 x 32 x 64, run-time modes), so these
+                       shapes reach neither the f64 small nor the f64 big tile.
+      K = 48, 48 + V   below the deep tile's range: f64 (70, 40, .) runs the small tile (32 x 32 x 16), (130, 132, .) and
+                       (64 + V, 132, .) the big tile (64 x 128 x 16; 64 + V: the row tail row_end - V of its 64 rows), with
+                       host_stage_mode<double> deciding at V = 2; f32 takes its small / big tile with a partial K tile.
+      K = 64 + V, 48 + V, M = 128 + V, 64 + V: the vector tails (k_end - V, row_end - V) on an unpacked stride.
+
+    Against a mix-up of the stride test and the length test in stage_mode / host_stage_mode (s_row % V for K % V) the
+    sharpness of this test rests on the emulator build alone: such a mix-up picks 16-byte loads for rows that start off a
+    16-byte boundary, which return the right bytes on the hardware (the GPU twin cannot see it), while the host compiler's
+    aligned 16-byte move faults on them and ends the emulator process."""
+    V = 16 // np.dtype(nat.NP_DTYPE[dtype]).itemsize
+    rs = np.random.RandomState(11)
+    every = layouts(V)
+    for (M, N, K), lays in (((70, 40, 64), every), ((130, 132, 64), every), ((70, 40, 64 + V), every[:5]),
+                            ((128 + V, 132, 64), every[:5]), ((70, 40, 48), every), ((130, 132, 48), every),
+                            ((70, 40, 48 + V), every[:5]), ((130, 132, 48 + V), every[:5]), ((64 + V, 132, 48), every[:5])):
+        for transA in (False, True):
+            for transB in (False, True):
+                A = rs.randn(*((K, M) if transA else (M, K)))
+                B = rs.randn(*((N, K) if transB else (K, N)))
+                for (pa, oa), (pb, ob), pc, oc in lays:
+                    what = 'gemm strides dtype %d engine %d %dx%dx%d tA %d tB %d A %d+%d B %d+%d C %d+%d' % (
+                        dtype, engine, M, N, K, transA, transB, pa, oa, pb, ob, pc, oc)
+                    gemm_check(rt, dtype, engine, A, B, what, transA=transA, transB=transB, pad_a=pa, off_a=oa, pad_b=pb,
+                               off_b=ob, pad_c=pc, off_c=oc)
+
+
+@pytest.mark.parametrize('dtype', [nat.SKF_F64, nat.SKF_F32])
+def test_gemm_many_slices(rt, dtype):
+    """splitk_reduce_z16_kernel (8 slices and more): A^T B with K = 1100, 8, 9 and 16 slices asked for on EXACTLY
+    splits * M * N elements of scratch between guard bands -- plain store, the split accumulate on ones, the masked store
+    with ldc = N + 3, nan_to_num.  A slice is a whole number of K tiles (slices_of): f64 (K tile 16) runs 8, 9 and 14
+    slices, all on the z16 kernel; f32 (K tile 32, 35 tiles) runs 7 (splitk_reduce_kernel), 9 and 12 (z16).  The bound
+    takes the slices that run."""
+    from guarded import guarded
+    rs = np.random.RandomState(12)
+    A, B = rs.randn(1100, 20), rs.randn(1100, 30)
+    M, N = 20, 30
+    size = np.dtype(nat.NP_DTYPE[dtype]).itemsize
+    mask = rs.rand(M, N) > 0.6
+    A2 = A.copy()
+    A2[3, 2], A2[5, 4] = np.nan, np.inf
+    ran = [slices_of(1100, s, 16 if dtype == nat.SKF_F64 else 32) for s in (8, 9, 16)]
+    assert ran == ([8, 9, 14] if dtype == nat.SKF_F64 else [7, 9, 12])
+    with guarded(rt) as g:
+        for splits, s in zip((8, 9, 16), ran):
+            kw = dict(splits=splits, s=s, transA=True, ws_bytes=splits * M * N * size)
+            what = 'gemm many slices dtype %d %d slices asked %d run' % (dtype, splits, s)
+            gemm_check(g.rt, dtype, nat.SKF_ENGINE_MFMA, A, B, what + ' store', **kw)
+            gemm_check(g.rt, dtype, nat.SKF_ENGINE_MFMA, A, B, what + ' epi 3', epi=3, ones=True, **kw)
+            gemm_check(g.rt, dtype, nat.SKF_ENGINE_MFMA, A, B, what + ' epi 4', epi=4, mask=mask, pad_c=3, **kw)
+            got = gemm_check(g.rt, dtype, nat.SKF_ENGINE_MFMA, A2, B, what + ' nan_to_num', nan=1, skip_rows=(2, 4), **kw)
+            assert np.isfinite(got).all() and (got[2] == 0).all() and (np.abs(got[4]) == np.finfo(got.dtype).max).all()
+    assert g.bands > 0
+
+
+@pytest.mark.parametrize('op', ['plain', 'plain256', 'tn', 'bits0', 'bits1'])
+def test_gemm_bf16_reduce_layouts(rt, op):
+    """bf16_splitk_reduce_kernel off its 16-byte path: M * N odd (the scalar path with two slices and more), ldc = N + 3, an
+    M * N % 4 == 0 product with ldc = N + 8, lda = Kp + 64 -- every run on exactly splits * M * N floats of scratch between
+    guard bands.  The smallest shapes with two K tiles of 64 per slice and a row, a column and a K tail; (4097, 33, 200): the
+    256-row kernel of the plain form."""
+    from guarded import guarded
+    rs = np.random.RandomState(13)
+
+    def ws(M, N, s):
+        return s * M * N * 4
+
+    with guarded(rt) as g:
+        r = g.rt
+        if op in ('plain', 'plain256'):
+            M, N, K = (129, 33, 200) if op == 'plain' else (4097, 33, 200)
+            A, B = rs.randn(M, K), rs.randn(K, N)
+            for s in ((2, 3) if op == 'plain' else (2,)):
+                for pad in (0, 3):
+                    run_gemm_bf16(r, A, B, s, ldc_pad=pad, ws_bytes=ws(M, N, s), check='bf16 %s %d slices ldc N + %d' % (op, s, pad))
+            run_gemm_bf16(r, A, B, 2, lda_pad=64, ws_bytes=ws(M, N, 2), check='bf16 %s lda Kp + 64' % op)
+            if op == 'plain':
+                run_gemm_bf16(r, A, B[:, :32], 2, ldc_pad=8, ws_bytes=ws(M, 32, 2), check='bf16 plain 129 x 32 ldc N + 8')
+        elif op == 'tn':
+            K, M, N = 200, 129, 33
+            R, G = rs.randn(K, M), rs.randn(K, N)
+            for s in (2, 3):
+                for pad in (0, 3):
+                    run_gemm_bf16_tn(r, R, G, s, ldc_pad=pad, ws_bytes=ws(M, N, s), check='bf16 tn %d slices ldc N + %d' % (s, pad))
+            run_gemm_bf16_tn(r, R, G, 2, lda_pad=64, ws_bytes=ws(M, N, 2), check='bf16 tn lda + 64')
+            run_gemm_bf16_tn(r, R, G[:, :32], 2, ldc_pad=8, ws_bytes=ws(M, 32, 2), check='bf16 tn 129 x 32 ldc N + 8')
+        else:
+            transposed = int(op[-1])
+            N, rows, cols = 33, 129, 201
+            Rb = (rs.rand(rows, cols) < 0.3).astype(np.float64)
+            G = rs.randn(rows if transposed else cols, N)
+            M = cols if transposed else rows
+            for pad in (0, 3):
+                run_gemm_bits(r, Rb, G, transposed, 2, ldc_pad=pad, ws_bytes=ws(M, N, 2), check='bf16 %s ldc N + %d' % (op, pad))
+    assert g.bands > 0
+
+
+def test_workspaces_are_exact(rt):
+    """skf_pinv_sym, skf_fill_unknown and the three completion operators (col_splits 0 and 3; top-k also 2, where the last
+    of its partial lists is written, and k = 64, where a list is as long as the granule of the sizes) on exactly the bytes their
+    query returns, between guard bands; one byte fewer: SKF_E_WORKSPACE and outputs untouched (the completion operators'
+    refusals: their own cases, under guard)."""
+    import complete_cases as CC
+    import ranks_cases as RC
+    import above_cases as AC
+    from guarded import guarded
+    rs = np.random.RandomState(14)
+    with guarded(rt) as g:
+        r, mem = g.rt, g.rt.mem
+        for n in (33, 70):
+            G = rs.rand(3 * n, n)
+            A = G.T @ G
+            assert relerr(A @ run_pinv(r, nat.SKF_F64, A) @ A, A) < 1e-11          # (run_pinv: exactly the queried bytes)
+            need = C.c_size_t()
+            r.call('skf_pinv_sym_workspace_bytes', n, C.byref(need))
+            a, k, ws = mem.from_host(A), mem.from_host(np.full((n, n), -7.0)), mem.empty(need.value)
+            rc = r.lib.skf_pinv_sym(nat.SKF_F64, a.ptr, n, k.ptr, n, n, ws.ptr, need.value - 1, None)
+            mem.synchronize()
+            assert rc == nat.SKF_E_WORKSPACE and (mem.to_host(k, (n, n), np.float64) == -7.0).all()
+        rows, cols = 37, 53
+        X = rs.rand(rows, cols)
+        X[rs.rand(rows, cols) < 0.2] = np.nan
+        need = C.c_size_t()
+        r.call('skf_fill_unknown_workspace_bytes', rows, cols, C.byref(need))
+        for strategy, want in ((0, np.where(np.isnan(X), np.nanmean(X), X)),
+                               (1, np.where(np.isnan(X), np.nanmean(X, axis=1)[:, None], X)),
+                               (2, np.where(np.isnan(X), np.nanmean(X, axis=0)[None, :], X))):
+            x, ws = mem.from_host(X), mem.empty(need.value)
+            rc = r.lib.skf_fill_unknown(nat.SKF_F64, x.ptr, cols, rows, cols, None, 0, strategy, 0.0, ws.ptr, need.value - 1, None)
+            mem.synchronize()
+            assert rc == nat.SKF_E_WORKSPACE
+            np.testing.assert_array_equal(mem.to_host(x, (rows, cols), np.float64), X)
+            r.call('skf_fill_unknown', nat.SKF_F64, x.ptr, cols, rows, cols, None, 0, strategy, 0.0, ws.ptr, need.value, None)
+            mem.synchronize()
+            np.testing.assert_allclose(mem.to_host(x, (rows, cols), np.float64), want, rtol=1e-13, atol=0)
+        for dtype in ('f64', 'f32'):
+            CC.exact_case(dtype, 67, 203, (5, 7), ks=(10, 64), patterns=('edges',), splits=(0, 2, 3))
+            RC.exact_case(dtype, 67, 203, (5, 7), patterns=('edges',), splits=(0, 3))
+            AC.exact_case(dtype, 67, 203, (5, 7), patterns=('edges',), splits=(0, 3))
+            CC.refusals_case(dtype)
+            RC.refusals_case(dtype)
+            AC.refusals_case(dtype)
+    assert g.bands > 0

@@ -52,6 +52,26 @@ def test_gemm_split_k(rt, dtype):
     K.test_gemm_split_k_and_nan_to_num(rt, dtype)
 
 
+@pytest.mark.parametrize('dtype', [nat.SKF_F64, nat.SKF_F32])
+@pytest.mark.parametrize('engine', [nat.SKF_ENGINE_MFMA, nat.SKF_ENGINE_VALU])
+def test_gemm_strides_and_alignment(rt, dtype, engine):
+    K.test_gemm_strides_and_alignment(rt, dtype, engine)
+
+
+@pytest.mark.parametrize('dtype', [nat.SKF_F64, nat.SKF_F32])
+def test_gemm_many_slices(rt, dtype):
+    K.test_gemm_many_slices(rt, dtype)
+
+
+@pytest.mark.parametrize('op', ['plain', 'plain256', 'tn', 'bits0', 'bits1'])
+def test_gemm_bf16_reduce_layouts(rt, op):
+    K.test_gemm_bf16_reduce_layouts(rt, op)
+
+
+def test_workspaces_are_exact(rt):
+    K.test_workspaces_are_exact(rt)
+
+
 def test_mfma_and_valu_engines_agree_bitwise_in_f32(rt):
     """v_mfma_f32_32x32x2_f32 is an exact k-ordered fma chain: identical to the VALU kernel when
     the K tiling is the same chain order (single K slice)."""
