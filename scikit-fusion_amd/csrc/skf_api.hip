@@ -120,6 +120,8 @@ static inline int wave_grid(int64_t rows) {
 
 #include "skf_pinv.inc"
 
+#include "skf_steps.inc"
+
 #include "skf_stages.inc"
 
 #include "skf_dist.inc"

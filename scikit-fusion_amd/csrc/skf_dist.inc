@@ -1,5 +1,7 @@
 // skf_dist.inc -- part of the one translation unit skf_api.hip (textually included there, inside its namespaces; not a
-// header of its own): collectives behind the boundary (RCCL by dlopen, callbacks, the null communicator) and the sharded iterations: skf_iterate_dist, ownership-aligned rows.
+// header of its own): collectives behind the boundary (RCCL by dlopen, callbacks, the null communicator) and the sharded
+// iterations: skf_iterate_dist, which cuts the staged schedule between its collectives, and the OWNED-ROWS schedule, which
+// orders the steps of skf_steps.inc over three streams with the exchanges between them.
 // ------------------------------------------------------------------------------------------
 // Collectives behind the boundary (include/skfusion_hip.h, skf_comm_*): RCCL bound at run time with dlopen -- no
 // torch, no link-time dependency -- or caller-supplied callbacks (CPU tests over gloo, other transports).
@@ -195,18 +197,9 @@ static size_t exchange_bytes(const skf_plan* p, int world) {
 // ------------------------------------------------------------------------------------------
 static bool owned_can_overlap(const skf_plan* p) {
     if (!p->overlap || p->engine != SKF_ENGINE_MFMA) return false;
-    for (const ThetaState& th : p->thetas)
-        if (!th.sparse) return false;
-    // ranks above 512 (DFMC: 256): a c x c product on the second stream could ask for the main stream's split-K scratch;
     // every rank <= 64: launch-bound graphs, one stream.  Mixed ranks (config 5: 16 ... 256) do overlap: the replicated
     // pseudo-inverses (0.65 ms at order 256) then run beside the list passes instead of in front of them.
-    const int cmax = (p->variant == SKF_DFMC) ? 256 : 512;
-    bool all_small = true;
-    for (const TypeState& t : p->types) {
-        if (t.c > cmax) return false;
-        if (t.c > SMALLC) all_small = false;
-    }
-    return !all_small;
+    return chains_fit_second_stream(p);
 }
 
 static void iterate_owned(skf_plan* p, hipStream_t st) {
@@ -292,50 +285,19 @@ static void iterate_owned(skf_plan* p, hipStream_t st) {
         // known-entries relations: the factor their stored residuals belong to (all rows: every one is current here)
         if (t.keep_prev) SKF_HIP(hipMemcpyAsync(t.Gp.ptr, t.G.ptr, (size_t)t.n * t.c * p->esz, hipMemcpyDeviceToDevice, ax));
         if (t.tn > 0) {
-            void* G = own(t.G, t);
-            void* E = own(t.E, t);
-            void* D = own(t.D, t);
             if (!touched[i]) {
-                SKF_HIP(hipMemsetAsync(E, 0, (size_t)t.tn * t.c * p->esz, ax));
-                SKF_HIP(hipMemsetAsync(D, 0, (size_t)t.tn * t.c * p->esz, ax));
+                zero_ed_rows(p, t, t.t0, t.tn, ax);
                 touched[i] = 1;
             }
-            if (fused) {
-                const void* Bn = t.Bn_tot.ptr;
-                const void* Bp = t.Bp_tot.ptr;
-                if (!p->f64) {
-                    cast_b_sums(t, ax);
-                    Bn = t.Bn32.ptr;
-                    Bp = t.Bp32.ptr;
-                }
-                side_update(p, nullptr, 0, 0, nullptr, 0, 0, t, G, E, D, (int)t.tn, Bn, Bp, true, true, 0, ax);
-            } else {
-                GemmArgs g = gemm_args(G, t.c, 1, t.Bn_tot.ptr, t.c, 1, E, t.c, (int)t.tn, t.c, t.c, EPI_ACC, 0);
-                mixed_gemm(p, g, ax);
-                g = gemm_args(G, t.c, 1, t.Bp_tot.ptr, t.c, 1, D, t.c, (int)t.tn, t.c, t.c, EPI_ACC, 0);
-                mixed_gemm(p, g, ax);
-            }
+            // (its own launch on the owned rows, the B sums rounded here for the fused form)
+            const BSums b = fused ? b_sums_master(p, t, ax) : BSums{t.Bn_tot.ptr, t.Bp_tot.ptr};
+            type_term(p, t, t.t0, t.tn, b.Bn, b.Bp, true, fused, ax);
             theta_terms_rows(p, (int)i, true, ax);
-            // G[own] <- G[own] * sqrt(E / max(D, eps))   (_dfmf.py:294-296); SKF_BF16: with the bf16 copies of those rows
-            if (c->null_comm) {
-                // rank-emulation runs (skf_comm_create_null): the factors stay as they were set -- with nothing exchanged the
-                // updated rows drift away from the rows of the ranks that do not exist, the Gram matrices go singular and the
-                // timed pseudo-inverses take their slow fallbacks (measured: 4-15 ms per iteration); the update launch
-                // itself (~10 us per type) is what the measurement then leaves out
-            } else if (p->bf16) {
-                hipLaunchKernelGGL(mult_update_transpose_kernel, dim3((unsigned)cdiv(t.c, 32), (unsigned)cdiv(t.tn, 32)), dim3(256), 0,
-                                   ax, (float*)G, (const float*)E, (const float*)D, (int64_t)t.tn, (int64_t)t.c,
-                                   (uint16_t*)t.GTb.ptr + t.t0, t.ldgt, (uint16_t*)t.Grow.ptr + t.t0 * t.ldrow, t.ldrow);
-                check_launch("mult_update_transpose(rows)");
-            } else if (p->f64) {
-                hipLaunchKernelGGL((mult_update_kernel<double>), dim3(elem_grid(t.tn * t.c)), dim3(256), 0, ax, (double*)G,
-                                   (const double*)E, (const double*)D, t.tn, t.c, (int64_t)t.c, (int64_t)t.c);
-                check_launch("mult_update(rows)");
-            } else {
-                hipLaunchKernelGGL((mult_update_kernel<float>), dim3(elem_grid(t.tn * t.c)), dim3(256), 0, ax, (float*)G,
-                                   (const float*)E, (const float*)D, t.tn, t.c, (int64_t)t.c, (int64_t)t.c);
-                check_launch("mult_update(rows)");
-            }
+            // rank-emulation runs (skf_comm_create_null): the factors stay as they were set -- with nothing exchanged the
+            // updated rows drift away from the rows of the ranks that do not exist, the Gram matrices go singular and the
+            // timed pseudo-inverses take their slow fallbacks (measured: 4-15 ms per iteration); the update launch
+            // itself (~10 us per type) is what the measurement then leaves out
+            if (!c->null_comm) update_rows(p, t, t.t0, t.tn, ax);
         }
         rec(ev_t(i, T_UPD), ax);
         wait(cs, ev_t(i, T_UPD));
@@ -362,8 +324,7 @@ static void iterate_owned(skf_plan* p, hipStream_t st) {
         } else if (r.kn) {                  // lists of known entries: the block's share of W from its stored residuals (skf_known.h)
             known_w(p, r, st);
         } else {
-            GemmArgs g = gemm_args(own(ti.G, ti), 1, ti.c, r.P.ptr, tj.c, 1, r.W.ptr, tj.c, ti.c, tj.c, (int)r.nr, EPI_STORE, 0);
-            wide_gemm(p, g, st);
+            w_product(p, r, false, st);
         }
         rec(ev_r(k, R_W), st);
         wait(cs, ev_r(k, R_W));
@@ -386,55 +347,20 @@ static void iterate_owned(skf_plan* p, hipStream_t st) {
     // second stream, behind the sum of W: S = K_i W K_j, its B / D terms, the rounding of S
     auto backbone_chain = [&](size_t k) {
         RelState& r = p->rels[k];
-        TypeState& ti = p->types[r.row];
-        TypeState& tj = p->types[r.col];
-        const int ci = ti.c, cj = tj.c;
         wait(ax, ev_r(k, R_WX));
-        bool s32_here = false;
+        // f32 engines, fused side products: the rounding of S leaves the S launch (the chain kernels have no such form)
+        const bool s32_here = !chain && !p->f64 && fused && !p->sw.no_pairs;
         if (chain) {
-            BackboneBatch bb;
-            bb.Ki[0] = (const double*)ti.K.ptr; bb.Kj[0] = (const double*)tj.K.ptr;
-            bb.W[0] = (const double*)r.W.ptr; bb.S[0] = (double*)r.S.ptr;
-            bb.ci[0] = ci; bb.cj[0] = cj;
-            const size_t smem = ((size_t)ci * ci + 2 * (size_t)ci * cj + (size_t)cj * cj) * 8;
-            static DeviceOnce once_bb, once_bt;
-            allow_dynamic_lds(once_bb, backbone_small_kernel, 4 * SMALLC * SMALLC * 8);
-            allow_dynamic_lds(once_bt, bterms_small_kernel, 4 * SMALLC * SMALLC * 8);
-            hipLaunchKernelGGL(backbone_small_kernel, dim3(1), dim3(256), smem, ax, bb);
-            check_launch("backbone_small");
-            BTermsArgs ba;
-            ba.S = (const double*)r.S.ptr; ba.Gram_i = (const double*)ti.Gram.ptr; ba.Gram_j = (const double*)tj.Gram.ptr;
-            ba.Bp_i = (double*)ti.Bp_tot.ptr; ba.Bn_i = (double*)ti.Bn_tot.ptr;
-            ba.Bp_j = (double*)tj.Bp_tot.ptr; ba.Bn_j = (double*)tj.Bn_tot.ptr;
-            ba.ci = ci; ba.cj = cj; ba.nan_to_num = nan_upd;
-            hipLaunchKernelGGL(bterms_small_kernel, dim3(1), dim3(256), smem, ax, ba);
-            check_launch("bterms_small");
+            backbone_small_batch(p, k, 1, ax);
+            bterms_small(p, r, nan_upd, ax);
+            Sm[k] = r.S.ptr;
         } else {
-            GemmArgs g = gemm_args(ti.K.ptr, ci, 1, r.W.ptr, cj, 1, r.T1.ptr, cj, ci, cj, ci, EPI_STORE, 0);       // T1 = K_i W
-            small_gemm(p, g, ax);
-            g = gemm_args(r.T1.ptr, cj, 1, tj.K.ptr, cj, 1, r.S.ptr, cj, ci, cj, cj, EPI_STORE, 1);                // S = T1 K_j
-            s32_here = !p->f64 && fused && !p->sw.no_pairs;        // f32 engines: the rounding of S leaves the same launch
-            if (s32_here) {
-                g.epi = EPI_STORE_F32;
-                g.C2 = r.S32.ptr;
-                g.ldc2 = cj;
-            }
-            small_gemm(p, g, ax);
-            relation_small_terms(p, r, nan_upd, EPI_SPLIT_ACC, ti.Bp_tot.ptr, ti.Bn_tot.ptr, tj.Bp_tot.ptr, tj.Bn_tot.ptr,
-                                 true, true, ax, r.T1.ptr);           // (T1 is free once S is there)
+            Sm[k] = backbone_general(p, r, nan_upd, s32_here, r.T1.ptr, ax);       // (paired: T1 is free once S is there)
         }
-        Sm[k] = r.S.ptr;
-        if (!p->f64 && fused) {
-            if (!s32_here) {
-                hipLaunchKernelGGL((cast_kernel<float, double>), dim3(elem_grid((int64_t)ci * cj)), dim3(256), 0, ax,
-                                   (float*)r.S32.ptr, (int64_t)cj, (const double*)r.S.ptr, (int64_t)cj, (int64_t)ci, (int64_t)cj);
-                check_launch("cast");
-            }
-            Sm[k] = r.S32.ptr;
-        }
+        if (!p->f64 && fused && !s32_here) Sm[k] = round_backbone(p, r, ax);
     };
     // second stream: row side on the local rows behind `ev_p`, column side on the owned rows of the column type behind the
-    // scattered Q;  E_i (+)= (P S^T)+, D_i (+)= (P S^T)-;  E_j (+)= (Q S)+, D_j (+)= (Q S)-
+    // scattered Q; E / D of the owned rows are overwritten (fused) or zeroed (unfused) on first touch
     auto side_products = [&](size_t k, hipEvent_t ev_p) {
         RelState& r = p->rels[k];
         TypeState& ti = p->types[r.row];
@@ -445,18 +371,8 @@ static void iterate_owned(skf_plan* p, hipStream_t st) {
             known_row_split(p, r, touched[r.row] != 0, ax);
             touched[r.row] = 1;
         } else if (!r.absent) {
-            if (fused) {
-                side_update(p, r.P.ptr, cj, cj, Sm[k], 1, cj, ti, own(ti.G, ti), own(ti.E, ti), own(ti.D, ti), (int)r.nr, nullptr,
-                            nullptr, false, touched[r.row] != 0, nan_upd, ax);
-            } else {
-                if (!touched[r.row]) {
-                    SKF_HIP(hipMemsetAsync(own(ti.E, ti), 0, (size_t)ti.tn * ci * p->esz, ax));
-                    SKF_HIP(hipMemsetAsync(own(ti.D, ti), 0, (size_t)ti.tn * ci * p->esz, ax));
-                }
-                GemmArgs g = gemm_args(r.P.ptr, cj, 1, r.S.ptr, 1, cj, own(ti.E, ti), ci, (int)r.nr, ci, cj, EPI_SPLIT_ACC, nan_upd);
-                g.C2 = own(ti.D, ti);
-                mixed_gemm(p, g, ax);
-            }
+            if (!fused && !touched[r.row]) zero_ed_rows(p, ti, ti.t0, ti.tn, ax);
+            row_side(p, r, fused, Sm[k], nullptr, nullptr, false, touched[r.row] != 0, nan_upd, ax);
             touched[r.row] = 1;
         }
         side_done(r.row);
@@ -466,19 +382,8 @@ static void iterate_owned(skf_plan* p, hipStream_t st) {
             if (!r.absent) copy2d(r.Sp.ptr, cj, r.S.ptr, cj, ci, cj, 8, ax);
         }
         if (tj.tn > 0) {
-            const void* Qo = (const char*)r.Q.ptr + (size_t)tj.t0 * ci * p->esz;
-            if (fused) {
-                side_update(p, Qo, ci, ci, Sm[k], cj, 1, tj, own(tj.G, tj), own(tj.E, tj), own(tj.D, tj), (int)tj.tn, nullptr,
-                            nullptr, false, touched[r.col] != 0, nan_upd, ax);
-            } else {
-                if (!touched[r.col]) {
-                    SKF_HIP(hipMemsetAsync(own(tj.E, tj), 0, (size_t)tj.tn * cj * p->esz, ax));
-                    SKF_HIP(hipMemsetAsync(own(tj.D, tj), 0, (size_t)tj.tn * cj * p->esz, ax));
-                }
-                GemmArgs g = gemm_args(Qo, ci, 1, r.S.ptr, cj, 1, own(tj.E, tj), cj, (int)tj.tn, cj, ci, EPI_SPLIT_ACC, nan_upd);
-                g.C2 = own(tj.D, tj);
-                mixed_gemm(p, g, ax);
-            }
+            if (!fused && !touched[r.col]) zero_ed_rows(p, tj, tj.t0, tj.tn, ax);
+            col_side(p, r, fused, tj.t0, tj.tn, Sm[k], nullptr, nullptr, false, touched[r.col] != 0, nan_upd, ax);
             touched[r.col] = 1;
         }
         side_done(r.col);
@@ -517,17 +422,8 @@ static void iterate_owned(skf_plan* p, hipStream_t st) {
                 GemmArgs g = gemm_args(r.S.ptr, 1, tj.c, ti.Gram.ptr, ti.c, 1, r.U2.ptr, ti.c, tj.c, ti.c, ti.c, EPI_STORE, 0);
                 small_gemm(p, g, ax);
             }
-        } else if (!r.absent) {
-            GemmArgs g = gemm_args(own(ti.G, ti), ti.c, 1, r.S.ptr, tj.c, 1, r.H.ptr, tj.c, (int)r.nr, tj.c, ti.c, EPI_STORE, 0);
-            if (multi) mixed_gemm_unsplit(p, g, ax);
-            else mixed_gemm(p, g, ax);
-            if (p->bf16 && r.mask) {        // bf16 operands of the completion tiles: H, and G_j from what this rank holds of it
-                launch_to_bf16<float>((uint16_t*)r.Hb.ptr, r.ldhb, (const float*)r.H.ptr, (int64_t)tj.c, r.nr, tj.c, false, ax);
-                if (tj.gather_master)
-                    launch_to_bf16<float>((uint16_t*)r.Gb.ptr, r.ldhb, (const float*)tj.G.ptr, (int64_t)tj.c, tj.n, tj.c, false, ax);
-                else
-                    launch_to_bf16<uint16_t>((uint16_t*)r.Gb.ptr, r.ldhb, (const uint16_t*)tj.Grow.ptr, tj.ldrow, tj.n, tj.c, false, ax);
-            }
+        } else if (!r.absent) {         // (bf16 operands of the completion tiles: G_j from what this rank holds of it)
+            completion_operands(p, r, multi, ax);
         }
         rec(ev_r(k, R_S), ax);
     }
@@ -536,7 +432,6 @@ static void iterate_owned(skf_plan* p, hipStream_t st) {
     for (size_t k = 0; k < nr; ++k) {
         RelState& r = p->rels[k];
         if (!(dfmc && r.masked)) continue;
-        TypeState& tj = p->types[r.col];
         wait(st, ev_r(k, R_S));
         if (r.kn) {                         // the row pass stands for completion + P: A = E T + G_i (S Gram_j S^T)
             if (!r.absent) {
@@ -544,18 +439,7 @@ static void iterate_owned(skf_plan* p, hipStream_t st) {
                 known_row_dense(p, r, st, false);
             }
         } else if (!r.absent) {
-            if (r.mask) {
-                if (p->bf16) {
-                    launch_tile_epilogue(p, r, MODE_COMPLETE, st, false);
-                } else {
-                    GemmArgs g = gemm_args(r.H.ptr, tj.c, 1, tj.G.ptr, 1, tj.c, r.Rw.ptr, r.ldr, (int)r.nr, (int)tj.n, tj.c,
-                                           EPI_MASKED_STORE, 0);
-                    g.mask = (const uint8_t*)r.Mb.ptr;
-                    g.ldmask = r.ldmb;
-                    g.mask_bits = 1;
-                    plan_gemm(p, g, st);
-                }
-            }
+            if (r.mask) complete_masked(p, r, st);
             contraction_P(p, r, st);
         }
         rec(ev_r(k, R_P2), st);

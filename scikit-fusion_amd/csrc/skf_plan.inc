@@ -455,16 +455,19 @@ static void gram_all(skf_plan* p, int nan, hipStream_t st, bool on_aux) {
     for (size_t i = 0; i < nt; ++i) gram(p, p->types[i], nan, st, on_aux);
 }
 
-static void mult_update(skf_plan* p, TypeState& t, hipStream_t st) {
-    const int64_t total = t.n * t.c;
+// G <- G * sqrt(E / max(D, eps)) on the rows [r0, r0 + n) of the type, master copies only
+static void mult_update_rows(skf_plan* p, TypeState& t, int64_t r0, int64_t n, hipStream_t st) {
+    const int64_t total = n * t.c;
+    const size_t off = (size_t)r0 * t.c;
     if (p->f64)
-        hipLaunchKernelGGL((mult_update_kernel<double>), dim3(elem_grid(total)), dim3(256), 0, st, (double*)t.G.ptr,
-                           (const double*)t.E.ptr, (const double*)t.D.ptr, t.n, t.c, (int64_t)t.c, (int64_t)t.c);
+        hipLaunchKernelGGL((mult_update_kernel<double>), dim3(elem_grid(total)), dim3(256), 0, st, (double*)t.G.ptr + off,
+                           (const double*)t.E.ptr + off, (const double*)t.D.ptr + off, n, t.c, (int64_t)t.c, (int64_t)t.c);
     else
-        hipLaunchKernelGGL((mult_update_kernel<float>), dim3(elem_grid(total)), dim3(256), 0, st, (float*)t.G.ptr,
-                           (const float*)t.E.ptr, (const float*)t.D.ptr, t.n, t.c, (int64_t)t.c, (int64_t)t.c);
+        hipLaunchKernelGGL((mult_update_kernel<float>), dim3(elem_grid(total)), dim3(256), 0, st, (float*)t.G.ptr + off,
+                           (const float*)t.E.ptr + off, (const float*)t.D.ptr + off, n, t.c, (int64_t)t.c, (int64_t)t.c);
     check_launch("mult_update");
 }
+static void mult_update(skf_plan* p, TypeState& t, hipStream_t st) { mult_update_rows(p, t, 0, t.n, st); }
 
 // the hub rows of a sparse constraint inside [r0, r0 + nr): their segments as partial sums, then the sums into E / D.  The
 // table is sorted by row, so the rows of the range are one sub-range of it (found here, on the host).  `E` / `D`: row 0 of

@@ -1,5 +1,6 @@
 // skf_schedule.inc -- part of the one translation unit skf_api.hip (textually included there, inside its namespaces; not a
-// header of its own): the relation pipeline on two streams, the three-launch iteration of small graphs, hipGraph capture, the fold-in.
+// header of its own): the relation PIPELINE -- the steps of skf_steps.inc ordered over two streams, relation by relation --,
+// the three-launch iteration of small graphs, the choice between the schedules (iterate_fit), hipGraph capture, the fold-in.
 // ------------------------------------------------------------------------------------------
 // The same DFMF iteration as stage_contract + stage_backbone + stage_accumulate, scheduled as a pipeline over
 // the relations (whole, unmasked relations; every rank between 65 and 512; MFMA engine): the main stream runs
@@ -14,17 +15,7 @@ static bool can_pipeline(const skf_plan* p) {
     if (!p->overlap || p->sliced || p->engine != SKF_ENGINE_MFMA || !p->pipeline) return false;
     if (p->variant != SKF_DFMF && p->variant != SKF_DFMC) return false;
     if (p->rels.empty() || p->rels.size() > 64) return false;
-    for (const ThetaState& th : p->thetas)
-        if (!th.sparse) return false;            // (dense constraint products share the split-K scratch of the main stream)
-    // every rank <= 64: the one-workgroup chains of the staged schedule are the faster path (launch-bound graphs);
-    // above 512 (DFMC: 256) a c x c product on the second stream could ask for the main stream's split-K scratch
-    const int cmax = (p->variant == SKF_DFMC) ? 256 : 512;
-    bool all_small = true;
-    for (const TypeState& t : p->types) {
-        if (t.c > cmax) return false;
-        if (t.c > SMALLC) all_small = false;
-    }
-    if (all_small) return false;
+    if (!chains_fit_second_stream(p)) return false;      // (every rank <= 64: the one-workgroup chains of the staged schedule)
     if (p->variant == SKF_DFMF)
         for (const TypeState& t : p->types)
             if (t.c <= SMALLC) return false;     // (DFMF: the mixed case stays on the schedule it was measured on)
@@ -100,92 +91,50 @@ static void iterate_fit_pipelined(skf_plan* p, hipStream_t st) {
     for (const ThetaState& th : p->thetas) has_theta[th.type] = 1;
     const bool early_ok = !dfmc && p->sw.early_update;
     // type-level terms E_i += G_i sum B-, D_i += G_i sum B+ as soon as the last relation of the type is through
-    auto type_term = [&](size_t i) {
+    // (its own launch, added into E / D: the B sums are complete only behind the last relation's backbone)
+    auto type_term_of = [&](size_t i) {
         TypeState& t = p->types[i];
-        const void* Bn = t.Bn_tot.ptr;
-        const void* Bp = t.Bp_tot.ptr;
-        if (!p->f64) {
-            cast_b_sums(t, ax);
-            Bn = t.Bn32.ptr;
-            Bp = t.Bp32.ptr;
-        }
+        const BSums b = b_sums_master(p, t, ax);
         if (!touched[i]) {                        // a type without relations here: E = D = 0 before the term is added
             SKF_HIP(hipMemsetAsync(t.E.ptr, 0, t.E.bytes, ax));
             SKF_HIP(hipMemsetAsync(t.D.ptr, 0, t.D.bytes, ax));
             touched[i] = 1;
         }
-        side_update(p, nullptr, 0, 0, nullptr, 0, 0, t, t.G.ptr, t.E.ptr, t.D.ptr, (int)t.n, Bn, Bp, true, true, 0, ax);
+        type_term(p, t, 0, t.n, b.Bn, b.Bp, true, true, ax);
     };
     std::vector<const void*> Sm(nr, nullptr);     // the backbone in the master type, per position in `order`
-    // second stream, behind event [0] of the relation: S = K_i W K_j, its B / D terms, the rounding of S
+    // second stream, behind event [0] of the relation: S = K_i W K_j, its B / D terms (paired through T1, which is free
+    // once S is there), the rounding of S
     auto backbone_chain = [&](size_t q) {
         RelState& r = p->rels[order[q]];
-        TypeState& ti = p->types[r.row];
-        TypeState& tj = p->types[r.col];
-        const int ci = ti.c, cj = tj.c;
         SKF_HIP(hipStreamWaitEvent(ax, p->ev_rel[4 * q], 0));
-        GemmArgs g = gemm_args(ti.K.ptr, ci, 1, r.W.ptr, cj, 1, r.T1.ptr, cj, ci, cj, ci, EPI_STORE, 0);       // T1 = K_i W
-        small_gemm(p, g, ax);
-        g = gemm_args(r.T1.ptr, cj, 1, tj.K.ptr, cj, 1, r.S.ptr, cj, ci, cj, cj, EPI_STORE, 1);                // S = T1 K_j
         const bool s32_here = !p->f64 && !p->sw.no_pairs;          // f32 engines: the rounding of S leaves the same launch
-        if (s32_here) {
-            g.epi = EPI_STORE_F32;
-            g.C2 = r.S32.ptr;
-            g.ldc2 = cj;
-        }
-        small_gemm(p, g, ax);
-        relation_small_terms(p, r, nan_upd, EPI_SPLIT_ACC, ti.Bp_tot.ptr, ti.Bn_tot.ptr, tj.Bp_tot.ptr, tj.Bn_tot.ptr,
-                             true, true, ax, r.T1.ptr);               // (T1 is free once S is there)
-        Sm[q] = r.S.ptr;
-        if (!p->f64) {
-            if (!s32_here) {
-                hipLaunchKernelGGL((cast_kernel<float, double>), dim3(elem_grid((int64_t)ci * cj)), dim3(256), 0, ax,
-                                   (float*)r.S32.ptr, (int64_t)cj, (const double*)r.S.ptr, (int64_t)cj, (int64_t)ci, (int64_t)cj);
-                check_launch("cast");
-            }
-            Sm[q] = r.S32.ptr;
-        }
+        Sm[q] = backbone_general(p, r, nan_upd, s32_here, r.T1.ptr, ax);
+        if (!p->f64 && !s32_here) Sm[q] = round_backbone(p, r, ax);
     };
     // second stream: the two side products of the relation behind `ev_p` (P) and event [3] (Q), then the type terms
-    // row side: E_i (+)= (P S^T)+, D_i (+)= (P S^T)-;  column side: E_j (+)= (Q S)+, D_j (+)= (Q S)-
     auto side_products = [&](size_t q, size_t ev_p) {
         RelState& r = p->rels[order[q]];
-        TypeState& ti = p->types[r.row];
-        TypeState& tj = p->types[r.col];
-        const int ni = (int)r.nr, nj = (int)tj.n, ci = ti.c, cj = tj.c;
         SKF_HIP(hipStreamWaitEvent(ax, p->ev_rel[ev_p], 0));
-        if (r.kn)
-            known_row_split(p, r, touched[r.row] != 0, ax);
-        else
-            side_update(p, r.P.ptr, cj, cj, Sm[q], 1, cj, ti, ti.G.ptr, ti.E.ptr, ti.D.ptr, ni, nullptr, nullptr, false,
-                        touched[r.row] != 0, nan_upd, ax);
+        if (r.kn) known_row_split(p, r, touched[r.row] != 0, ax);
+        else row_side(p, r, true, Sm[q], nullptr, nullptr, false, touched[r.row] != 0, nan_upd, ax);
         touched[r.row] = 1;
-        if (--rels_left[r.row] == 0) type_term(r.row);            // (before the wait for Q: under the relation's own Q)
+        if (--rels_left[r.row] == 0) type_term_of(r.row);         // (before the wait for Q: under the relation's own Q)
         // the type-level term of the column type needs the B sums only (complete with this relation's backbone), not Q:
         // it goes out under the relation's own Q as well, and only the column side product remains behind Q
         const bool last_col = --rels_left[r.col] == 0;
-        if (last_col) type_term(r.col);
+        if (last_col) type_term_of(r.col);
         SKF_HIP(hipStreamWaitEvent(ax, p->ev_rel[4 * q + 3], 0));
-        side_update(p, r.Q.ptr, ci, ci, Sm[q], cj, 1, tj, tj.G.ptr, tj.E.ptr, tj.D.ptr, nj, nullptr, nullptr, false,
-                    touched[r.col] != 0, nan_upd, ax);
+        col_side(p, r, true, 0, p->types[r.col].n, Sm[q], nullptr, nullptr, false, touched[r.col] != 0, nan_upd, ax);
         touched[r.col] = 1;
-    };
-    auto w_product = [&](RelState& r, bool by_q) {        // W = G_i^T P, or (R^T G_i)^T G_j through the narrower factor
-        TypeState& ti = p->types[r.row];
-        TypeState& tj = p->types[r.col];
-        GemmArgs g = by_q ? gemm_args(r.Q.ptr, 1, ti.c, tj.G.ptr, tj.c, 1, r.W.ptr, tj.c, ti.c, tj.c, (int)tj.n, EPI_STORE, 0)
-                          : gemm_args(ti.G.ptr, 1, ti.c, r.P.ptr, tj.c, 1, r.W.ptr, tj.c, ti.c, tj.c, (int)r.nr, EPI_STORE, 0);
-        wide_gemm(p, g, st);
     };
 
     // ---- masked relations (DFMC), before their completion: the contraction W needs; second stream: backbone, H = G_i S
     for (size_t q = 0; q < nr; ++q) {
         RelState& r = p->rels[order[q]];
         if (!(dfmc && r.masked)) continue;
-        TypeState& ti = p->types[r.row];
-        TypeState& tj = p->types[r.col];
-        const bool by_q = ti.c < tj.c;
-        if (r.kn) {           // known entries only: W from the stored residuals; second stream: backbone, gathered vectors, c x c operands
+        const bool by_q = p->types[r.row].c < p->types[r.col].c;      // (W through the narrower factor)
+        if (r.kn) {          // known entries only: W from the stored residuals; second stream: backbone, gathered vectors, c x c operands
             // (Measured, profiles/r03_c5_known_entries.txt: on a third stream, beside the matrix-core contractions of the
             // unmasked relations, the pass over the stored residuals just time-slices the chip with them -- 2.0 ms instead
             // of 0.55 ms for user x tag, 92.2 vs 91.6 it/s.  Its 10 000 workgroups leave no CU to share.)
@@ -198,12 +147,10 @@ static void iterate_fit_pipelined(skf_plan* p, hipStream_t st) {
         }
         if (by_q) contraction_Q(p, r, st);
         else contraction_P(p, r, st);
-        w_product(r, by_q);
+        w_product(p, r, by_q, st);
         SKF_HIP(hipEventRecord(p->ev_rel[4 * q], st));
         backbone_chain(q);
-        GemmArgs g = gemm_args(ti.G.ptr, ti.c, 1, r.S.ptr, tj.c, 1, r.H.ptr, tj.c, (int)r.nr, tj.c, ti.c, EPI_STORE, 0);
-        mixed_gemm_unsplit(p, g, ax);
-        if (p->bf16 && r.mask) tile_epilogue_operands(p, r, ax);
+        completion_operands(p, r, true, ax);
         SKF_HIP(hipEventRecord(p->ev_rel[4 * q + 1], ax));
     }
     // ---- unmasked relations: P, W, Q on the main stream.  W goes out between P and Q: the backbone chain and the row
@@ -219,13 +166,13 @@ static void iterate_fit_pipelined(skf_plan* p, hipStream_t st) {
         const bool w_by_q = (q + 1 < nr) && 5 * p->types[r.col].n <= 3 * r.nr;
         contraction_P(p, r, st);
         if (!w_by_q) {
-            w_product(r, false);
+            w_product(p, r, false, st);
             SKF_HIP(hipEventRecord(p->ev_rel[4 * q], st));
         }
         contraction_Q(p, r, st);
         SKF_HIP(hipEventRecord(p->ev_rel[4 * q + 3], st));
         if (w_by_q) {
-            w_product(r, true);
+            w_product(p, r, true, st);
             SKF_HIP(hipEventRecord(p->ev_rel[4 * q], st));
         }
         backbone_chain(q);
@@ -239,7 +186,7 @@ static void iterate_fit_pipelined(skf_plan* p, hipStream_t st) {
             for (int side = 0; side < 2; ++side) {
                 const size_t i = side == 0 ? (size_t)r.row : (size_t)r.col;
                 if (rels_left[i] == 0 && !updated[i] && !has_theta[i] && q + 1 < nr) {
-                    update_type(p, p->types[i], ax);
+                    update_rows(p, p->types[i], 0, p->types[i].n, ax);
                     updated[i] = 1;
                 }
             }
@@ -248,7 +195,6 @@ static void iterate_fit_pipelined(skf_plan* p, hipStream_t st) {
     for (size_t q = 0; q < nr; ++q) {
         RelState& r = p->rels[order[q]];
         if (!(dfmc && r.masked)) continue;
-        TypeState& tj = p->types[r.col];
         SKF_HIP(hipStreamWaitEvent(st, p->ev_rel[4 * q + 1], 0));
         if (r.kn) {           // the two residual passes over the lists stand for completion, P and Q
             known_row_pass(p, r, st);
@@ -260,18 +206,7 @@ static void iterate_fit_pipelined(skf_plan* p, hipStream_t st) {
             side_products(q, 4 * q + 2);
             continue;
         }
-        if (r.mask) {
-            if (p->bf16) {
-                launch_tile_epilogue(p, r, MODE_COMPLETE, st, false);
-            } else {
-                GemmArgs g = gemm_args(r.H.ptr, tj.c, 1, tj.G.ptr, 1, tj.c, r.Rw.ptr, r.ldr, (int)r.nr, (int)tj.n, tj.c,
-                                       EPI_MASKED_STORE, 0);
-                g.mask = (const uint8_t*)r.Mb.ptr;
-                g.ldmask = r.ldmb;
-                g.mask_bits = 1;
-                plan_gemm(p, g, st);
-            }
-        }
+        if (r.mask) complete_masked(p, r, st);
         contraction_P(p, r, st);
         SKF_HIP(hipEventRecord(p->ev_rel[4 * q + 2], st));
         contraction_Q(p, r, st);
@@ -279,7 +214,7 @@ static void iterate_fit_pipelined(skf_plan* p, hipStream_t st) {
         side_products(q, 4 * q + 2);
     }
     for (size_t i = 0; i < nt; ++i)
-        if (rels_left[i] == 0 && !touched[i]) type_term(i);          // types without relations in this plan
+        if (rels_left[i] == 0 && !touched[i]) type_term_of(i);          // types without relations in this plan
     theta_terms(p, ax);
     SKF_HIP(hipEventRecord(p->ev_join, ax));
     SKF_HIP(hipStreamWaitEvent(st, p->ev_join, 0));

@@ -1,5 +1,8 @@
 // skf_stages.inc -- part of the one translation unit skf_api.hip (textually included there, inside its namespaces; not a
-// header of its own): DFMC on known-entry lists (launches around skf_known.h) and the staged form of the iteration: contract, backbone, accumulate, update.
+// header of its own): the passes over entry lists (launches around skf_known.h: known entries, stored entries, fold-in lists,
+// 0/1 relations), the c x c / n x c x c algebra of DFMC on known entries around them, and the STAGED schedule of an iteration
+// -- contract, backbone, accumulate, update -- which orders the steps of skf_steps.inc on one stream (the pseudo-inverses on
+// a second one) and is what skf_iterate_dist cuts between its collectives.
 // ------------------------------------------------------------------------------------------
 // DFMC on the known entries only (skf_known.h): launches of the list passes and the c x c / n x c x c algebra around them
 // ------------------------------------------------------------------------------------------
@@ -528,119 +531,25 @@ static void stage_contract(skf_plan* p, hipStream_t st) {
             SKF_HIP(hipMemsetAsync(r.W.ptr, 0, r.W.bytes, st));
         } else if (w_by_q) {
             contraction_Q(p, r, st);
-            GemmArgs g = gemm_args(r.Q.ptr, 1, ti.c, tj.G.ptr, tj.c, 1, r.W.ptr, tj.c, ti.c, tj.c, (int)tj.n, EPI_STORE, 0);
-            wide_gemm(p, g, st);
+            w_product(p, r, true, st);
         } else {
             contraction_P(p, r, st);
         }
         if (!(dfmc && r.masked)) contraction_Q(p, r, st);     // a masked relation is completed first
-        if (!r.absent && !w_by_q) {
-            GemmArgs g = gemm_args(rows_of(p, ti.G, ti, r.r0), 1, ti.c, r.P.ptr, tj.c, 1, r.W.ptr, tj.c, ti.c, tj.c,
-                                   (int)r.nr, EPI_STORE, 0);
-            wide_gemm(p, g, st);
-        }
+        if (!r.absent && !w_by_q) w_product(p, r, false, st);
     }
     if (p->overlap) SKF_HIP(hipStreamWaitEvent(st, p->ev_join, 0));
 }
 
-// SKF_BF16: one elementwise pass over the stored relation against its reconstruction H G_j^T (r.H = G_i S must
-// be current): DFMC completion of the unknown entries, or the squared residual into p->sqpart (one f64 per tile)
-enum { MODE_COMPLETE = 0, MODE_SQERR = 1 };
-static void tile_epilogue_operands(skf_plan* p, RelState& r, hipStream_t st) {      // bf16 H and G_j of the tile kernels
-    TypeState& tj = p->types[r.col];
-    const int nr = (int)r.nr, nj = (int)tj.n, cj = tj.c;
-    launch_to_bf16<float>((uint16_t*)r.Hb.ptr, r.ldhb, (const float*)r.H.ptr, (int64_t)cj, nr, cj, false, st);
-    launch_to_bf16<float>((uint16_t*)r.Gb.ptr, r.ldhb, (const float*)tj.G.ptr, (int64_t)cj, nj, cj, false, st);
-}
-
-static void launch_tile_epilogue(skf_plan* p, RelState& r, int mode, hipStream_t st, bool operands = true) {
-    TypeState& tj = p->types[r.col];
-    const int nr = (int)r.nr, nj = (int)tj.n;
-    if (operands) tile_epilogue_operands(p, r, st);
-    Bf16GemmArgs g;
-    memset(&g, 0, sizeof g);
-    // transposed product: tile rows = relation columns (A = bf16 G_j), tile columns = relation rows (Bt = bf16 H)
-    g.A = (const uint16_t*)r.Gb.ptr; g.Bt = (const uint16_t*)r.Hb.ptr;
-    g.lda = r.ldhb; g.ldb = r.ldhb;
-    g.M = nj; g.N = nr; g.Kp = (int)r.ldhb; g.k_chunk = (int)r.ldhb;
-    g.a_kstep = 64; g.b_kstep = 64;
-    g.R = (uint16_t*)r.Rb.ptr; g.ldr = r.ldrb;
-    if (r.binary) { g.Rbits = (const uint8_t*)r.Bb.ptr; g.ldrbits = r.ldbb; }
-    g.mbits = (const uint8_t*)r.Mb.ptr; g.ldmb = r.ldmb;
-    g.sq = (double*)p->sqpart.ptr;
-    if (mode == MODE_COMPLETE && r.use_klist) {
-        g.koff = (const uint32_t*)r.Koff.ptr;
-        g.klist = (const uint32_t*)r.Klist.ptr;
-    }
-    if (mode == MODE_COMPLETE) {
-        // 128 relation columns x 256 relation rows per workgroup, 256 threads, 68 KiB of LDS: two workgroups per CU, one
-        // tile's write-out under the other's K loop (3.9 vs 4.7 ms at config 5).  The residual pass only reads the
-        // relation and is faster on the 256 x 256 tile (4.7 vs 4.9 ms): it stays there.
-        dim3 grid(cdiv(nr, 256), cdiv(nj, 128));
-        const int smem = 256 * (128 + 8) * 2;
-        static DeviceOnce once;
-        allow_dynamic_lds(once, gemm_bf16_kernel<256, 0, EPI_T_COMPLETE>, smem);
-        hipLaunchKernelGGL((gemm_bf16_kernel<256, 0, EPI_T_COMPLETE>), grid, dim3(256), smem, st, g);
-        check_launch("tile_epilogue_bf16");
-        return;
-    }
-    dim3 grid(cdiv(nr, 256), cdiv(nj, 256));
-    const int smem = (3 * 256 + 2 * 256) * 8 * 16;
-    static DeviceOnce once;
-    allow_dynamic_lds(once, gemm_bf16_v2_kernel<256, 0, false, EPI_T_SQERR>, smem);
-    hipLaunchKernelGGL((gemm_bf16_v2_kernel<256, 0, false, EPI_T_SQERR>), grid, dim3(512), smem, st, g);
-    check_launch("tile_epilogue_bf16");
-}
-
 // Stage 2 (SKF_STAGE_BACKBONE): S = K_i W K_j; DFMC: completion, then P and Q of masked relations.
-// every rank <= SMALLC: the c x c chains run in the one-workgroup kernels (SKF_NO_SMALL_CHAIN=1: off)
-static bool small_chain(const skf_plan* p) {
-    if (p->sw.no_small_chain) return false;
-    for (const TypeState& t : p->types)
-        if (t.c > SMALLC) return false;
-    return true;
-}
-
 static void stage_backbone(skf_plan* p, hipStream_t st) {
     const bool dfmc = (p->variant == SKF_DFMC);
     const bool chain = small_chain(p);
-    if (chain) {
-        for (size_t k0 = 0; k0 < p->rels.size(); k0 += CHAIN_MAXB) {
-            BackboneBatch bb;
-            int nb = 0;
-            for (size_t k = k0; k < p->rels.size() && nb < CHAIN_MAXB; ++k, ++nb) {
-                RelState& r = p->rels[k];
-                bb.Ki[nb] = (const double*)p->types[r.row].K.ptr;
-                bb.Kj[nb] = (const double*)p->types[r.col].K.ptr;
-                bb.W[nb] = (const double*)r.W.ptr;
-                bb.S[nb] = (double*)r.S.ptr;
-                bb.ci[nb] = p->types[r.row].c;
-                bb.cj[nb] = p->types[r.col].c;
-            }
-            size_t smem = 0;
-            for (int q = 0; q < nb; ++q) {
-                const size_t need = ((size_t)bb.ci[q] * bb.ci[q] + 2 * (size_t)bb.ci[q] * bb.cj[q] + (size_t)bb.cj[q] * bb.cj[q]) * 8;
-                if (need > smem) smem = need;
-            }
-            static DeviceOnce once_bb, once_bt;
-            allow_dynamic_lds(once_bb, backbone_small_kernel, 4 * SMALLC * SMALLC * 8);
-            allow_dynamic_lds(once_bt, bterms_small_kernel, 4 * SMALLC * SMALLC * 8);
-            hipLaunchKernelGGL(backbone_small_kernel, dim3(nb), dim3(256), smem, st, bb);
-            check_launch("backbone_small");
-        }
-    }
+    if (chain)
+        for (size_t k0 = 0; k0 < p->rels.size(); k0 += CHAIN_MAXB)
+            backbone_small_batch(p, k0, (int)std::min<size_t>(CHAIN_MAXB, p->rels.size() - k0), st);
     for (RelState& r : p->rels) {
-        TypeState& ti = p->types[r.row];
-        TypeState& tj = p->types[r.col];
-        const int nr = (int)r.nr, nj = (int)tj.n, ci = ti.c, cj = tj.c;
-        GemmArgs g;
-        if (!chain) {
-            // T1 = K_i W ; S = T1 K_j
-            g = gemm_args(ti.K.ptr, ci, 1, r.W.ptr, cj, 1, r.T1.ptr, cj, ci, cj, ci, EPI_STORE, 0);
-            small_gemm(p, g, st);
-            g = gemm_args(r.T1.ptr, cj, 1, tj.K.ptr, cj, 1, r.S.ptr, cj, ci, cj, cj, EPI_STORE, 1);
-            small_gemm(p, g, st);
-        }
+        if (!chain) backbone_product(p, r, false, st);      // (rounded in stage_accumulate, with the B sums, in one launch)
         if (!(dfmc && r.masked)) continue;
         if (r.kn) {                 // completion, P and Q of _dfmc.py:319-325, 341-345 on the known entries
             known_operands(p, r, st, false);
@@ -650,21 +559,8 @@ static void stage_backbone(skf_plan* p, hipStream_t st) {
         }
         if (!r.absent) {
             // H = G_i[blk] S ; Rw[mask] = (H G_j^T)[mask] ; P = Rw G_j        (_dfmc.py:319-325)
-            g = gemm_args(rows_of(p, ti.G, ti, r.r0), ci, 1, r.S.ptr, cj, 1, r.H.ptr, cj, nr, cj, ci, EPI_STORE, 0);
-            mixed_gemm(p, g, st);
-            if (r.mask) {
-                if (p->bf16) {
-                    // completed entries go to the one stored copy as bf16: bf16 operands on the matrix cores,
-                    // the write-out is the bound (gemm_bf16_v2_kernel<.., EPI_T_COMPLETE>)
-                    launch_tile_epilogue(p, r, MODE_COMPLETE, st);
-                } else {
-                    g = gemm_args(r.H.ptr, cj, 1, tj.G.ptr, 1, cj, r.Rw.ptr, r.ldr, nr, nj, cj, EPI_MASKED_STORE, 0);
-                    g.mask = (const uint8_t*)r.Mb.ptr;
-                    g.ldmask = r.ldmb;
-                    g.mask_bits = 1;
-                    plan_gemm(p, g, st);
-                }
-            }
+            completion_operands(p, r, false, st);
+            if (r.mask) complete_masked(p, r, st);
             contraction_P(p, r, st);
         }
         contraction_Q(p, r, st);
@@ -672,8 +568,6 @@ static void stage_backbone(skf_plan* p, hipStream_t st) {
 }
 
 // Stage 3 (SKF_STAGE_ACCUMULATE): the E / D sums of this plan's row blocks, column sides and constraints.
-// The G_i B^-+ terms of _dfmf.py:278-282 are linear in B: they are added once per type with the
-// sums of B^+ / B^- over the relations (half the n x c x c work of adding them relation by relation).
 static void stage_accumulate(skf_plan* p, hipStream_t st) {
     const bool dfmc = (p->variant == SKF_DFMC);
     const int nan_upd = dfmc ? 0 : 1;       // _update_G_for_Rij (_dfmc.py:127-178) has no nan_to_num
@@ -699,21 +593,8 @@ static void stage_accumulate(skf_plan* p, hipStream_t st) {
     // of every type: it sums over all relations; otherwise over the plan's own relations.
     const bool chain = small_chain(p);
     for (RelState& r : p->rels) {
-        TypeState& ti = p->types[r.row];
-        TypeState& tj = p->types[r.col];
-        if (chain) {
-            BTermsArgs ba;
-            ba.S = (const double*)r.S.ptr; ba.Gram_i = (const double*)ti.Gram.ptr; ba.Gram_j = (const double*)tj.Gram.ptr;
-            ba.Bp_i = (double*)ti.Bp_tot.ptr; ba.Bn_i = (double*)ti.Bn_tot.ptr;
-            ba.Bp_j = (double*)tj.Bp_tot.ptr; ba.Bn_j = (double*)tj.Bn_tot.ptr;
-            ba.ci = ti.c; ba.cj = tj.c; ba.nan_to_num = nan_upd;
-            const size_t smem = ((size_t)ti.c * ti.c + 2 * (size_t)ti.c * tj.c + (size_t)tj.c * tj.c) * 8;
-            hipLaunchKernelGGL(bterms_small_kernel, dim3(1), dim3(256), smem, st, ba);
-            check_launch("bterms_small");
-            continue;
-        }
-        relation_small_terms(p, r, nan_upd, EPI_SPLIT_ACC, ti.Bp_tot.ptr, ti.Bn_tot.ptr, tj.Bp_tot.ptr, tj.Bn_tot.ptr,
-                             true, true, st);
+        if (chain) bterms_small(p, r, nan_upd, st);
+        else bd_terms(p, r, nan_upd, nullptr, st);
     }
     // c x c operands of the fused side products in the master type: the f32 engines round S of every
     // relation with a side here and sum B+- of every type in ONE batched launch
@@ -722,11 +603,9 @@ static void stage_accumulate(skf_plan* p, hipStream_t st) {
         const bool cast = !p->f64 && fused;
         CastBatch cb;
         int ne = 0, max_count = 1;
-        bool overflow = false;
         auto add = [&](const Slot& src, const Slot& dst, int count) -> const void* {
             if (!cast) return src.ptr;
             if (ne >= CAST_MAXB) {                   // very large graphs: one launch per matrix
-                overflow = true;
                 hipLaunchKernelGGL((cast_kernel<float, double>), dim3(elem_grid(count)), dim3(256), 0, st, (float*)dst.ptr,
                                    (int64_t)count, (const double*)src.ptr, (int64_t)count, (int64_t)1, (int64_t)count);
                 check_launch("cast");
@@ -748,7 +627,6 @@ static void stage_accumulate(skf_plan* p, hipStream_t st) {
             RelState& r = p->rels[k];
             S_m[k] = (!r.absent || r.col_side) ? add(r.S, r.S32, p->types[r.row].c * p->types[r.col].c) : r.S.ptr;
         }
-        (void)overflow;
         if (cast && ne > 0) {
             hipLaunchKernelGGL(cast_batched_kernel, dim3(elem_grid(max_count), ne), dim3(256), 0, st, cb);
             check_launch("cast_batched");
@@ -756,74 +634,30 @@ static void stage_accumulate(skf_plan* p, hipStream_t st) {
     }
     // type-level term on rows [t0, t0 + tn): separately (row blocks / VALU engine), or inside the
     // last side product of the type (fused engine on whole matrices)
-    auto type_term = [&](size_t i) {
+    auto type_term_of = [&](size_t i) {
         TypeState& t = p->types[i];
         if (t.tn <= 0) return;
-        void* G = rows_of(p, t.G, t, t.t0);
-        void* E = rows_of(p, t.E, t, t.t0);
-        void* D = rows_of(p, t.D, t, t.t0);
-        if (fused) {
-            side_update(p, nullptr, 0, 0, nullptr, 0, 0, t, G, E, D, (int)t.tn, Bn_m[i], Bp_m[i], true,
-                        touched[i] != 0, 0, st);
-        } else {
-            GemmArgs g = gemm_args(G, t.c, 1, t.Bn_tot.ptr, t.c, 1, E, t.c, (int)t.tn, t.c, t.c, EPI_ACC, 0);
-            mixed_gemm(p, g, st);
-            g = gemm_args(G, t.c, 1, t.Bp_tot.ptr, t.c, 1, D, t.c, (int)t.tn, t.c, t.c, EPI_ACC, 0);
-            mixed_gemm(p, g, st);
-        }
+        type_term(p, t, t.t0, t.tn, Bn_m[i], Bp_m[i], touched[i] != 0, fused, st);
         touched[i] = 1;
     };
     const bool fuse_type_term = fused && !p->sliced;
     for (size_t rk = 0; rk < p->rels.size(); ++rk) {
         RelState& r = p->rels[rk];
-        TypeState& ti = p->types[r.row];
-        TypeState& tj = p->types[r.col];
-        const int nr = (int)r.nr, nj = (int)tj.n, ci = ti.c, cj = tj.c;
-        const bool row_side = !r.absent, col_side = r.col_side;
-        void* Gi = rows_of(p, ti.G, ti, r.r0);
-        void* Ei = rows_of(p, ti.E, ti, r.r0);
-        void* Di = rows_of(p, ti.D, ti, r.r0);
-        GemmArgs g;
-        if (fused) {
-            // row side: A = P S^T (Sop(k,j) = S[j][k]);  column side: C = Q S
-            if (!row_side && !col_side) continue;
-            const void* Sm = S_m[rk];
-            if (row_side && r.kn) {
-                const bool last = fuse_type_term && --sides_left[r.row] == 0;
-                known_row_side(p, r, touched[r.row] != 0, st, false);
-                touched[r.row] = 1;
-                if (last) type_term(r.row);
-            } else if (row_side) {
-                const bool last = fuse_type_term && --sides_left[r.row] == 0;
-                side_update(p, r.P.ptr, cj, cj, Sm, 1, cj, ti, Gi, Ei, Di, nr, Bn_m[r.row], Bp_m[r.row], last,
-                            touched[r.row] != 0, nan_upd, st);
-                touched[r.row] = 1;
-            }
-            if (col_side) {
-                const bool last = fuse_type_term && --sides_left[r.col] == 0;
-                side_update(p, r.Q.ptr, ci, ci, Sm, cj, 1, tj, tj.G.ptr, tj.E.ptr, tj.D.ptr, nj, Bn_m[r.col],
-                            Bp_m[r.col], last, touched[r.col] != 0, nan_upd, st);
-                touched[r.col] = 1;
-            }
-            continue;
+        if (!r.absent) {
+            const bool last = fuse_type_term && --sides_left[r.row] == 0;
+            if (r.kn) known_row_side(p, r, touched[r.row] != 0, st, false);
+            else row_side(p, r, fused, S_m[rk], Bn_m[r.row], Bp_m[r.row], last, touched[r.row] != 0, nan_upd, st);
+            touched[r.row] = 1;
+            if (r.kn && last) type_term_of(r.row);
         }
-        if (row_side && r.kn) {
-            known_row_side(p, r, true, st, false);
-        } else if (row_side) {
-            // E_i += (P S^T)+ ; D_i += (P S^T)-          (_dfmf.py:254-258, 278-279)
-            g = gemm_args(r.P.ptr, cj, 1, r.S.ptr, 1, cj, Ei, ci, nr, ci, cj, EPI_SPLIT_ACC, nan_upd);
-            g.C2 = Di;
-            mixed_gemm(p, g, st);
-        }
-        if (col_side) {
-            // E_j += (Q S)+ ; D_j += (Q S)-              (_dfmf.py:266-270, 281-282)
-            g = gemm_args(r.Q.ptr, ci, 1, r.S.ptr, cj, 1, tj.E.ptr, cj, nj, cj, ci, EPI_SPLIT_ACC, nan_upd);
-            g.C2 = tj.D.ptr;
-            mixed_gemm(p, g, st);
+        if (r.col_side) {
+            const bool last = fuse_type_term && --sides_left[r.col] == 0;
+            col_side(p, r, fused, 0, p->types[r.col].n, S_m[rk], Bn_m[r.col], Bp_m[r.col], last, touched[r.col] != 0, nan_upd, st);
+            touched[r.col] = 1;
         }
     }
     if (!fuse_type_term)
-        for (size_t i = 0; i < nt; ++i) type_term(i);     // E_i += G_i sum B- ; D_i += G_i sum B+
+        for (size_t i = 0; i < nt; ++i) type_term_of(i);     // E_i += G_i sum B- ; D_i += G_i sum B+
     theta_terms(p, st);
 }
 
@@ -836,24 +670,12 @@ static void accumulate_fit(skf_plan* p, hipStream_t st) {
     stage_accumulate(p, st);
 }
 
-// G_i <- G_i * sqrt(E_i / max(D_i, eps)) of one type   (_dfmf.py:294-296)
-static void update_type(skf_plan* p, TypeState& t, hipStream_t st) {
-    if (p->bf16 && t.n > 0) {                  // update and G^T refresh in one pass
-        hipLaunchKernelGGL(mult_update_transpose_kernel, dim3((unsigned)cdiv(t.c, 32), (unsigned)cdiv(t.n, 32)), dim3(256), 0,
-                           st, (float*)t.G.ptr, (const float*)t.E.ptr, (const float*)t.D.ptr, (int64_t)t.n, (int64_t)t.c,
-                           (uint16_t*)t.GTb.ptr, t.ldgt, (uint16_t*)t.Grow.ptr, t.ldrow);
-        check_launch("mult_update_transpose");
-        return;
-    }
-    mult_update(p, t, st);
-    refresh_gt(p, t, st);
-}
-
-// ... of every type (`done`: types the schedule has updated already)
+// G_i <- G_i * sqrt(E_i / max(D_i, eps)) of every type (`done`: types the schedule has updated already); SKF_BF16: the
+// update refreshes the bf16 copies of the factor in the same pass
 static void apply_update(skf_plan* p, hipStream_t st, const std::vector<char>* done = nullptr) {
     for (TypeState& t : p->types)          // known-entries relations: the factors their stored residuals belong to
         if (t.keep_prev) SKF_HIP(hipMemcpyAsync(t.Gp.ptr, t.G.ptr, t.G.bytes, hipMemcpyDeviceToDevice, st));
     p->kn_first = false;
     for (size_t i = 0; i < p->types.size(); ++i)
-        if (!(done && (*done)[i])) update_type(p, p->types[i], st);
+        if (!(done && (*done)[i])) update_rows(p, p->types[i], 0, p->types[i].n, st);
 }

@@ -760,6 +760,61 @@ def test_gram_products_of_all_types_in_one_launch_keep_every_bit(dtype, monkeypa
             assert relerr(G[t, t], Go[t, t]) < 1e-10
 
 
+# Launches per iteration of six plans on the three general schedules, MEASURED ON THE COMMIT BEFORE the steps of an iteration
+# were stated once in csrc/skf_steps.inc (record: profiles/r23_schedule_steps.txt; emulator and MI355X gave the same numbers).
+# The schedules only order the steps: regrouping the host code must neither add nor drop a launch.
+# (plan: variant, dtype, share of the masked relation that is known (None: DFMF), switches, owned rows over the null communicator)
+SCHEDULE_LAUNCHES = {
+    'staged f64 dfmf': ('dfmf', 'f64', None, {'SKF_NO_PIPELINE': '1'}, False, 46),
+    'pipelined f32 dfmf': ('dfmf', 'f32', None, {}, False, 46),
+    'pipelined f32 dfmf, chain products one to a launch': ('dfmf', 'f32', None, {'SKF_CHAIN_PAIRS': '0'}, False, 55),
+    'pipelined bf16 dfmc, dense masked relation': ('dfmc', 'bf16', 0.6, {'SKF_DFMC_SPARSE': '0'}, False, 51),
+    'pipelined bf16 dfmc, known-entry relation': ('dfmc', 'bf16', 0.2, {'SKF_DFMC_SPARSE': '1'}, False, 57),
+    'owned f32 dfmf, world 1, null communicator': ('dfmf', 'f32', None, {}, True, 43),
+}
+
+
+def schedule_launches(plan, monkeypatch):
+    """Launches per iteration (skf_launch_count over the second and third iteration: the first one of a DFMC fit also clears
+    the unknown entries and has no previous residuals) of one plan of SCHEDULE_LAUNCHES: three types of 200 / 150 / 130
+    objects at ranks 65 / 66 / 72 (no multiple of a tile, above the one-workgroup chains), three relations -- one with
+    values and, for DFMC, a mask; one with negative values; one of zeros and ones."""
+    from skfusion_amd._engine import DevicePlan, launch_count
+    variant, dtype, known, env, owned, _ = SCHEDULE_LAUNCHES[plan]
+    for name in ('SKF_NO_PIPELINE', 'SKF_CHAIN_PAIRS', 'SKF_DFMC_SPARSE', 'SKF_EARLY_UPDATE', 'SKF_NO_OVERLAP'):
+        monkeypatch.delenv(name, raising=False)
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    rs = np.random.RandomState(3)
+    types, n, rank = ['a', 'b', 'c'], {'a': 200, 'b': 150, 'c': 130}, {'a': 65, 'b': 66, 'c': 72}
+    unknown = (rs.rand(200, 150) >= known) if known is not None else None
+    rel = [('a', 'b', rs.rand(200, 150), unknown), ('a', 'c', rs.rand(200, 130) - 0.2, None),
+           ('b', 'c', (rs.rand(150, 130) < 0.2).astype(np.float64), None)]
+    code = {'dfmf': nat.SKF_DFMF, 'dfmc': nat.SKF_DFMC}[variant]
+    if owned:
+        from skfusion_amd.fusion.decomposition._dfmf import owned_plan
+        p = owned_plan(code, rel, [], types, n, rank, dtype, None, 0, 1)
+        p.attach_null_comm(0, 1)
+    else:
+        p = DevicePlan(types, n, rank, rel, [], code, dtype=dtype)
+    try:
+        for t in types:
+            p.set_factor(t, rs.rand(n[t], rank[t]) + 0.05)
+        step = p.iterate_dist if owned else p.iterate
+        step(1)
+        before = launch_count()
+        step(2)
+        p.synchronize()
+        return (launch_count() - before) / 2.0
+    finally:
+        p.close()
+
+
+@pytest.mark.parametrize('plan', sorted(SCHEDULE_LAUNCHES))
+def test_launches_per_iteration_of_the_general_schedules_are_pinned(plan, monkeypatch):
+    assert schedule_launches(plan, monkeypatch) == SCHEDULE_LAUNCHES[plan][-1], plan
+
+
 def test_dfmc_runs_the_relation_pipeline_with_the_completion_between_its_contractions(monkeypatch):
     """DFMC with a rank above 64 runs the relation pipeline too: a masked relation is contracted once before its
     completion (through the narrower factor) and twice after it; its backbone and reconstruction operands are computed

@@ -218,6 +218,19 @@ def test_gram_products_of_all_types_in_one_launch_on_the_hardware(dtype, monkeyp
     E.test_gram_products_of_all_types_in_one_launch_keep_every_bit(dtype, monkeypatch, three=True)
 
 
+def _schedule_plans():
+    import test_emul_engine as E
+    return sorted(E.SCHEDULE_LAUNCHES)
+
+
+@pytest.mark.parametrize('plan', _schedule_plans())
+def test_launches_per_iteration_of_the_general_schedules_are_pinned_on_the_hardware(plan, monkeypatch):
+    """The launch counts of the staged, pipelined and owned-rows schedules as measured before their steps were stated once
+    (test_emul_engine.SCHEDULE_LAUNCHES), on real streams."""
+    import test_emul_engine as E
+    assert E.schedule_launches(plan, monkeypatch) == E.SCHEDULE_LAUNCHES[plan][-1], plan
+
+
 def test_fit_with_a_rank_above_256_on_the_hardware(monkeypatch):
     """Orders 300 / 70 / 40 in one batch of step-per-launch sweeps inside a fit, and the Cholesky route, against the oracle."""
     import test_emul_engine as E
