@@ -640,6 +640,53 @@ int skf_complete_above(int32_t dtype, const void* H, int64_t ldh, int64_t m, con
                        int64_t* n_found /* host */, int32_t col_splits /* 0 = choose */,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the column-mean initialisers on the device (reference _init.py:20-61: `random_c` :20-41, `random_vcol` :44-61) ----
+ * The reference fills factor column k of an object type with the mean of take = int(0.2 m) randomly chosen columns of every
+ * relation that touches the type, oriented so that the type's objects are its rows (V, n x m), and `random_c` draws them
+ * from the half of the columns with the largest 2-norm: G = 1e-5 + sum over the views of |mean of the chosen columns|.
+ * With W (m x c) the 0/1 matrix of the chosen columns the means are (V W) / take -- the contraction the plan runs for that
+ * relation in every stored form (P = R G_j / Q = R^T G_i), with a right operand that is exact in bf16.  The random stream
+ * stays on the host: the caller draws the indices and hands them over.
+ *
+ * Both operators take relations of a bound SKF_DFMF / SKF_DFMC plan that the plan holds WHOLE and UNMASKED: dense (the
+ * engine's type; SKF_BF16: its padded bf16 copy or the bitmap of a SKF_REL_BINARY relation) or SKF_REL_SPARSE_CSR without
+ * SKF_REL_FILL_RANK1.  SKF_E_INVALID, with a message, before any HIP call and with nothing written: a masked relation, one
+ * given as its known entries, a rank-one fill, SKF_OPT_OWNED_ROWS plans and row blocks, SKF_TRANSFORM plans.  (A 0/1 relation
+ * that SKF_BF16 keeps as lists of its ones beside its bitmap is read through the bitmap.)  The plan's own workspace is not touched: scratch is the caller's (256-byte aligned; NULL,
+ * short or misaligned: SKF_E_WORKSPACE).
+ *
+ * skf_plan_relation_norms: the f64 sum of SQUARES of every row (row_sq[n_i]) and of every column (col_sq[n_j]) of relation
+ * `rel` as stored -- device outputs, a null pointer is skipped; the caller takes the square roots.  One pass over a dense /
+ * bitmap relation: partial sums over fixed slabs of rows and blocks of columns, stored and added first to last -- no atomics,
+ * a grid fixed by the shape alone, the same bits on every run; a relation kept as lists: each line's stored entries in list
+ * order (needs no scratch). */
+int skf_plan_relation_norms_workspace_bytes(const skf_plan* plan, int32_t rel, size_t* bytes);
+int skf_plan_relation_norms(skf_plan* plan, int32_t rel, double* row_sq, double* col_sq, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
+/* One oriented view of skf_plan_init_column_means: relation `rel`, read as V = R when `type` is its row type and as V = R^T
+ * when it is its column type; sel[c * take] (device, int32, row-major): row k holds the columns of V averaged into factor
+ * column k.  The indices of one row are DISTINCT -- the caller's duty (an index given twice would count once, where the
+ * reference's mean counts it twice); an index outside [0, m) is found on the device before anything is written:
+ * SKF_E_INVALID.  take < 1 (a view of fewer than 5 columns, where the reference's mean of nothing is NaN) or take > m:
+ * SKF_E_INVALID.  The size query reads rel and take only. */
+typedef struct {
+    int32_t rel;
+    int32_t take;
+    const int32_t* sel;
+} skf_init_view;
+
+/* G0 (n x c of `type`, device, MASTER type, leading dimension ld >= c; nothing past column c of a row is touched)
+ *   = round( 1e-5 + sum over the views, in the order given, of | (V W) / (double)take | )
+ * accumulated in f64 and rounded once.  The products run through the plan's contraction launches with W as the right operand
+ * (bf16 operands and f32 accumulation for SKF_BF16, the master type otherwise), so data whose partial sums are exact --
+ * 0/1 entries, small integers -- give the bits of the reference's float64 statement cast to the master type, in every engine.
+ * The caller then hands G0 to skf_set_factor.  Scratch grows with m * c + n * c, never with n * m. */
+int skf_plan_init_column_means_workspace_bytes(const skf_plan* plan, int32_t type, int32_t n_views, const skf_init_view* views,
+                                               size_t* bytes);
+int skf_plan_init_column_means(skf_plan* plan, int32_t type, int32_t n_views, const skf_init_view* views, void* G0, int64_t ld,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* K = pinv(A) for symmetric A (n x n): f64 Jacobi eigen-decomposition + the singular-value
  * cut-off of scipy.linalg.pinv (reference _dfmf.py:232, _dfmc.py:307). */
 int skf_pinv_sym_workspace_bytes(int32_t n, size_t* bytes);
@@ -690,8 +737,9 @@ const char* skf_version(void);
  * adds entry points only -- skf_small_graph_limits, skf_comm_info, skf_launch_count; later: skf_fold_lists and the flag
  * SKF_REL_FOLD_CSR; skf_complete_topk_workspace_bytes, skf_complete_topk, skf_complete_entries and SKF_TOPK_MAX;
  * skf_get_constraint_lists and the flag SKF_OPT_THETA_OWNED_ROWS; skf_plan_set_relation_fill and the flag SKF_REL_FILL_RANK1;
- * skf_complete_ranks_workspace_bytes and skf_complete_ranks; skf_complete_above_workspace_bytes and skf_complete_above -- the
- * structs are those of version 4). */
+ * skf_complete_ranks_workspace_bytes and skf_complete_ranks; skf_complete_above_workspace_bytes and skf_complete_above;
+ * skf_plan_relation_norms, skf_plan_init_column_means, their workspace queries and skf_init_view, a struct of their own -- the
+ * structs before it are those of version 4). */
 #define SKF_ABI_VERSION 5
 int skf_abi_version(void);
 

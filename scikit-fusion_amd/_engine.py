@@ -766,6 +766,60 @@ class DevicePlan(object):
             self.rt.mem.synchronize()
             self._pending_uploads = None
 
+    # -- the column-mean initialisers on the device (csrc/skf_init.h; reference _init.py:20-61) -----------
+    def relation_norms(self, rel):
+        """(row_sq, col_sq): the float64 sums of SQUARES of every row and every column of relation `rel` as the plan
+        stores it (skf_plan_relation_norms) -- what `random_c` ranks the columns of the relation's two views by.  Exact for
+        data whose squares add up exactly; the same bits on every run.  SkfNativeError (SKF_E_INVALID) for a relation the
+        plan does not hold whole and unmasked."""
+        i, j = self.relations[rel][0], self.relations[rel][1]
+        ni, nj = self.n_obj[self.index[i]], self.n_obj[self.index[j]]
+        mem = self.rt.mem
+        need = C.c_size_t()
+        self.rt.call('skf_plan_relation_norms_workspace_bytes', self.handle, rel, C.byref(need))
+        ws = mem.empty(max(need.value, 1))
+        rs, cs = mem.empty(max(ni, 1) * 8), mem.empty(max(nj, 1) * 8)
+        self.rt.call('skf_plan_relation_norms', self.handle, rel, rs.ptr, cs.ptr, ws.ptr, need.value, self.stream)
+        mem.synchronize()
+        return mem.to_host(rs, (ni,), np.float64), mem.to_host(cs, (nj,), np.float64)
+
+    def init_column_means(self, t, views, sync=True):
+        """The factor of type `t` <- 1e-5 + sum over `views` of |mean of the chosen columns| (skf_plan_init_column_means,
+        then skf_set_factor): `views` = [(relation index, sel)] in the order the reference walks the relations of `t`, sel an
+        integer array c x take whose row k names the columns -- of the relation when `t` is its row type, of its transpose
+        when `t` is its column type -- averaged into factor column k.  The indices of a row must be distinct (checked here:
+        ValueError); their range is checked on the device (SkfNativeError, SKF_E_INVALID, nothing written).
+        sync=False: the caller synchronises before the plan is iterated."""
+        k = self.index[t]
+        n, c = self.n_obj[k], self.rank[k]
+        mem = self.rt.mem
+        desc = (nat.InitView * max(len(views), 1))()
+        keep = []
+        for v, (rel, sel) in enumerate(views):
+            s = np.ascontiguousarray(sel, dtype=np.int32)
+            if s.ndim != 2 or s.shape[0] != c:
+                raise ValueError('view %d of %s: the selection has shape %r, expected (%d, take)' % (v, t, s.shape, c))
+            if s.shape[1] > 1:
+                ordered = np.sort(s, axis=1)
+                if (ordered[:, 1:] == ordered[:, :-1]).any():
+                    raise ValueError('view %d of %s: a column is chosen twice for one factor column' % (v, t))
+            buf = mem.from_host(s if s.size else np.zeros(1, dtype=np.int32), sync=False)
+            keep.append(buf)
+            desc[v].rel, desc[v].take, desc[v].sel = int(rel), int(s.shape[1]), buf.ptr
+        mem.synchronize()                               # the uploads (torch's stream) before the engine's launches
+        need = C.c_size_t()
+        self.rt.call('skf_plan_init_column_means_workspace_bytes', self.handle, k, len(views), desc, C.byref(need))
+        ws = mem.empty(need.value)
+        g0 = mem.empty(max(n * c, 1) * np.dtype(self.np_dtype).itemsize)
+        self.rt.call('skf_plan_init_column_means', self.handle, k, len(views), desc, g0.ptr, c, ws.ptr, need.value, self.stream)
+        self.rt.call('skf_set_factor', self.handle, k, g0.ptr, c, self.stream)
+        keep += [ws, g0]
+        self._pending_init = getattr(self, '_pending_init', None) or []
+        self._pending_init.append(keep)                 # alive until the launches have run
+        if sync:
+            mem.synchronize()
+            self._pending_init = None
+
     def fetch_results(self, types, n_rel):
         """Issues the copies of every factor of `types` and the first `n_rel` backbones into device buffers; the caller
         synchronises once (for any number of plans) and calls read_results."""

@@ -73,6 +73,11 @@ class Options(C.Structure):
                 ('flags', C.c_int32)]
 
 
+class InitView(C.Structure):
+    """skf_init_view: one oriented view of skf_plan_init_column_means."""
+    _fields_ = [('rel', C.c_int32), ('take', C.c_int32), ('sel', C.c_void_p)]
+
+
 SKF_OPT_OWNED_ROWS = 1
 SKF_OPT_THETA_OWNED_ROWS = 2   # constraints given as their entries: the CSR of the owned rows (needs SKF_OPT_OWNED_ROWS)
 SKF_TOPK_MAX = 64            # include/skfusion_hip.h: longest list skf_complete_topk keeps per row
@@ -160,6 +165,10 @@ SIGNATURES = {
     'skf_complete_above_workspace_bytes': (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
     'skf_complete_above': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, C.c_int64,
                                      _P, _P, _P, C.POINTER(C.c_int64), C.c_int32, _P, C.c_size_t, _P]),
+    'skf_plan_relation_norms_workspace_bytes': (C.c_int, [_P, C.c_int32, C.POINTER(C.c_size_t)]),
+    'skf_plan_relation_norms': (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
+    'skf_plan_init_column_means_workspace_bytes': (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(InitView), C.POINTER(C.c_size_t)]),
+    'skf_plan_init_column_means': (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(InitView), _P, C.c_int64, _P, C.c_size_t, _P]),
     'skf_pinv_sym_workspace_bytes': (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
     'skf_pinv_sym': (C.c_int, [C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_size_t, _P]),
     'skf_fill_uniform': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, C.c_int64, C.c_uint64,

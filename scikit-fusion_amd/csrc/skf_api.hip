@@ -1,6 +1,7 @@
 // skf_api.hip -- C ABI (include/skfusion_hip.h) and the host-side plan / launch schedule of the
 // DFMF / DFMC / fold-in iteration.  Kernels: skf_kernels.h; the pseudo-inverse: skf_pinv.h; the completion operators
-// (skf_complete_*): kernels skf_complete.h, host side and entry points skf_complete.inc.
+// (skf_complete_*): kernels skf_complete.h, host side and entry points skf_complete.inc; the column-mean initialisers on the
+// device (skf_plan_relation_norms, skf_plan_init_column_means): kernels skf_init.h, host side and entry points skf_init.inc.
 //
 // One iteration (reference _dfmf.py:228-296, 2-GEMM form of SURVEY.md 7.0; everything reads the
 // OLD factors, G is replaced at the very end):
@@ -18,6 +19,7 @@
 #include "skf_pinv.h"
 #include "skf_small.h"
 #include "skf_complete.h"
+#include "skf_init.h"
 // the product build compiles the GEMM-class kernel templates in units of their own, side by side with this file
 // (tools/gen_inst_units.py, __graft_entry__.build); a build of this file alone (emulator, probes) instantiates them here
 #ifdef SKF_SPLIT_BUILD
@@ -131,6 +133,8 @@ static inline int wave_grid(int64_t rows) {
 #include "skf_bind.inc"
 
 #include "skf_complete.inc"
+
+#include "skf_init.inc"
 
 }  // namespace skf
 

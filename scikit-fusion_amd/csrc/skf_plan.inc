@@ -364,16 +364,37 @@ static hipEvent_t next_event(skf_plan* p) {
     return p->ev_pool[p->ev_used++];
 }
 
-// one of the two contractions that stream a relation matrix: P = R G_j or Q = R^T G_i
-static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void* dst, hipStream_t st, int sq_first = 0);
+// The right operand of a relation contraction (relation_gemm below) when it is NOT the factor of the type on the other side (skf_init.inc: the 0/1
+// selection matrix of the column-mean initialisers): `n` columns -- the rank of whatever the caller forms, not of that type
+// --, in the layout the relation's stored form reads: dense / bitmap relations of SKF_BF16 the bf16 Bt[n][ld] with the inner
+// dimension zero padded as G^T is kept; every other form [inner][ld] in the master type (dense: what g.B / g.sb_k name
+// already; SKF_REL_SPARSE_CSR: the gathered rows).  `part`: split-K slices / outputs of the list parts -- the caller's own,
+// sized for ITS column count (the plan's scratch is sized for the iteration's).  The iteration passes none.
+struct RelRight {
+    const void* B;
+    int64_t ld;
+    int n;
+    void* part;
+    size_t part_bytes;
+};
+static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void* dst, hipStream_t st, int sq_first = 0,
+                       const RelRight* rhs = nullptr);
 static void ones_pass(skf_plan* p, const RelState& r, bool is_q, void* dst, int64_t ld_out, int64_t n_out, int w, hipStream_t st);
-static void relation_gemm(skf_plan* p, GemmArgs g, hipStream_t st, const RelState* r = nullptr, bool is_q = false) {
+// one of the two contractions that stream a relation matrix: P = R G_j or Q = R^T G_i
+static void relation_gemm(skf_plan* p, GemmArgs g, hipStream_t st, const RelState* r = nullptr, bool is_q = false,
+                          const RelRight* rhs = nullptr) {
+    if (rhs && (!r || g.N != rhs->n)) SKF_FAIL(SKF_E_STATE, "relation contraction: right operand without its relation / column count");
     if (r && r->sp0) {             // the stored entries as valued lists (every engine): no matrix to stream
         if (g.ldc != g.N) SKF_FAIL(SKF_E_STATE, "SKF_REL_SPARSE_CSR relation: strided contraction output");
-        sparse_pass(p, *r, is_q, false, g.C, st);
+        sparse_pass(p, *r, is_q, false, g.C, st, 0, rhs);
         return;
     }
-    if (r && p->bf16 && r->sparse && r->sp_gather) {       // the ones as lists over the bf16 rows of the factor
+    // (a 0/1 relation that SKF_BF16 keeps as lists of its ones beside its bitmap: the lists gather factor rows only -- a
+    //  right operand of the caller's goes through the bitmap)
+    const bool ones = p->bf16 && r && r->sparse && !rhs;
+    void* const part = rhs ? rhs->part : p->part.ptr;
+    const size_t part_bytes = rhs ? rhs->part_bytes : p->part_bytes;
+    if (ones && r->sp_gather) {    // the ones as lists over the bf16 rows of the factor
         ones_pass(p, *r, is_q, g.C, g.ldc, g.M, g.N, st);
         return;
     }
@@ -381,7 +402,11 @@ static void relation_gemm(skf_plan* p, GemmArgs g, hipStream_t st, const RelStat
     if (p->bf16) {
         const TypeState& ti = p->types[r->row];
         const TypeState& tj = p->types[r->col];
-        if (r->sparse) {               // a handful of ones per row / column: gather the factor's f32 rows (binary_spmm_kernel)
+        // the bf16 right operand and its leading dimension: the stored transpose of the factor on the other side, or the caller's
+        const uint16_t* btj = rhs ? (const uint16_t*)rhs->B : (const uint16_t*)tj.GTb.ptr;
+        const uint16_t* bti = rhs ? (const uint16_t*)rhs->B : (const uint16_t*)ti.GTb.ptr + r->r0;
+        const int64_t ldbj = rhs ? rhs->ld : tj.ldgt, ldbi = rhs ? rhs->ld : ti.ldgt;
+        if (ones) {                    // a handful of ones per row / column: gather the factor's f32 rows (binary_spmm_kernel)
             const int wgrid = (int)(((int64_t)g.M + 3) / 4 < 4096 ? ((int64_t)g.M + 3) / 4 : 4096);
             hipLaunchKernelGGL(binary_spmm_kernel, dim3(wgrid), dim3(256), 0, st,
                                (const int64_t*)(is_q ? r->SpCp.ptr : r->SpRp.ptr), (const int*)(is_q ? r->SpRi.ptr : r->SpCi.ptr),
@@ -389,25 +414,26 @@ static void relation_gemm(skf_plan* p, GemmArgs g, hipStream_t st, const RelStat
             check_launch("binary_spmm");
         } else if (r->binary) {        // the relation as a bitmap: 1/16 of the bytes, expanded to bf16 0 / 1 on the way into LDS
             if (!is_q)
-                run_gemm_bf16((const uint16_t*)r->Bb.ptr, r->ldbb, (const uint16_t*)tj.GTb.ptr, tj.ldgt, (float*)g.C,
-                              g.ldc, g.M, g.N, (int)r->ldrb, 0, p->part.ptr, p->part_bytes, true, st, false, true);
+                run_gemm_bf16((const uint16_t*)r->Bb.ptr, r->ldbb, btj, ldbj, (float*)g.C,
+                              g.ldc, g.M, g.N, (int)r->ldrb, 0, part, part_bytes, true, st, false, true);
             else
-                run_gemm_bf16((const uint16_t*)r->Bb.ptr, r->ldbb, (const uint16_t*)ti.GTb.ptr + r->r0, ti.ldgt, (float*)g.C,
-                              g.ldc, g.M, g.N, (int)r->kq, 0, p->part.ptr, p->part_bytes, true, st, true, true);
+                run_gemm_bf16((const uint16_t*)r->Bb.ptr, r->ldbb, bti, ldbi, (float*)g.C,
+                              g.ldc, g.M, g.N, (int)r->kq, 0, part, part_bytes, true, st, true, true);
         } else if (!is_q)      // P = R G_j :  A = R (bf16), Bt = G_j^T (bf16)
-            run_gemm_bf16((const uint16_t*)r->Rb.ptr, r->ldrb, (const uint16_t*)tj.GTb.ptr, tj.ldgt, (float*)g.C,
-                          g.ldc, g.M, g.N, (int)r->ldrb, 0, p->part.ptr, p->part_bytes, true, st);
+            run_gemm_bf16((const uint16_t*)r->Rb.ptr, r->ldrb, btj, ldbj, (float*)g.C,
+                          g.ldc, g.M, g.N, (int)r->ldrb, 0, part, part_bytes, true, st);
         else            // Q = R^T G_i :  A = the same row-major R read transposed out of LDS, Bt = G_i^T (bf16)
-            run_gemm_bf16((const uint16_t*)r->Rb.ptr, r->ldrb, (const uint16_t*)ti.GTb.ptr + r->r0, ti.ldgt, (float*)g.C,
-                          g.ldc, g.M, g.N, (int)r->kq, 0, p->part.ptr, p->part_bytes, true, st, true);
+            run_gemm_bf16((const uint16_t*)r->Rb.ptr, r->ldrb, bti, ldbi, (float*)g.C,
+                          g.ldc, g.M, g.N, (int)r->kq, 0, part, part_bytes, true, st, true);
     } else {
-        kind_gemm(p, kind_relation(p), g, st);
+        const ProductKind k = kind_relation(p);
+        run_gemm(k.ty, p->engine, g, 0, part, part_bytes, st, k.relation);
     }
     if (p->profiling) {
         SKF_HIP(hipEventRecord(next_event(p), st));
         // what the launch executes and the relation bytes it reads as stored (include/skfusion_hip.h, skf_plan_get_profile)
         const double cells = (double)g.M * (double)g.K;
-        if (p->bf16 && r && r->sparse) {
+        if (ones) {
             p->prof_flops += 2.0 * (double)r->sp_nnz * (double)g.N;
             p->prof_bytes += 4.0 * (double)r->sp_nnz;
         } else {

@@ -221,17 +221,23 @@ static void fill_err_terms(skf_plan* p, const RelState& r, hipStream_t st) {
 // of SKF_BF16 gathers the f32 masters too: |R|^2 - 2 <R, X> is a sum of same-signed terms r x over the stored entries that
 // has to cancel against the exact trace term, so bf16 roundings of x (2^-9 each, not averaged out by differing signs as in
 // a sum of squared residuals) would show in the error at 4e-4 relative; the pass is not on the hot path.
-static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void* dst, hipStream_t st, int sq_first) {
+// `rhs` (RelRight, skf_plan.inc; err == false, no rank-one fill): the gathered rows are the caller's [n_in][rhs->ld] matrix
+// in the master type in EVERY engine, rhs->n wide, and the outputs of the parts go to the caller's scratch.
+static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void* dst, hipStream_t st, int sq_first,
+                       const RelRight* rhs) {
     const TypeState& ti = p->types[r.row];
     const TypeState& tj = p->types[r.col];
     const TypeState& tin = is_q ? ti : tj;                   // the gathered factor
     const int64_t n_out = is_q ? tj.n : r.nr;
     const int parts = is_q ? r.kn_pr : r.kn_pc;
-    const int w = tin.c;
+    const int w = rhs ? rhs->n : tin.c;
+    if (rhs && (err || r.fill)) SKF_FAIL(SKF_E_STATE, "SKF_REL_SPARSE_CSR relation: a right operand of the caller's in an error pass / with a rank-one fill");
+    if (rhs && parts > 1 && rhs->part_bytes < (size_t)parts * n_out * w * p->esz)
+        SKF_FAIL(SKF_E_STATE, "SKF_REL_SPARSE_CSR relation: the caller's scratch does not hold the outputs of the list parts");
     // Q gathers rows of G_i through column lists whose indices are LOCAL rows: the gathered base is the first row of the
     // block (row ownership: the owned rows; a whole relation: row 0)
     const int64_t in0 = is_q ? r.r0 : 0;
-    const bool bf16_rows = p->bf16 && !err;
+    const bool bf16_rows = p->bf16 && !err && !rhs;
     SrpPass d = {};
     d.ptr = is_q ? r.KcPtr.ptr : r.KrPtr.ptr;
     d.idx = is_q ? r.KcIdx.ptr : r.KrIdx.ptr;
@@ -242,8 +248,9 @@ static int sparse_pass(skf_plan* p, const RelState& r, bool is_q, bool err, void
     d.ldi = bf16_rows ? tin.ldrow : w; d.n_in = tin.n - in0;
     d.Fo = bf16_rows ? nullptr : r.H.ptr; d.ldo = d.ldi;
     d.bf16_rows = bf16_rows;
+    if (rhs) { d.Fi = (const char*)rhs->B + (size_t)in0 * rhs->ld * p->esz; d.ldi = rhs->ld; d.ldo = d.ldi; }
     d.dst = dst;
-    d.part = is_q ? r.Qpart.ptr : r.Apart.ptr;
+    d.part = rhs ? rhs->part : (is_q ? r.Qpart.ptr : r.Apart.ptr);
     d.n_out = n_out; d.ld_out = w;
     d.parts = parts; d.w = w; d.mode = err ? SRP_ERR : SRP_APPLY;
     d.sq_first = sq_first;

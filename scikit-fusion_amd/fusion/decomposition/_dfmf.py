@@ -5,7 +5,8 @@ are LISTS of matrices; the result is ``(G, S)`` with ``G[(t, t)]`` and ``S[(i, j
 
 Extra keyword-only engine options (defaults keep the reference behaviour):
   dtype   'f64' (default, parity with the float64 reference) | 'f32'
-  G0      dict {(t,t): ndarray} overriding the initialiser (warm start / parity tests)
+  G0      dict {(t,t): ndarray} overriding the initialiser (warm start / parity tests), or a `_init.DeviceInit`: the
+          draws of a column-mean initialiser, which the bound plan turns into its factors on the device (whole fits only)
 """
 import logging
 
@@ -13,7 +14,7 @@ import numpy as np
 
 from ... import _native as nat
 from ..._engine import DevicePlan, flatten_relations, flatten_thetas, count_objects
-from ._init import initialize, host_view
+from ._init import initialize, host_view, DeviceInit
 
 log = logging.getLogger('skfusion_amd')
 
@@ -317,7 +318,10 @@ def run_fits_concurrent(variant, R, M, Theta, obj_types, obj_type2rank, max_iter
                 plans.append(plan)
                 if batch_only and not plan.batchable():        # (decided on the first plan, before a second workspace exists)
                     return None
-                plan.set_factors({t: G0[t, t] for t in obj_types}, sync=False)
+                if isinstance(G0, DeviceInit):                 # the plan initialises itself (column means on the device)
+                    G0.apply(plan, obj_types)
+                else:
+                    plan.set_factors({t: G0[t, t] for t in obj_types}, sync=False)
             rt.mem.synchronize()                               # the uploads went out on the plans' own streams
             if len(plans) > 1 and DevicePlan.iterate_batch(plans, max_iter):
                 pass      # a small graph: every launch served all the restarts of the batch (skf_iterate_batch), one stream
@@ -369,7 +373,10 @@ def run_fit(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type,
     plan = DevicePlan(obj_types, n_obj, obj_type2rank, rel_list, flatten_thetas(Theta), variant,
                       dtype=dtype, engine=engine)
     try:
-        plan.set_factors({t: G0[t, t] for t in obj_types})
+        if isinstance(G0, DeviceInit):          # the plan initialises itself (column means on the device), after bind
+            G0.apply(plan, obj_types)
+        else:
+            plan.set_factors({t: G0[t, t] for t in obj_types})
         if not (callback or stopping or stopping_system or compute_err):
             plan.iterate(max_iter)              # whole loop device-resident, no host sync
         else:

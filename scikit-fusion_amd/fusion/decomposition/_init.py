@@ -1,10 +1,12 @@
-"""Factor initialisers (host side, NumPy).
+"""Factor initialisers.
 
 They run once per fit, consume a ``numpy.random.RandomState`` (MT19937) stream and must draw
 from it in exactly the reference's order for seeded results to agree (reference
-``_init.py:6-61``: `random` :11-17, `random_c` :20-41, `random_vcol` :44-61), so they stay
-on the host; the resulting G0 is uploaded once.  ``R`` maps (row_type, col_type) to the FIRST
-relation matrix of that pair (reference _dfmf.py:191).
+``_init.py:6-61``: `random` :11-17, `random_c` :20-41, `random_vcol` :44-61), so the DRAWS stay
+on the host.  `initialize` also forms G0 there, in NumPy, and the result is uploaded once;
+`draw_positions` / `DeviceInit` make the same draws without the data and leave the column means
+of `random_c` / `random_vcol` to the device (csrc/skf_init.h).  ``R`` maps (row_type, col_type)
+to the FIRST relation matrix of that pair (reference _dfmf.py:191).
 """
 import numpy as np
 
@@ -147,6 +149,80 @@ def _random_c(obj_types, n_obj, rank, R, random_state, pools=None):
 
 
 INIT_TYPES = {"random": _random, "random_c": _random_c, "random_vcol": _random_vcol}
+COLUMN_MEAN_TYPES = ('random_c', 'random_vcol')
+
+
+# ---- the column-mean initialisers on the device ------------------------------------------------------------------------------
+# `RandomState.shuffle` makes the same draws and the same swaps whatever the sequence holds, so the host can shuffle an index
+# array arange(len(pool)) cumulatively exactly where `_column_means_init` shuffles the pool, without knowing what the pool
+# holds: the chosen columns are pool0[idx[:take]] and the stream is consumed as before.  What needs the data -- the column
+# norms that rank the pool of `random_c`, the means themselves -- runs on the device (csrc/skf_init.h).
+
+def draw_positions(obj_types, obj_type2rank, shapes, init_typ, random_state):
+    """The random draws of one `initialize` call with a column-mean initialiser, without the data: for every object type
+    (in the caller's order) and every oriented view of it (in the order of `_views_of`) the c x take positions into the
+    view's column pool -- ``{type: [((pair, transposed?), int64 array c x take)]}``.  `shapes`: {(row_type, col_type):
+    (n_row, n_col)} of the FIRST relation of every pair, in the order of R.  The pool of `random_vcol` is every column of
+    the view, so its positions are the columns themselves; `random_c` draws from the strongest half (`DeviceInit`)."""
+    if init_typ not in COLUMN_MEAN_TYPES:
+        raise KeyError(init_typ)
+    out = {}
+    for t in _ordered(obj_types):
+        c = obj_type2rank[t]
+        views = []
+        for pair, shape in shapes.items():
+            if t not in pair:
+                continue
+            transposed = t != pair[0]
+            n_cols = int(shape[0] if transposed else shape[1])
+            take = int(.2 * n_cols)
+            idx = np.arange(int(.5 * n_cols) if init_typ == 'random_c' else n_cols)
+            pos = np.empty((c, take), dtype=np.int64)
+            for k in range(c):
+                random_state.shuffle(idx)
+                pos[k] = idx[:take]
+            views.append(((pair, transposed), pos))
+        out[t] = views
+    return out
+
+
+def strongest_half_of(squares):
+    """The pool of `random_c` from the sums of squares of a view's columns: the square roots ranked by the stable descending
+    sort of `_random_c`, so that exact sums tie exactly as the reference's norms do."""
+    norms = np.sqrt(np.asarray(squares, dtype=np.float64))
+    order = sorted(range(len(norms)), key=norms.__getitem__, reverse=True)
+    return np.asarray(order[:int(.5 * len(norms))], dtype=np.int64)
+
+
+class DeviceInit(object):
+    """What stands in for the G0 of one restart when its plan initialises itself on the device: the positions drawn for
+    this restart and `pools`, the dict the restarts of ONE fit share -- {(pair, transposed?): strongest half}, filled from the
+    device norms by the first plan that needs them, as `pools` of `_random_c` is filled by the first restart."""
+
+    def __init__(self, positions, init_typ, pools):
+        self.positions, self.init_typ, self.pools = positions, init_typ, pools
+
+    def _pool(self, plan, rel, key):
+        if key not in self.pools:
+            row_sq, col_sq = plan.relation_norms(rel)           # (one pass gives both orientations)
+            self.pools[key[0], False] = strongest_half_of(col_sq)
+            self.pools[key[0], True] = strongest_half_of(row_sq)
+        return self.pools[key]
+
+    def apply(self, plan, obj_types):
+        """Initialise every factor of the bound `plan`: the selections go up, the plan forms G0 and takes it as its
+        factor.  Between bind and the first iteration; one synchronisation at the end."""
+        first = {}
+        for k, rel in enumerate(plan.relations):
+            first.setdefault((rel[0], rel[1]), k)               # the FIRST relation of a pair (reference _dfmf.py:191)
+        for t in obj_types:
+            views = []
+            for key, pos in self.positions[t]:
+                rel = first[key[0]]
+                views.append((rel, self._pool(plan, rel, key)[pos] if self.init_typ == 'random_c' else pos))
+            plan.init_column_means(t, views, sync=False)
+        plan.synchronize()
+        plan._pending_init = None                               # (selections, scratch and G0 buffers: the launches are through)
 
 
 def initialize(obj_types, obj_type2n_obj, obj_type2rank, R, init_typ, random_state, pools=None):

@@ -8,7 +8,7 @@ from ..base import FusionFit
 from . import _dfmc
 from ..._distributed import my_runs, gather_runs
 from .dfmf import (graph_matrices, store_runs, initial_factors, _random_state, concurrent_streams,
-                   device_fill_dtype)
+                   device_fill_dtype, init_device_wanted, init_device_covered)
 
 __all__ = ['Dfmc']
 
@@ -27,7 +27,7 @@ class Dfmc(FusionFit):
     def __init__(self, max_iter=100, init_type='random_c', n_run=1, stopping=None,
                  stopping_system=None, verbose=0, compute_err=False, callback=None,
                  random_state=None, n_jobs=1, dtype='f64', shard='runs', device_fill=False, sparse_relations=None,
-                 sparse_constraints=None):
+                 sparse_constraints=None, init_device=None):
         super(Dfmc, self).__init__()
         self._set_params(vars())
 
@@ -40,7 +40,8 @@ class Dfmc(FusionFit):
                                      known_entries=self.shard in ('runs', 'owned'),
                                      sparse_relations=getattr(self, 'sparse_relations', None), shard=self.shard,
                                      sparse_constraints=getattr(self, 'sparse_constraints', None), variant='dfmc')
-        G0 = initial_factors(R, object_types, rank, self.init_type, self.random_state, self.n_run)
+        self.init_on_device_ = init_device_wanted(self) and init_device_covered(R, M)
+        G0 = initial_factors(R, object_types, rank, self.init_type, self.random_state, self.n_run, self.init_on_device_)
         kw = dict(R=R, M=M, Theta=Theta, obj_types=object_types, obj_type2rank=rank,
                   max_iter=self.max_iter, init_type=self.init_type, stopping=self.stopping,
                   stopping_system=self.stopping_system, verbose=self.verbose,

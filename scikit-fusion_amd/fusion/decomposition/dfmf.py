@@ -197,12 +197,21 @@ def graph_matrices(fusion_graph, with_masks=False, device_dtype=None, known_entr
     return (R, Theta, M) if with_masks else (R, Theta)
 
 
-def initial_factors(R, object_types, rank, init_type, random_state, n_run):
+def initial_factors(R, object_types, rank, init_type, random_state, n_run, on_device=False):
     """G0 of every restart, drawn in run order from the ONE shared RandomState (the reference
     passes the same generator object to all runs, dfmf.py:92, consumed sequentially for
     n_jobs=1).  Every rank draws all of them so that the result of run k does not depend on how
-    many GPUs share the work."""
+    many GPUs share the work.
+    `on_device` (a column-mean initialiser, `init_device_wanted` and `init_device_covered`): the draws only -- one
+    `_init.DeviceInit` per restart, which the restart's plan turns into its factors after bind; the stream is consumed as
+    the host initialiser consumes it, and the relations are never read here."""
     n_obj = count_objects(object_types, R)
+    if on_device:
+        from ._init import draw_positions, DeviceInit
+        shapes = {k: tuple(v[0].shape) for k, v in R.items()}
+        pools = {}                               # column rankings of `random_c` from the device norms, shared by the restarts
+        return [DeviceInit(draw_positions(object_types, rank, shapes, init_type, random_state), init_type, pools)
+                for _ in range(n_run)]
     # ('random' never reads the relations: they may live on the device already, `device_fill`)
     R_first = {} if init_type == 'random' else {k: host_view(v[0]) for k, v in R.items()}
     pools = {}                                   # column rankings of `random_c`, shared by the restarts (R_first stays alive here)
@@ -210,11 +219,78 @@ def initial_factors(R, object_types, rank, init_type, random_state, n_run):
             for _ in range(n_run)]
 
 
+INIT_DEVICE_MIN = 1 << 34   # init_device=None: gathered elements (sum of n_rows * take * c over the oriented views) from which the
+                            # device initialiser runs -- about two minutes of the host initialiser at the 1.5e8 elements/s
+                            # measured for it (profiles/init_device.txt); every test and bench.py path stays below it
+
+
+def _first_relations(fusion_graph):
+    """The first relation of every pair of different object types (reference _dfmf.py:191: the one the initialisers
+    read), in the walking order of `graph_matrices`."""
+    for row_type, col_type in product(fusion_graph.object_types, repeat=2):
+        if row_type != col_type:
+            for relation in fusion_graph.get_relations(row_type, col_type):
+                yield relation
+                break
+
+
+def init_device_work(fusion_graph):
+    """What the host initialiser gathers: sum over the oriented views of n_rows * take * c elements."""
+    total = 0
+    for rel in _first_relations(fusion_graph):
+        n_r, n_c = rel.data.shape
+        total += n_r * int(.2 * n_c) * int(rel.row_type.rank) + n_c * int(.2 * n_r) * int(rel.col_type.rank)
+    return total
+
+
+def init_device_wanted(fuser):
+    """Whether the fit may initialise on the device, as far as the graph alone tells (before any matrix is formed):
+    `init_device` is not False, a column-mean initialiser, whole relations on this process (shard='runs'), no preprocessor
+    on a relation between two types (it would have to run on the host first), every first relation of a pair with at least
+    5 columns in both orientations (fewer: take = 0 and the reference's mean of nothing, NaN -- the host keeps that), and
+    -- `init_device=None` -- at least INIT_DEVICE_MIN gathered elements.  `init_device_covered` has the last word."""
+    from ._init import COLUMN_MEAN_TYPES
+    want = getattr(fuser, 'init_device', None)
+    if want is False or fuser.init_type not in COLUMN_MEAN_TYPES or fuser.shard != 'runs':
+        return False
+    graph = fuser.fusion_graph
+    if any(rel.preprocessor for rel in graph.relations if rel.row_type != rel.col_type):
+        return False
+    if any(min(rel.data.shape) < 5 for rel in _first_relations(graph)):
+        return False
+    return bool(want) or init_device_work(graph) >= INIT_DEVICE_MIN
+
+
+def init_device_covered(R, M=None):
+    """... and as far as the matrices tell: the first relation of every pair in a form the device initialiser reads --
+    unmasked, and dense (host or device) or the stored entries of a relation that is zero elsewhere; not the known entries
+    of a masked relation, not entries plus rank one."""
+    from ..._engine import KnownEntries, DeviceKnownEntries
+    for key, mats in R.items():
+        if M is not None and M.get(key) is not None and M[key][0] is not None:
+            return False
+        m = mats[0]
+        if isinstance(m, (KnownEntries, DeviceKnownEntries)) and (m.unstored != 'zero' or m.by_col or m.row_fill is not None):
+            return False
+    return True
+
+
+def _fills_without_mask(fusion_graph):
+    """Every relation between two types is a plain ndarray or a scipy.sparse matrix whose unstored entries are zero: no
+    fill leaves a mask behind, so what `init_device_wanted` says holds for the filled matrices too."""
+    return all(isinstance(rel.data, np.ndarray) and not np.ma.isMaskedArray(rel.data) or rel.is_zero_unstored()
+               for rel in fusion_graph.relations if rel.row_type != rel.col_type)
+
+
 def device_fill_dtype(fuser):
     """The engine dtype when the fill strategies of the relations may run on the device: asked for
     (`device_fill=True`), whole relations on this process (shard='runs'), and an initialiser that does not read the
-    filled values on the host ('random'; the column-mean initialisers `random_c` / `random_vcol` do)."""
-    if getattr(fuser, 'device_fill', False) and fuser.shard == 'runs' and fuser.init_type == 'random':
+    filled values on the host: 'random', or a column-mean initialiser (`random_c` / `random_vcol`) when it will run on the
+    device (`init_device_wanted`, and relations whose fill leaves no mask: the decision cannot be taken back once the
+    filled matrix exists in HBM only)."""
+    if not (getattr(fuser, 'device_fill', False) and fuser.shard == 'runs'):
+        return None
+    if fuser.init_type == 'random' or (init_device_wanted(fuser) and _fills_without_mask(fuser.fusion_graph)):
         return fuser.dtype
     return None
 
@@ -313,12 +389,19 @@ class Dfmf(FusionFit):
     as entries plus rank one under the same ``sparse_relations`` rule with shard='runs' and never expanded either: every
     fill writes a rank-one pattern a b^T into the unknown cells, so the filled matrix is a b^T + D with D sparse on the
     stored pattern (``Relation.filled_entries``; see ``filled_entries_apply`` for what is still expanded).
+    init_device=None | True | False: the column means of `random_c` / `random_vcol` (reference _init.py:20-61) are formed on
+    the device -- one contraction per relation view against the 0/1 matrix of the chosen columns, the random stream drawn on
+    the host exactly as before -- when the fit is eligible (``init_device_wanted``, ``init_device_covered``: shard='runs', no
+    preprocessor, the first relation of every pair whole, unmasked, dense or stored entries, at least 5 columns both ways);
+    True: whenever eligible; None: when the host initialiser would gather at least 2^34 elements; False: never.  An
+    ineligible fit initialises on the host whatever this says.  ``init_on_device_`` (after ``fuse``) says what ran.
+    ``device_fill=True`` goes with these initialisers when they run on the device.
     """
 
     def __init__(self, max_iter=100, init_type='random_c', n_run=1, stopping=None,
                  stopping_system=None, verbose=0, compute_err=False, callback=None,
                  random_state=None, n_jobs=1, dtype='f64', shard='runs', device_fill=False, sparse_relations=None,
-                 sparse_constraints=None):
+                 sparse_constraints=None, init_device=None):
         super(Dfmf, self).__init__()
         self._set_params(vars())
 
@@ -330,7 +413,8 @@ class Dfmf(FusionFit):
         R, Theta = graph_matrices(fusion_graph, device_dtype=device_fill_dtype(self),
                                   sparse_relations=getattr(self, 'sparse_relations', None), shard=self.shard,
                                   sparse_constraints=getattr(self, 'sparse_constraints', None))
-        G0 = initial_factors(R, object_types, rank, self.init_type, self.random_state, self.n_run)
+        self.init_on_device_ = init_device_wanted(self) and init_device_covered(R)
+        G0 = initial_factors(R, object_types, rank, self.init_type, self.random_state, self.n_run, self.init_on_device_)
         kw = dict(R=R, Theta=Theta, obj_types=object_types, obj_type2rank=rank,
                   max_iter=self.max_iter, init_type=self.init_type, stopping=self.stopping,
                   stopping_system=self.stopping_system, verbose=self.verbose,
