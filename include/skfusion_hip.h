@@ -640,6 +640,38 @@ int skf_complete_above(int32_t dtype, const void* H, int64_t ldh, int64_t m, con
                        int64_t* n_found /* host */, int32_t col_splits /* 0 = choose */,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* One counting pass of a radix select over EVERY candidate score of X = H Gc^T (H, Gc as for skf_complete_topk), without X:
+ * what finds the n-th largest score of a whole relation -- the cut-off of "the n most confident pairs over all rows", which
+ * the reference's users read off the sorted dense product (fusion/base/base.py `complete`) -- in KEY_BITS / 11 passes.
+ *   Candidate: a pair (r, j), j in [0, n_cols), j not in row r's exclusion list, score(r, j) not NaN; score(r, j) is the same
+ *     chain of matrix instructions as in skf_complete_topk.
+ *   Key: u = the bits of score + 0 as an unsigned integer of KEY_BITS = 32 (SKF_F32) / 64 (SKF_F64);
+ *     key = u ^ (sign bit of u set ? all ones : the sign bit).  key(a) < key(b) <=> a < b; -0.0 and +0.0 share one key;
+ *     -inf and +inf are ordinary keys, the smallest and the largest.
+ *   Counting: a candidate counts when the top prefix_bits of its key equal prefix; it adds one to
+ *     hist[(key >> (KEY_BITS - prefix_bits - digit_bits)) & (2^digit_bits - 1)].  hist (device, uint64 [1 << digit_bits]) is
+ *     ADDED to, never cleared: the caller clears it once, sums the row blocks of one pass on the device and reads it back once
+ *     per pass.  Integer atomics only: the counts do not depend on col_splits (0 = the library chooses, at most 32), the
+ *     launch geometry or the order of arrival.
+ *   Selection (the caller's): walk a pass's histogram from the highest digit down to the bin that holds the n-th candidate,
+ *     append the digit to the prefix, take the counts above the bin off n, repeat until prefix_bits == KEY_BITS.  Then the
+ *     prefix is key(T), T the n-th largest candidate score, g = the candidates > T, e = the last bin = the candidates == T, and
+ *   P3: skf_complete_above with thr[r] = T in every row returns exactly g + e entries on the same inputs, g of them > T and e
+ *     of them == T, with g < n <= g + e -- for every col_splits and every cut of the rows into blocks of either operator.  For
+ *     a single row and n <= 64 the n best pairs are skf_complete_topk's list, index for index and bit for bit.
+ *   Refused with SKF_E_INVALID and nothing written: digit_bits outside 1 .. 11, prefix_bits < 0, prefix_bits + digit_bits >
+ *     KEY_BITS, prefix >= 2^prefix_bits, hist NULL, the operand checks of skf_complete_topk; SKF_E_WORKSPACE for a workspace
+ *     that is NULL, too small or not 256-byte aligned (skf_complete_digits_workspace_bytes: flag words only).  Exclusion: as
+ *     for skf_complete_topk (both pointers NULL = none), validated on the device before anything is counted.  m == 0 (or
+ *     n_cols == 0) succeeds and adds nothing.
+ *   dtype SKF_F64 / SKF_F32; 1 <= c <= 1024; m and n_cols < 2^31. */
+int skf_complete_digits_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int32_t col_splits, size_t* bytes);
+int skf_complete_digits(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols,
+                        int32_t c, const int64_t* excl_indptr, const int32_t* excl_indices,
+                        uint64_t prefix, int32_t prefix_bits, int32_t digit_bits,
+                        uint64_t* hist /* device, [1 << digit_bits], ADDED to */,
+                        int32_t col_splits /* 0 = choose */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the column-mean initialisers on the device (reference _init.py:20-61: `random_c` :20-41, `random_vcol` :44-61) ----
  * The reference fills factor column k of an object type with the mean of take = int(0.2 m) randomly chosen columns of every
  * relation that touches the type, oriented so that the type's objects are its rows (V, n x m), and `random_c` draws them
@@ -739,7 +771,7 @@ const char* skf_version(void);
  * skf_get_constraint_lists and the flag SKF_OPT_THETA_OWNED_ROWS; skf_plan_set_relation_fill and the flag SKF_REL_FILL_RANK1;
  * skf_complete_ranks_workspace_bytes and skf_complete_ranks; skf_complete_above_workspace_bytes and skf_complete_above;
  * skf_plan_relation_norms, skf_plan_init_column_means, their workspace queries and skf_init_view, a struct of their own -- the
- * structs before it are those of version 4). */
+ * structs before it are those of version 4; skf_complete_digits_workspace_bytes and skf_complete_digits). */
 #define SKF_ABI_VERSION 5
 int skf_abi_version(void);
 

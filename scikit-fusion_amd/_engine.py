@@ -1334,10 +1334,39 @@ class AboveLimit(ValueError):
         self.found = found
 
 
+def digit_walk(counts, n):
+    """One step of the radix select, a pure function of one pass's histogram: ``(digit, above)`` -- the bin that holds the
+    ``n``-th candidate (1-based) when the bins are walked from the highest digit down, and the candidates in the bins above
+    it.  With fewer than ``n`` candidates in the histogram: the lowest bin that holds one (the smallest candidates).  An empty
+    histogram: ``(None, 0)``."""
+    counts = np.asarray(counts, dtype=np.uint64).astype(object)      # Python integers: sums of uint64 counts cannot wrap
+    above = 0
+    last = None
+    for d in range(len(counts) - 1, -1, -1):
+        if counts[d] == 0:
+            continue
+        if above + counts[d] >= n:
+            return d, int(above)
+        above += counts[d]
+        last = d
+    if last is None:
+        return None, 0
+    return last, int(above - counts[last])
+
+
+def score_of_key(key, np_dtype):
+    """The score whose order-preserving key (csrc/skf_complete.h ``score_key``) is ``key``, as a scalar of ``np_dtype``."""
+    bits = 8 * np.dtype(np_dtype).itemsize
+    sign, ones = 1 << (bits - 1), (1 << bits) - 1
+    u = key ^ sign if key & sign else key ^ ones
+    return np.array([u], dtype=np.uint64).astype('u%d' % (bits // 8)).view(np_dtype)[0]
+
+
 class DeviceCompleter(object):
     """The consuming side of a completion model without the dense reconstruction: for ``X = G_row S G_col^T`` the ``k`` best
     columns of every row (``topk``), the predictions at given pairs (``entries``), the position of given pairs in
-    their row's ranking (``ranks``) and every pair at or above a threshold as CSR (``above``), all on the device (csrc/skf_complete.h).  The reference forms ``X`` on the host (fusion/base/base.py ``complete``) and its users rank or
+    their row's ranking (``ranks``), every pair at or above a threshold as CSR (``above``) and the n-th largest score over all
+    row blocks (``kth``, by counting passes ``digits``), all on the device (csrc/skf_complete.h).  The reference forms ``X`` on the host (fusion/base/base.py ``complete``) and its users rank or
     index that array (examples/movielens_completion.py:121-126).  ``S`` and ``G_col`` are uploaded ONCE and stay resident
     across blocks (the contract of ``DeviceReconstructor``); per block only ``H = G_row[block] S`` (``skf_gemm``), the
     block's exclusion lists, its outputs and the partial lists of the column splits live in HBM -- never anything of size
@@ -1483,7 +1512,7 @@ class DeviceCompleter(object):
 
     ABOVE_PER_ROW = 64                   # entries per row the first call of `above` makes room for
 
-    def above(self, G_row_block, thr, exclude=None, col_splits=0, capacity=None, max_entries=None):
+    def above(self, G_row_block, thr, exclude=None, col_splits=0, capacity=None, max_entries=None, count_only=False):
         """``(indptr int64 [m + 1], indices int32 [n], values float64 [n])``: canonical CSR over the rows of the block of
         every column whose score is at or above the row's threshold -- ``score >= thr`` in the SCORING type (``thr``, a
         scalar or one value per row, is cast to it first), IEEE: a NaN score or threshold selects nothing, ``-inf``
@@ -1492,7 +1521,8 @@ class DeviceCompleter(object):
         fills; the first call makes room for ``capacity`` entries (default: ``ABOVE_PER_ROW`` per row, or what an earlier
         block needed) and is repeated ONCE with the exact count when they do not suffice -- the arrays are the same either
         way.  ``max_entries``: a count beyond it raises ``AboveLimit`` before anything of that size is allocated.
-        ``col_splits`` 0 lets the library choose; the result does not depend on it."""
+        ``col_splits`` 0 lets the library choose; the result does not depend on it.  ``count_only=True``: the count pass and
+        the scan alone (``out_indices`` NULL) -- returns ``indptr`` and nothing else, allocates no entry buffer."""
         A = self._rows_of(G_row_block)
         m = A.shape[0]
         rt, mem = self.rt, self.rt.mem
@@ -1504,10 +1534,19 @@ class DeviceCompleter(object):
         need = C.c_size_t()
         rt.call('skf_complete_above_workspace_bytes', self.code, m, self.nj, int(col_splits), C.byref(need))
         if m == 0:
+            if count_only:
+                return np.zeros(1, dtype=np.int64)
             return np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float64)
         with self._on_device(A, own, xl) as (h, (bt,), xp, xi):
             ws = self._scratch('ws', need.value)
             op = self._scratch('above_ptr', (m + 1) * 8)
+            if count_only:
+                found = C.c_int64(-1)
+                self.peak_bytes = max(self.peak_bytes, self.device_bytes)
+                rt.call('skf_complete_above', self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, bt, xp, xi, 0,
+                        op.ptr, None, None, C.byref(found), int(col_splits), ws.ptr, ws.nbytes, mem.stream)
+                mem.synchronize()
+                return mem.to_host(op, (m + 1,), np.int64)
             if capacity is None:
                 have = self._bufs.get('above_idx')
                 cap = min(m * self.nj, max(self.ABOVE_PER_ROW * m, have.nbytes // 4 if have else 0))
@@ -1529,6 +1568,59 @@ class DeviceCompleter(object):
                     break
                 cap = n                  # the count pass has said how many there are: once more, with room for them
             return mem.to_host(op, (m + 1,), np.int64), mem.to_host(oi, (n,), np.int32), mem.to_host(ov, (n,), self.npd).astype(np.float64)
+
+    DIGIT_PLAN = {4: (11, 11, 10), 8: (11, 11, 11, 11, 11, 9)}      # item size of the scoring type -> digit bits per pass
+
+    def digits(self, G_row_block, prefix, prefix_bits, digit_bits, hist, exclude=None, col_splits=0):
+        """One counting pass of the radix select over the block's candidates (admissible, not NaN): every candidate whose
+        order-preserving key (csrc/skf_complete.h) begins with the ``prefix_bits`` bits of ``prefix`` adds one to the bin of
+        its next ``digit_bits`` (at most 11) bits in ``hist``, a device buffer of ``1 << digit_bits`` uint64 words OWNED BY
+        THE CALLER: it is added to, never cleared, so the blocks of one pass sum on the device.  ``exclude`` as for
+        ``topk``; the counts do not depend on ``col_splits``."""
+        A = self._rows_of(G_row_block)
+        m = A.shape[0]
+        rt, mem = self.rt, self.rt.mem
+        if hist.nbytes < 8 << max(int(digit_bits), 0):
+            raise ValueError('hist: a device buffer of 1 << digit_bits uint64 words')
+        xl = self._exclusion(exclude, m)
+        need = C.c_size_t()
+        rt.call('skf_complete_digits_workspace_bytes', self.code, m, self.nj, int(col_splits), C.byref(need))
+        with self._on_device(A, [], xl) as (h, _, xp, xi):
+            ws = self._scratch('ws', need.value)
+            self.peak_bytes = max(self.peak_bytes, self.device_bytes)
+            rt.call('skf_complete_digits', self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, xp, xi,
+                    int(prefix), int(prefix_bits), int(digit_bits), hist.ptr, int(col_splits), ws.ptr, ws.nbytes, mem.stream)
+            mem.synchronize()
+
+    def kth(self, blocks, n, col_splits=0):
+        """``(T, n_greater, n_equal, n_candidates)``: ``T`` (float64 of the scoring type's value) is the ``n``-th largest
+        candidate score over ALL the row blocks -- ``blocks()`` returns a fresh iterator of ``(G_row_block, exclude)`` and
+        is called once per pass --, ``n_greater`` candidates score above it and ``n_equal`` equal it:
+        ``n_greater < n <= n_greater + n_equal``, and ``above(T)`` over the same blocks returns exactly ``n_greater +
+        n_equal`` entries (P3 of csrc/skf_complete.h).  Fewer than ``n`` candidates: the smallest candidate score, and
+        ``n_greater + n_equal == n_candidates``; none at all: ``T`` is NaN.  A radix select: 3 passes of ``digits`` over
+        the blocks in f32 (11 / 11 / 10 key bits), 6 in f64 (11 x 5 + 9); after each the 2048 counts are read back and
+        ``digit_walk`` extends the prefix.  Nothing but the histogram (16 KB) is held beside a block's usual state."""
+        n = int(n)
+        if n < 1:
+            raise ValueError('n must be at least 1')
+        mem = self.rt.mem
+        prefix, pbits, greater, cands, equal = 0, 0, 0, 0, 0
+        for db in self.DIGIT_PLAN[self.es]:
+            hist = self._bufs['hist'] = mem.from_host(np.zeros(1 << db, dtype=np.uint64))
+            for G_row_block, exclude in blocks():
+                self.digits(G_row_block, prefix, pbits, db, hist, exclude=exclude, col_splits=col_splits)
+            counts = mem.to_host(hist, (1 << db,), np.uint64)
+            if pbits == 0:
+                cands = int(counts.astype(object).sum())
+                if cands == 0:
+                    return float('nan'), 0, 0, 0
+                n = min(n, cands)
+            d, above = digit_walk(counts, n - greater)
+            greater += above
+            equal = int(counts[d])
+            prefix, pbits = (prefix << db) | d, pbits + db
+        return float(score_of_key(prefix, self.npd)), greater, equal, cands
 
     def entries(self, G_row, rows, cols):
         """``float64 [n]``: ``X[rows[e], cols[e]]``.  Only the DISTINCT rows of ``G_row`` that ``rows`` names are uploaded

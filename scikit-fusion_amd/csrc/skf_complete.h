@@ -38,6 +38,16 @@
 // with the IEEE comparison (a NaN score or threshold selects nothing), as canonical CSR.  Same product, hence
 //   P2: with thr[r] = the k-th value of complete_topk on the same inputs, row r's entries ordered by (value descending,
 //       column ascending) begin with top-k's list, bit for bit, and every further entry equals thr[r].
+//
+// The n BEST pairs of the whole relation (link prediction: "the 10 000 most confident new pairs, over all rows") need a cut-off
+// nobody knows in advance: the exact n-th largest score over every candidate -- a column inside the relation, not in the
+// row's exclusion list, with a score that is not NaN.  complete_digits_kernel is one counting pass of a radix select for
+// it: the histogram of one digit of an order-preserving integer key of the candidates under a key prefix (see there).  The
+// caller walks the histograms from the top digit down (32 or 64 key bits in passes of at most 11) and holds, at the end,
+// T = the n-th largest candidate score, g = the candidates > T and e = the candidates == T.  Same product, integer counts, hence
+//   P3: skf_complete_above with thr[r] = T in every row returns exactly g + e entries on the same inputs, g of them > T and e
+//       of them == T, with g < n <= g + e -- for every col_splits and every cut of the rows into blocks; for a single row
+//       and n <= 64 the n best pairs are complete_topk's list, index for index and bit for bit.
 #pragma once
 #include "skf_kernels.h"
 
@@ -734,6 +744,129 @@ static __global__ __launch_bounds__(256) void above_offsets_kernel(int64_t* __re
         }
         base += total;
     }
+}
+
+// ---- one digit of a radix select over every admissible score -------------------------------------------------------------------
+// The n best pairs of the WHOLE relation need the n-th largest score over all rows, and that is a selection, not a sort: a
+// few counting passes over the tiles the passes above walk, each of which histograms one digit of an order-preserving
+// integer key of the scores whose higher digits equal the prefix found so far.
+//     key(s): u = the bits of s + 0 as an unsigned integer of KEY_BITS (32 / 64); key = u ^ (sign(u) ? all ones : sign bit)
+// so that key(a) < key(b) <=> a < b for a, b not NaN; -0.0 + 0 = +0.0: the two zeros share one key (no -0.0 comes out of
+// accumulators that start at +0, the rule is stated all the same); +-inf are ordinary keys.  A CANDIDATE is a score whose
+// column is inside the relation, not in the row's exclusion list, and that is not NaN.  The bit cast is a plain
+// __builtin_memcpy: the host emulator runs this file too.
+template <typename T> struct ScoreKey;
+template <> struct ScoreKey<float> {
+    typedef unsigned int key_t;
+    static constexpr int BITS = 32;
+};
+template <> struct ScoreKey<double> {
+    typedef unsigned long long key_t;
+    static constexpr int BITS = 64;
+};
+template <typename T>
+static __device__ __forceinline__ typename ScoreKey<T>::key_t score_key(T s) {
+    typedef typename ScoreKey<T>::key_t K;
+    const T z = s + (T)0;
+    K u;
+    __builtin_memcpy(&u, &z, sizeof u);
+    const K sign = (K)1 << (ScoreKey<T>::BITS - 1);
+    return u ^ ((u & sign) ? ~(K)0 : sign);
+}
+
+constexpr int DIGIT_MAX_BITS = 11;                   // 2048 uint32 bins in LDS: 8 KB beside the 35 KB buffer of the f64 kernel
+// A workgroup sees at most 64 x 64 scores per tile, all of which may fall into ONE bin: after 2^19 tiles a bin holds at most
+// 2^31 and is added to the caller's histogram and cleared, long before its 32 bits could wrap.  (A split walks up to
+// 2^31 / 64 = 2^25 tiles.)
+constexpr int64_t DIGIT_FLUSH_TILES = (int64_t)1 << 19;
+
+template <typename T>
+struct DigitArgs {
+    const T* H;  int64_t ldh;  int64_t m;           // [m][c]
+    const T* Gc; int64_t ldg;  int64_t n_cols;      // [n_cols][c]
+    int c;
+    const int64_t* xptr; const int* xidx;           // exclusion CSR over the m rows (validated by the caller), or both null
+    int tiles_per_split;                            // column tiles (of TOPK_BN) a split walks
+    unsigned long long prefix;                      // a candidate counts when the top prefix_bits of its key equal it
+    int prefix_bits, digit_bits;                    // prefix_bits + digit_bits <= KEY_BITS, 1 <= digit_bits <= DIGIT_MAX_BITS
+    unsigned long long* hist;                       // [1 << digit_bits], ADDED to
+};
+
+// all threads: the workgroup's non-zero bins go to the caller's histogram with integer atomics and are cleared
+static __device__ __forceinline__ void digit_flush(unsigned* bins, int nbins, unsigned long long* hist) {
+    __syncthreads();
+    for (int d = threadIdx.x; d < nbins; d += TOPK_THREADS) {
+        const unsigned n = bins[d];
+        if (n) {
+            atomicAdd(&hist[d], (unsigned long long)n);
+            bins[d] = 0;
+        }
+    }
+    __syncthreads();
+}
+
+// grid (64-row tile, column split) and walk as complete_above_kernel: the same product, hence the bits every other operator
+// sees, and the exclusion mask published per tile by the owner lanes.  Thread (row = t & 63, quarter = t >> 6) then walks
+// its 16 scores: a candidate under the prefix adds one to the LDS bin of its digit
+//     (key >> (KEY_BITS - prefix_bits - digit_bits)) & (2^digit_bits - 1).
+// Real scores share a handful of exponents -- in the first pass nearly every score of a tile meets in the same few words --
+// so a thread MERGES RUNS: consecutive candidates with one digit become one atomicAdd of their count.  Counts are integers:
+// the histogram does not depend on the splits, the launch geometry or the order of arrival.  No float atomics.
+template <typename T>
+__global__ __launch_bounds__(TOPK_THREADS) void complete_digits_kernel(DigitArgs<T> a) {
+    typedef typename ScoreKey<T>::key_t K;
+    constexpr int OPER = 2 * TOPK_BM * TOPK_LD, TILE = TOPK_BM * TOPK_SLD;
+    __shared__ T buf[OPER > TILE ? OPER : TILE];
+    __shared__ unsigned long long xmask[TOPK_BM];        // the excluded columns of the tile, per row
+    __shared__ unsigned bins[1 << DIGIT_MAX_BITS];
+    const T* sc = buf;
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r = t & 63, q = t >> 6;
+    const int64_t row0 = (int64_t)blockIdx.x * TOPK_BM;
+    const TileRange tiles = split_tiles(a.n_cols, a.tiles_per_split);
+    const bool rin = row0 + r < a.m;
+    const int nbins = 1 << a.digit_bits;
+    const int shift = ScoreKey<T>::BITS - a.prefix_bits - a.digit_bits;      // 0 .. KEY_BITS - 1
+    const K dmask = (K)(nbins - 1), prefix = (K)a.prefix;
+
+    for (int d = t; d < nbins; d += TOPK_THREADS) bins[d] = 0;
+    __syncthreads();
+
+    const bool owner = lane < 16;                        // of row wave * 16 + lane of the tile
+    const int orow = wave * 16 + lane;
+    int64_t xp = 0, xe = 0;                              // the row's exclusion list from the split's first column on
+    if (owner && row0 + orow < a.m && a.xptr) excl_seek(a.xptr, a.xidx, row0 + orow, tiles.lo * TOPK_BN, xp, xe);
+
+    for (int64_t tile = tiles.lo; tile < tiles.hi; ++tile) {
+        const int64_t col0 = tile * TOPK_BN;
+        topk_score_tile<T>(a.H, a.ldh, a.m, row0, a.Gc, a.ldg, a.c,
+                           [&](int rr) { return col0 + rr < a.n_cols ? (int)(col0 + rr) : -1; }, buf);
+        if (owner) xmask[orow] = excl_tile_mask(a.xidx, xp, xe, col0);
+        __syncthreads();
+        if (rin) {
+            const unsigned xm = (unsigned)(xmask[r] >> (16 * q)) & 0xffffu;
+            int run_d = 0, run_n = 0;                    // the run of equal digits so far
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                const T s = sc[r * TOPK_SLD + 16 * q + b];
+                const K v = score_key<T>(s) >> shift;    // the prefix and the digit; the prefix is 0 for prefix_bits == 0
+                const int d = (int)(v & dmask);
+                if (col0 + 16 * q + b < a.n_cols && !((xm >> b) & 1u) && s == s && (v >> a.digit_bits) == prefix) {
+                    if (run_n && d != run_d) {
+                        atomicAdd(&bins[run_d], (unsigned)run_n);
+                        run_n = 0;
+                    }
+                    run_d = d;
+                    ++run_n;
+                }
+            }
+            if (run_n) atomicAdd(&bins[run_d], (unsigned)run_n);
+        }
+        if (((tile - tiles.lo + 1) & (DIGIT_FLUSH_TILES - 1)) == 0) digit_flush(bins, nbins, a.hist);
+        // (the first barrier of the next tile's product separates these reads from the next tile and mask)
+    }
+    digit_flush(bins, nbins, a.hist);
 }
 
 }  // namespace skf

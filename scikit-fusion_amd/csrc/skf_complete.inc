@@ -1,5 +1,5 @@
 // skf_complete.inc -- part of the one translation unit skf_api.hip (textually included there, inside its namespaces; not a
-// header of its own): the host side of the consuming operators skf_complete_topk / _entries / _ranks / _above (kernels:
+// header of its own): the host side of the consuming operators skf_complete_topk / _entries / _ranks / _above / _digits (kernels:
 // skf_complete.h), their C entry points included.  Every rule of the front end is stated once and named after what it checks;
 // an entry point reads as its own order of them:
 //   SKF_E_INVALID refusals (shape, operands, lists that come in pairs) -> SKF_E_WORKSPACE refusals -> the first HIP call
@@ -232,6 +232,38 @@ static void run_complete_above(const Scored& s, const void* thr, int64_t capacit
     }
 }
 
+// ---- one digit of the radix select over every candidate score -----------------------------------------------------------------
+// Workspace: [0, 256) the flag word of the exclusion check, nothing else: the histogram is the caller's.
+static size_t digits_workspace() { return 256; }
+
+static void digits_check_query(int32_t dtype, int64_t m, int64_t n_cols, int32_t col_splits) {
+    check_shape("digits", dtype, m, n_cols);
+    check_col_splits("digits", col_splits, OVER_MAX_REFUSE);
+}
+
+// the digit asked for lies inside the key of the scoring type, and the prefix inside its own bits
+static void check_digit(int32_t dtype, uint64_t prefix, int32_t prefix_bits, int32_t digit_bits) {
+    const int key_bits = 8 * (int)dtype_size(dtype);
+    if (digit_bits < 1 || digit_bits > DIGIT_MAX_BITS)
+        SKF_FAIL(SKF_E_INVALID, "skf_complete_digits: digit_bits = %d outside 1 .. %d", digit_bits, DIGIT_MAX_BITS);
+    if (prefix_bits < 0 || prefix_bits > key_bits - digit_bits)
+        SKF_FAIL(SKF_E_INVALID, "skf_complete_digits: prefix_bits = %d with digit_bits = %d outside the %d key bits", prefix_bits,
+                 digit_bits, key_bits);
+    if ((prefix >> prefix_bits) != 0)                   // (prefix_bits <= 63 here)
+        SKF_FAIL(SKF_E_INVALID, "skf_complete_digits: prefix %llu does not fit its %d bits", (unsigned long long)prefix, prefix_bits);
+}
+
+template <typename T>
+static void launch_complete_digits(const Scored& s, uint64_t prefix, int prefix_bits, int digit_bits, uint64_t* hist, int splits,
+                                   hipStream_t st) {
+    DigitArgs<T> a;
+    fill_operands(a, s, splits);
+    a.prefix = prefix; a.prefix_bits = prefix_bits; a.digit_bits = digit_bits;
+    a.hist = (unsigned long long*)hist;
+    hipLaunchKernelGGL((complete_digits_kernel<T>), dim3(cdiv(s.m, TOPK_BM), splits), dim3(TOPK_THREADS), 0, st, a);
+    check_launch("complete_digits");
+}
+
 // ---- the C entry points --------------------------------------------------------------------------------------------------------
 // When there is nothing to score the three list operators differ, on purpose: top-k leaves at m == 0 (no row to write; with
 // n_cols == 0 it still validates and launches: every slot gets -1 / -inf), ranks leaves at n_targets == 0 before any list
@@ -373,6 +405,35 @@ int skf_complete_above(int32_t dtype, const void* H, int64_t ldh, int64_t m, con
         }
         by_dtype(dtype, [&](auto t) {
             run_complete_above<decltype(t)>(s, thr, capacity, out_indptr, out_indices, out_values, n_found, splits, (char*)workspace, st);
+        });
+    });
+}
+
+int skf_complete_digits_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int32_t col_splits, size_t* bytes) {
+    return guarded([&] {
+        if (!bytes) SKF_FAIL(SKF_E_INVALID, "null argument");
+        digits_check_query(dtype, m, n_cols, col_splits);
+        *bytes = digits_workspace();
+    });
+}
+
+int skf_complete_digits(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int32_t c,
+                        const int64_t* excl_indptr, const int32_t* excl_indices, uint64_t prefix, int32_t prefix_bits,
+                        int32_t digit_bits, uint64_t* hist, int32_t col_splits, void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded([&] {
+        const Scored s = {dtype, H, ldh, m, Gc, ldg, n_cols, c, excl_indptr, excl_indices};
+        digits_check_query(dtype, m, n_cols, col_splits);
+        check_operands("digits", s);
+        check_digit(dtype, prefix, prefix_bits, digit_bits);
+        if (!hist) SKF_FAIL(SKF_E_INVALID, "skf_complete_digits: null argument");
+        const int splits = topk_col_splits(m, n_cols, col_splits);
+        check_workspace("digits", workspace, workspace_bytes, digits_workspace());
+        if (m == 0) return;
+        hipStream_t st = as_stream(stream);
+        validate_exclusion("digits", s, (int*)workspace, st);
+        if (n_cols == 0) return;                        // no column: no candidate
+        by_dtype(dtype, [&](auto t) {
+            launch_complete_digits<decltype(t)>(s, prefix, prefix_bits, digit_bits, hist, splits, st);
         });
     });
 }

@@ -435,6 +435,125 @@ class FusionFit(FusionBase):
             return out
         return self._per_run(one, run)
 
+    # ---- the n best pairs of a whole relation: a global selection on the device, never densified ---------------------------
+    def _best_preamble(self, relation, method, n, rows, exclude, block_rows):
+        self._check_raw_scores(relation, method)
+        n = int(n)
+        if n < 0:
+            raise DataFusionError("%s: n = %d is negative" % (method, n))
+        n_i, n_j = self._relation_shape(relation)
+        rows = self._row_vector(rows, n_i)
+        lists = self._exclusion_lists(relation, exclude, (n_i, n_j))
+        step = max(1, int(block_rows))
+
+        def blocks_of(G1):
+            """A callable that returns a fresh iterator of (G_row_block, exclude) over the listed rows, in order."""
+            def blocks():
+                for b0 in range(0, rows.size, step):
+                    blk = rows[b0:b0 + step]
+                    yield G1[blk], lists(blk) if lists else None
+            return blocks
+        return n, rows, n_j, blocks_of
+
+    def complete_kth(self, relation, n, rows=None, exclude=None, run=None, dtype='f64', block_rows=8192):
+        """``(threshold, n_greater, n_equal)``: the ``n``-th largest score the model gives to any admissible pair of
+        ``rows`` x all columns (``rows``: default every row object; a row listed twice is two rows) -- the cut-off to hand
+        to ``complete_above`` for "the ``n`` most confident pairs", and the size to expect from it: ``n_greater`` pairs
+        score above ``threshold`` and ``n_equal`` equal it, ``n_greater < n <= n_greater + n_equal``, and
+        ``complete_above(relation, threshold, ...)`` with the same arguments returns exactly ``n_greater + n_equal``
+        entries.  NaN scores and excluded pairs (``exclude`` as for ``complete_topk``) are no candidates.  With fewer than
+        ``n`` candidates ``threshold`` is the smallest candidate score; with none, or ``n == 0``, it is NaN.  The device
+        runs a radix select over the score tiles, ``block_rows`` rows at a time -- three passes in f32, six in f64 --
+        and nothing of size ``n_i x n_j`` is formed; the result does not depend on ``block_rows``.  ``dtype`` and the
+        refusal of post-processed relations as in ``complete_above``.  ``n_run > 1`` and ``run=None``: a generator over
+        the runs.  Extension of the reference API."""
+        n, rows, n_j, blocks_of = self._best_preamble(relation, 'complete_kth', n, rows, exclude, block_rows)
+
+        def one(r):
+            G1, comp = self._completer(relation, r, dtype)
+            if n == 0 or rows.size == 0:
+                return float('nan'), 0, 0
+            return comp.kth(blocks_of(G1), n)[:3]
+        return self._per_run(one, run)
+
+    def complete_best(self, relation, n, rows=None, exclude=None, run=None, dtype='f64', block_rows=8192, ties='first',
+                      max_entries=2 ** 28):
+        """``scipy.sparse.csr_matrix`` of shape ``(len(rows), n_j)``, float64, sorted indices: the ``n`` best pairs of
+        ``rows`` x all columns TOGETHER, with their scores -- link prediction's "the ``n`` most confident new pairs of this
+        relation" without forming ``complete(relation)``.  Total order: higher score first, equal scores by lower position
+        in ``rows``, then by lower column; a NaN score and an excluded pair (``exclude`` as for ``complete_topk``) are
+        never selected.  ``ties='first'``: exactly ``min(n, candidates)`` entries, the first of that order;
+        ``ties='all'``: every pair that equals the ``n``-th score as well, i.e. ``complete_above`` at
+        ``complete_kth``'s threshold.  ``rows``: default every row object; otherwise an integer array in any order, a row
+        listed twice is two rows.  ``n = 0`` gives an empty matrix; ``n > max_entries`` is refused before anything runs
+        (and ``ties='all'`` once the ties push the result beyond it).  The device selects the threshold
+        (``complete_kth``) and fills per block of ``block_rows`` rows; when the tie at the threshold holds more pairs than
+        are wanted, two count passes per block say which rows the quota reaches, and only the row in which it runs out is
+        trimmed on the host: nothing larger than the result is kept.  The bytes do not depend on ``block_rows``.
+        ``dtype`` and the refusal of post-processed relations as in ``complete_above``.  ``n_run > 1`` and ``run=None``: a
+        generator over the runs.  Extension of the reference API."""
+        n, rows, n_j, blocks_of = self._best_preamble(relation, 'complete_best', n, rows, exclude, block_rows)
+        import scipy.sparse
+        from .._engine import AboveLimit
+        if ties not in ('first', 'all'):
+            raise DataFusionError("ties must be 'first' or 'all', not %r" % (ties,))
+        limit = int(max_entries)
+        if n > limit:
+            raise DataFusionError("complete_best: n = %d, max_entries = %d" % (n, limit))
+
+        def one(r):
+            G1, comp = self._completer(relation, r, dtype)
+            indptr = np.zeros(rows.size + 1, dtype=np.int64)
+            idx, val = [np.zeros(0, dtype=np.int32)], [np.zeros(0)]
+            T, greater, equal, cands = comp.kth(blocks_of(G1), n) if n and rows.size else (float('nan'), 0, 0, 0)
+            if cands:
+                want = greater + equal if ties == 'all' else min(n, cands)
+                if want > limit:
+                    raise DataFusionError("complete_best: %d entries with the ties at the %d-th score, max_entries = %d"
+                                          % (want, n, limit))
+                need = want - greater                   # of the `equal` pairs at T, the first `need` in (row, column) order
+                ftype = np.dtype(comp.npd).type         # the next score above T in the SCORING type; above +inf: NaN, nothing
+                strict = float(np.nextafter(ftype(T), ftype(np.inf))) if T < np.inf else np.nan
+                plain = need == equal                   # the whole tie is wanted: above(T) as it is
+                found, at = 0, 0
+                for A, xl in blocks_of(G1)():
+                    thr = T
+                    cut = None
+                    if not plain:
+                        tied = np.diff(comp.above(A, T, exclude=xl, count_only=True)) - np.diff(comp.above(A, strict, exclude=xl, count_only=True))
+                        before = np.cumsum(tied) - tied     # tied pairs of the block ahead of each row
+                        thr = np.where(before < need, T, strict)
+                        over = np.nonzero((before < need) & (before + tied > need))[0]
+                        if over.size:                   # the row in which the quota runs out: its surplus goes, from the right
+                            cut = (int(over[0]), int(before[over[0]] + tied[over[0]] - need))
+                        need = max(0, need - int(tied.sum()))
+                    try:
+                        p, i, v = comp.above(A, thr, exclude=xl, max_entries=want - found + n_j)     # (+ the one row to trim)
+                    except AboveLimit as over_limit:
+                        raise RuntimeError("complete_best: %d entries in one block, the histograms said %d in all"
+                                           % (over_limit.found, want))
+                    if cut is not None:
+                        q, surplus = cut
+                        row = np.arange(p[q], p[q + 1])
+                        drop = row[v[row] == T][-surplus:]
+                        keep = np.ones(i.size, dtype=bool)
+                        keep[drop] = False
+                        i, v = i[keep], v[keep]
+                        p = p.copy()
+                        p[q + 1:] -= surplus
+                    indptr[at + 1:at + A.shape[0] + 1] = found + p[1:]
+                    found += int(p[-1])
+                    at += A.shape[0]
+                    idx.append(i)
+                    val.append(v)
+                if found != want:
+                    raise RuntimeError("complete_best: %d entries filled, the histograms said %d (threshold %r, %d above, "
+                                       "%d equal)" % (found, want, T, greater, equal))
+            out = scipy.sparse.csr_matrix((np.concatenate(val), np.concatenate(idx), indptr), shape=(rows.size, n_j))
+            out.has_sorted_indices = True      # (ascending within a row by construction)
+            return out
+        return self._per_run(one, run)
+
 
 # ---- persistence of a fitted model (SURVEY.md 8 f4; the reference has none: its accessors base.py:35-56,
 # 169-189 are the only consumers of factors_ / backbones_) ----------------------------------------------
