@@ -672,6 +672,41 @@ int skf_complete_digits(int32_t dtype, const void* H, int64_t ldh, int64_t m, co
                         uint64_t* hist /* device, [1 << digit_bits], ADDED to */,
                         int32_t col_splits /* 0 = choose */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The k-th best score of EVERY row of X = H Gc^T (H, Gc as for skf_complete_topk) for any k, without X: Recall@100 / @1000,
+ * R-precision and candidate generation need per-row lists far beyond SKF_TOPK_MAX, and a row's k best columns are
+ * skf_complete_above at the row's own k-th score.  One radix select per row over the keys of skf_complete_digits, in digits of
+ * 7 bits (5 passes for SKF_F32, 10 for SKF_F64): a counting pass over the score tiles fills one histogram per row, one wave
+ * per row extends the row's prefix, and so on -- every pass of one call is enqueued on the stream, nothing travels to the
+ * host in between, and out_thr is a device array that skf_complete_above takes as it is.
+ *   Candidates, scores and keys: as for skf_complete_digits, per row.  want (device, int64 [m], each >= 0): how many of row
+ *     r's candidates are wanted.  With cands_r candidates in row r and n_r = min(want[r], cands_r):
+ *       n_r == 0: out_thr[r] = NaN, out_greater[r] = out_equal[r] = 0;
+ *       otherwise: out_thr[r] (dtype) = the n_r-th largest candidate score of the row, out_greater[r] = the candidates above it,
+ *         out_equal[r] = the candidates equal to it: out_greater[r] < n_r <= out_greater[r] + out_equal[r].
+ *     out_cands[r] = cands_r unless out_cands is NULL.  All outputs on the device.  Integer counts and integer atomics only: the
+ *     outputs do not depend on col_splits (0 = the library chooses, at most 32), the launch geometry or the order of arrival.
+ *   P4: skf_complete_above on the same inputs with thr = out_thr returns exactly out_greater[r] + out_equal[r] entries in row r,
+ *     out_greater[r] of them above out_thr[r] -- for every col_splits of either operator and every cut of the rows into blocks.
+ *     A NaN threshold selects nothing.
+ *   P5: with want[r] = k <= SKF_TOPK_MAX, row r's P4 entries ordered by (value descending, column ascending) begin with
+ *     skf_complete_topk's list for that k -- its first min(k, cands_r) slots -- index for index and bit for bit.
+ *   Refused with SKF_E_INVALID: a NULL want, out_thr, out_greater or out_equal, the operand checks of skf_complete_topk,
+ *     col_splits outside 0 .. 32, exclusion lists that are not canonical and a negative want[r] (both found on the device, in
+ *     one round trip, before anything is counted); SKF_E_WORKSPACE for a workspace that is NULL, too small or not 256-byte
+ *     aligned.  Every refusal leaves every output as it was; the argument checks answer before any HIP call.  The only host
+ *     synchronisation is that of the list check.  m == 0 succeeds and writes nothing; n_cols == 0 succeeds without a product
+ *     launch: every row gets NaN / 0.
+ *   Workspace (skf_complete_row_kth_workspace_bytes): flag words, the row histograms (uint32 [m][128]) and two 64-bit words
+ *     per row -- 528 m bytes and a little; it grows with m and never with m x n_cols.  skf_complete_topk keeps its limit.
+ *   dtype SKF_F64 / SKF_F32 (the type of H, Gc and out_thr); 1 <= c <= 1024; m and n_cols < 2^31. */
+int skf_complete_row_kth_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int32_t col_splits, size_t* bytes);
+int skf_complete_row_kth(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols,
+                         int32_t c, const int64_t* want /* device [m], each >= 0 */,
+                         const int64_t* excl_indptr, const int32_t* excl_indices,
+                         void* out_thr /* dtype [m], device */, int64_t* out_greater /* [m] */, int64_t* out_equal /* [m] */,
+                         int64_t* out_cands /* [m] or NULL */, int32_t col_splits /* 0 = choose */,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the column-mean initialisers on the device (reference _init.py:20-61: `random_c` :20-41, `random_vcol` :44-61) ----
  * The reference fills factor column k of an object type with the mean of take = int(0.2 m) randomly chosen columns of every
  * relation that touches the type, oriented so that the type's objects are its rows (V, n x m), and `random_c` draws them
@@ -771,7 +806,8 @@ const char* skf_version(void);
  * skf_get_constraint_lists and the flag SKF_OPT_THETA_OWNED_ROWS; skf_plan_set_relation_fill and the flag SKF_REL_FILL_RANK1;
  * skf_complete_ranks_workspace_bytes and skf_complete_ranks; skf_complete_above_workspace_bytes and skf_complete_above;
  * skf_plan_relation_norms, skf_plan_init_column_means, their workspace queries and skf_init_view, a struct of their own -- the
- * structs before it are those of version 4; skf_complete_digits_workspace_bytes and skf_complete_digits). */
+ * structs before it are those of version 4; skf_complete_digits_workspace_bytes and skf_complete_digits;
+ * skf_complete_row_kth_workspace_bytes and skf_complete_row_kth). */
 #define SKF_ABI_VERSION 5
 int skf_abi_version(void);
 

@@ -1365,8 +1365,9 @@ def score_of_key(key, np_dtype):
 class DeviceCompleter(object):
     """The consuming side of a completion model without the dense reconstruction: for ``X = G_row S G_col^T`` the ``k`` best
     columns of every row (``topk``), the predictions at given pairs (``entries``), the position of given pairs in
-    their row's ranking (``ranks``), every pair at or above a threshold as CSR (``above``) and the n-th largest score over all
-    row blocks (``kth``, by counting passes ``digits``), all on the device (csrc/skf_complete.h).  The reference forms ``X`` on the host (fusion/base/base.py ``complete``) and its users rank or
+    their row's ranking (``ranks``), every pair at or above a threshold as CSR (``above``), the n-th largest score over all
+    row blocks (``kth``, by counting passes ``digits``) and every row's own k-th score for any k with the columns at or above
+    it (``row_kth``, ``row_best``), all on the device (csrc/skf_complete.h).  The reference forms ``X`` on the host (fusion/base/base.py ``complete``) and its users rank or
     index that array (examples/movielens_completion.py:121-126).  ``S`` and ``G_col`` are uploaded ONCE and stay resident
     across blocks (the contract of ``DeviceReconstructor``); per block only ``H = G_row[block] S`` (``skf_gemm``), the
     block's exclusion lists, its outputs and the partial lists of the column splits live in HBM -- never anything of size
@@ -1525,7 +1526,7 @@ class DeviceCompleter(object):
         the scan alone (``out_indices`` NULL) -- returns ``indptr`` and nothing else, allocates no entry buffer."""
         A = self._rows_of(G_row_block)
         m = A.shape[0]
-        rt, mem = self.rt, self.rt.mem
+        rt = self.rt
         t = np.asarray(thr, dtype=np.float64)
         if t.ndim > 1 or (t.ndim == 1 and t.shape != (m,)):
             raise ValueError('thr: a scalar or one value per row of the block')
@@ -1538,36 +1539,116 @@ class DeviceCompleter(object):
                 return np.zeros(1, dtype=np.int64)
             return np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float64)
         with self._on_device(A, own, xl) as (h, (bt,), xp, xi):
-            ws = self._scratch('ws', need.value)
-            op = self._scratch('above_ptr', (m + 1) * 8)
-            if count_only:
-                found = C.c_int64(-1)
-                self.peak_bytes = max(self.peak_bytes, self.device_bytes)
-                rt.call('skf_complete_above', self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, bt, xp, xi, 0,
-                        op.ptr, None, None, C.byref(found), int(col_splits), ws.ptr, ws.nbytes, mem.stream)
-                mem.synchronize()
-                return mem.to_host(op, (m + 1,), np.int64)
-            if capacity is None:
-                have = self._bufs.get('above_idx')
-                cap = min(m * self.nj, max(self.ABOVE_PER_ROW * m, have.nbytes // 4 if have else 0))
-            else:
-                cap = int(capacity)
+            return self._above_on_device(h, m, bt, xp, xi, col_splits, need.value, capacity, max_entries, count_only)
+
+    def _above_on_device(self, h, m, bt, xp, xi, col_splits, ws_bytes, capacity, max_entries, count_only=False):
+        """The device part of ``above`` for a block that is already there: ``h`` its H, ``bt`` the DEVICE address of its
+        ``m`` thresholds in the scoring type, ``xp`` / ``xi`` those of its lists (``row_best`` hands the thresholds of the
+        select over without a trip to the host)."""
+        rt, mem = self.rt, self.rt.mem
+        ws = self._scratch('ws', ws_bytes)
+        op = self._scratch('above_ptr', (m + 1) * 8)
+        if count_only:
             found = C.c_int64(-1)
-            for attempt in (0, 1):
-                oi = self._scratch('above_idx', max(cap, 1) * 4)
-                ov = self._scratch('above_val', max(cap, 1) * self.es)
-                self.peak_bytes = max(self.peak_bytes, self.device_bytes)
-                rc = rt.lib.skf_complete_above(self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, bt, xp, xi, cap,
-                                               op.ptr, oi.ptr, ov.ptr, C.byref(found), int(col_splits), ws.ptr, ws.nbytes, mem.stream)
-                mem.synchronize()
-                n = found.value
-                if max_entries is not None and n > max_entries:
-                    raise AboveLimit(n)
-                if rc != nat.SKF_E_WORKSPACE or attempt or n <= cap:
-                    rt.check(rc)
-                    break
-                cap = n                  # the count pass has said how many there are: once more, with room for them
-            return mem.to_host(op, (m + 1,), np.int64), mem.to_host(oi, (n,), np.int32), mem.to_host(ov, (n,), self.npd).astype(np.float64)
+            self.peak_bytes = max(self.peak_bytes, self.device_bytes)
+            rt.call('skf_complete_above', self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, bt, xp, xi, 0,
+                    op.ptr, None, None, C.byref(found), int(col_splits), ws.ptr, ws.nbytes, mem.stream)
+            mem.synchronize()
+            return mem.to_host(op, (m + 1,), np.int64)
+        if capacity is None:
+            have = self._bufs.get('above_idx')
+            cap = min(m * self.nj, max(self.ABOVE_PER_ROW * m, have.nbytes // 4 if have else 0))
+        else:
+            cap = int(capacity)
+        found = C.c_int64(-1)
+        for attempt in (0, 1):
+            oi = self._scratch('above_idx', max(cap, 1) * 4)
+            ov = self._scratch('above_val', max(cap, 1) * self.es)
+            self.peak_bytes = max(self.peak_bytes, self.device_bytes)
+            rc = rt.lib.skf_complete_above(self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, bt, xp, xi, cap,
+                                           op.ptr, oi.ptr, ov.ptr, C.byref(found), int(col_splits), ws.ptr, ws.nbytes, mem.stream)
+            mem.synchronize()
+            n = found.value
+            if max_entries is not None and n > max_entries:
+                raise AboveLimit(n)
+            if rc != nat.SKF_E_WORKSPACE or attempt or n <= cap:
+                rt.check(rc)
+                break
+            cap = n                  # the count pass has said how many there are: once more, with room for them
+        return mem.to_host(op, (m + 1,), np.int64), mem.to_host(oi, (n,), np.int32), mem.to_host(ov, (n,), self.npd).astype(np.float64)
+
+    def _wants(self, k, m):
+        """``k`` -- a scalar or one value per row, integers >= 0 -- as int64 [m]."""
+        w = np.asarray(k)
+        if w.dtype.kind not in 'iu' or w.ndim > 1 or (w.ndim == 1 and w.shape != (m,)):
+            raise ValueError('k: a non-negative integer or one per row of the block')
+        w = np.ascontiguousarray(np.broadcast_to(w.astype(np.int64), (m,)))
+        if m and w.min() < 0:
+            raise ValueError('k: a non-negative integer or one per row of the block')
+        return w
+
+    def _row_kth_on_device(self, h, m, wp, xp, xi, col_splits, ws_bytes):
+        """The select of ``row_kth`` on a block that is already there (``wp``: the device address of its ``want``): returns the
+        scratch Buffers ``(thr, greater, equal, cands)``, written by the stream -- nothing is read back here."""
+        rt, mem = self.rt, self.rt.mem
+        ws = self._scratch('ws', ws_bytes)
+        thr = self._scratch('row_thr', m * self.es)
+        out = [self._scratch(name, m * 8) for name in ('row_greater', 'row_equal', 'row_cands')]
+        self.peak_bytes = max(self.peak_bytes, self.device_bytes)
+        rt.call('skf_complete_row_kth', self.code, h.ptr, self.cj, m, self.b.ptr, self.cj, self.nj, self.cj, wp, xp, xi, thr.ptr,
+                out[0].ptr, out[1].ptr, out[2].ptr, int(col_splits), ws.ptr, ws.nbytes, mem.stream)
+        return [thr] + out
+
+    def _row_kth_to_host(self, bufs, m):
+        mem = self.rt.mem
+        mem.synchronize()
+        return (mem.to_host(bufs[0], (m,), self.npd).astype(np.float64),) + tuple(mem.to_host(b, (m,), np.int64) for b in bufs[1:])
+
+    def _row_workspaces(self, m, col_splits):
+        rt = self.rt
+        need_kth, need_above = C.c_size_t(), C.c_size_t()
+        rt.call('skf_complete_row_kth_workspace_bytes', self.code, m, self.nj, int(col_splits), C.byref(need_kth))
+        rt.call('skf_complete_above_workspace_bytes', self.code, m, self.nj, int(col_splits), C.byref(need_above))
+        return need_kth.value, need_above.value
+
+    def row_kth(self, G_row_block, k, exclude=None, col_splits=0):
+        """``(thr float64 [m], greater int64 [m], equal int64 [m], cands int64 [m])``: per row of the block the ``k``-th
+        largest candidate score (``k``: a scalar or one value per row, any size; candidates: admissible columns whose score
+        is not NaN, ``cands`` of them), the candidates above it and those equal to it -- ``greater < min(k, cands) <=
+        greater + equal``, and ``above(thr)`` returns exactly ``greater + equal`` entries in the row (P4 of
+        csrc/skf_complete.h).  A row with ``k == 0`` or without candidates: NaN, 0, 0.  One radix select per row, every pass
+        on the device.  ``exclude`` as for ``topk``; the result does not depend on ``col_splits``."""
+        A = self._rows_of(G_row_block)
+        m = A.shape[0]
+        want = self._wants(k, m)
+        xl = self._exclusion(exclude, m)
+        need_kth, _ = self._row_workspaces(m, col_splits)
+        if m == 0:
+            return np.zeros(0), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+        with self._on_device(A, [want], xl) as (h, (wp,), xp, xi):
+            return self._row_kth_to_host(self._row_kth_on_device(h, m, wp, xp, xi, col_splits, need_kth), m)
+
+    def row_best(self, G_row_block, k, exclude=None, col_splits=0, max_entries=None):
+        """``(indptr, indices, values, thr, greater, equal)``: the CSR of ``above`` at every row's own ``k``-th score, and what
+        ``row_kth`` says of it -- per row the ``greater`` columns that beat the ``k``-th score and the ``equal`` that tie with
+        it.  H is formed once and the lists are uploaded once; the thresholds of the select stay on the device and go
+        straight into the count and the fill.  ``max_entries`` and the accounting in ``peak_bytes`` as for ``above``."""
+        A = self._rows_of(G_row_block)
+        m = A.shape[0]
+        want = self._wants(k, m)
+        xl = self._exclusion(exclude, m)
+        need_kth, need_above = self._row_workspaces(m, col_splits)
+        if m == 0:
+            return (np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0), np.zeros(0), np.zeros(0, dtype=np.int64),
+                    np.zeros(0, dtype=np.int64))
+        with self._on_device(A, [want], xl) as (h, (wp,), xp, xi):
+            self._scratch('ws', max(need_kth, need_above))
+            bufs = self._row_kth_on_device(h, m, wp, xp, xi, col_splits, need_kth)
+            # room for what is wanted and a tie of one more per row; a longer tie costs one more count pass
+            have = self._bufs.get('above_idx')
+            cap = min(m * self.nj, max(int(np.minimum(want, self.nj).sum()) + m, have.nbytes // 4 if have else 0))
+            csr = self._above_on_device(h, m, bufs[0].ptr, xp, xi, col_splits, need_above, cap, max_entries)
+            return csr + self._row_kth_to_host(bufs, m)[:3]
 
     DIGIT_PLAN = {4: (11, 11, 10), 8: (11, 11, 11, 11, 11, 9)}      # item size of the scoring type -> digit bits per pass
 

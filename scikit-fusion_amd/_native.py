@@ -168,6 +168,9 @@ SIGNATURES = {
     'skf_complete_digits_workspace_bytes': (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
     'skf_complete_digits': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_uint64,
                                       C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_size_t, _P]),
+    'skf_complete_row_kth_workspace_bytes': (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    'skf_complete_row_kth': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P,
+                                       _P, _P, _P, _P, C.c_int32, _P, C.c_size_t, _P]),
     'skf_plan_relation_norms_workspace_bytes': (C.c_int, [_P, C.c_int32, C.POINTER(C.c_size_t)]),
     'skf_plan_relation_norms': (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
     'skf_plan_init_column_means_workspace_bytes': (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(InitView), C.POINTER(C.c_size_t)]),

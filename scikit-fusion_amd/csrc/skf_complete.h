@@ -48,6 +48,18 @@
 //   P3: skf_complete_above with thr[r] = T in every row returns exactly g + e entries on the same inputs, g of them > T and e
 //       of them == T, with g < n <= g + e -- for every col_splits and every cut of the rows into blocks; for a single row
 //       and n <= 64 the n best pairs are complete_topk's list, index for index and bit for bit.
+//
+// The k best columns of EVERY row for any k (Recall@100 / @1000, R-precision, candidate lists: far beyond top-k's 64 slots) are
+// above(r) at the row's own k-th score.  complete_row_digits_kernel / complete_row_walk_kernel run the selection above once
+// per row -- one histogram and one prefix per row, every pass and every walk enqueued on the stream, no host round trip -- and
+// leave, for want[r] with n_r = min(want[r], candidates of row r) > 0: thr[r] = the n_r-th largest candidate score of the row,
+// greater[r] = the candidates above it, equal[r] = the candidates equal to it, greater[r] < n_r <= greater[r] + equal[r]; for
+// n_r == 0: NaN, 0, 0.  Same product, integer counts, hence
+//   P4: skf_complete_above on the same inputs with thr = that device array returns exactly greater[r] + equal[r] entries in row
+//       r, greater[r] of them above thr[r], for every col_splits of either operator and every cut of the rows into blocks; a
+//       NaN threshold selects nothing.
+//   P5: with want[r] = k <= 64, row r's P4 entries ordered by (value descending, column ascending) begin with
+//       complete_topk's list for that k -- its first min(k, candidates) slots -- index for index and bit for bit.
 #pragma once
 #include "skf_kernels.h"
 
@@ -867,6 +879,221 @@ __global__ __launch_bounds__(TOPK_THREADS) void complete_digits_kernel(DigitArgs
         // (the first barrier of the next tile's product separates these reads from the next tile and mask)
     }
     digit_flush(bins, nbins, a.hist);
+}
+
+// ---- the k best columns of EVERY row, for any k: one radix select per row, all passes on the device --------------------------
+// complete_topk's lists end at 64 entries; beyond that a row's k best columns are above(r) at the row's own k-th score, and that
+// score is the selection of complete_digits_kernel run per row: rows are independent, so the passes of a block of rows follow
+// each other on the stream -- a counting pass (complete_row_digits_kernel), then one wave per row that reads the row's
+// histogram and extends the row's prefix (complete_row_walk_kernel) -- with no host round trip, and the thresholds go to
+// complete_above_kernel as a device pointer.  A digit has ROW_DIGIT_BITS bits (the last one what is left of the key):
+//     width 8: 4 passes in f32, 8 in f64, 64 x 257 words of bins = 64.25 KB beside the 17 / 35 KB tile buffer: one workgroup per CU
+//     width 7: 5 / 10 passes, 32.25 KB of bins: two to three workgroups per CU
+// Both compile (-DSKF_ROW_DIGIT_BITS=8).  Measured on the MI355X (profiles/row_best.txt, one block of 8192 rows x 400 000
+// columns): a pass at width 8 costs 1.6 to 1.8 times a pass at width 7 -- the lone workgroup per CU has nothing to hide its
+// barriers and LDS atomics behind -- so the whole select is 1.27 to 1.46 times faster at width 7 in spite of its extra passes.
+#ifndef SKF_ROW_DIGIT_BITS
+#define SKF_ROW_DIGIT_BITS 7
+#endif
+constexpr int ROW_DIGIT_BITS = SKF_ROW_DIGIT_BITS;
+static_assert(ROW_DIGIT_BITS >= 6 && ROW_DIGIT_BITS <= 8, "the walk gives every lane of a wave at least one bin; 64 rows of 2^9 bins do not fit the LDS");
+constexpr int ROW_BINS = 1 << ROW_DIGIT_BITS;
+// Real scores share a few exponents: in the first pass the 64 lanes of a wave -- 64 ROWS, one quarter -- mostly hold the same
+// digit.  With a row stride of 2^D words they would all hit one bank; with 2^D + 1 lane r hits bank (r + d) mod 64.
+constexpr int ROW_BIN_LD = ROW_BINS + 1;
+static inline size_t row_bins_bytes() { return (size_t)TOPK_BM * ROW_BIN_LD * sizeof(unsigned); }
+
+template <typename T>
+struct RowDigitArgs {
+    const T* H;  int64_t ldh;  int64_t m;           // [m][c]
+    const T* Gc; int64_t ldg;  int64_t n_cols;      // [n_cols][c]
+    int c;
+    const int64_t* xptr; const int* xidx;           // exclusion CSR over the m rows (validated by the caller), or both null
+    int tiles_per_split;                            // column tiles (of TOPK_BN) a split walks
+    const unsigned long long* prefix;               // [m]: a candidate of row r counts when the top prefix_bits of its key equal prefix[r]
+    const int64_t* need;                            // [m]: prefix_bits > 0 and need[r] == 0: the row has nothing to select, it is skipped
+    int prefix_bits, digit_bits;                    // prefix_bits + digit_bits <= KEY_BITS, 1 <= digit_bits <= ROW_DIGIT_BITS
+    unsigned* hist;                                 // [m][ROW_BINS], ADDED to (a row has < 2^31 columns: 32 bits cannot wrap)
+};
+
+// grid (64-row tile, column split), walk, product, exclusion mask and candidate rule of complete_digits_kernel; one histogram
+// PER ROW in LDS (dynamic: [64][ROW_BIN_LD] words) and one prefix per row.  Thread (row = t & 63, quarter = t >> 6) walks its
+// 16 scores and merges runs of equal digits into one LDS atomicAdd.  A workgroup sees at most 2^31 columns of a row: the
+// bins need no intermediate flush.  At the end the non-zero bins are added to the row's histogram in the workspace with
+// integer atomics: the counts do not depend on the splits, the launch geometry or the order of arrival.  No float atomics.
+template <typename T>
+__global__ __launch_bounds__(TOPK_THREADS) void complete_row_digits_kernel(RowDigitArgs<T> a) {
+    typedef typename ScoreKey<T>::key_t K;
+    constexpr int OPER = 2 * TOPK_BM * TOPK_LD, TILE = TOPK_BM * TOPK_SLD;
+    __shared__ T buf[OPER > TILE ? OPER : TILE];
+    __shared__ unsigned long long xmask[TOPK_BM];        // the excluded columns of the tile, per row
+    __shared__ int any;                                  // a row of these 64 still selects
+    HIP_DYNAMIC_SHARED(double, dyn)                      // bins[64][ROW_BIN_LD] (row_bins_bytes)
+    unsigned* bins = (unsigned*)dyn;
+    const T* sc = buf;
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r = t & 63, q = t >> 6;
+    const int64_t row0 = (int64_t)blockIdx.x * TOPK_BM;
+    const TileRange tiles = split_tiles(a.n_cols, a.tiles_per_split);
+    const bool rin = row0 + r < a.m && (a.prefix_bits == 0 || a.need[row0 + r] > 0);
+    const int shift = ScoreKey<T>::BITS - a.prefix_bits - a.digit_bits;      // 0 .. KEY_BITS - 1
+    const K dmask = (K)((1 << a.digit_bits) - 1);
+    const K prefix = (rin && a.prefix_bits) ? (K)a.prefix[row0 + r] : (K)0;
+
+    if (t == 0) any = 0;
+    for (int i = t; i < TOPK_BM * ROW_BIN_LD; i += TOPK_THREADS) bins[i] = 0;
+    __syncthreads();
+    if (q == 0 && rin) any = 1;
+    __syncthreads();
+    if (!any) return;                                    // every row of the tile is through: no product
+
+    const bool owner = lane < 16;                        // of row wave * 16 + lane of the tile
+    const int orow = wave * 16 + lane;
+    int64_t xp = 0, xe = 0;                              // the row's exclusion list from the split's first column on
+    if (owner && row0 + orow < a.m && a.xptr) excl_seek(a.xptr, a.xidx, row0 + orow, tiles.lo * TOPK_BN, xp, xe);
+    unsigned* mine = bins + r * ROW_BIN_LD;
+
+    for (int64_t tile = tiles.lo; tile < tiles.hi; ++tile) {
+        const int64_t col0 = tile * TOPK_BN;
+        topk_score_tile<T>(a.H, a.ldh, a.m, row0, a.Gc, a.ldg, a.c,
+                           [&](int rr) { return col0 + rr < a.n_cols ? (int)(col0 + rr) : -1; }, buf);
+        if (owner) xmask[orow] = excl_tile_mask(a.xidx, xp, xe, col0);
+        __syncthreads();
+        if (rin) {
+            const unsigned xm = (unsigned)(xmask[r] >> (16 * q)) & 0xffffu;
+            int run_d = 0, run_n = 0;                    // the run of equal digits so far
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                const T s = sc[r * TOPK_SLD + 16 * q + b];
+                const K v = score_key<T>(s) >> shift;    // the prefix and the digit; the prefix is 0 for prefix_bits == 0
+                const int d = (int)(v & dmask);
+                if (col0 + 16 * q + b < a.n_cols && !((xm >> b) & 1u) && s == s && (v >> a.digit_bits) == prefix) {
+                    if (run_n && d != run_d) {
+                        atomicAdd(&mine[run_d], (unsigned)run_n);
+                        run_n = 0;
+                    }
+                    run_d = d;
+                    ++run_n;
+                }
+            }
+            if (run_n) atomicAdd(&mine[run_d], (unsigned)run_n);
+        }
+        // (the first barrier of the next tile's product separates these reads from the next tile and mask)
+    }
+    __syncthreads();
+    for (int i = t; i < TOPK_BM * ROW_BINS; i += TOPK_THREADS) {
+        const int rr = i >> ROW_DIGIT_BITS, d = i & (ROW_BINS - 1);
+        const unsigned n = bins[rr * ROW_BIN_LD + d];
+        if (n && row0 + rr < a.m) atomicAdd(&a.hist[(row0 + rr) * ROW_BINS + d], n);
+    }
+}
+
+// want[r] >= 0 for every row, or bad[0] = 2 (the list check beside it writes 1: whichever lands, the call is refused for a
+// defect its message names)
+static __global__ __launch_bounds__(256) void row_want_check_kernel(const int64_t* __restrict__ want, int64_t m, int* __restrict__ bad) {
+    int off = 0;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < m; r += (int64_t)gridDim.x * blockDim.x)
+        if (want[r] < 0) off = 1;
+    if (off) *bad = 2;
+}
+
+struct RowWalkArgs {
+    unsigned* hist;                                 // [m][ROW_BINS]: read, then cleared for the next pass
+    int64_t m;
+    int digit_bits;                                 // of the pass just counted
+    int first, last;                                // first: no prefix yet, cands / need are set; last: the key is complete, thr is written
+    const int64_t* want;                            // [m]
+    unsigned long long* prefix;                     // [m]
+    int64_t* need;                                  // [m]: the candidate wanted among those under the prefix, 1-based; 0: none
+    int64_t* greater; int64_t* equal;               // [m]
+    int64_t* cands;                                 // [m] or null
+    void* thr;                                      // [m] of T
+};
+
+// One wave per row, after every counting pass: lane l holds bins ROW_BINS - 1 - PER l, ... downwards (PER = ROW_BINS / 64), so
+// an inclusive scan over the lanes counts the candidates from the highest digit down.  The lane in which the running count
+// reaches need[r] finds the bin; digit, the count above it and the bin's own count go round by shuffle.  Integers only: the
+// result is a pure function of the histogram.  (The bins past 2^digit_bits of a short last digit are zero.)
+template <typename T>
+__global__ __launch_bounds__(256) void complete_row_walk_kernel(RowWalkArgs a) {
+    typedef typename ScoreKey<T>::key_t K;
+    constexpr int PER = ROW_BINS / 64;
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t row = wave; row < a.m; row += nwaves) {                     // (wave-uniform: the shuffles below)
+        unsigned* h = a.hist + row * ROW_BINS;
+        int64_t cnt[PER], sum = 0;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int d = ROW_BINS - 1 - (lane * PER + i);
+            cnt[i] = (int64_t)h[d];
+            h[d] = 0;
+            sum += cnt[i];
+        }
+        int64_t incl = sum;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int64_t up = __shfl_up(incl, (unsigned)off);
+            if (lane >= off) incl += up;
+        }
+        const int64_t total = __shfl(incl, 63);
+        int64_t need = 0;
+        if (a.first) {
+            const int64_t w = a.want[row];
+            need = w < total ? w : total;
+        } else {
+            need = a.need[row];
+        }
+        // the lane and the bin in which the count from the top reaches `need` (need <= total: the bin chosen before holds it)
+        const int64_t before = incl - sum;
+        int digit = 0;
+        int64_t above = 0, eq = 0;
+        const bool here = need > 0 && before < need && need <= incl;
+        if (here) {
+            int64_t ahead = before;
+#pragma unroll
+            for (int i = 0; i < PER; ++i) {                                  // (exactly one bin of the lane holds it)
+                if (ahead < need && need <= ahead + cnt[i]) {
+                    digit = ROW_BINS - 1 - (lane * PER + i);
+                    above = ahead;
+                    eq = cnt[i];
+                }
+                ahead += cnt[i];
+            }
+        }
+        const unsigned long long who = __ballot(here);
+        const int src = who ? __ffsll((long long)who) - 1 : 0;
+        digit = __shfl(digit, src);
+        above = __shfl(above, src);
+        eq = __shfl(eq, src);
+        if (lane == 0) {
+            if (a.first && a.cands) a.cands[row] = total;
+            if (need == 0) {                                                 // no candidate, or none wanted
+                a.need[row] = 0;
+                a.greater[row] = 0;
+                a.equal[row] = 0;
+                if (a.first) a.prefix[row] = 0;
+                if (a.last) {
+                    const T none = (T)NAN;
+                    ((T*)a.thr)[row] = none;
+                }
+            } else {
+                const K key = (a.first ? (K)0 : (K)a.prefix[row] << a.digit_bits) | (K)digit;
+                a.prefix[row] = (unsigned long long)key;
+                a.need[row] = need - above;
+                a.greater[row] = (a.first ? 0 : a.greater[row]) + above;
+                a.equal[row] = eq;
+                if (a.last) {                                                // the score whose key this is; key(+0.0) -> +0.0
+                    const K sign = (K)1 << (ScoreKey<T>::BITS - 1);
+                    const K u = (key & sign) ? key ^ sign : ~key;
+                    T s;
+                    __builtin_memcpy(&s, &u, sizeof s);
+                    ((T*)a.thr)[row] = s;
+                }
+            }
+        }
+    }
 }
 
 }  // namespace skf

@@ -1,6 +1,6 @@
 // skf_complete.inc -- part of the one translation unit skf_api.hip (textually included there, inside its namespaces; not a
-// header of its own): the host side of the consuming operators skf_complete_topk / _entries / _ranks / _above / _digits (kernels:
-// skf_complete.h), their C entry points included.  Every rule of the front end is stated once and named after what it checks;
+// header of its own): the host side of the consuming operators skf_complete_topk / _entries / _ranks / _above / _digits /
+// _row_kth (kernels: skf_complete.h), their C entry points included.  Every rule of the front end is stated once and named after what it checks;
 // an entry point reads as its own order of them:
 //   SKF_E_INVALID refusals (shape, operands, lists that come in pairs) -> SKF_E_WORKSPACE refusals -> the first HIP call
 //   -> validation of the lists on the device -> the launches.
@@ -88,7 +88,7 @@ static void check_col_splits(const char* op, int32_t col_splits, OverMaxSplits o
     }
 }
 
-// the operands every pass's argument block begins with (TopkArgs / RankArgs / AboveArgs<T>, skf_complete.h),
+// the operands every pass's argument block begins with (TopkArgs / RankArgs / AboveArgs / DigitArgs / RowDigitArgs<T>, skf_complete.h),
 // tiles_per_split included
 template <typename T, template <typename> class Args>
 static void fill_operands(Args<T>& a, const Scored& s, int splits) {
@@ -264,6 +264,69 @@ static void launch_complete_digits(const Scored& s, uint64_t prefix, int prefix_
     check_launch("complete_digits");
 }
 
+// ---- the k-th best score of every row ------------------------------------------------------------------------------------------
+// Workspace: [0, 256) the flag word of the checks; the row histograms, uint32 [m][ROW_BINS]; one key prefix and one `need`
+// word per row.  It grows with m, never with m x n_cols.
+static size_t row_kth_workspace(int64_t m) {
+    return 256 + align_up((size_t)m * ROW_BINS * sizeof(unsigned), 256) + 2 * align_up((size_t)m * sizeof(int64_t), 256);
+}
+
+static void row_kth_check_query(int32_t dtype, int64_t m, int64_t n_cols, int32_t col_splits) {
+    check_shape("row_kth", dtype, m, n_cols);
+    check_col_splits("row_kth", col_splits, OVER_MAX_REFUSE);
+}
+
+// validate_exclusion and, under the same verdict word and read-back, want[r] >= 0.  m > 0.
+static void validate_row_kth(const Scored& s, const int64_t* want, int* flag_word, hipStream_t st) {
+    int64_t nnz = 0;
+    if (s.xptr) {
+        SKF_HIP(hipMemcpyAsync(&nnz, s.xptr + s.m, sizeof nnz, hipMemcpyDeviceToHost, st));
+        SKF_HIP(hipStreamSynchronize(st));
+    }
+    const int bad = nnz < 0 ? 1 : device_flag(flag_word, st, [&] {
+        if (s.xptr) {
+            hipLaunchKernelGGL(known_csr_check_kernel, dim3(wave_grid(s.m)), dim3(256), 0, st, s.xptr, (const int*)s.xidx, s.m, s.n_cols, nnz, flag_word);
+            check_launch("known_csr_check");
+        }
+        hipLaunchKernelGGL(row_want_check_kernel, dim3(elem_grid(s.m)), dim3(256), 0, st, want, s.m, flag_word);
+        check_launch("row_want_check");
+    });
+    if (bad == 1)
+        SKF_FAIL(SKF_E_INVALID, "skf_complete_row_kth: the exclusion lists are not canonical for %lld rows x %lld columns (indptr from 0 "
+                 "to the count, non-decreasing; indices in range and strictly ascending within a row)", (long long)s.m, (long long)s.n_cols);
+    if (bad) SKF_FAIL(SKF_E_INVALID, "skf_complete_row_kth: a want[r] is negative");
+}
+
+// every pass and every walk of the select, enqueued: no host round trip in between
+template <typename T>
+static void launch_complete_row_kth(const Scored& s, const int64_t* want, void* thr, int64_t* greater, int64_t* equal, int64_t* cands,
+                                    int splits, char* ws, hipStream_t st) {
+    constexpr int KEY_BITS = ScoreKey<T>::BITS;
+    RowDigitArgs<T> a;
+    fill_operands(a, s, splits);
+    a.hist = (unsigned*)(ws + 256);
+    unsigned long long* prefix = (unsigned long long*)(ws + 256 + align_up((size_t)s.m * ROW_BINS * sizeof(unsigned), 256));
+    int64_t* need = (int64_t*)((char*)prefix + align_up((size_t)s.m * sizeof(int64_t), 256));
+    a.prefix = prefix; a.need = need;
+    RowWalkArgs w = {a.hist, s.m, 0, 0, 0, want, prefix, need, greater, equal, cands, thr};
+    SKF_HIP(hipMemsetAsync(a.hist, 0, (size_t)s.m * ROW_BINS * sizeof(unsigned), st));
+    static DeviceOnce once;
+    allow_dynamic_lds(once, complete_row_digits_kernel<T>, (int)row_bins_bytes());
+    // no column: no candidate -- one walk over the empty histograms writes NaN / 0 to every row
+    for (int pbits = 0; pbits < KEY_BITS;) {
+        const int db = s.n_cols == 0 ? KEY_BITS : std::min(ROW_DIGIT_BITS, KEY_BITS - pbits);
+        if (s.n_cols > 0) {
+            a.prefix_bits = pbits; a.digit_bits = db;
+            hipLaunchKernelGGL((complete_row_digits_kernel<T>), dim3(cdiv(s.m, TOPK_BM), splits), dim3(TOPK_THREADS), row_bins_bytes(), st, a);
+            check_launch("complete_row_digits");
+        }
+        w.digit_bits = db; w.first = pbits == 0; w.last = pbits + db == KEY_BITS;
+        hipLaunchKernelGGL((complete_row_walk_kernel<T>), dim3(wave_grid(s.m)), dim3(256), 0, st, w);
+        check_launch("complete_row_walk");
+        pbits += db;
+    }
+}
+
 // ---- the C entry points --------------------------------------------------------------------------------------------------------
 // When there is nothing to score the three list operators differ, on purpose: top-k leaves at m == 0 (no row to write; with
 // n_cols == 0 it still validates and launches: every slot gets -1 / -inf), ranks leaves at n_targets == 0 before any list
@@ -434,6 +497,34 @@ int skf_complete_digits(int32_t dtype, const void* H, int64_t ldh, int64_t m, co
         if (n_cols == 0) return;                        // no column: no candidate
         by_dtype(dtype, [&](auto t) {
             launch_complete_digits<decltype(t)>(s, prefix, prefix_bits, digit_bits, hist, splits, st);
+        });
+    });
+}
+
+int skf_complete_row_kth_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int32_t col_splits, size_t* bytes) {
+    return guarded([&] {
+        if (!bytes) SKF_FAIL(SKF_E_INVALID, "null argument");
+        row_kth_check_query(dtype, m, n_cols, col_splits);
+        *bytes = row_kth_workspace(m);
+    });
+}
+
+int skf_complete_row_kth(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int32_t c,
+                         const int64_t* want, const int64_t* excl_indptr, const int32_t* excl_indices, void* out_thr,
+                         int64_t* out_greater, int64_t* out_equal, int64_t* out_cands, int32_t col_splits, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    return guarded([&] {
+        const Scored s = {dtype, H, ldh, m, Gc, ldg, n_cols, c, excl_indptr, excl_indices};
+        row_kth_check_query(dtype, m, n_cols, col_splits);
+        check_operands("row_kth", s);
+        if (!want || !out_thr || !out_greater || !out_equal) SKF_FAIL(SKF_E_INVALID, "skf_complete_row_kth: null argument");
+        const int splits = topk_col_splits(m, n_cols, col_splits);
+        check_workspace("row_kth", workspace, workspace_bytes, row_kth_workspace(m));
+        if (m == 0) return;
+        hipStream_t st = as_stream(stream);
+        validate_row_kth(s, want, (int*)workspace, st);
+        by_dtype(dtype, [&](auto t) {
+            launch_complete_row_kth<decltype(t)>(s, want, out_thr, out_greater, out_equal, out_cands, splits, (char*)workspace, st);
         });
     });
 }

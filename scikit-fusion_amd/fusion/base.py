@@ -554,6 +554,126 @@ class FusionFit(FusionBase):
             return out
         return self._per_run(one, run)
 
+    # ---- the k best columns of every row for any k: one selection per row on the device, never densified -------------------
+    def _row_preamble(self, relation, method, k, rows, exclude, block_rows):
+        self._check_raw_scores(relation, method)
+        n_i, n_j = self._relation_shape(relation)
+        rows = self._row_vector(rows, n_i)
+        want = np.asarray(k)
+        if want.dtype.kind not in 'iu':
+            raise DataFusionError("%s: k must be an integer or one integer per row, not %s" % (method, want.dtype))
+        if want.ndim > 1 or (want.ndim == 1 and want.shape != rows.shape):
+            raise DataFusionError("%s: k must be a scalar or one value per row (%d), not of shape %r"
+                                  % (method, rows.size, tuple(want.shape)))
+        if want.size and want.min() < 0:
+            raise DataFusionError("%s: k = %d is negative" % (method, int(want.min())))
+        scalar = want.ndim == 0
+        want = np.ascontiguousarray(np.broadcast_to(want.astype(np.int64), rows.shape))
+        lists = self._exclusion_lists(relation, exclude, (n_i, n_j))
+        return rows, want, scalar, n_j, lists, max(1, int(block_rows))
+
+    def complete_row_kth(self, relation, k, rows=None, exclude=None, run=None, dtype='f64', block_rows=8192):
+        """``(thresholds float64 [n], n_greater int64 [n], n_equal int64 [n])``: for each of ``rows`` (default: every row
+        object; otherwise an integer array in any order, a row listed twice is two rows) the ``k``-th largest score the model
+        gives to an admissible column of that row -- ``k`` a non-negative integer or one per row, of ANY size: the per-row
+        cut-off of Recall@100 / @1000, of R-precision (``k`` = a row's number of held-out pairs) and of candidate lists for a
+        second stage --, the number of columns that score above it and the number that equal it.  NaN scores and excluded
+        pairs (``exclude`` as for ``complete_topk``) are no candidates; with fewer than ``k`` candidates the threshold is
+        the row's smallest candidate score; with none, or ``k == 0``, it is NaN and both counts are 0.
+        ``complete_above(relation, thresholds, rows=rows, exclude=exclude)`` returns exactly ``n_greater + n_equal``
+        entries per row.  The device runs one radix select per row over the score tiles, ``block_rows`` rows at a time --
+        five passes in f32, ten in f64, no host round trip between them -- and nothing of size ``n_i x n_j`` is formed;
+        the result does not depend on ``block_rows``.  ``dtype`` and the refusal of post-processed relations as in
+        ``complete_above``.  ``n_run > 1`` and ``run=None``: a generator over the runs.  Extension of the reference API."""
+        rows, want, _, n_j, lists, step = self._row_preamble(relation, 'complete_row_kth', k, rows, exclude, block_rows)
+
+        def one(r):
+            G1, comp = self._completer(relation, r, dtype)
+            thr = np.empty(rows.size, dtype=np.float64)
+            greater, equal = np.empty(rows.size, dtype=np.int64), np.empty(rows.size, dtype=np.int64)
+            for b0 in range(0, rows.size, step):
+                blk = rows[b0:b0 + step]
+                thr[b0:b0 + step], greater[b0:b0 + step], equal[b0:b0 + step], _ = comp.row_kth(
+                    G1[blk], want[b0:b0 + step], exclude=lists(blk) if lists else None)
+            return thr, greater, equal
+        return self._per_run(one, run)
+
+    def complete_row_best(self, relation, k, rows=None, exclude=None, run=None, dtype='f64', block_rows=8192, ties='first',
+                          ordered=False, max_entries=2 ** 28):
+        """``scipy.sparse.csr_matrix`` of shape ``(len(rows), n_j)``, float64, sorted indices: for each of ``rows`` (default:
+        every row object; otherwise an integer array in any order, a row listed twice is two rows) the ``k`` columns the
+        model ranks highest, with their scores -- ``complete_topk`` without its limit of 64: ``k`` is a non-negative integer
+        or one per row, of any size (``k_r = 0``: an empty row).  Order, candidates and ``exclude`` as for
+        ``complete_topk``: higher score first, equal scores by lower column; NaN scores and excluded pairs never.
+        ``ties='first'``: exactly ``min(k_r, candidates_r)`` entries per row, the first of that order -- of the pairs equal
+        to the row's ``k_r``-th score the ones with the lowest columns; ``ties='all'``: every pair equal to the row's
+        ``k_r``-th score as well, i.e. ``complete_above`` at ``complete_row_kth``'s thresholds.  ``ordered=True``
+        (``ties='first'`` and a scalar ``k`` only): ``(indices int32 [n, k], scores float64 [n, k])`` in
+        ``complete_topk``'s layout instead, best first, slots without a candidate ``-1`` / ``-inf``; for ``k <= 64`` these are
+        ``complete_topk``'s arrays.  Per block of ``block_rows`` rows the device selects every row's threshold, counts and
+        fills with the thresholds left where they are; the surplus of a tie is trimmed on the host, block by block, and
+        nothing larger than one block's result is held beside the output.  ``sum(min(k_r, n_j)) > max_entries`` is refused
+        before anything runs, and so is a block whose ties push the result beyond it.  The bytes do not depend on
+        ``block_rows``.  ``dtype`` and the refusal of post-processed relations as in ``complete_above``.  ``n_run > 1`` and
+        ``run=None``: a generator over the runs.  Extension of the reference API."""
+        rows, want, scalar, n_j, lists, step = self._row_preamble(relation, 'complete_row_best', k, rows, exclude, block_rows)
+        import scipy.sparse
+        from .._engine import AboveLimit
+        if ties not in ('first', 'all'):
+            raise DataFusionError("ties must be 'first' or 'all', not %r" % (ties,))
+        if ordered not in (False, True):
+            raise DataFusionError("ordered must be True or False, not %r" % (ordered,))
+        if ordered and (ties != 'first' or not scalar):
+            raise DataFusionError("complete_row_best: ordered=True needs ties='first' and a scalar k")
+        limit = int(max_entries)
+        asked = int(np.minimum(want, n_j).sum())
+        if asked > limit:
+            raise DataFusionError("complete_row_best: %d entries asked for, max_entries = %d" % (asked, limit))
+        width = int(np.asarray(k)) if scalar else 0
+
+        def one(r):
+            G1, comp = self._completer(relation, r, dtype)
+            indptr = np.zeros(rows.size + 1, dtype=np.int64)
+            idx, val, found = [np.zeros(0, dtype=np.int32)], [np.zeros(0)], 0
+            for b0 in range(0, rows.size, step):
+                blk = rows[b0:b0 + step]
+                w = want[b0:b0 + step]
+                try:
+                    p, i, v, thr, greater, equal = comp.row_best(G1[blk], w, exclude=lists(blk) if lists else None,
+                                                                 max_entries=limit - found)
+                except AboveLimit as over:
+                    raise DataFusionError("complete_row_best: %d entries with the ties in the first %d rows, max_entries = %d "
+                                          "(lower k or raise max_entries)" % (found + over.found, b0 + blk.size, limit))
+                if ties == 'first':
+                    # of a row's pairs equal to its threshold the first min(k, greater + equal) - greater stay (columns ascend)
+                    keep_eq = np.minimum(w, greater + equal) - greater
+                    if (keep_eq < equal).any():
+                        row_of = np.repeat(np.arange(blk.size), np.diff(p))
+                        tied = v == thr[row_of]
+                        before = np.concatenate([[0], np.cumsum(tied)])     # tied pairs of the block ahead of each entry
+                        seen = before[1:] - before[p[:-1]][row_of]          # ... of the entry's own row, the entry included
+                        keep = ~tied | (seen <= keep_eq[row_of])
+                        i, v = i[keep], v[keep]
+                        p = np.concatenate([[0], np.cumsum(np.bincount(row_of[keep], minlength=blk.size))]).astype(np.int64)
+                indptr[b0 + 1:b0 + blk.size + 1] = found + p[1:]
+                found += int(p[-1])
+                idx.append(i)
+                val.append(v)
+            idx, val = np.concatenate(idx), np.concatenate(val)
+            if ordered:
+                oi = np.full((rows.size, width), -1, dtype=np.int32)
+                ov = np.full((rows.size, width), -np.inf)
+                row_of = np.repeat(np.arange(rows.size), np.diff(indptr))
+                o = np.lexsort((idx, -val, row_of))                     # by row, then value descending, then column ascending
+                slot = np.arange(idx.size) - indptr[row_of]             # (row_of[o] == row_of: the rows stay in place)
+                oi[row_of, slot] = idx[o]
+                ov[row_of, slot] = val[o]
+                return oi, ov
+            out = scipy.sparse.csr_matrix((val, idx, indptr), shape=(rows.size, n_j))
+            out.has_sorted_indices = True      # (ascending within a row by construction)
+            return out
+        return self._per_run(one, run)
+
 
 # ---- persistence of a fitted model (SURVEY.md 8 f4; the reference has none: its accessors base.py:35-56,
 # 169-189 are the only consumers of factors_ / backbones_) ----------------------------------------------
