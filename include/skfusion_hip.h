@@ -754,6 +754,34 @@ int skf_plan_init_column_means_workspace_bytes(const skf_plan* plan, int32_t typ
 int skf_plan_init_column_means(skf_plan* plan, int32_t type, int32_t n_views, const skf_init_view* views, void* G0, int64_t ld,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* ... and for relations with MISSING values.  The four functions above refuse a relation whose unstored entries are not zero;
+ * these take every form those take -- through the same launches, with the same bits -- and two more:
+ *   known entries   the lists of a masked relation of a SKF_DFMC plan, built from its mask (known_bound) or handed over as
+ *                   SKF_REL_KNOWN_CSR.  What lies beneath the unknown entries is the caller's constant: `fill` / fills[v].
+ *   rank one        SKF_REL_SPARSE_CSR | SKF_REL_FILL_RANK1: an entry not stored holds a_r b_c, the lists hold d = v - a_r b_c.
+ * With V (n x m) the oriented view, C_k the `take` columns of row k of sel, stored(r) the stored columns of line r in list order
+ * (a, b in the view's orientation), everything in f64, every sum in list order, one owner per output element, no atomics:
+ *   known entries   mean_rk = (sum over stored(r) in C_k of v_rc + (take - |stored(r) in C_k|) f) / take
+ *                   sq_c    = sum over the stored rows of v_rc^2 + (n - cnt_c) f^2
+ *   rank one        mean_rk = (sum over stored(r) in C_k of d_rc + a_r B_k) / take,  B_k = sum over C_k of b_c in the order of sel
+ *                   sq_c    = sum over the stored rows of (d_rc + a_r b_c)^2 + b_c^2 (|a|^2 - sum over the stored rows of a_r^2)
+ *   G0 = round(1e-5 + sum over the views, in the order given, of |mean|), the views over a fill and the products of the
+ * other forms adding into one f64 accumulator.  The epilogues are a product, rounded, then a sum, rounded (no fused
+ * multiply-add).  A view over a fill is one pass over its lists against m * c one-byte flags of the chosen columns -- a wave
+ * per line, a long line serially in its wave -- so scratch grows with m * c bytes + n * c * 8, never with n * m.
+ * Refused as above (SKF_E_INVALID, nothing written, no HIP call): a masked relation the plan keeps DENSE, SKF_OPT_OWNED_ROWS
+ * plans, row blocks and absent relations, SKF_TRANSFORM plans and fold-in lists, and a fill that is not finite (read for
+ * known-entry relations only; fills: host, one per view, may be NULL when no view is a known-entry relation).  Order of the
+ * checks, the flag word, ld, alignment and SKF_E_WORKSPACE: as above.  The norms of the two list forms need no scratch. */
+int skf_plan_relation_norms_filled_workspace_bytes(const skf_plan* plan, int32_t rel, size_t* bytes);
+int skf_plan_relation_norms_filled(skf_plan* plan, int32_t rel, double fill, double* row_sq, double* col_sq, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+int skf_plan_init_column_means_filled_workspace_bytes(const skf_plan* plan, int32_t type, int32_t n_views, const skf_init_view* views,
+                                                      size_t* bytes);
+int skf_plan_init_column_means_filled(skf_plan* plan, int32_t type, int32_t n_views, const skf_init_view* views,
+                                      const double* fills /* host, [n_views]; read for known-entry views only */, void* G0, int64_t ld,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* K = pinv(A) for symmetric A (n x n): f64 Jacobi eigen-decomposition + the singular-value
  * cut-off of scipy.linalg.pinv (reference _dfmf.py:232, _dfmc.py:307). */
 int skf_pinv_sym_workspace_bytes(int32_t n, size_t* bytes);
@@ -807,7 +835,8 @@ const char* skf_version(void);
  * skf_complete_ranks_workspace_bytes and skf_complete_ranks; skf_complete_above_workspace_bytes and skf_complete_above;
  * skf_plan_relation_norms, skf_plan_init_column_means, their workspace queries and skf_init_view, a struct of their own -- the
  * structs before it are those of version 4; skf_complete_digits_workspace_bytes and skf_complete_digits;
- * skf_complete_row_kth_workspace_bytes and skf_complete_row_kth). */
+ * skf_complete_row_kth_workspace_bytes and skf_complete_row_kth; skf_plan_relation_norms_filled,
+ * skf_plan_init_column_means_filled and their workspace queries). */
 #define SKF_ABI_VERSION 5
 int skf_abi_version(void);
 

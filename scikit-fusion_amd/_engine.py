@@ -150,9 +150,11 @@ class KnownEntries(object):
 class DeviceKnownEntries(object):
     """KnownEntries uploaded ONCE in the engine's element type (upload_graph: shared by the plans of concurrent restarts)."""
 
-    def __init__(self, indptr, indices, values, shape, known, unstored='unknown', by_col=False, row_fill=None, col_fill=None):
+    def __init__(self, indptr, indices, values, shape, known, unstored='unknown', by_col=False, row_fill=None, col_fill=None,
+                 fill=0.0):
         self.indptr, self.indices, self.values = indptr, indices, values
         self.row_fill, self.col_fill = row_fill, col_fill        # device vectors in the master type (SKF_REL_FILL_RANK1) or None
+        self.fill = float(fill)         # KnownEntries.fill: the constant beneath the unknown entries (the initialisers read it)
         self.shape, self.known = tuple(shape), int(known)
         self.unstored = unstored        # 'unknown': SKF_REL_KNOWN_CSR, 'zero': SKF_REL_SPARSE_CSR (fits) / SKF_REL_FOLD_CSR (fold-ins)
         self.by_col = bool(by_col)      # lists compressed along the column type (fold-ins whose target it is)
@@ -171,7 +173,8 @@ def upload_known_entries(ke, dtype, mem):
     fills = (None, None)
     if ke.row_fill is not None:         # the fill vectors in the master type, like the values beside them
         fills = tuple(keep(np.ascontiguousarray(v, dtype=nat.NP_DTYPE[code])) for v in (ke.row_fill, ke.col_fill))
-    return DeviceKnownEntries(keep(ke.indptr), keep(ke.indices), keep(vals), ke.shape, ke.known, ke.unstored, ke.by_col, *fills)
+    return DeviceKnownEntries(keep(ke.indptr), keep(ke.indices), keep(vals), ke.shape, ke.known, ke.unstored, ke.by_col, *fills,
+                              fill=ke.fill)
 
 
 def pack_mask(mask, mem):
@@ -564,6 +567,9 @@ class DevicePlan(object):
         rdesc = (nat.RelationDesc * max(len(relations), 1))()
         csr = []                                         # (relation, DeviceKnownEntries): skf_plan_set_known_entries
         self.local_rows = []                             # rows of every relation this plan holds (its block, or all of them)
+        # relations with missing values kept as lists: {relation: the constant beneath its unknown entries (KnownEntries.fill),
+        # or None for entries plus rank one} -- what the column-mean initialisers need beside the lists (the `_filled` entry points)
+        self.rel_over_fill = {}
         for k, rel in enumerate(relations):
             i, j, data, mask = rel[:4]
             block = rel[4] if len(rel) > 4 else None
@@ -607,6 +613,10 @@ class DevicePlan(object):
                     rdesc[k].flags |= nat.SKF_REL_FILL_RANK1
                 rdesc[k].known_bound = dev.known
                 csr.append((k, dev))
+                if dev.unstored != 'zero':
+                    self.rel_over_fill[k] = float(dev.fill)
+                elif dev.row_fill is not None:
+                    self.rel_over_fill[k] = None
                 continue
             rows_here = n_obj[i]
             if block is not None:
@@ -767,19 +777,28 @@ class DevicePlan(object):
             self._pending_uploads = None
 
     # -- the column-mean initialisers on the device (csrc/skf_init.h; reference _init.py:20-61) -----------
-    def relation_norms(self, rel):
+    def relation_norms(self, rel, fill=None):
         """(row_sq, col_sq): the float64 sums of SQUARES of every row and every column of relation `rel` as the plan
         stores it (skf_plan_relation_norms) -- what `random_c` ranks the columns of the relation's two views by.  Exact for
         data whose squares add up exactly; the same bits on every run.  SkfNativeError (SKF_E_INVALID) for a relation the
-        plan does not hold whole and unmasked."""
+        plan does not hold whole and unmasked.  A relation with missing values kept as lists -- its known entries over the
+        constant the plan remembers (KnownEntries.fill; `fill` overrides it, and names it for lists the plan built from a
+        mask), or entries plus rank one -- goes through skf_plan_relation_norms_filled: every line of the FILLED relation."""
         i, j = self.relations[rel][0], self.relations[rel][1]
         ni, nj = self.n_obj[self.index[i]], self.n_obj[self.index[j]]
         mem = self.rt.mem
         need = C.c_size_t()
-        self.rt.call('skf_plan_relation_norms_workspace_bytes', self.handle, rel, C.byref(need))
+        filled = fill is not None or rel in self.rel_over_fill
+        if fill is None:
+            fill = self.rel_over_fill.get(rel) or 0.0
+        self.rt.call('skf_plan_relation_norms_filled_workspace_bytes' if filled else 'skf_plan_relation_norms_workspace_bytes',
+                     self.handle, rel, C.byref(need))
         ws = mem.empty(max(need.value, 1))
         rs, cs = mem.empty(max(ni, 1) * 8), mem.empty(max(nj, 1) * 8)
-        self.rt.call('skf_plan_relation_norms', self.handle, rel, rs.ptr, cs.ptr, ws.ptr, need.value, self.stream)
+        if filled:
+            self.rt.call('skf_plan_relation_norms_filled', self.handle, rel, float(fill), rs.ptr, cs.ptr, ws.ptr, need.value, self.stream)
+        else:
+            self.rt.call('skf_plan_relation_norms', self.handle, rel, rs.ptr, cs.ptr, ws.ptr, need.value, self.stream)
         mem.synchronize()
         return mem.to_host(rs, (ni,), np.float64), mem.to_host(cs, (nj,), np.float64)
 
@@ -789,13 +808,22 @@ class DevicePlan(object):
         integer array c x take whose row k names the columns -- of the relation when `t` is its row type, of its transpose
         when `t` is its column type -- averaged into factor column k.  The indices of a row must be distinct (checked here:
         ValueError); their range is checked on the device (SkfNativeError, SKF_E_INVALID, nothing written).
+        A view may be (relation index, sel, fill): the constant beneath the unknown entries of a known-entry relation, where
+        the plan does not remember it (lists built from a mask) or to override it.  When a view is a relation with missing
+        values kept as lists, the call goes through skf_plan_init_column_means_filled (all views of the type in one call).
         sync=False: the caller synchronises before the plan is iterated."""
         k = self.index[t]
         n, c = self.n_obj[k], self.rank[k]
         mem = self.rt.mem
         desc = (nat.InitView * max(len(views), 1))()
+        fills = (C.c_double * max(len(views), 1))()
+        filled = False
         keep = []
-        for v, (rel, sel) in enumerate(views):
+        for v, view in enumerate(views):
+            rel, sel = view[0], view[1]
+            fill = view[2] if len(view) > 2 else None
+            filled = filled or fill is not None or rel in self.rel_over_fill
+            fills[v] = float(fill if fill is not None else (self.rel_over_fill.get(rel) or 0.0))
             s = np.ascontiguousarray(sel, dtype=np.int32)
             if s.ndim != 2 or s.shape[0] != c:
                 raise ValueError('view %d of %s: the selection has shape %r, expected (%d, take)' % (v, t, s.shape, c))
@@ -808,10 +836,15 @@ class DevicePlan(object):
             desc[v].rel, desc[v].take, desc[v].sel = int(rel), int(s.shape[1]), buf.ptr
         mem.synchronize()                               # the uploads (torch's stream) before the engine's launches
         need = C.c_size_t()
-        self.rt.call('skf_plan_init_column_means_workspace_bytes', self.handle, k, len(views), desc, C.byref(need))
+        self.rt.call('skf_plan_init_column_means_filled_workspace_bytes' if filled else 'skf_plan_init_column_means_workspace_bytes',
+                     self.handle, k, len(views), desc, C.byref(need))
         ws = mem.empty(need.value)
         g0 = mem.empty(max(n * c, 1) * np.dtype(self.np_dtype).itemsize)
-        self.rt.call('skf_plan_init_column_means', self.handle, k, len(views), desc, g0.ptr, c, ws.ptr, need.value, self.stream)
+        if filled:
+            self.rt.call('skf_plan_init_column_means_filled', self.handle, k, len(views), desc, fills, g0.ptr, c, ws.ptr, need.value,
+                         self.stream)
+        else:
+            self.rt.call('skf_plan_init_column_means', self.handle, k, len(views), desc, g0.ptr, c, ws.ptr, need.value, self.stream)
         self.rt.call('skf_set_factor', self.handle, k, g0.ptr, c, self.stream)
         keep += [ws, g0]
         self._pending_init = getattr(self, '_pending_init', None) or []

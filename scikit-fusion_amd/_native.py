@@ -175,6 +175,11 @@ SIGNATURES = {
     'skf_plan_relation_norms': (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
     'skf_plan_init_column_means_workspace_bytes': (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(InitView), C.POINTER(C.c_size_t)]),
     'skf_plan_init_column_means': (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(InitView), _P, C.c_int64, _P, C.c_size_t, _P]),
+    'skf_plan_relation_norms_filled_workspace_bytes': (C.c_int, [_P, C.c_int32, C.POINTER(C.c_size_t)]),
+    'skf_plan_relation_norms_filled': (C.c_int, [_P, C.c_int32, C.c_double, _P, _P, _P, C.c_size_t, _P]),
+    'skf_plan_init_column_means_filled_workspace_bytes': (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(InitView), C.POINTER(C.c_size_t)]),
+    'skf_plan_init_column_means_filled': (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(InitView), C.POINTER(C.c_double), _P, C.c_int64, _P,
+                                                    C.c_size_t, _P]),
     'skf_pinv_sym_workspace_bytes': (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
     'skf_pinv_sym': (C.c_int, [C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_size_t, _P]),
     'skf_fill_uniform': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, C.c_int64, C.c_uint64,

@@ -11,20 +11,29 @@
 // 0/1 relation that SKF_BF16 keeps as lists of its ones BESIDE its bitmap is covered through the bitmap (its list kernels read
 // bf16 factor rows of the widths 64 / 128 / 256 only).  Refused: everything the plan does not hold whole -- SKF_OPT_OWNED_ROWS
 // plans, row blocks -- and SKF_TRANSFORM plans.
+//
+// The `_filled` entry points take the same forms the same way (same launches, same bits) and, beside them, the two forms of a
+// relation with MISSING values (`filled`; kernels and statement: skf_init.h): INIT_KNOWN, the known-entry lists of a masked
+// relation (from a mask or from the caller's CSR) over the constant the caller passes, and INIT_RANK1, entries plus rank one
+// (SKF_REL_SPARSE_CSR | SKF_REL_FILL_RANK1).  A masked relation the plan keeps DENSE stays refused.
 
-enum InitForm { INIT_DENSE, INIT_BITS, INIT_LISTS };
+enum InitForm { INIT_DENSE, INIT_BITS, INIT_LISTS, INIT_KNOWN, INIT_RANK1 };
+static bool over_fill(InitForm f) { return f == INIT_KNOWN || f == INIT_RANK1; }
 
 // the form of relation `rel` for the two operators here, or the refusal
-static InitForm init_form(const skf_plan* p, int32_t rel, const char* op) {
+static InitForm init_form(const skf_plan* p, int32_t rel, const char* op, bool filled = false) {
     if (rel < 0 || rel >= (int)p->rels.size()) SKF_FAIL(SKF_E_INVALID, "%s: relation index %d out of range", op, rel);
     const RelState& r = p->rels[rel];
     if (p->variant == SKF_TRANSFORM) SKF_FAIL(SKF_E_INVALID, "%s: not for SKF_TRANSFORM plans", op);
     if (p->owned || p->sliced || r.absent || r.nr != p->types[r.row].n)
         SKF_FAIL(SKF_E_INVALID, "%s: relation %d is not held whole here (SKF_OPT_OWNED_ROWS plans and row blocks initialise on the host)", op, rel);
-    if (r.masked || r.kn || r.kn_csr || r.mask) SKF_FAIL(SKF_E_INVALID, "%s: relation %d is masked / given as its known entries", op, rel);
-    if (r.fill) SKF_FAIL(SKF_E_INVALID, "%s: relation %d carries a rank-one fill (SKF_REL_FILL_RANK1)", op, rel);
+    const bool known_lists = filled && r.kn && !r.sp0;
+    if (!known_lists && (r.masked || r.kn || r.kn_csr || r.mask))
+        SKF_FAIL(SKF_E_INVALID, filled ? "%s: relation %d is masked and kept dense" : "%s: relation %d is masked / given as its known entries", op, rel);
+    if (r.fill && !filled) SKF_FAIL(SKF_E_INVALID, "%s: relation %d carries a rank-one fill (SKF_REL_FILL_RANK1)", op, rel);
     if (r.fold) SKF_FAIL(SKF_E_INVALID, "%s: relation %d is a fold-in list", op, rel);
-    if (r.sp0) return INIT_LISTS;
+    if (known_lists) return INIT_KNOWN;
+    if (r.sp0) return r.fill ? INIT_RANK1 : INIT_LISTS;
     if (p->bf16 && r.binary) return INIT_BITS;
     return INIT_DENSE;
 }
@@ -66,6 +75,23 @@ static void launch_norms_lists(const RelState& r, int64_t rows, int64_t cols, do
     check_launch("norms_lists");
 }
 
+// The lines of a relation kept as lists over a fill (INIT_KNOWN: the constant `fill`; INIT_RANK1: a b^T): rows from the row
+// lists, columns from the column lists, one thread per line (norms_filled_kernel)
+template <typename TM>
+static void launch_norms_filled(const RelState& r, InitForm form, double fill, int64_t rows, int64_t cols, double* row_sq, double* col_sq,
+                                hipStream_t st) {
+    const bool rank1 = form == INIT_RANK1;
+    const TM* a = rank1 ? (const TM*)r.Fa.ptr : nullptr;
+    const TM* b = rank1 ? (const TM*)r.Fb.ptr : nullptr;
+    if (row_sq)
+        hipLaunchKernelGGL((norms_filled_kernel<TM>), dim3(cdiv(rows, 256)), dim3(256), 0, st, (const int64_t*)r.KrPtr.ptr, r.kn_pc,
+                           (const int*)r.KrIdx.ptr, (const TM*)r.KrVal.ptr, rows, cols, fill, a, b, r.fill_bb, row_sq);
+    if (col_sq)
+        hipLaunchKernelGGL((norms_filled_kernel<TM>), dim3(cdiv(cols, 256)), dim3(256), 0, st, (const int64_t*)r.KcPtr.ptr, r.kn_pr,
+                           (const int*)r.KcIdx.ptr, (const TM*)r.KcVal.ptr, cols, rows, fill, b, a, r.fill_aa, col_sq);
+    check_launch("norms_filled");
+}
+
 // ---- the initialiser -----------------------------------------------------------------------------------------------------------
 // One oriented view of the call: V = R (the type is the relation's row type) or R^T (its column type), n x m
 struct InitView {
@@ -78,25 +104,30 @@ struct InitView {
     bool w_bf16;            // W in the bf16 Bt[c][ldw] layout (dense / bitmap relations of SKF_BF16), else [m][c] in the master type
     int64_t ldw;
     size_t w_bytes, part_bytes;
+    double fill;            // INIT_KNOWN: the constant beneath the unknown entries
 };
 
 // Scratch of skf_plan_init_column_means: [0, 256) the flag word of the index check; W (the largest of the views); the f64
 // accumulator n x c; the product of one view n x c in the master type; split-K slices / outputs of list parts (the largest)
-struct InitLayout { size_t w, acc, x, part, part_bytes, total; };
+// (views over a fill: W is their flags, one byte per (view column, factor column); they need no product, and the rank-one
+// form the c column sums B at the end)
+struct InitLayout { size_t w, acc, x, part, part_bytes, bk, total; };
 
 static void init_views(const skf_plan* p, int32_t type, int32_t n_views, const skf_init_view* views, bool need_sel,
-                       std::vector<InitView>& out, InitLayout& l) {
-    const char* op = "skf_plan_init_column_means";
+                       std::vector<InitView>& out, InitLayout& l, bool filled = false, const double* fills = nullptr) {
+    const char* op = filled ? "skf_plan_init_column_means_filled" : "skf_plan_init_column_means";
     if (!p) SKF_FAIL(SKF_E_INVALID, "null plan");
     if (type < 0 || type >= (int)p->types.size()) SKF_FAIL(SKF_E_INVALID, "%s: type index %d out of range", op, type);
     if (n_views < 1 || !views) SKF_FAIL(SKF_E_INVALID, "%s: no views (a type that no relation touches has no column means)", op);
     const TypeState& t = p->types[type];
     const int c = t.c;
     size_t w_max = 0, part_max = 0;
+    bool products = false, colsums = false;
     out.clear();
     for (int v = 0; v < n_views; ++v) {
         InitView iv;
-        iv.form = init_form(p, views[v].rel, op);
+        iv.form = init_form(p, views[v].rel, op, filled);
+        iv.fill = 0.0;
         iv.r = &p->rels[views[v].rel];
         if (iv.r->row != type && iv.r->col != type) SKF_FAIL(SKF_E_INVALID, "%s: relation %d does not touch type %d", op, views[v].rel, type);
         iv.transposed = iv.r->col == type;
@@ -106,8 +137,18 @@ static void init_views(const skf_plan* p, int32_t type, int32_t n_views, const s
         // (fewer than 5 columns: the reference takes the mean of nothing, NaN; the host initialiser keeps that behaviour)
         if (iv.take < 1 || iv.take > iv.m) SKF_FAIL(SKF_E_INVALID, "%s: view %d averages take = %d of %lld columns", op, v, iv.take, (long long)iv.m);
         if (need_sel && !iv.sel) SKF_FAIL(SKF_E_INVALID, "%s: view %d has no index array", op, v);
-        iv.w_bf16 = p->bf16 && iv.form != INIT_LISTS;
-        if (iv.w_bf16) {
+        iv.w_bf16 = p->bf16 && iv.form != INIT_LISTS && !over_fill(iv.form);
+        if (over_fill(iv.form)) {
+            if (iv.form == INIT_KNOWN && need_sel) {
+                if (!fills) SKF_FAIL(SKF_E_INVALID, "%s: view %d is a known-entry relation and no fills are given", op, v);
+                if (!std::isfinite(fills[v])) SKF_FAIL(SKF_E_INVALID, "%s: the fill of view %d is not finite", op, v);
+                iv.fill = fills[v];
+            }
+            iv.ldw = c;
+            iv.w_bytes = (size_t)iv.m * c;
+            iv.part_bytes = 0;
+            colsums = colsums || iv.form == INIT_RANK1;
+        } else if (iv.w_bf16) {
             // the inner dimension of the contraction as the relation is kept: Q = R^T .. runs over pad64(rows), P = R .. over pad64(columns)
             iv.ldw = iv.transposed ? iv.r->kq : iv.r->ldrb;
             iv.w_bytes = (size_t)c * iv.ldw * 2;
@@ -122,6 +163,7 @@ static void init_views(const skf_plan* p, int32_t type, int32_t n_views, const s
                 iv.part_bytes = kind_part_bytes(p, kind_relation(p), t.n, c, iv.m);
             }
         }
+        products = products || !over_fill(iv.form);
         w_max = std::max(w_max, iv.w_bytes);
         part_max = std::max(part_max, iv.part_bytes);
         out.push_back(iv);
@@ -130,9 +172,46 @@ static void init_views(const skf_plan* p, int32_t type, int32_t n_views, const s
     l.w = 256;
     l.acc = l.w + align_up(w_max, 256);
     l.x = l.acc + align_up((size_t)t.n * c * 8, 256);
-    l.part = l.x + align_up((size_t)t.n * c * p->esz, 256);
+    l.part = l.x + (products ? align_up((size_t)t.n * c * p->esz, 256) : 0);
     l.part_bytes = part_max;
-    l.total = l.part + align_up(part_max, 256);
+    l.bk = l.part + align_up(part_max, 256);
+    l.total = l.bk + (colsums ? align_up((size_t)c * 8, 256) : 0);
+}
+
+// acc += |mean| of one view kept as lists over a fill: the flags of the chosen columns, the column sums of the fill vector
+// (rank one), one pass over the view's lists with the epilogue in it
+template <typename TM, int NJ>
+static void launch_list_means(const TypeState& t, const InitView& iv, const uint8_t* flags, const double* B, double* acc, hipStream_t st) {
+    const RelState& r = *iv.r;
+    const Slot& sp = iv.transposed ? r.KcPtr : r.KrPtr;
+    const Slot& si = iv.transposed ? r.KcIdx : r.KrIdx;
+    const Slot& sv = iv.transposed ? r.KcVal : r.KrVal;
+    const TM* own = iv.form == INIT_RANK1 ? (const TM*)(iv.transposed ? r.Fb.ptr : r.Fa.ptr) : nullptr;
+    hipLaunchKernelGGL((init_list_means_kernel<TM, NJ>), dim3(cdiv(t.n, 4)), dim3(256), 0, st, (const int64_t*)sp.ptr,
+                       iv.transposed ? r.kn_pr : r.kn_pc, (const int*)si.ptr, (const TM*)sv.ptr, flags, t.n, t.c, iv.take, iv.fill, own,
+                       iv.form == INIT_RANK1 ? B : (const double*)nullptr, acc);
+    check_launch("init_list_means");
+}
+
+template <typename TM>
+static void init_over_fill(const TypeState& t, const InitView& iv, uint8_t* flags, double* B, double* acc, hipStream_t st) {
+    const RelState& r = *iv.r;
+    SKF_HIP(hipMemsetAsync(flags, 0, iv.w_bytes, st));
+    hipLaunchKernelGGL((init_sel_scatter_kernel<uint8_t>), dim3(elem_grid((int64_t)t.c * iv.take)), dim3(256), 0, st, iv.sel, t.c, iv.take,
+                       flags, (int64_t)t.c, (int64_t)1, (uint8_t)1);
+    check_launch("init_sel_scatter");
+    if (iv.form == INIT_RANK1) {
+        hipLaunchKernelGGL((init_fill_colsum_kernel<TM>), dim3(cdiv(t.c, 256)), dim3(256), 0, st, iv.sel, t.c, iv.take,
+                           (const TM*)(iv.transposed ? r.Fa.ptr : r.Fb.ptr), B);
+        check_launch("init_fill_colsum");
+    }
+    const int nj = (t.c + 63) / 64;
+    if (nj <= 1) launch_list_means<TM, 1>(t, iv, flags, B, acc, st);
+    else if (nj <= 2) launch_list_means<TM, 2>(t, iv, flags, B, acc, st);
+    else if (nj <= 4) launch_list_means<TM, 4>(t, iv, flags, B, acc, st);
+    else if (nj <= 8) launch_list_means<TM, 8>(t, iv, flags, B, acc, st);
+    else if (nj <= 16) launch_list_means<TM, 16>(t, iv, flags, B, acc, st);
+    else SKF_FAIL(SKF_E_INVALID, "skf_plan_init_column_means_filled: rank %d above 1024", t.c);
 }
 
 // x = V W for one view, through the contraction the plan runs for this relation and orientation (relation_gemm)
@@ -155,6 +234,10 @@ static void run_init_column_means(skf_plan* p, const TypeState& t, const std::ve
     check_launch("init_acc_start");
     for (const InitView& iv : vs) {
         void* W = ws + l.w;
+        if (over_fill(iv.form)) {
+            init_over_fill<T>(t, iv, (uint8_t*)W, (double*)(ws + l.bk), acc, st);
+            continue;
+        }
         SKF_HIP(hipMemsetAsync(W, 0, iv.w_bytes, st));
         const int sgrid = elem_grid((int64_t)t.c * iv.take);
         if (iv.w_bf16)
@@ -173,48 +256,102 @@ static void run_init_column_means(skf_plan* p, const TypeState& t, const std::ve
 }
 
 // ---- the C entry points --------------------------------------------------------------------------------------------------------
+// (the bodies of the entry points; `filled`: the _filled ones, which take the forms over a fill as well)
+static void norms_workspace_bytes(const skf_plan* p, int32_t rel, size_t* bytes, bool filled) {
+    if (!p || !bytes) SKF_FAIL(SKF_E_INVALID, "null argument");
+    const InitForm form = init_form(p, rel, filled ? "skf_plan_relation_norms_filled" : "skf_plan_relation_norms", filled);
+    const RelState& r = p->rels[rel];
+    *bytes = form == INIT_LISTS || over_fill(form) ? 0 : norm_layout(r.nr, p->types[r.col].n).total;
+}
+
+static void relation_norms(skf_plan* p, int32_t rel, bool filled, double fill, double* row_sq, double* col_sq, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    if (!p) SKF_FAIL(SKF_E_INVALID, "null plan");
+    const InitForm form = init_form(p, rel, filled ? "skf_plan_relation_norms_filled" : "skf_plan_relation_norms", filled);
+    if (form == INIT_KNOWN && !std::isfinite(fill)) SKF_FAIL(SKF_E_INVALID, "skf_plan_relation_norms_filled: the fill is not finite");
+    const RelState& r = p->rels[rel];
+    const int64_t rows = r.nr, cols = p->types[r.col].n;
+    const NormLayout l = norm_layout(rows, cols);
+    if (l.cblocks > 65535) SKF_FAIL(SKF_E_INVALID, "skf_plan_relation_norms: more than 65535 * 256 columns");
+    if (!p->bound) SKF_FAIL(SKF_E_STATE, "workspace not bound");
+    if (form != INIT_LISTS && !over_fill(form)) {
+        if (!workspace || workspace_bytes < l.total)
+            SKF_FAIL(SKF_E_WORKSPACE, "skf_plan_relation_norms: workspace %zu B < required %zu B (or null)", workspace ? workspace_bytes : (size_t)0, l.total);
+        if (((uintptr_t)workspace & 255) != 0) SKF_FAIL(SKF_E_WORKSPACE, "skf_plan_relation_norms: workspace must be 256-byte aligned");
+    }
+    if ((!row_sq && !col_sq) || rows == 0 || cols == 0) return;
+    hipStream_t st = as_stream(stream);
+    char* ws = (char*)workspace;
+    if (over_fill(form)) {
+        if (p->f64) launch_norms_filled<double>(r, form, fill, rows, cols, row_sq, col_sq, st);
+        else launch_norms_filled<float>(r, form, fill, rows, cols, row_sq, col_sq, st);
+    } else if (form == INIT_LISTS) {
+        if (p->f64) launch_norms_lists<double>(r, rows, cols, row_sq, col_sq, st);
+        else launch_norms_lists<float>(r, rows, cols, row_sq, col_sq, st);
+    } else if (form == INIT_BITS) {
+        launch_norms_tile(NormBits{(const uint8_t*)r.Bb.ptr, r.ldbb}, rows, cols, l, ws, row_sq, col_sq, st);
+    } else if (p->bf16) {
+        launch_norms_tile(NormDense<uint16_t>{(const uint16_t*)r.Rb.ptr, r.ldrb}, rows, cols, l, ws, row_sq, col_sq, st);
+    } else if (p->f64) {
+        launch_norms_tile(NormDense<double>{(const double*)r.R, r.ldr}, rows, cols, l, ws, row_sq, col_sq, st);
+    } else {
+        launch_norms_tile(NormDense<float>{(const float*)r.R, r.ldr}, rows, cols, l, ws, row_sq, col_sq, st);
+    }
+}
+
+static void init_column_means(skf_plan* p, int32_t type, int32_t n_views, const skf_init_view* views, bool filled, const double* fills,
+                              void* G0, int64_t ld, void* workspace, size_t workspace_bytes, void* stream) {
+    std::vector<InitView> vs;
+    InitLayout l;
+    init_views(p, type, n_views, views, true, vs, l, filled, fills);
+    const TypeState& t = p->types[type];
+    if (!G0) SKF_FAIL(SKF_E_INVALID, "skf_plan_init_column_means: null argument");
+    if (ld < t.c) SKF_FAIL(SKF_E_INVALID, "skf_plan_init_column_means: ld %lld < rank %d", (long long)ld, t.c);
+    if (!p->bound) SKF_FAIL(SKF_E_STATE, "workspace not bound");
+    if (!workspace || workspace_bytes < l.total)
+        SKF_FAIL(SKF_E_WORKSPACE, "skf_plan_init_column_means: workspace %zu B < required %zu B (or null)", workspace ? workspace_bytes : (size_t)0, l.total);
+    if (((uintptr_t)workspace & 255) != 0) SKF_FAIL(SKF_E_WORKSPACE, "skf_plan_init_column_means: workspace must be 256-byte aligned");
+    if (t.n == 0) return;
+    hipStream_t st = as_stream(stream);
+    // every index of every view against its view's columns, before anything is written; the flag word is the first of the
+    // scratch and gets its old content back when the call is refused
+    int keep = 0;
+    int* flag = (int*)workspace;
+    SKF_HIP(hipMemcpyAsync(&keep, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    const int bad = device_flag(flag, st, [&] {
+        for (const InitView& iv : vs) {
+            const int64_t total = (int64_t)t.c * iv.take;
+            hipLaunchKernelGGL(init_sel_check_kernel, dim3(elem_grid(total)), dim3(256), 0, st, iv.sel, total, iv.m, flag);
+        }
+        check_launch("init_sel_check");
+    });
+    if (bad) {
+        SKF_HIP(hipMemcpyAsync(flag, &keep, sizeof(int), hipMemcpyHostToDevice, st));
+        SKF_HIP(hipStreamSynchronize(st));
+        SKF_FAIL(SKF_E_INVALID, "skf_plan_init_column_means: an index names a column outside its view");
+    }
+    if (p->f64) run_init_column_means<double>(p, t, vs, l, (char*)workspace, G0, ld, st);
+    else run_init_column_means<float>(p, t, vs, l, (char*)workspace, G0, ld, st);
+}
+
 extern "C" {
 
 int skf_plan_relation_norms_workspace_bytes(const skf_plan* p, int32_t rel, size_t* bytes) {
-    return guarded([&] {
-        if (!p || !bytes) SKF_FAIL(SKF_E_INVALID, "null argument");
-        const InitForm form = init_form(p, rel, "skf_plan_relation_norms");
-        const RelState& r = p->rels[rel];
-        *bytes = form == INIT_LISTS ? 0 : norm_layout(r.nr, p->types[r.col].n).total;
-    });
+    return guarded([&] { norms_workspace_bytes(p, rel, bytes, false); });
 }
 
 int skf_plan_relation_norms(skf_plan* p, int32_t rel, double* row_sq, double* col_sq, void* workspace, size_t workspace_bytes,
                             void* stream) {
-    return guarded([&] {
-        if (!p) SKF_FAIL(SKF_E_INVALID, "null plan");
-        const InitForm form = init_form(p, rel, "skf_plan_relation_norms");
-        const RelState& r = p->rels[rel];
-        const int64_t rows = r.nr, cols = p->types[r.col].n;
-        const NormLayout l = norm_layout(rows, cols);
-        if (l.cblocks > 65535) SKF_FAIL(SKF_E_INVALID, "skf_plan_relation_norms: more than 65535 * 256 columns");
-        if (!p->bound) SKF_FAIL(SKF_E_STATE, "workspace not bound");
-        if (form != INIT_LISTS) {
-            if (!workspace || workspace_bytes < l.total)
-                SKF_FAIL(SKF_E_WORKSPACE, "skf_plan_relation_norms: workspace %zu B < required %zu B (or null)", workspace ? workspace_bytes : (size_t)0, l.total);
-            if (((uintptr_t)workspace & 255) != 0) SKF_FAIL(SKF_E_WORKSPACE, "skf_plan_relation_norms: workspace must be 256-byte aligned");
-        }
-        if ((!row_sq && !col_sq) || rows == 0 || cols == 0) return;
-        hipStream_t st = as_stream(stream);
-        char* ws = (char*)workspace;
-        if (form == INIT_LISTS) {
-            if (p->f64) launch_norms_lists<double>(r, rows, cols, row_sq, col_sq, st);
-            else launch_norms_lists<float>(r, rows, cols, row_sq, col_sq, st);
-        } else if (form == INIT_BITS) {
-            launch_norms_tile(NormBits{(const uint8_t*)r.Bb.ptr, r.ldbb}, rows, cols, l, ws, row_sq, col_sq, st);
-        } else if (p->bf16) {
-            launch_norms_tile(NormDense<uint16_t>{(const uint16_t*)r.Rb.ptr, r.ldrb}, rows, cols, l, ws, row_sq, col_sq, st);
-        } else if (p->f64) {
-            launch_norms_tile(NormDense<double>{(const double*)r.R, r.ldr}, rows, cols, l, ws, row_sq, col_sq, st);
-        } else {
-            launch_norms_tile(NormDense<float>{(const float*)r.R, r.ldr}, rows, cols, l, ws, row_sq, col_sq, st);
-        }
-    });
+    return guarded([&] { relation_norms(p, rel, false, 0.0, row_sq, col_sq, workspace, workspace_bytes, stream); });
+}
+
+int skf_plan_relation_norms_filled_workspace_bytes(const skf_plan* p, int32_t rel, size_t* bytes) {
+    return guarded([&] { norms_workspace_bytes(p, rel, bytes, true); });
+}
+
+int skf_plan_relation_norms_filled(skf_plan* p, int32_t rel, double fill, double* row_sq, double* col_sq, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    return guarded([&] { relation_norms(p, rel, true, fill, row_sq, col_sq, workspace, workspace_bytes, stream); });
 }
 
 int skf_plan_init_column_means_workspace_bytes(const skf_plan* p, int32_t type, int32_t n_views, const skf_init_view* views, size_t* bytes) {
@@ -229,39 +366,23 @@ int skf_plan_init_column_means_workspace_bytes(const skf_plan* p, int32_t type, 
 
 int skf_plan_init_column_means(skf_plan* p, int32_t type, int32_t n_views, const skf_init_view* views, void* G0, int64_t ld,
                                void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded([&] { init_column_means(p, type, n_views, views, false, nullptr, G0, ld, workspace, workspace_bytes, stream); });
+}
+
+int skf_plan_init_column_means_filled_workspace_bytes(const skf_plan* p, int32_t type, int32_t n_views, const skf_init_view* views,
+                                                      size_t* bytes) {
     return guarded([&] {
+        if (!bytes) SKF_FAIL(SKF_E_INVALID, "null argument");
         std::vector<InitView> vs;
         InitLayout l;
-        init_views(p, type, n_views, views, true, vs, l);
-        const TypeState& t = p->types[type];
-        if (!G0) SKF_FAIL(SKF_E_INVALID, "skf_plan_init_column_means: null argument");
-        if (ld < t.c) SKF_FAIL(SKF_E_INVALID, "skf_plan_init_column_means: ld %lld < rank %d", (long long)ld, t.c);
-        if (!p->bound) SKF_FAIL(SKF_E_STATE, "workspace not bound");
-        if (!workspace || workspace_bytes < l.total)
-            SKF_FAIL(SKF_E_WORKSPACE, "skf_plan_init_column_means: workspace %zu B < required %zu B (or null)", workspace ? workspace_bytes : (size_t)0, l.total);
-        if (((uintptr_t)workspace & 255) != 0) SKF_FAIL(SKF_E_WORKSPACE, "skf_plan_init_column_means: workspace must be 256-byte aligned");
-        if (t.n == 0) return;
-        hipStream_t st = as_stream(stream);
-        // every index of every view against its view's columns, before anything is written; the flag word is the first of the
-        // scratch and gets its old content back when the call is refused
-        int keep = 0;
-        int* flag = (int*)workspace;
-        SKF_HIP(hipMemcpyAsync(&keep, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-        const int bad = device_flag(flag, st, [&] {
-            for (const InitView& iv : vs) {
-                const int64_t total = (int64_t)t.c * iv.take;
-                hipLaunchKernelGGL(init_sel_check_kernel, dim3(elem_grid(total)), dim3(256), 0, st, iv.sel, total, iv.m, flag);
-            }
-            check_launch("init_sel_check");
-        });
-        if (bad) {
-            SKF_HIP(hipMemcpyAsync(flag, &keep, sizeof(int), hipMemcpyHostToDevice, st));
-            SKF_HIP(hipStreamSynchronize(st));
-            SKF_FAIL(SKF_E_INVALID, "skf_plan_init_column_means: an index names a column outside its view");
-        }
-        if (p->f64) run_init_column_means<double>(p, t, vs, l, (char*)workspace, G0, ld, st);
-        else run_init_column_means<float>(p, t, vs, l, (char*)workspace, G0, ld, st);
+        init_views(p, type, n_views, views, false, vs, l, true);
+        *bytes = l.total;
     });
+}
+
+int skf_plan_init_column_means_filled(skf_plan* p, int32_t type, int32_t n_views, const skf_init_view* views, const double* fills, void* G0,
+                                      int64_t ld, void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded([&] { init_column_means(p, type, n_views, views, true, fills, G0, ld, workspace, workspace_bytes, stream); });
 }
 
 }  // extern "C"

@@ -24,6 +24,8 @@ class Dfmc(FusionFit):
     ``filled_entries_apply``); one whose unstored entries are zero on its stored entries (``sparse_relations``, see ``Dfmf``); a
     ``scipy.sparse`` constraint as its entries (``sparse_constraints``, see ``Dfmf``)."""
 
+    _variant = 'dfmc'
+
     def __init__(self, max_iter=100, init_type='random_c', n_run=1, stopping=None,
                  stopping_system=None, verbose=0, compute_err=False, callback=None,
                  random_state=None, n_jobs=1, dtype='f64', shard='runs', device_fill=False, sparse_relations=None,

@@ -234,12 +234,49 @@ def _first_relations(fusion_graph):
                 break
 
 
-def init_device_work(fusion_graph):
-    """What the host initialiser gathers: sum over the oriented views of n_rows * take * c elements."""
+INIT_KNOWN_MIN = 1 << 33    # init_device=None, relations with missing values kept as lists: the work of the host initialiser
+                            # (`init_known_work`: entries walked + cells of the column buffers) from which the device
+                            # initialiser runs -- about two minutes of `_init._KnownView` at the 7.1e7 entries/s measured for
+                            # its row means, both orientations averaged (profiles/init_known.txt; the column buffers fill
+                            # faster); every test, tool default and bench.py path stays below it
+
+
+def _kept_as_lists(rel, fuser):
+    """Whether a first relation with missing values (``unstored='unknown'``) enters this fit as lists -- its known entries
+    (Dfmc) or entries plus rank one --, as `graph_matrices` will decide: the host initialiser then reads it through
+    `_init._KnownView`, and gathers nothing."""
+    if not rel.is_known_entries():
+        return False
+    variant = getattr(fuser, '_variant', 'dfmf')
+    if variant == 'dfmc' and known_entries_apply(rel, fuser.shard in ('runs', 'owned')):
+        return True
+    return filled_entries_apply(rel, getattr(fuser, 'sparse_relations', None), fuser.shard, variant)
+
+
+def init_device_work(fusion_graph, fuser=None):
+    """What the host initialiser gathers: sum over the oriented views of n_rows * take * c elements (relations it reads
+    as matrices; with `fuser`: not those `init_known_work` counts)."""
     total = 0
     for rel in _first_relations(fusion_graph):
+        if fuser is not None and _kept_as_lists(rel, fuser):
+            continue
         n_r, n_c = rel.data.shape
         total += n_r * int(.2 * n_c) * int(rel.row_type.rank) + n_c * int(.2 * n_r) * int(rel.col_type.rank)
+    return total
+
+
+def init_known_work(fusion_graph, fuser):
+    """What the host initialiser walks for the relations with missing values kept as lists (`_init._KnownView`): per
+    oriented view one pass over all stored entries per factor column, c * nnz, and for `random_c` one dense column buffer
+    per column of the view, n * m."""
+    total = 0
+    for rel in _first_relations(fusion_graph):
+        if not _kept_as_lists(rel, fuser):
+            continue
+        n_r, n_c = rel.data.shape
+        total += int(rel.data.nnz) * (int(rel.row_type.rank) + int(rel.col_type.rank))
+        if fuser.init_type == 'random_c':
+            total += 2 * n_r * n_c
     return total
 
 
@@ -248,7 +285,8 @@ def init_device_wanted(fuser):
     `init_device` is not False, a column-mean initialiser, whole relations on this process (shard='runs'), no preprocessor
     on a relation between two types (it would have to run on the host first), every first relation of a pair with at least
     5 columns in both orientations (fewer: take = 0 and the reference's mean of nothing, NaN -- the host keeps that), and
-    -- `init_device=None` -- at least INIT_DEVICE_MIN gathered elements.  `init_device_covered` has the last word."""
+    -- `init_device=None` -- at least INIT_DEVICE_MIN gathered elements, or at least INIT_KNOWN_MIN entries walked through
+    relations with missing values kept as lists.  `init_device_covered` has the last word."""
     from ._init import COLUMN_MEAN_TYPES
     want = getattr(fuser, 'init_device', None)
     if want is False or fuser.init_type not in COLUMN_MEAN_TYPES or fuser.shard != 'runs':
@@ -258,19 +296,20 @@ def init_device_wanted(fuser):
         return False
     if any(min(rel.data.shape) < 5 for rel in _first_relations(graph)):
         return False
-    return bool(want) or init_device_work(graph) >= INIT_DEVICE_MIN
+    return bool(want) or init_device_work(graph, fuser) >= INIT_DEVICE_MIN or init_known_work(graph, fuser) >= INIT_KNOWN_MIN
 
 
 def init_device_covered(R, M=None):
     """... and as far as the matrices tell: the first relation of every pair in a form the device initialiser reads --
-    unmasked, and dense (host or device) or the stored entries of a relation that is zero elsewhere; not the known entries
-    of a masked relation, not entries plus rank one."""
+    unmasked (a relation given as a MaskedArray initialises on the host), and dense (host or device), the stored entries of
+    a relation that is zero elsewhere, or a relation with missing values kept as lists compressed by row: its known entries
+    (``unstored='unknown'``, Dfmc) or entries plus rank one (`row_fill` set).  Lists compressed by column stay uncovered."""
     from ..._engine import KnownEntries, DeviceKnownEntries
     for key, mats in R.items():
         if M is not None and M.get(key) is not None and M[key][0] is not None:
             return False
         m = mats[0]
-        if isinstance(m, (KnownEntries, DeviceKnownEntries)) and (m.unstored != 'zero' or m.by_col or m.row_fill is not None):
+        if isinstance(m, (KnownEntries, DeviceKnownEntries)) and m.by_col:
             return False
     return True
 
@@ -392,11 +431,15 @@ class Dfmf(FusionFit):
     init_device=None | True | False: the column means of `random_c` / `random_vcol` (reference _init.py:20-61) are formed on
     the device -- one contraction per relation view against the 0/1 matrix of the chosen columns, the random stream drawn on
     the host exactly as before -- when the fit is eligible (``init_device_wanted``, ``init_device_covered``: shard='runs', no
-    preprocessor, the first relation of every pair whole, unmasked, dense or stored entries, at least 5 columns both ways);
-    True: whenever eligible; None: when the host initialiser would gather at least 2^34 elements; False: never.  An
+    preprocessor, the first relation of every pair whole, not a MaskedArray, dense, stored entries, or a relation with missing
+    values kept as lists -- there one pass over the lists per view --, at least 5 columns both ways);
+    True: whenever eligible; None: when the host initialiser would gather at least 2^34 elements or walk at least 2^33
+    entries of relations with missing values; False: never.  An
     ineligible fit initialises on the host whatever this says.  ``init_on_device_`` (after ``fuse``) says what ran.
     ``device_fill=True`` goes with these initialisers when they run on the device.
     """
+
+    _variant = 'dfmf'
 
     def __init__(self, max_iter=100, init_type='random_c', n_run=1, stopping=None,
                  stopping_system=None, verbose=0, compute_err=False, callback=None,
