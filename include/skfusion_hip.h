@@ -536,7 +536,9 @@ int skf_gemm_bits(const void* A, int64_t lda_bytes, const void* Bt, int64_t ldb,
                   size_t workspace_bytes, void* stream);
 
 /* dst (bf16, ld ldd) = round-to-nearest-even(src) or its transpose; src dtype SKF_F64 / SKF_F32 /
- * SKF_BF16.  Padding columns of dst are left untouched (zero them beforehand). */
+ * SKF_BF16.  Padding columns of dst are left untouched (zero them beforehand).  SKF_F64 is rounded to f32 first (two
+ * roundings, as the host's to_bf16_bits: at most 2^-17 bf16 ulp from one); a NaN becomes a quiet NaN of the same sign; a
+ * bf16 source is copied.  SKF_E_INVALID for lds < cols and for ldd below a row of dst (cols; rows when transposed). */
 int skf_to_bf16(void* dst, int64_t ldd, int32_t src_dtype, const void* src, int64_t lds,
                 int64_t rows, int64_t cols, int32_t transpose, void* stream);
 
@@ -803,7 +805,7 @@ int skf_fill_unknown(int32_t dtype, void* data, int64_t ld, int64_t rows, int64_
                      int64_t mask_ld, int32_t strategy, double value, void* workspace, size_t workspace_bytes,
                      void* stream);
 
-/* dst(r,c) = (dst_dtype) src(r,c), dtypes SKF_F64 / SKF_F32 */
+/* dst(r,c) = (dst_dtype) src(r,c), dtypes SKF_F64 / SKF_F32; SKF_E_INVALID for ldd < cols or lds < cols */
 int skf_cast(int32_t dst_dtype, void* dst, int64_t ldd, int32_t src_dtype, const void* src,
              int64_t lds, int64_t rows, int64_t cols, void* stream);
 

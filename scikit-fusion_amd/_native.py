@@ -31,10 +31,13 @@ NP_DTYPE = {SKF_F64: np.float64, SKF_F32: np.float32, SKF_BF16: np.float32}   # 
 
 
 def to_bf16_bits(a):
-    """float array -> uint16 bf16 bit patterns (round to nearest even), host side."""
+    """float array -> uint16 bf16 bit patterns (round to nearest even), host side; a NaN becomes a quiet NaN of the same
+    sign with the upper payload bits kept, as the device's f32_to_bf16_rne does (the increment would carry it into a zero
+    or an infinity)."""
     u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
     r = ((u >> 16) & 1) + np.uint32(0x7FFF)
-    return ((u + r) >> 16).astype(np.uint16)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    return np.where(nan, (u >> 16) | np.uint32(0x40), (u + r) >> 16).astype(np.uint16)
 
 
 def from_bf16_bits(b):

@@ -1632,6 +1632,11 @@ int skf_to_bf16(void* dst, int64_t ldd, int32_t src_dtype, const void* src, int6
                 int32_t transpose, void* stream) {
     return guarded([&] {
         if (!dst || !src || rows < 0 || cols < 0) SKF_FAIL(SKF_E_INVALID, "bad argument");
+        if (src_dtype != SKF_F64 && src_dtype != SKF_F32 && src_dtype != SKF_BF16) SKF_FAIL(SKF_E_INVALID, "bad source dtype");
+        // a row of dst holds `rows` elements when transposed, `cols` otherwise; a row of src always `cols`
+        if (lds < cols || ldd < (transpose ? rows : cols))
+            SKF_FAIL(SKF_E_INVALID, "skf_to_bf16: ld too small (ldd %lld, lds %lld for %lld x %lld%s)", (long long)ldd, (long long)lds,
+                     (long long)rows, (long long)cols, transpose ? ", transposed" : "");
         hipStream_t st = as_stream(stream);
         if (src_dtype == SKF_F64) launch_to_bf16<double>((uint16_t*)dst, ldd, (const double*)src, lds, rows, cols, transpose != 0, st);
         else if (src_dtype == SKF_F32) launch_to_bf16<float>((uint16_t*)dst, ldd, (const float*)src, lds, rows, cols, transpose != 0, st);
@@ -1763,6 +1768,8 @@ int skf_cast(int32_t dst_dtype, void* dst, int64_t ldd, int32_t src_dtype, const
              int64_t cols, void* stream) {
     return guarded([&] {
         if (!dst || !src || rows < 0 || cols < 0) SKF_FAIL(SKF_E_INVALID, "bad argument");
+        if (ldd < cols || lds < cols) SKF_FAIL(SKF_E_INVALID, "skf_cast: ld too small (ldd %lld, lds %lld for %lld columns)",
+                                               (long long)ldd, (long long)lds, (long long)cols);
         hipStream_t st = as_stream(stream);
         const int grid = elem_grid(rows * cols);
         if (dst_dtype == SKF_F32 && src_dtype == SKF_F64)
