@@ -1,5 +1,5 @@
 """Scores at or above a per-row threshold as CSR at BASELINE config 5's shape -- 100 000 users x 40 000 movies, ranks
-256 / 256, 80 M excluded (known) pairs -- selected on the device (`_engine.DeviceCompleter.above`, csrc/skf_complete.h) against
+256 / 256, 80 M excluded (known) pairs -- selected on the device (`_complete.DeviceCompleter.above`, csrc/skf_complete.h) against
 
   (a) the only route the project had before: `DeviceReconstructor.block` (what `complete_blocks(block_rows=4096)` runs per
       block) pulled to the host, the known pairs masked, one `>=` and one `nonzero` per block, in the same process;

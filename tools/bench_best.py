@@ -1,4 +1,4 @@
-"""The n best pairs of a whole relation (`FusionFit.complete_best`, `_engine.DeviceCompleter.kth` / `digits`,
+"""The n best pairs of a whole relation (`FusionFit.complete_best`, `_complete.DeviceCompleter.kth` / `digits`,
 csrc/skf_complete.h complete_digits_kernel) at 100 000 x 400 000 with 40 excluded columns per row, in blocks of 8192 rows:
 
     python tools/bench_best.py [--out profiles/best_pairs.txt] [--configs 16:f32,128:f32,128:f64:24576] [--n 100000]

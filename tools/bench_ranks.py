@@ -1,5 +1,5 @@
 """Ranks of held-out pairs at BASELINE config 5's shape -- 100 000 users x 40 000 movies, ranks 256 / 256, 10 targets per
-row, 80 M excluded (known) pairs -- counted on the device (`_engine.DeviceCompleter.ranks`, csrc/skf_complete.h) against
+row, 80 M excluded (known) pairs -- counted on the device (`_complete.DeviceCompleter.ranks`, csrc/skf_complete.h) against
 
   (a) `DeviceCompleter.topk` with k = 64 on the same blocks: the same matrix work (2 m n c flop), so it is the yardstick,
   (b) the only route to a rank beyond 64 the project had before: `DeviceReconstructor.block` (what

@@ -1,4 +1,4 @@
-"""The k best columns of every row for any k (`_engine.DeviceCompleter.row_kth` / `row_best`, csrc/skf_complete.h
+"""The k best columns of every row for any k (`_complete.DeviceCompleter.row_kth` / `row_best`, csrc/skf_complete.h
 complete_row_digits_kernel / complete_row_walk_kernel) on one resident block of 8192 rows against 400 000 columns with 40
 excluded columns per row, for BOTH widths of the select's digit (SKF_ROW_DIGIT_BITS = 8: 4 / 8 passes, one workgroup per CU;
 7: 5 / 10 passes, two to three):

@@ -1,5 +1,5 @@
 """Top-k completion at BASELINE config 5's shape -- 100 000 users x 40 000 movies, ranks 256 / 256, k = 10, 80 M excluded
-(known) pairs -- fused on the device (`_engine.DeviceCompleter.topk`, csrc/skf_complete.h) against the only route the
+(known) pairs -- fused on the device (`_complete.DeviceCompleter.topk`, csrc/skf_complete.h) against the only route the
 project had before: `DeviceReconstructor.block` (what `complete_blocks(block_rows=4096)` runs per block) pulled to the host,
 the known pairs masked, `np.argpartition` + a sort of the k per row.
 
