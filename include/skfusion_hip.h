@@ -674,6 +674,47 @@ int skf_complete_digits(int32_t dtype, const void* H, int64_t ldh, int64_t m, co
                         uint64_t* hist /* device, [1 << digit_bits], ADDED to */,
                         int32_t col_splits /* 0 = choose */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The histogram BY VALUE of every candidate score of X = H Gc^T (H, Gc as for skf_complete_topk) and of the scores of given
+ * target pairs, in one walk and without X: how many pairs lie above each of many cut-offs, precision / recall / false-positive
+ * rate at those cut-offs against a gold standard, the micro-averaged ROC and PR curves and the AUROC, which the reference's
+ * users read from roc_auc_score on the dense product (examples/pharma_chaining.py:100, examples/movielens_completion.py:121-126).
+ *   Candidate: as for skf_complete_digits -- j in [0, n_cols), j not in row r's exclusion list, score(r, j) not NaN; score(r, j)
+ *     is the same chain of matrix instructions as in skf_complete_topk.
+ *   Bin of a candidate score s: bin(s) = #{ t < n_edges : edges[t] <= s }, 0 .. n_edges, with the IEEE comparison in dtype -- the
+ *     one skf_complete_above makes: s >= edges[t] <=> bin(s) > t; -0.0 and +0.0 compare equal; -inf and +inf are ordinary
+ *     scores and ordinary edges.  edges (device, dtype [n_edges], 1 <= n_edges <= SKF_HIST_MAX_EDGES): none NaN, non-decreasing;
+ *     equal neighbours are allowed and give empty bins.
+ *   Counting: every candidate adds one to hist[bin]; with targets -- a CSR over the m rows exactly as skf_complete_ranks takes
+ *     it, tgt_indptr[m] == n_targets -- a candidate that is a target adds one to hist_tgt[bin] as well: hist counts all
+ *     candidates, targets included, and a target that is excluded or scores NaN is no candidate and is counted nowhere.  Both
+ *     histograms (device, uint64 [n_edges + 1]) are ADDED to, never cleared: the caller clears them once and sums row blocks on
+ *     the device, as with skf_complete_digits.  Integer atomics only: the counts do not depend on col_splits (0 = the library
+ *     chooses, at most 32), the launch geometry or the order of arrival.
+ *   P6: for every t, the sum of hist[b] over b > t (the increments of one call) equals *n_found of skf_complete_above on the
+ *     same inputs with thr[r] = edges[t] in every row -- for every col_splits of either operator and every cut of the rows
+ *     into blocks.
+ *   P7: a counted target e lands in bin #{ t : edges[t] <= v }, v = out_val[e] of skf_complete_ranks on the same inputs: both
+ *     scores are formed by the same chain of matrix instructions.
+ *   Refused with SKF_E_INVALID before any HIP call: the operand checks of skf_complete_topk, n_edges outside 1 ..
+ *     SKF_HIST_MAX_EDGES, edges or hist NULL, tgt_indptr / tgt_indices / hist_tgt not all NULL or all given (and n_targets != 0
+ *     without them, n_targets < 0), col_splits outside 0 .. 32; SKF_E_WORKSPACE for a workspace that is NULL, too small or not
+ *     256-byte aligned (skf_complete_hist_workspace_bytes: flag words only).  Refused with SKF_E_INVALID on the device, in one
+ *     round trip, before anything is counted: exclusion or target lists that are not canonical (tgt_indptr[m] != n_targets
+ *     included), a NaN edge, an edge smaller than the one before it.  Every refusal leaves both histograms, and the memory
+ *     behind them, as they were.  m == 0 or n_cols == 0 succeeds and adds nothing.
+ *   LDS: the edges and the bins are sized by n_edges and by whether targets are given; 16 edges do not pay for 2047.
+ *   dtype SKF_F64 / SKF_F32 (the type of H, Gc and edges); 1 <= c <= 1024; m and n_cols < 2^31. */
+#define SKF_HIST_MAX_EDGES 2047
+int skf_complete_hist_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int64_t n_targets, int32_t col_splits,
+                                      size_t* bytes);
+int skf_complete_hist(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols,
+                      int32_t c, const void* edges /* dtype [n_edges], device */, int32_t n_edges,
+                      const int64_t* excl_indptr, const int32_t* excl_indices,
+                      const int64_t* tgt_indptr, const int32_t* tgt_indices, int64_t n_targets,
+                      uint64_t* hist /* device [n_edges + 1], ADDED to */,
+                      uint64_t* hist_tgt /* device [n_edges + 1], ADDED to; NULL iff no targets */,
+                      int32_t col_splits /* 0 = choose */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The k-th best score of EVERY row of X = H Gc^T (H, Gc as for skf_complete_topk) for any k, without X: Recall@100 / @1000,
  * R-precision and candidate generation need per-row lists far beyond SKF_TOPK_MAX, and a row's k best columns are
  * skf_complete_above at the row's own k-th score.  One radix select per row over the keys of skf_complete_digits, in digits of
@@ -838,7 +879,8 @@ const char* skf_version(void);
  * skf_plan_relation_norms, skf_plan_init_column_means, their workspace queries and skf_init_view, a struct of their own -- the
  * structs before it are those of version 4; skf_complete_digits_workspace_bytes and skf_complete_digits;
  * skf_complete_row_kth_workspace_bytes and skf_complete_row_kth; skf_plan_relation_norms_filled,
- * skf_plan_init_column_means_filled and their workspace queries). */
+ * skf_plan_init_column_means_filled and their workspace queries; skf_complete_hist_workspace_bytes, skf_complete_hist and
+ * SKF_HIST_MAX_EDGES). */
 #define SKF_ABI_VERSION 5
 int skf_abi_version(void);
 

@@ -177,8 +177,9 @@ class DeviceCompleter(_ResidentFactors):
     """The consuming side of a completion model without the dense reconstruction: for ``X = G_row S G_col^T`` the ``k`` best
     columns of every row (``topk``), the predictions at given pairs (``entries``), the position of given pairs in
     their row's ranking (``ranks``), every pair at or above a threshold as CSR (``above``), the n-th largest score over all
-    row blocks (``kth``, by counting passes ``digits``) and every row's own k-th score for any k with the columns at or above
-    it (``row_kth``, ``row_best``), all on the device (csrc/skf_complete.h).  The reference forms ``X`` on the host (fusion/base/base.py ``complete``) and its users rank or
+    row blocks (``kth``, by counting passes ``digits``), every row's own k-th score for any k with the columns at or above
+    it (``row_kth``, ``row_best``) and the histogram of every score by value with that of given pairs (``hist``,
+    ``histogram``), all on the device (csrc/skf_complete.h).  The reference forms ``X`` on the host (fusion/base/base.py ``complete``) and its users rank or
     index that array (examples/movielens_completion.py:121-126).  ``S`` and ``G_col`` are uploaded ONCE and stay resident
     across blocks (the contract of ``DeviceReconstructor``); per block only ``H = G_row[block] S`` (``skf_gemm``), the
     block's exclusion lists, its outputs and the partial lists of the column splits live in HBM -- never anything of size
@@ -500,6 +501,82 @@ class DeviceCompleter(_ResidentFactors):
             equal = int(counts[d])
             prefix, pbits = (prefix << db) | d, pbits + db
         return float(score_of_key(prefix, self.npd)), greater, equal, cands
+
+    def hist(self, G_row_block, edges, hist, exclude=None, targets=None, hist_targets=None, col_splits=0):
+        """One walk of ``skf_complete_hist`` over the block: every candidate (admissible, not NaN) adds one to the bin
+        ``#{t : edges[t] <= score}`` of ``hist``, and a candidate that is one of ``targets`` (``(indptr, indices)``: CSR over the
+        rows of THIS block, as for ``ranks``) adds one to that bin of ``hist_targets`` as well.  ``edges`` (the scoring type,
+        non-decreasing, no NaN, at most ``SKF_HIST_MAX_EDGES``), ``hist`` and ``hist_targets`` (``len(edges) + 1`` uint64 words
+        each) are device buffers OWNED BY THE CALLER: the histograms are added to, never cleared, so the blocks of one walk
+        sum on the device.  ``exclude`` as for ``topk``; the counts do not depend on ``col_splits``."""
+        A, m, xl = self._block(G_row_block, exclude)
+        n_edges = edges.nbytes // self.es
+        if (targets is None) != (hist_targets is None):
+            raise ValueError('targets and hist_targets come together')
+        if hist.nbytes < 8 * (n_edges + 1) or (hist_targets is not None and hist_targets.nbytes < 8 * (n_edges + 1)):
+            raise ValueError('hist: a device buffer of len(edges) + 1 uint64 words')
+        tgt = []
+        if targets is not None:
+            tgt = [np.ascontiguousarray(targets[0], dtype=np.int64), np.ascontiguousarray(targets[1], dtype=np.int32)]
+            if tgt[0].shape != (m + 1,):
+                raise ValueError('targets: indptr must have one entry per row of the block, plus one')
+        n = int(tgt[1].size) if tgt else 0
+        need = self._workspace('hist', m, n, int(col_splits))
+        with self._on_device(A, tgt, xl) as (h, tl, xp, xi):
+            ws = self._scratch('ws', need)
+            tp, ti = tl if tgt else (None, None)
+            self._launch('hist', h, m, edges.ptr, n_edges, xp, xi, tp, ti, n, hist.ptr, hist_targets.ptr if tgt else None,
+                         int(col_splits), ws.ptr, ws.nbytes)
+            self.rt.mem.synchronize()
+
+    def histogram(self, blocks, edges, col_splits=0):
+        """``(counts int64 [len(edges) + 1], target_counts or None, n_candidates)`` over ALL the row blocks: ``counts[b]``
+        candidates score in bin ``b = #{t : edges[t] <= score}`` -- the comparison is made in the scoring type, to which
+        ``edges`` (a host array of ANY length >= 1, non-decreasing, no NaN) is cast -- and ``target_counts[b]`` of them are
+        targets.  ``blocks()`` returns a fresh iterator of ``(G_row_block, exclude, targets_or_None)`` and is called once per
+        walk; the blocks give targets all or none.  More than ``SKF_HIST_MAX_EDGES`` edges take one walk per chunk of that
+        many; a chunk's counts at or above each of its edges are exact, and the bins of the whole are their differences:
+        integer arithmetic, the histogram one walk over all the edges would give.  Beside a block's usual state only the
+        edges of a chunk and its two histograms (at most 16 KB each) are held."""
+        e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).astype(self.npd))
+        if e.ndim != 1 or e.size < 1:
+            raise ValueError('edges: a one-dimensional array of at least one value')
+        if np.isnan(e).any() or (e[1:] < e[:-1]).any():
+            raise ValueError('edges: no NaN, non-decreasing')
+        mem = self.rt.mem
+        at_or_above = [[], []]               # per edge, Python integers: all candidates / targets at or above it
+        total, with_targets = [0, 0], None
+        for c0 in range(0, e.size, nat.SKF_HIST_MAX_EDGES):
+            chunk = e[c0:c0 + nat.SKF_HIST_MAX_EDGES]
+            self._bufs['hist_edges'] = de = mem.from_host(chunk)
+            bufs = [None, None]
+            for G_row_block, exclude, targets in blocks():
+                if with_targets is None:
+                    with_targets = targets is not None
+                if (targets is not None) != with_targets:
+                    raise ValueError('histogram: the blocks give targets all or none')
+                for i in range(1 + with_targets):
+                    if bufs[i] is None:
+                        bufs[i] = self._bufs[('hist', 'hist_targets')[i]] = mem.from_host(np.zeros(chunk.size + 1, dtype=np.uint64))
+                self.hist(G_row_block, de, bufs[0], exclude=exclude, targets=targets, hist_targets=bufs[1], col_splits=col_splits)
+            for i in range(2):
+                if bufs[i] is None:          # no block at all, or no targets
+                    got = [0] * (chunk.size + 1)
+                else:
+                    got = [int(v) for v in mem.to_host(bufs[i], (chunk.size + 1,), np.uint64)]
+                total[i] = sum(got)
+                run = 0
+                tail = []
+                for v in reversed(got[1:]):
+                    run += v
+                    tail.append(run)
+                at_or_above[i].extend(reversed(tail))
+        out = []
+        for i in range(2):
+            a = at_or_above[i]
+            bins = [total[i] - a[0]] + [a[t] - a[t + 1] for t in range(len(a) - 1)] + [a[-1]]
+            out.append(np.array(bins, dtype=np.int64))
+        return out[0], out[1] if with_targets else None, total[0]
 
     def entries(self, G_row, rows, cols):
         """``float64 [n]``: ``X[rows[e], cols[e]]``.  Only the DISTINCT rows of ``G_row`` that ``rows`` names are uploaded

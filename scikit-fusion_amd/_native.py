@@ -84,7 +84,8 @@ class InitView(C.Structure):
 SKF_OPT_OWNED_ROWS = 1
 SKF_OPT_THETA_OWNED_ROWS = 2   # constraints given as their entries: the CSR of the owned rows (needs SKF_OPT_OWNED_ROWS)
 SKF_TOPK_MAX = 64            # include/skfusion_hip.h: longest list skf_complete_topk keeps per row
-SKF_ABI_VERSION = 5          # include/skfusion_hip.h: the struct layouts above belong to this version
+SKF_HIST_MAX_EDGES = 2047    # include/skfusion_hip.h: most edges of one skf_complete_hist walk
+SKF_ABI_VERSION = 5         # include/skfusion_hip.h: the struct layouts above belong to this version
 
 
 class GemmDesc(C.Structure):
@@ -171,6 +172,9 @@ SIGNATURES = {
     'skf_complete_digits_workspace_bytes': (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
     'skf_complete_digits': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_uint64,
                                       C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_size_t, _P]),
+    'skf_complete_hist_workspace_bytes': (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    'skf_complete_hist': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P,
+                                    _P, _P, C.c_int64, _P, _P, C.c_int32, _P, C.c_size_t, _P]),
     'skf_complete_row_kth_workspace_bytes': (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
     'skf_complete_row_kth': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P,
                                        _P, _P, _P, _P, C.c_int32, _P, C.c_size_t, _P]),

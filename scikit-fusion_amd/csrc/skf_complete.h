@@ -60,6 +60,16 @@
 //       NaN threshold selects nothing.
 //   P5: with want[r] = k <= 64, row r's P4 entries ordered by (value descending, column ascending) begin with
 //       complete_topk's list for that k -- its first min(k, candidates) slots -- index for index and bit for bit.
+//
+// How the scores of a whole relation are DISTRIBUTED (link prediction is judged by it: the pairs above each of many cut-offs,
+// precision / recall / false-positive rate against a gold standard, the micro-averaged ROC and PR curves and the AUROC the
+// reference's users read from roc_auc_score on the dense product, examples/pharma_chaining.py:100) is one more walk:
+// complete_hist_kernel bins every candidate score by VALUE against up to 2047 edges, bin(s) = #{ t : edges[t] <= s }, and in the
+// same launch, with the same bits, the scores of given target pairs.  Same product, the comparison of above(), integer counts:
+//   P6: for every t, the sum of hist[b] over b > t (the increments of one call) equals *n_found of skf_complete_above on the
+//       same inputs with thr[r] = edges[t] in every row, for every col_splits of either operator and every cut of the rows
+//       into blocks.
+//   P7: a counted target e lands in bin #{ t : edges[t] <= v }, v the out_val[e] of the rank pass on the same inputs.
 #pragma once
 #include "skf_kernels.h"
 
@@ -879,6 +889,154 @@ __global__ __launch_bounds__(TOPK_THREADS) void complete_digits_kernel(DigitArgs
         // (the first barrier of the next tile's product separates these reads from the next tile and mask)
     }
     digit_flush(bins, nbins, a.hist);
+}
+
+// ---- the histogram of every candidate score BY VALUE, and of the scores of given pairs -------------------------------------------
+// complete_digits_kernel bins by key bits; a curve over cut-offs needs bins by value: bin(s) = #{ t < n_edges : edges[t] <= s },
+// 0 .. n_edges, for edges that do not descend (validated by the caller: hist_edges_check_kernel).  `<=` is the comparison of
+// above_quarter_mask read from the other side, so the candidates of the bins above t are above() at thr = edges[t] (P6).
+constexpr int HIST_MAX_EDGES = 2047;                 // with bin 0: 2048 uint32 bins, the histogram of an 11-bit digit
+
+// The search descends a perfect binary tree of 2^steps - 1 nodes, steps = ceil(log2(n_edges + 1)), over the edges padded with
+// NaN at the upper end (NaN <= s is false for every s: a padded entry is never passed, and the search needs no bound check).
+// The table holds the tree in BREADTH-FIRST order, the root at [1] ([0] is not used): node k = 2^l + p, the p-th of level l,
+// is entry ((2 p + 1) << (steps - 1 - l)) - 1 of the padded edges; the children of k are 2 k and 2 k + 1.  The sorted order
+// would put the 2^l nodes of a level 2^(steps - l) words apart -- on ONE bank from the level on whose stride reaches the bank
+// row, as many LDS cycles as the lanes hold distinct nodes; breadth first they are adjacent words, 32 nodes on 32 banks.
+static inline int hist_steps(int n_edges) {
+    int steps = 0;
+    while ((1 << steps) < n_edges + 1) ++steps;
+    return steps;
+}
+// bytes of dynamic LDS: the padded table (T, a whole number of 8-byte words), bins [n_edges + 1] and, with targets, theirs.
+// At the maximum the f64 kernel holds 16 + 8 + 8 KB beside the 35 KB buffer and the mask words: 67 KB, two workgroups per CU;
+// 16 edges in f32 cost 128 + 68 (+ 68) bytes.
+static inline size_t hist_lds_bytes(int n_edges, bool targets, size_t esz) {
+    const size_t table = (((size_t)1 << hist_steps(n_edges)) * esz + 7) / 8 * 8;
+    return table + (targets ? 2 : 1) * (size_t)(n_edges + 1) * sizeof(unsigned);
+}
+
+// bad[0] = 1 when an edge is NaN or smaller than the one before it (IEEE <=; equal neighbours pass: an empty bin)
+template <typename T>
+__global__ __launch_bounds__(256) void hist_edges_check_kernel(const T* __restrict__ edges, int n_edges, int* __restrict__ bad) {
+    int off = 0;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n_edges; e += gridDim.x * blockDim.x)
+        if (edges[e] != edges[e] || (e > 0 && !(edges[e - 1] <= edges[e]))) off = 1;
+    if (off) *bad = 1;
+}
+
+template <typename T>
+struct HistArgs {
+    const T* H;  int64_t ldh;  int64_t m;           // [m][c]
+    const T* Gc; int64_t ldg;  int64_t n_cols;      // [n_cols][c]
+    int c;
+    const int64_t* xptr; const int* xidx;           // exclusion CSR over the m rows (validated by the caller), or both null
+    int tiles_per_split;                            // column tiles (of TOPK_BN) a split walks
+    const int64_t* tptr; const int* tidx;           // target CSR over the m rows (validated by the caller), or both null
+    const T* edges;                                 // [n_edges], none NaN, non-decreasing (validated by the caller)
+    int n_edges, steps;                             // 1 <= n_edges <= HIST_MAX_EDGES; steps = hist_steps(n_edges)
+    unsigned long long* hist;                       // [n_edges + 1], ADDED to
+    unsigned long long* hist_tgt;                   // [n_edges + 1], ADDED to; null iff no targets
+};
+
+// grid (64-row tile, column split), walk, product, exclusion mask and candidate rule of complete_digits_kernel.  The edges are
+// staged once per workgroup; thread (row = t & 63, quarter = t >> 6) then finds the bins of its 16 scores by a binary search
+// of a fixed number of steps without a branch -- k = 1; steps times: k = 2 k + (table[k] <= s); bin = k - 2^steps, the
+// edges passed on the way down -- all 16 searches side by side, so that every step issues 16 independent LDS reads (the
+// first reads one address in all lanes: a broadcast).  Real scores of one tile row fall into few bins: a thread MERGES RUNS
+// of equal consecutive bins into one LDS atomicAdd, as the digits kernel does.  With targets the owner lanes publish a second
+// 64-bit mask per row and tile through a second cursor (the code of the exclusion cursor on the target lists); a candidate
+// whose bit is set adds one to the second set of bins as well -- targets are few: no runs there.  A target that is excluded
+// or scores NaN is no candidate and is counted nowhere.  Overflow: a workgroup sees at most 64 x 64 scores per tile, all of
+// which may fall into ONE bin: after DIGIT_FLUSH_TILES = 2^19 tiles a bin holds at most 2^31 and is flushed and cleared, long
+// before its 32 bits could wrap, and a target bin never holds more than the bin beside it.  (A split of that length has 2^25
+// columns: no test reaches it, and none tries.)  Counts are integers: the histograms do not depend on the splits, the launch
+// geometry or the order of arrival.  No float atomics, no atomics on positions.
+template <typename T>
+__global__ __launch_bounds__(TOPK_THREADS) void complete_hist_kernel(HistArgs<T> a) {
+    constexpr int OPER = 2 * TOPK_BM * TOPK_LD, TILE = TOPK_BM * TOPK_SLD;
+    __shared__ T buf[OPER > TILE ? OPER : TILE];
+    __shared__ unsigned long long xmask[TOPK_BM];        // the excluded columns of the tile, per row
+    __shared__ unsigned long long tmask[TOPK_BM];        // the target columns of the tile, per row
+    HIP_DYNAMIC_SHARED(double, dyn)                      // hist_lds_bytes: the padded edges, the bins, the target bins
+    const T* sc = buf;
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r = t & 63, q = t >> 6;
+    const int64_t row0 = (int64_t)blockIdx.x * TOPK_BM;
+    const TileRange tiles = split_tiles(a.n_cols, a.tiles_per_split);
+    const bool rin = row0 + r < a.m;
+    const bool targets = a.tptr != nullptr;
+    const int nbins = a.n_edges + 1, table = 1 << a.steps;
+    T* ed = (T*)dyn;
+    unsigned* bins = (unsigned*)((char*)dyn + ((size_t)table * sizeof(T) + 7) / 8 * 8);
+    unsigned* tbins = bins + nbins;                      // (only with targets)
+
+    for (int k = t; k < table; k += TOPK_THREADS) {
+        const int l = k ? 31 - __builtin_clz((unsigned)k) : 0;          // the level of node k; k = 0 is no node
+        const int e = (((2 * (k - (1 << l)) + 1) << (a.steps - 1 - l))) - 1;
+        ed[k] = (k && e < a.n_edges) ? a.edges[e] : (T)NAN;
+    }
+    for (int d = t; d < nbins; d += TOPK_THREADS) bins[d] = 0;
+    if (targets)
+        for (int d = t; d < nbins; d += TOPK_THREADS) tbins[d] = 0;
+    if (t < TOPK_BM) tmask[t] = 0;
+    __syncthreads();
+
+    const bool owner = lane < 16;                        // of row wave * 16 + lane of the tile
+    const int orow = wave * 16 + lane;
+    int64_t xp = 0, xe = 0;                              // the row's exclusion list from the split's first column on
+    int64_t tp = 0, te = 0;                              // ... and its target list
+    if (owner && row0 + orow < a.m && a.xptr) excl_seek(a.xptr, a.xidx, row0 + orow, tiles.lo * TOPK_BN, xp, xe);
+    if (owner && row0 + orow < a.m && targets) excl_seek(a.tptr, a.tidx, row0 + orow, tiles.lo * TOPK_BN, tp, te);
+
+    for (int64_t tile = tiles.lo; tile < tiles.hi; ++tile) {
+        const int64_t col0 = tile * TOPK_BN;
+        topk_score_tile<T>(a.H, a.ldh, a.m, row0, a.Gc, a.ldg, a.c,
+                           [&](int rr) { return col0 + rr < a.n_cols ? (int)(col0 + rr) : -1; }, buf);
+        if (owner) xmask[orow] = excl_tile_mask(a.xidx, xp, xe, col0);
+        if (owner && targets) tmask[orow] = excl_tile_mask(a.tidx, tp, te, col0);
+        __syncthreads();
+        if (rin) {
+            const unsigned xm = (unsigned)(xmask[r] >> (16 * q)) & 0xffffu;
+            const unsigned tm = (unsigned)(tmask[r] >> (16 * q)) & 0xffffu;
+            T sv[16];
+            int at[16];
+            unsigned ok = 0;                             // bit b: score b is a candidate
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                sv[b] = sc[r * TOPK_SLD + 16 * q + b];
+                at[b] = 1;
+                if (col0 + 16 * q + b < a.n_cols && !((xm >> b) & 1u) && sv[b] == sv[b]) ok |= 1u << b;
+            }
+            for (int step = 0; step < a.steps; ++step) {
+#pragma unroll
+                for (int b = 0; b < 16; ++b) at[b] = 2 * at[b] + (ed[at[b]] <= sv[b] ? 1 : 0);
+            }
+            int run_d = 0, run_n = 0;                    // the run of equal bins so far
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                if ((ok >> b) & 1u) {
+                    const int d = at[b] - table;
+                    if (run_n && d != run_d) {
+                        atomicAdd(&bins[run_d], (unsigned)run_n);
+                        run_n = 0;
+                    }
+                    run_d = d;
+                    ++run_n;
+                    if ((tm >> b) & 1u) atomicAdd(&tbins[d], 1u);
+                }
+            }
+            if (run_n) atomicAdd(&bins[run_d], (unsigned)run_n);
+        }
+        if (((tile - tiles.lo + 1) & (DIGIT_FLUSH_TILES - 1)) == 0) {
+            digit_flush(bins, nbins, a.hist);
+            if (targets) digit_flush(tbins, nbins, a.hist_tgt);
+        }
+        // (the first barrier of the next tile's product separates these reads from the next tile and masks)
+    }
+    digit_flush(bins, nbins, a.hist);
+    if (targets) digit_flush(tbins, nbins, a.hist_tgt);
 }
 
 // ---- the k best columns of EVERY row, for any k: one radix select per row, all passes on the device --------------------------

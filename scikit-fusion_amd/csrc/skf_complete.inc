@@ -1,6 +1,6 @@
 // skf_complete.inc -- part of the one translation unit skf_api.hip (textually included there, inside its namespaces; not a
 // header of its own): the host side of the consuming operators skf_complete_topk / _entries / _ranks / _above / _digits /
-// _row_kth (kernels: skf_complete.h), their C entry points included.  Every rule of the front end is stated once and named after what it checks;
+// _hist / _row_kth (kernels: skf_complete.h), their C entry points included.  Every rule of the front end is stated once and named after what it checks;
 // an entry point reads as its own order of them:
 //   SKF_E_INVALID refusals (shape, operands, lists that come in pairs) -> SKF_E_WORKSPACE refusals -> the first HIP call
 //   -> validation of the lists on the device -> the launches.
@@ -88,7 +88,7 @@ static void check_col_splits(const char* op, int32_t col_splits, OverMaxSplits o
     }
 }
 
-// the operands every pass's argument block begins with (TopkArgs / RankArgs / AboveArgs / DigitArgs / RowDigitArgs<T>, skf_complete.h),
+// the operands every pass's argument block begins with (TopkArgs / RankArgs / AboveArgs / DigitArgs / HistArgs / RowDigitArgs<T>, skf_complete.h),
 // tiles_per_split included
 template <typename T, template <typename> class Args>
 static void fill_operands(Args<T>& a, const Scored& s, int splits) {
@@ -262,6 +262,70 @@ static void launch_complete_digits(const Scored& s, uint64_t prefix, int prefix_
     a.hist = (unsigned long long*)hist;
     hipLaunchKernelGGL((complete_digits_kernel<T>), dim3(cdiv(s.m, TOPK_BM), splits), dim3(TOPK_THREADS), 0, st, a);
     check_launch("complete_digits");
+}
+
+// ---- the histogram of every candidate score by value, and of given pairs -----------------------------------------------------
+// Workspace: [0, 256) three verdict words -- the exclusion lists, the target lists, the edges --, nothing else: the histograms
+// are the caller's.
+static_assert(SKF_HIST_MAX_EDGES == HIST_MAX_EDGES, "include/skfusion_hip.h and skf_complete.h disagree on the number of edges");
+static size_t hist_workspace() { return 256; }
+
+static void hist_check_query(int32_t dtype, int64_t m, int64_t n_cols, int64_t n_targets, int32_t col_splits) {
+    check_shape("hist", dtype, m, n_cols);
+    if (n_targets < 0) SKF_FAIL(SKF_E_INVALID, "skf_complete_hist: n_targets = %lld is negative", (long long)n_targets);
+    check_col_splits("hist", col_splits, OVER_MAX_REFUSE);
+}
+
+// The exclusion lists, the target lists (tptr[m] == n_targets is part of their check) and the edges, each by its own kernel
+// into its own verdict word, read back together: one round trip (and, as for every operator, the read-back of the exclusion
+// lists' own count ahead of it).  m > 0.
+template <typename T>
+static void validate_hist(const Scored& s, const int64_t* tptr, const int* tidx, int64_t n_targets, const void* edges, int n_edges,
+                          int* flags, hipStream_t st) {
+    int64_t nnz = 0;
+    if (s.xptr) {
+        SKF_HIP(hipMemcpyAsync(&nnz, s.xptr + s.m, sizeof nnz, hipMemcpyDeviceToHost, st));
+        SKF_HIP(hipStreamSynchronize(st));
+    }
+    int bad[3] = {nnz < 0, 0, 0};
+    if (!bad[0]) {
+        SKF_HIP(hipMemsetAsync(flags, 0, sizeof bad, st));
+        if (s.xptr) {
+            hipLaunchKernelGGL(known_csr_check_kernel, dim3(wave_grid(s.m)), dim3(256), 0, st, s.xptr, (const int*)s.xidx, s.m, s.n_cols, nnz, flags);
+            check_launch("known_csr_check");
+        }
+        if (tptr) {
+            hipLaunchKernelGGL(known_csr_check_kernel, dim3(wave_grid(s.m)), dim3(256), 0, st, tptr, tidx, s.m, s.n_cols, n_targets, flags + 1);
+            check_launch("known_csr_check");
+        }
+        hipLaunchKernelGGL((hist_edges_check_kernel<T>), dim3(cdiv(n_edges, 256)), dim3(256), 0, st, (const T*)edges, n_edges, flags + 2);
+        check_launch("hist_edges_check");
+        SKF_HIP(hipMemcpyAsync(bad, flags, sizeof bad, hipMemcpyDeviceToHost, st));
+        SKF_HIP(hipStreamSynchronize(st));
+    }
+    if (bad[0])
+        SKF_FAIL(SKF_E_INVALID, "skf_complete_hist: the exclusion lists are not canonical for %lld rows x %lld columns (indptr from 0 "
+                 "to the count, non-decreasing; indices in range and strictly ascending within a row)", (long long)s.m, (long long)s.n_cols);
+    if (bad[1])
+        SKF_FAIL(SKF_E_INVALID, "skf_complete_hist: the target lists are not canonical for %lld rows x %lld columns and %lld targets "
+                 "(indptr from 0 to the count, non-decreasing; indices in range and strictly ascending within a row)",
+                 (long long)s.m, (long long)s.n_cols, (long long)n_targets);
+    if (bad[2]) SKF_FAIL(SKF_E_INVALID, "skf_complete_hist: the %d edges hold a NaN or descend", n_edges);
+}
+
+template <typename T>
+static void launch_complete_hist(const Scored& s, const int64_t* tptr, const int* tidx, const void* edges, int n_edges, uint64_t* hist,
+                                 uint64_t* hist_tgt, int splits, hipStream_t st) {
+    HistArgs<T> a;
+    fill_operands(a, s, splits);
+    a.tptr = tptr; a.tidx = tidx;
+    a.edges = (const T*)edges; a.n_edges = n_edges; a.steps = hist_steps(n_edges);
+    a.hist = (unsigned long long*)hist; a.hist_tgt = (unsigned long long*)hist_tgt;
+    static DeviceOnce once;
+    allow_dynamic_lds(once, complete_hist_kernel<T>, (int)hist_lds_bytes(HIST_MAX_EDGES, true, sizeof(T)));
+    hipLaunchKernelGGL((complete_hist_kernel<T>), dim3(cdiv(s.m, TOPK_BM), splits), dim3(TOPK_THREADS),
+                       hist_lds_bytes(n_edges, tptr != nullptr, sizeof(T)), st, a);
+    check_launch("complete_hist");
 }
 
 // ---- the k-th best score of every row ------------------------------------------------------------------------------------------
@@ -497,6 +561,42 @@ int skf_complete_digits(int32_t dtype, const void* H, int64_t ldh, int64_t m, co
         if (n_cols == 0) return;                        // no column: no candidate
         by_dtype(dtype, [&](auto t) {
             launch_complete_digits<decltype(t)>(s, prefix, prefix_bits, digit_bits, hist, splits, st);
+        });
+    });
+}
+
+int skf_complete_hist_workspace_bytes(int32_t dtype, int64_t m, int64_t n_cols, int64_t n_targets, int32_t col_splits, size_t* bytes) {
+    return guarded([&] {
+        if (!bytes) SKF_FAIL(SKF_E_INVALID, "null argument");
+        hist_check_query(dtype, m, n_cols, n_targets, col_splits);
+        *bytes = hist_workspace();
+    });
+}
+
+int skf_complete_hist(int32_t dtype, const void* H, int64_t ldh, int64_t m, const void* Gc, int64_t ldg, int64_t n_cols, int32_t c,
+                      const void* edges, int32_t n_edges, const int64_t* excl_indptr, const int32_t* excl_indices,
+                      const int64_t* tgt_indptr, const int32_t* tgt_indices, int64_t n_targets, uint64_t* hist, uint64_t* hist_tgt,
+                      int32_t col_splits, void* workspace, size_t workspace_bytes, void* stream) {
+    return guarded([&] {
+        const Scored s = {dtype, H, ldh, m, Gc, ldg, n_cols, c, excl_indptr, excl_indices};
+        hist_check_query(dtype, m, n_cols, n_targets, col_splits);
+        check_operands("hist", s);
+        if (n_edges < 1 || n_edges > SKF_HIST_MAX_EDGES)
+            SKF_FAIL(SKF_E_INVALID, "skf_complete_hist: n_edges = %d outside 1 .. %d", n_edges, SKF_HIST_MAX_EDGES);
+        if (!edges || !hist) SKF_FAIL(SKF_E_INVALID, "skf_complete_hist: null argument");
+        if ((tgt_indptr == nullptr) != (tgt_indices == nullptr) || (tgt_indptr == nullptr) != (hist_tgt == nullptr))
+            SKF_FAIL(SKF_E_INVALID, "skf_complete_hist: tgt_indptr, tgt_indices and hist_tgt come together (all NULL: no targets)");
+        if (!tgt_indptr && n_targets != 0) SKF_FAIL(SKF_E_INVALID, "skf_complete_hist: n_targets = %lld without target lists", (long long)n_targets);
+        const int splits = topk_col_splits(m, n_cols, col_splits);
+        check_workspace("hist", workspace, workspace_bytes, hist_workspace());
+        if (m == 0) return;
+        hipStream_t st = as_stream(stream);
+        by_dtype(dtype, [&](auto t) {
+            validate_hist<decltype(t)>(s, tgt_indptr, (const int*)tgt_indices, n_targets, edges, n_edges, (int*)workspace, st);
+        });
+        if (n_cols == 0) return;                        // no column: no candidate
+        by_dtype(dtype, [&](auto t) {
+            launch_complete_hist<decltype(t)>(s, tgt_indptr, (const int*)tgt_indices, edges, n_edges, hist, hist_tgt, splits, st);
         });
     });
 }

@@ -1,11 +1,13 @@
 """The completion operators of a fitted model (``FusionFit`` inherits them): predictions at given pairs, the k best columns of
-a row, ranks of held-out pairs, scores above a threshold, the n best pairs of a relation and the k best columns of every row
-for any k -- all on the device, never densified (``_complete.DeviceCompleter``).
+a row, ranks of held-out pairs, scores above a threshold, the n best pairs of a relation, the k best columns of every row
+for any k and the histogram of a relation's scores with the ROC / PR curves read from it -- all on the device, never
+densified (``_complete.DeviceCompleter``).
 
 Every operator is written from the same pieces: one ``_Query`` (the checked rows, the relation's shape, the exclusion lists
 and the walk over row blocks), for the CSR-returning ones one ``_CsrRows`` (the result, filled block by block, and the
 translation of the device's ``AboveLimit``), and ``_per_run`` for the runs.
 """
+import collections
 import contextlib
 
 import numpy as np
@@ -198,9 +200,16 @@ class CompletionOperators(object):
                                       % (relation.row_type.name, relation.col_type.name))
         if not scipy.sparse.issparse(exclude):
             raise DataFusionError("exclude must be None, 'known' or a scipy.sparse matrix, not %s" % type(exclude).__name__)
-        if tuple(exclude.shape) != tuple(shape):
-            raise DataFusionError("exclude has shape %r, the relation %r" % (tuple(exclude.shape), tuple(shape)))
-        csr = scipy.sparse.csr_matrix(exclude)      # (duplicates of a COO matrix are summed; stored zeros stay entries)
+        return self._pair_lists(exclude, shape, 'exclude')
+
+    @staticmethod
+    def _pair_lists(pairs, shape, what):
+        """A function ``rows -> (indptr int64, indices int32)`` for the stored entries of the scipy.sparse matrix ``pairs`` of
+        the relation's ``shape``: CSR with strictly ascending columns, sliced per block, never expanded."""
+        import scipy.sparse
+        if tuple(pairs.shape) != tuple(shape):
+            raise DataFusionError("%s has shape %r, the relation %r" % (what, tuple(pairs.shape), tuple(shape)))
+        csr = scipy.sparse.csr_matrix(pairs)        # (duplicates of a COO matrix are summed; stored zeros stay entries)
         if not csr.has_sorted_indices:
             csr = csr.sorted_indices()
 
@@ -480,3 +489,137 @@ class CompletionOperators(object):
                 return oi, ov
             return out.finish(q.n_j)
         return self._per_run(one, run)
+
+    # ---- how the scores of a relation are distributed: histograms and ROC / PR curves on the device, never densified -------
+    def _hist_query(self, relation, method, edges, rows, exclude, targets, what, block_rows):
+        """``(q, edges float64 [n], lists of the target pairs or None)`` of the two operators below, checked."""
+        import scipy.sparse
+        q = _Query(self, relation, method, rows, exclude, block_rows)
+        tl = None
+        if targets is not None:
+            if not scipy.sparse.issparse(targets):
+                raise DataFusionError("%s must be a scipy.sparse matrix, not %s" % (what, type(targets).__name__))
+            tl = self._pair_lists(targets, (q.n_i, q.n_j), what)
+        if edges is not None:
+            edges = np.asarray(edges)
+            if edges.dtype.kind not in 'fiu' or edges.ndim != 1 or edges.size < 1:
+                raise DataFusionError("%s: edges must be a one-dimensional array of at least one number, not %s of shape %r"
+                                      % (method, edges.dtype, tuple(edges.shape)))
+            edges = edges.astype(np.float64)
+            if np.isnan(edges).any() or (edges[1:] < edges[:-1]).any():
+                raise DataFusionError("%s: edges must not hold NaN and must not descend" % method)
+        return q, edges, tl
+
+    @staticmethod
+    def _hist_blocks(q, G1, tl):
+        """What ``DeviceCompleter.histogram`` walks once per chunk of edges."""
+        return lambda: ((G1[blk], xl, tl(blk) if tl else None) for _, blk, xl in q.blocks())
+
+    def complete_histogram(self, relation, edges, rows=None, exclude=None, targets=None, run=None, dtype='f64', block_rows=8192):
+        """``counts int64 [len(edges) + 1]``: how the scores the model gives to the admissible pairs of ``rows`` x all columns
+        (``rows``: default every row object; a row listed twice is two rows) are distributed over the bins that ``edges`` cut:
+        ``counts[b]`` pairs score in bin ``b = #{t : edges[t] <= score}``, so that ``counts[t + 1:].sum()`` pairs score at or
+        above ``edges[t]`` -- the size ``complete_above`` returns at that threshold, for every threshold at once and in one
+        walk over the score tiles.  ``edges`` is one-dimensional, of any length, without NaN and non-decreasing (``-inf`` and
+        ``+inf`` are ordinary edges); it is CAST TO THE SCORING TYPE of ``dtype`` ('f64' | 'f32' | 'bf16' -> f32), as
+        ``threshold`` is in ``complete_above``, and the comparison is made in that type: a cast that merges two edges leaves
+        an empty bin.  NaN scores and excluded pairs (``exclude`` as for ``complete_topk``) are counted nowhere.  ``targets``
+        -- a scipy.sparse matrix of the relation's shape whose stored entries are pairs of interest, e.g. a gold standard;
+        kept as CSR, sliced per block, never expanded -- gives ``(counts, target_counts)``: ``target_counts[b]`` of the
+        ``counts[b]`` pairs are targets (a target that is excluded or scores NaN is counted in neither).  The device bins
+        ``block_rows`` rows at a time, 2047 edges per walk; nothing of size ``n_i x n_j`` is formed and the result does not
+        depend on ``block_rows``.  A relation with a postprocessor is refused, as in ``complete_topk``.  ``n_run > 1`` and
+        ``run=None``: a generator over the runs.  Extension of the reference API."""
+        q, edges, tl = self._hist_query(relation, 'complete_histogram', edges, rows, exclude, targets, 'targets', block_rows)
+        if edges is None:
+            raise DataFusionError("complete_histogram: edges must be a one-dimensional array of at least one number, not None")
+
+        def one(r):
+            G1, comp = self._completer(relation, r, dtype)
+            counts, target_counts, _ = comp.histogram(self._hist_blocks(q, G1, tl), edges)
+            if tl and target_counts is None:            # (no row at all)
+                target_counts = np.zeros_like(counts)
+            return (counts, target_counts) if tl else counts
+        return self._per_run(one, run)
+
+    def complete_curve(self, relation, positives, edges=None, n_edges=2047, rows=None, exclude=None, run=None, dtype='f64',
+                       block_rows=8192):
+        """The global (micro-averaged) ROC and precision-recall curves of the model's scores against the gold standard
+        ``positives`` -- a scipy.sparse matrix of the relation's shape whose stored entries are the positive pairs -- over the
+        admissible pairs of ``rows`` x all columns, without the dense product the reference's users hand to ``roc_auc_score``
+        (examples/pharma_chaining.py:100).  Returns a ``CompletionCurve``:
+          ``thresholds`` float64, ascending (``edges`` in the scoring type); ``predicted[t]`` the candidates -- admissible pairs
+          whose score is not NaN -- scoring at or above ``thresholds[t]``; ``true_positives[t]`` the positives among them;
+          ``n_candidates``; ``n_positives`` the positives that are candidates (an excluded or NaN-scored positive is not
+          counted) and ``n_positives_given`` the stored entries of ``positives`` in ``rows``; ``precision``, ``recall`` and
+          ``fpr`` float64 per threshold, NaN where the denominator is 0; ``auroc = (lo, hi)``, the exact bounds of the area
+          under the ROC curve given the histogram: within a bin every negative ahead of every positive, and the reverse --
+          ``hi - lo`` is the share of (positive, negative) pairs that meet in one bin; when every bin holds one distinct score
+          ``(lo + hi) / 2`` is the mid-rank AUROC exactly.  ``(nan, nan)`` without a positive or without a negative.
+        ``edges=None`` takes the distinct values of up to ``n_edges`` evenly spaced order statistics of the positives' own
+        scores (``complete_entries``, cast to the scoring type): that puts the resolution where the curve moves, and the width
+        ``hi - lo`` the result carries is all that is promised of it.  ``edges``, ``exclude``, ``dtype``, ``block_rows`` and the
+        refusal of post-processed relations as in ``complete_histogram``.  ``n_run > 1`` and ``run=None``: a generator over the
+        runs.  Extension of the reference API."""
+        q, edges, tl = self._hist_query(relation, 'complete_curve', edges, rows, exclude, positives, 'positives', block_rows)
+        if tl is None:
+            raise DataFusionError("positives must be a scipy.sparse matrix, not None")
+        n_edges = int(n_edges)
+        if n_edges < 1:
+            raise DataFusionError("complete_curve: n_edges = %d, at least 1 is needed" % n_edges)
+        given = [tl(blk) for _, blk, _ in q.blocks()]
+        n_given = int(sum(p[-1] for p, _ in given))
+
+        def one(r):
+            G1, comp = self._completer(relation, r, dtype)
+            e = edges
+            if e is None:
+                prow = np.concatenate([np.repeat(blk, np.diff(p)) for (_, blk, _), (p, _) in zip(q.blocks(), given)] + [np.zeros(0, dtype=np.int64)])
+                pcol = np.concatenate([i for _, i in given] + [np.zeros(0, dtype=np.int32)])
+                s = comp.entries(G1, prow, pcol).astype(comp.npd)
+                s = np.sort(s[~np.isnan(s)])
+                e = np.unique(s[np.unique(np.linspace(0, s.size - 1, min(n_edges, s.size)).round().astype(np.int64))]) if s.size else np.zeros(1)
+            e = np.asarray(e, dtype=np.float64).astype(comp.npd).astype(np.float64)
+            counts, pos, _ = comp.histogram(self._hist_blocks(q, G1, tl), e)
+            if pos is None:                             # (no row at all)
+                pos = np.zeros_like(counts)
+            return curve_of(e, counts, pos, n_given)
+        return self._per_run(one, run)
+
+
+CompletionCurve = collections.namedtuple('CompletionCurve', 'thresholds predicted true_positives n_candidates n_positives '
+                                         'n_positives_given precision recall fpr auroc')
+
+
+def auroc_bounds(counts, target_counts):
+    """``(lo, hi)`` as ``fractions.Fraction``, or None without a positive or without a negative: the area under the ROC curve
+    of a histogram with ``target_counts[b]`` positives among the ``counts[b]`` scores of bin ``b`` (bins ascending), with every
+    negative of a bin ahead of every positive of it, and the reverse.  Python integers throughout."""
+    import fractions
+    pos = [int(v) for v in target_counts]
+    neg = [int(c) - p for c, p in zip(counts, pos)]
+    P, N = sum(pos), sum(neg)
+    if P == 0 or N == 0:
+        return None
+    below = lo = tie = 0
+    for p, n in zip(pos, neg):
+        lo += p * below
+        tie += p * n
+        below += n
+    return fractions.Fraction(lo, P * N), fractions.Fraction(lo + tie, P * N)
+
+
+def curve_of(thresholds, counts, target_counts, n_positives_given):
+    """The ``CompletionCurve`` of one histogram (``counts`` / ``target_counts`` int64 [len(thresholds) + 1])."""
+    predicted = np.cumsum(counts[::-1])[::-1][1:].astype(np.int64)
+    tp = np.cumsum(target_counts[::-1])[::-1][1:].astype(np.int64)
+    cands, P = int(counts.sum()), int(target_counts.sum())
+    N = cands - P
+    nan = np.full(predicted.size, np.nan)
+    precision = np.divide(tp, predicted, out=nan.copy(), where=predicted > 0)
+    recall = tp / float(P) if P else nan.copy()
+    fpr = (predicted - tp) / float(N) if N else nan.copy()
+    bounds = auroc_bounds(counts, target_counts)
+    auroc = (float('nan'), float('nan')) if bounds is None else (float(bounds[0]), float(bounds[1]))
+    return CompletionCurve(np.asarray(thresholds, dtype=np.float64), predicted, tp, cands, P, int(n_positives_given), precision, recall,
+                           fpr, auroc)
