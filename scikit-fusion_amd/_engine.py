@@ -4,7 +4,6 @@
 _dfmf.py:330), keeps every matrix resident in HBM for the whole ``max_iter`` loop and copies
 ``G`` / ``S`` back once at the end (or per iteration when a callback is installed).
 """
-import os
 import ctypes as C
 
 import numpy as np
@@ -13,6 +12,9 @@ from . import _native as nat
 # the consuming side of a fitted model has a module of its own; its names stay importable from here
 from ._complete import (DeviceMatrix, DeviceReconstructor, _device_gemm, chain_backbone, device_reconstruct,      # noqa: F401
                         AboveLimit, digit_walk, score_of_key, DeviceCompleter)
+# ... and so has the communicator glue of the sharded fits (the RCCL rendezvous, its cache, the torch.distributed transport)
+from ._comm import (_all_reduce_sum, _exchange, _RCCL, _group_token, release_rccl_comms, comm_info,              # noqa: F401
+                    _shared_rccl_comm, _torch_collective)
 
 
 class PackedMask(object):
@@ -298,80 +300,6 @@ def upload_matrix(data, dtype='f64', runtime=None):
     return DeviceMatrix(rt.mem.from_host(up), arr.shape)
 
 
-def _all_reduce_sum(t):
-    """Sum a tensor view over the process group (RCCL for GPU tensors; a gloo group -- CPU tests,
-    single-GPU smoke runs -- stages GPU tensors through the host)."""
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
-        return
-    if t.is_cuda and dist.get_backend() == 'gloo':
-        h = t.cpu()
-        dist.all_reduce(h, op=dist.ReduceOp.SUM)
-        t.copy_(h)
-    else:
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-
-
-def _exchange(mem, tensors, reduce=None):
-    """All-reduce(sum) the given workspace views between two stages of a sharded iteration.
-    RCCL: issued on the engine's own stream (stream order replaces host synchronisation).  gloo
-    (CPU tests, single-GPU smoke runs) or a caller-supplied `reduce`: bracketed by device syncs."""
-    import os
-    tensors = [t for t in tensors if t is not None]
-    if not tensors:
-        return
-    if reduce is None:
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()):
-            return
-        if dist.get_world_size() <= 1 and not os.environ.get('SKF_FORCE_COLLECTIVES'):
-            return
-        if tensors[0].is_cuda and dist.get_backend() != 'gloo' and hasattr(mem, 'stream_scope'):
-            with mem.stream_scope():
-                for t in tensors:
-                    dist.all_reduce(t, op=dist.ReduceOp.SUM)
-            return
-        reduce = _all_reduce_sum
-    mem.synchronize()
-    for t in tensors:
-        reduce(t)
-    mem.synchronize()
-
-
-_RCCL = {}          # (rank, world, identity of the default process group) -> communicator handle (None: RCCL not bound on every rank)
-
-
-def _group_token(dist):
-    """What tells one default process group from the next one with the same (rank, world): the name torch gives every group
-    it creates, else the identity of the group object."""
-    try:
-        pg = dist.distributed_c10d._get_default_group()
-        return getattr(pg, 'group_name', None) or id(pg)
-    except Exception:
-        return None
-
-
-def release_rccl_comms(runtime=None):
-    """Destroy the RCCL communicators this process created (atexit; call it before destroy_process_group when the process
-    goes on to create another group -- a later group with the same rank / world never reuses a handle of an earlier one
-    either way: the cache is keyed on the group)."""
-    for key, comm in list(_RCCL.items()):
-        _RCCL.pop(key, None)
-        if comm:
-            try:
-                (runtime or nat.get_runtime()).lib.skf_comm_destroy(comm)
-            except Exception:
-                pass
-
-
-def comm_info(rt, comm):
-    """dict(rank, world, transport: 'single' | 'rccl' | 'callback' | 'null', transport_ranks) of a communicator handle
-    (skf_comm_info; transport_ranks of an RCCL communicator is what ncclCommCount reports)."""
-    r, w, k, n = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
-    rt.call('skf_comm_info', comm, C.byref(r), C.byref(w), C.byref(k), C.byref(n))
-    return {'rank': r.value, 'world': w.value, 'transport': nat.COMM_KIND[k.value], 'transport_ranks': n.value}
-
-
 def launch_count(runtime=None):
     """Kernel launches this thread has issued through the library so far (skf_launch_count); callers take differences."""
     rt = runtime or nat.get_runtime()
@@ -389,122 +317,19 @@ def split_clamps(runtime=None):
     return n.value
 
 
-def _shared_rccl_comm(rt, dist):
-    """The process's RCCL communicator for the CURRENT default process group (created once per group, reused by every plan
-    and restart), or None when it cannot be had on EVERY rank -- all ranks then agree on the callback path instead of some
-    blocking in a broadcast the others never reach.  A failure is remembered for that group only.  Collective: every rank
-    of the group must call it."""
-    import torch
-    rank, world = dist.get_rank(), dist.get_world_size()
-    key = (rank, world, _group_token(dist))
-    if key in _RCCL:
-        return _RCCL[key]
-    # (communicators made for EARLIER process groups stay alive until release_rccl_comms() / process exit: a DevicePlan created
-    #  under such a group may still hold the handle, and a destroyed handle handed to skf_iterate_dist is a use after free --
-    #  a process that cycles through many groups keeps one idle communicator per group, which is the cheaper mistake)
-    if not getattr(_shared_rccl_comm, '_atexit', False):
-        import atexit
-        atexit.register(release_rccl_comms)
-        _shared_rccl_comm._atexit = True
-    import logging
-    log = logging.getLogger('skfusion_amd')
-    where = 'cuda' if dist.get_backend() != 'gloo' else 'cpu'
+class _RowBlock(object):
+    """The row-block dict a relation may carry as its fifth element (`_distributed.partition_rows`, `owned_plan`), read once:
+    every key but `n_rows` may be left out and then stands for the value here.  `binary` None: no verdict on the whole
+    relation came with the block, the data decides; `entries`: 'unknown' | 'zero' for a relation given as its entries."""
 
-    def all_agree(ok):
-        flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device=where)
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        return int(flag.item()) == 1
-
-    # 1. every rank checks LOCALLY that it can resolve RCCL (ncclGetUniqueId needs no peer) and the ranks agree BEFORE anyone
-    #    enters ncclCommInitRank: that call is a rendezvous, and a rank that cannot load the library would leave the others
-    #    waiting in it until the transport's own timeout
-    mine, ident = None, [None]
-    try:
-        buf = (C.c_char * 128)()
-        rt.call('skf_comm_unique_id', buf)
-        mine = bytes(buf)
-    except nat.SkfNativeError as exc:
-        log.warning('RCCL not bound on rank %d (%s): collectives through torch.distributed', rank, exc)
-    if not all_agree(mine is not None):
-        _RCCL[key] = None
-        return None
-    if rank == 0:
-        ident[0] = mine
-    dist.broadcast_object_list(ident, src=0)
-    # 2. the rendezvous itself, bounded: a rank still inside ncclCommInitRank after SKF_COMM_TIMEOUT seconds (default 60)
-    #    gives up loudly instead of hanging until the NCCL watchdog fires
-    import threading
-    comm, box = nat._P(), {}
-
-    device = torch.cuda.current_device() if torch.cuda.is_available() else None
-
-    def create():
-        try:
-            if device is not None:
-                torch.cuda.set_device(device)       # the current device is per THREAD: RCCL binds the communicator to it
-            raw = (C.c_char * 128).from_buffer_copy(ident[0])
-            rt.call('skf_comm_create', raw, rank, world, C.byref(comm))
-            box['ok'] = True
-        except nat.SkfNativeError as exc:
-            box['error'] = exc
-    limit = float(os.environ.get('SKF_COMM_TIMEOUT', '60'))
-    th = threading.Thread(target=create, name='skf_comm_create', daemon=True)
-    th.start()
-    th.join(limit)
-    if th.is_alive():
-        # (the peers that did get through are now in the all_agree all-reduce below and would wait there for this rank: the
-        #  caller must treat this error as fatal for the process group -- let it propagate and the launcher tears the job down)
-        raise RuntimeError('skf_comm_create: rank %d of %d still waits in ncclCommInitRank after %.0f s -- the ranks disagree '
-                           '(a peer failed or never called it); SKF_COMM_TIMEOUT sets the limit' % (rank, world, limit))
-    ok = bool(box.get('ok'))
-    if not ok:
-        log.warning('skf_comm_create failed on rank %d (%s)', rank, box.get('error'))
-    if not all_agree(ok):
-        if ok:
-            rt.lib.skf_comm_destroy(comm)
-        _RCCL[key] = None
-        return None
-    _RCCL[key] = comm
-    return comm
-
-
-def _torch_collective(mem, ws, dist, rank, world):
-    """skf_collective_fn over torch.distributed on views of the workspace `ws`: the transport of gloo groups (CPU tests,
-    smoke runs: device views are staged through the host) and the fall-back of a group whose backend takes device tensors
-    (nccl = RCCL) when the library could not bind RCCL itself on every rank, or `force_callback` -- there the collective
-    runs on the device view directly (the nccl backend rejects host tensors)."""
-    def collective(user, op, buf, count, dtype, stream):
-        try:
-            import torch
-            if dtype == nat.SKF_BF16:           # bf16 rows travel as bytes (all-gather only; gloo has no 16-bit integer type)
-                npd, count = np.uint8, count * 2
-            else:
-                npd = nat.NP_DTYPE[dtype]
-            es = np.dtype(npd).itemsize
-            n = count * (1 if op == 0 else world)
-            view = mem.as_tensor(ws, int(buf) - ws.ptr, n * es, npd)
-            mem.synchronize()
-            on_device = view.is_cuda and dist.get_backend() != 'gloo'
-            host = view if on_device else (view.cpu() if view.is_cuda else view)
-            if op in (0, 1):              # (reduce-scatter: the all-reduce of the whole buffer covers the owned range)
-                dist.all_reduce(host, op=dist.ReduceOp.SUM)
-            elif on_device:
-                dist.all_gather_into_tensor(host, host[rank * count:(rank + 1) * count].clone())
-            else:
-                parts = [torch.empty(count, dtype=host.dtype) for _ in range(world)]
-                dist.all_gather(parts, host[rank * count:(rank + 1) * count].clone())
-                host = torch.cat(parts)
-            if on_device:
-                torch.cuda.synchronize()      # the backend's own stream: the engine's next launch must see the result
-            elif view.is_cuda or host is not view:
-                view.copy_(host)
-            mem.synchronize()
-            return 0
-        except Exception:                 # never unwind through the C frames
-            import traceback
-            traceback.print_exc()
-            return 1
-    return collective
+    def __init__(self, block):
+        self.row_begin, self.n_rows = block.get('row_begin', 0), int(block['n_rows'])
+        self.absent = bool(block.get('absent', False))
+        self.col_side = bool(block.get('col_side', True))
+        self.masked = bool(block.get('masked', False))
+        self.known_lists = bool(block.get('known_lists', False))
+        self.entries = block.get('entries')
+        self.binary = block.get('binary')
 
 
 class DevicePlan(object):
@@ -540,164 +365,35 @@ class DevicePlan(object):
         self.relations = relations
         self.handle = nat._P()
         self._keep, self._keep_rel = [], []
-        mem, lib = self.rt.mem, self.rt.lib
+        self.owned = bool(owned)
+        # (what the describing methods below read)
+        self._n, self._variant, self._target, self._part, self._sparse_known = n_obj, variant, target, part, sparse_known
+        mem = self.rt.mem
 
         tdesc = (nat.TypeDesc * len(self.types))()
         for k in range(len(self.types)):
             tdesc[k].n_obj, tdesc[k].rank = self.n_obj[k], self.rank[k]
         rdesc = (nat.RelationDesc * max(len(relations), 1))()
-        csr = []                                         # (relation, DeviceKnownEntries): skf_plan_set_known_entries
         self.local_rows = []                             # rows of every relation this plan holds (its block, or all of them)
         # relations with missing values kept as lists: {relation: the constant beneath its unknown entries (KnownEntries.fill),
         # or None for entries plus rank one} -- what the column-mean initialisers need beside the lists (the `_filled` entry points)
         self.rel_over_fill = {}
+        csr = []                                         # (relation, DeviceKnownEntries): skf_plan_set_known_entries
         for k, rel in enumerate(relations):
-            i, j, data, mask = rel[:4]
-            block = rel[4] if len(rel) > 4 else None
-            rdesc[k].row_type, rdesc[k].col_type = self.index[i], self.index[j]
-            self.local_rows.append(int(block['n_rows']) if block is not None else n_obj[i])
-            if block is not None and block.get('absent') and block.get('entries'):
-                # row ownership, a relation given as its entries, no row of it here: no lists, only the flags
-                if not owned:
-                    raise ValueError('relation (%s,%s): known entries take a row block under row ownership only' % (i, j))
-                rdesc[k].flags = nat.SKF_REL_ABSENT | (nat.SKF_REL_SPARSE_CSR if block['entries'] == 'zero'
-                                                       else nat.SKF_REL_KNOWN_CSR)
-                continue
-            if isinstance(data, (KnownEntries, DeviceKnownEntries)):
-                # the known entries only (SKF_REL_KNOWN_CSR), or the stored entries of a relation that is zero elsewhere
-                # (SKF_REL_SPARSE_CSR): no dense form, no mask; always kept as lists.  Row ownership: the CSR of the owned
-                # rows, indptr rebased to 0, columns over the whole column type
-                if mask is not None or (block is not None and not owned):
-                    raise ValueError('relation (%s,%s): known entries take no mask and no row block' % (i, j))
-                if tuple(data.shape) != (self.local_rows[k], n_obj[j]):
-                    raise ValueError('relation (%s,%s) dimension mismatch: %r vs object counts (%d,%d)'
-                                     % (i, j, tuple(data.shape), self.local_rows[k], n_obj[j]))
-                if block is not None:
-                    rdesc[k].row_begin, rdesc[k].n_rows = int(block['row_begin']), self.local_rows[k]
-                dev = data if isinstance(data, DeviceKnownEntries) else upload_known_entries(data, self.dtype, mem)
-                self._keep_rel.append(dev)
-                if variant == nat.SKF_TRANSFORM and dev.unstored == 'zero':
-                    # a fold-in: the stored entries compressed along the target's side (SKF_REL_FOLD_CSR)
-                    if dev.row_fill is not None:
-                        raise ValueError('relation (%s,%s): a filled relation with missing values is for fits, not fold-ins' % (i, j))
-                    if dev.by_col != (j == target and i != target):
-                        raise ValueError('relation (%s,%s): a fold-in takes the lists compressed along the target %s'
-                                         % (i, j, target))
-                    rdesc[k].flags |= nat.SKF_REL_FOLD_CSR
-                    rdesc[k].known_bound = dev.known
-                    csr.append((k, dev))
-                    continue
-                if dev.by_col:
-                    raise ValueError('relation (%s,%s): lists compressed along the column type are for fold-ins' % (i, j))
-                rdesc[k].flags |= nat.SKF_REL_SPARSE_CSR if dev.unstored == 'zero' else nat.SKF_REL_KNOWN_CSR
-                if dev.row_fill is not None:            # a filled relation with missing values: entries plus rank one
-                    rdesc[k].flags |= nat.SKF_REL_FILL_RANK1
-                rdesc[k].known_bound = dev.known
+            dev = self._describe_relation(k, rel, rdesc[k])
+            if dev is not None:
                 csr.append((k, dev))
-                if dev.unstored != 'zero':
-                    self.rel_over_fill[k] = float(dev.fill)
-                elif dev.row_fill is not None:
-                    self.rel_over_fill[k] = None
-                continue
-            rows_here = n_obj[i]
-            if block is not None:
-                rows_here = int(block['n_rows'])
-                rdesc[k].row_begin, rdesc[k].n_rows = int(block['row_begin']), rows_here
-                rdesc[k].flags = ((nat.SKF_REL_ABSENT if block.get('absent') else 0) |
-                                  (0 if block.get('col_side', True) else nat.SKF_REL_NO_COL_SIDE) |
-                                  (nat.SKF_REL_MASKED if block.get('masked') else 0))
-                if block.get('absent'):
-                    if block.get('known_lists'):
-                        rdesc[k].flags |= nat.SKF_REL_KNOWN_LISTS
-                    continue
-            if isinstance(data, DeviceMatrix):
-                arr, buf, ld = data, data.buf, data.ld
-                if data.binary and mask is None and self.dtype == nat.SKF_BF16:
-                    rdesc[k].flags |= nat.SKF_REL_BINARY
-            else:
-                arr = np.ascontiguousarray(data, dtype=self.np_dtype)
-                if arr.ndim != 2:
-                    raise ValueError('relation %d is not a matrix' % k)
-                # SKF_BF16: a 0 / 1 relation is kept as a bitmap on the device (1/16 of the bytes per iteration).  A row
-                # block carries the verdict on the WHOLE relation (`binary`), so that every rank of a row-sharded fit
-                # takes the same contraction path for it
-                if self.dtype == nat.SKF_BF16 and mask is None:
-                    binary = block['binary'] if (block is not None and 'binary' in block) else is_binary_matrix(arr)
-                    if binary:
-                        rdesc[k].flags |= nat.SKF_REL_BINARY
-                # SKF_BF16: relations are handed over as bf16 bit patterns
-                up = nat.to_bf16_bits(arr) if self.dtype == nat.SKF_BF16 else arr
-                buf, ld = mem.from_host(up), arr.shape[1]
-            if tuple(arr.shape) != (rows_here, n_obj[j]):
-                raise ValueError('relation (%s,%s) dimension mismatch: %r vs object counts (%d,%d)'
-                                 % (i, j, tuple(arr.shape), rows_here, n_obj[j]))
-            self._keep_rel.append(buf)
-            rdesc[k].data, rdesc[k].ld = buf.ptr, ld
-            if isinstance(mask, PackedMask):             # packed bits already in HBM (upload_graph)
-                if tuple(mask.shape) != tuple(arr.shape):
-                    raise ValueError('mask shape mismatch for relation (%s,%s)' % (i, j))
-                self._keep_rel.append(mask.buf)
-                rdesc[k].mask, rdesc[k].mask_ld = mask.buf.ptr, mask.ld
-                rdesc[k].flags |= nat.SKF_REL_MASK_BITS
-                rdesc[k].known_bound = mask.known
-            elif isinstance(mask, DeviceMatrix):         # uint8 bytes already in HBM (device-generated data)
-                if tuple(mask.shape) != tuple(arr.shape):
-                    raise ValueError('mask shape mismatch for relation (%s,%s)' % (i, j))
-                self._keep_rel.append(mask.buf)
-                rdesc[k].mask, rdesc[k].mask_ld = mask.buf.ptr, mask.ld
-                rdesc[k].known_bound = mask.known
-            elif mask is not None:
-                pm = pack_mask(mask, mem)
-                if pm.shape != arr.shape:
-                    raise ValueError('mask shape mismatch for relation (%s,%s)' % (i, j))
-                self._keep_rel.append(pm.buf)
-                rdesc[k].mask, rdesc[k].mask_ld = pm.buf.ptr, pm.ld
-                rdesc[k].flags |= nat.SKF_REL_MASK_BITS
-                rdesc[k].known_bound = pm.known
-            if sparse_known is False or (block is not None and not block.get('known_lists')):
-                rdesc[k].known_bound = 0
-            if block is not None and block.get('known_lists'):       # (row ownership: decided for all ranks alike by the caller)
-                rdesc[k].flags |= nat.SKF_REL_KNOWN_LISTS
         hdesc = (nat.ThetaDesc * max(len(thetas), 1))()
-        theta_csr = []                                   # (constraint, DeviceKnownEntries): skf_plan_set_constraint_entries
         self.theta_rows = []                             # rows of every constraint kept here (the owned rows of a slice, or all)
+        theta_csr = []                                   # (constraint, DeviceKnownEntries): skf_plan_set_constraint_entries
         for k, (t, data) in enumerate(thetas):
-            self.theta_rows.append(int(n_obj[t]))
-            if isinstance(data, (KnownEntries, DeviceKnownEntries)):
-                # the stored entries of a constraint that is zero elsewhere (skf_theta_desc.data == NULL): no dense form,
-                # always kept as lists; values in the master type
-                if data.unstored != 'zero' or data.by_col:
-                    raise ValueError("constraint on %s: entries need unstored='zero', compressed along the rows" % (t,))
-                if owned:           # the rows [begin, begin + count) this part owns, over all columns
-                    self.theta_rows[k] = owned_rows(self.dtype, n_obj[t], part[0], part[1], self.rt)[1]
-                if tuple(data.shape) != (self.theta_rows[k], n_obj[t]):
-                    raise ValueError('constraint on %s dimension mismatch: %r vs (%d,%d)'
-                                     % (t, tuple(data.shape), self.theta_rows[k], n_obj[t]))
-                dev = data if isinstance(data, DeviceKnownEntries) else upload_known_entries(data, self.dtype, mem)
-                self._keep.append(dev)
-                hdesc[k].type, hdesc[k].data, hdesc[k].ld, hdesc[k].nnz = self.index[t], None, 0, dev.known
+            dev = self._describe_constraint(k, t, data, hdesc[k])
+            if dev is not None:
                 theta_csr.append((k, dev))
-                continue
-            if isinstance(data, DeviceMatrix):           # master dtype, already in HBM
-                if tuple(data.shape) != (n_obj[t], n_obj[t]):
-                    raise ValueError('constraint on %s dimension mismatch' % (t,))
-                self._keep.append(data.buf)
-                hdesc[k].type, hdesc[k].data, hdesc[k].ld = self.index[t], data.buf.ptr, data.ld
-                hdesc[k].nnz = _sparse_bound(getattr(data, 'nnz', 0), n_obj[t])
-                continue
-            arr = np.ascontiguousarray(data, dtype=self.np_dtype)
-            if arr.shape != (n_obj[t], n_obj[t]):
-                raise ValueError('constraint on %s dimension mismatch' % (t,))
-            buf = mem.from_host(arr)
-            self._keep.append(buf)
-            hdesc[k].type, hdesc[k].data, hdesc[k].ld = self.index[t], buf.ptr, arr.shape[1]
-            # a sparse constraint (lambda I, a few must-link pairs per object, dicty's ppi) is kept as CSR on the device
-            hdesc[k].nnz = _sparse_bound(int(np.count_nonzero(arr)), n_obj[t])
         opt = nat.Options(self.dtype, variant, self.index[target] if target is not None else -1,
                           nat.SKF_ENGINE_MFMA if engine is None else engine,
                           part[0] if part else 0, part[1] if part else 0,
                           (nat.SKF_OPT_OWNED_ROWS | (nat.SKF_OPT_THETA_OWNED_ROWS if theta_csr else 0)) if owned else 0)
-        self.owned = bool(owned)
         self.rt.call('skf_plan_create', len(self.types), tdesc, len(relations), rdesc, len(thetas),
                      hdesc, C.byref(opt), C.byref(self.handle))
         for k, dev in csr:
@@ -712,6 +408,153 @@ class DevicePlan(object):
         self.ws = mem.empty(nbytes.value)
         self.rt.call('skf_plan_bind_workspace', self.handle, self.ws.ptr, nbytes.value, self.stream)
         self._scalar = mem.empty(8)
+
+    # -- the descriptors: one method per kind of input; each returns the lists to hand over after skf_plan_create, or None --
+    def _describe_relation(self, k, rel, rd):
+        i, j, data, mask = rel[:4]
+        blk = _RowBlock(rel[4]) if len(rel) > 4 and rel[4] is not None else None
+        rd.row_type, rd.col_type = self.index[i], self.index[j]
+        self.local_rows.append(blk.n_rows if blk is not None else self._n[i])
+        if blk is not None and blk.absent and blk.entries:
+            return self._relation_without_entries_here(rd, i, j, blk)
+        if isinstance(data, (KnownEntries, DeviceKnownEntries)):
+            return self._relation_entries(k, rd, i, j, data, mask, blk)
+        return self._relation_dense(k, rd, i, j, data, mask, blk)
+
+    def _check_shape(self, k, i, j, shape):
+        """The one dimension check of a relation: the rows this plan holds of it, all columns."""
+        rows, cols = self.local_rows[k], self._n[j]
+        if tuple(shape) != (rows, cols):
+            raise ValueError('relation (%s,%s) dimension mismatch: %r vs object counts (%d,%d)' % (i, j, tuple(shape), rows, cols))
+
+    def _relation_without_entries_here(self, rd, i, j, blk):
+        """Row ownership, a relation given as its entries, no row of it here: no lists, only the flags."""
+        if not self.owned:
+            raise ValueError('relation (%s,%s): known entries take a row block under row ownership only' % (i, j))
+        rd.flags = nat.SKF_REL_ABSENT | (nat.SKF_REL_SPARSE_CSR if blk.entries == 'zero' else nat.SKF_REL_KNOWN_CSR)
+
+    def _relation_entries(self, k, rd, i, j, data, mask, blk):
+        """The known entries only (SKF_REL_KNOWN_CSR), or the stored entries of a relation that is zero elsewhere
+        (SKF_REL_SPARSE_CSR; with fill vectors SKF_REL_FILL_RANK1; in a fold-in SKF_REL_FOLD_CSR): no dense form, no mask;
+        always kept as lists.  Row ownership: the CSR of the owned rows, indptr rebased to 0, columns over the whole column
+        type."""
+        variant, target = self._variant, self._target
+        if mask is not None or (blk is not None and not self.owned):
+            raise ValueError('relation (%s,%s): known entries take no mask and no row block' % (i, j))
+        self._check_shape(k, i, j, data.shape)
+        if blk is not None:
+            rd.row_begin, rd.n_rows = int(blk.row_begin), self.local_rows[k]
+        dev = data if isinstance(data, DeviceKnownEntries) else upload_known_entries(data, self.dtype, self.rt.mem)
+        self._keep_rel.append(dev)
+        rd.known_bound = dev.known
+        if variant == nat.SKF_TRANSFORM and dev.unstored == 'zero':
+            # a fold-in: the stored entries compressed along the target's side
+            if dev.row_fill is not None:
+                raise ValueError('relation (%s,%s): a filled relation with missing values is for fits, not fold-ins' % (i, j))
+            if dev.by_col != (j == target and i != target):
+                raise ValueError('relation (%s,%s): a fold-in takes the lists compressed along the target %s'
+                                 % (i, j, target))
+            rd.flags |= nat.SKF_REL_FOLD_CSR
+            return dev
+        if dev.by_col:
+            raise ValueError('relation (%s,%s): lists compressed along the column type are for fold-ins' % (i, j))
+        rd.flags |= nat.SKF_REL_SPARSE_CSR if dev.unstored == 'zero' else nat.SKF_REL_KNOWN_CSR
+        if dev.unstored != 'zero':
+            self.rel_over_fill[k] = float(dev.fill)
+        elif dev.row_fill is not None:                  # a filled relation with missing values: entries plus rank one
+            rd.flags |= nat.SKF_REL_FILL_RANK1
+            self.rel_over_fill[k] = None
+        return dev
+
+    def _relation_dense(self, k, rd, i, j, data, mask, blk):
+        """A dense relation, or the rows of its block: a host array (uploaded here; SKF_BF16: as bf16 bit patterns) or a
+        DeviceMatrix, with its mask in any of the three forms."""
+        if blk is not None:
+            rd.row_begin, rd.n_rows = int(blk.row_begin), blk.n_rows
+            rd.flags = ((nat.SKF_REL_ABSENT if blk.absent else 0) | (0 if blk.col_side else nat.SKF_REL_NO_COL_SIDE) |
+                        (nat.SKF_REL_MASKED if blk.masked else 0) |
+                        (nat.SKF_REL_KNOWN_LISTS if blk.known_lists else 0))      # (row ownership: decided for all ranks alike by the caller)
+            if blk.absent:
+                return None
+        bf16_bitmap = self.dtype == nat.SKF_BF16 and mask is None     # a 0 / 1 relation is kept as a bitmap (1/16 of the bytes)
+        if isinstance(data, DeviceMatrix):
+            shape, buf, ld, binary = data.shape, data.buf, data.ld, data.binary
+        else:
+            arr = np.ascontiguousarray(data, dtype=self.np_dtype)
+            if arr.ndim != 2:
+                raise ValueError('relation %d is not a matrix' % k)
+            # A row block carries the verdict on the WHOLE relation (`binary`), so that every rank of a row-sharded fit
+            # takes the same contraction path for it
+            binary = bf16_bitmap and (blk.binary if blk is not None and blk.binary is not None else is_binary_matrix(arr))
+            # SKF_BF16: relations are handed over as bf16 bit patterns
+            buf = self.rt.mem.from_host(nat.to_bf16_bits(arr) if self.dtype == nat.SKF_BF16 else arr)
+            shape, ld = arr.shape, arr.shape[1]
+        if binary and bf16_bitmap:
+            rd.flags |= nat.SKF_REL_BINARY
+        self._check_shape(k, i, j, shape)
+        self._keep_rel.append(buf)
+        rd.data, rd.ld = buf.ptr, ld
+        if mask is not None:
+            mbuf, rd.mask_ld, rd.known_bound, is_bits = self._mask_buffer(mask, shape, i, j)
+            self._keep_rel.append(mbuf)
+            rd.mask = mbuf.ptr
+            if is_bits:
+                rd.flags |= nat.SKF_REL_MASK_BITS
+        if self._sparse_known is False or (blk is not None and not blk.known_lists):
+            rd.known_bound = 0
+        return None
+
+    def _mask_buffer(self, mask, shape, i, j):
+        """(buffer, ld, known entries, is_bits) of a mask in any of its three forms: packed bits already in HBM
+        (PackedMask: upload_graph), uint8 bytes already in HBM (DeviceMatrix: device-generated data), or a host array,
+        packed and uploaded here."""
+        on_device = isinstance(mask, (PackedMask, DeviceMatrix))
+        m = mask if on_device else pack_mask(mask, self.rt.mem)
+        if tuple(m.shape) != tuple(shape):
+            raise ValueError('mask shape mismatch for relation (%s,%s)' % (i, j))
+        return m.buf, m.ld, m.known, not isinstance(mask, DeviceMatrix)
+
+    def _describe_constraint(self, k, t, data, hd):
+        n = self._n[t]
+        self.theta_rows.append(int(n))
+        hd.type = self.index[t]
+        if isinstance(data, (KnownEntries, DeviceKnownEntries)):
+            return self._constraint_entries(k, hd, t, n, data)
+        if isinstance(data, DeviceMatrix):
+            return self._constraint_device(hd, t, n, data)
+        return self._constraint_host(hd, t, n, data)
+
+    def _constraint_entries(self, k, hd, t, n, data):
+        """The stored entries of a constraint that is zero elsewhere (skf_theta_desc.data == NULL): no dense form, always
+        kept as lists; values in the master type.  Row ownership: the rows [begin, begin + count) this part owns, over all
+        columns."""
+        if data.unstored != 'zero' or data.by_col:
+            raise ValueError("constraint on %s: entries need unstored='zero', compressed along the rows" % (t,))
+        if self.owned:
+            self.theta_rows[k] = owned_rows(self.dtype, n, self._part[0], self._part[1], self.rt)[1]
+        if tuple(data.shape) != (self.theta_rows[k], n):
+            raise ValueError('constraint on %s dimension mismatch: %r vs (%d,%d)' % (t, tuple(data.shape), self.theta_rows[k], n))
+        dev = data if isinstance(data, DeviceKnownEntries) else upload_known_entries(data, self.dtype, self.rt.mem)
+        self._keep.append(dev)
+        hd.data, hd.ld, hd.nnz = None, 0, dev.known
+        return dev
+
+    def _constraint_device(self, hd, t, n, data):
+        """A dense constraint already in HBM, master dtype; `nnz` as its maker counted it (0: nobody did)."""
+        if tuple(data.shape) != (n, n):
+            raise ValueError('constraint on %s dimension mismatch' % (t,))
+        self._keep.append(data.buf)
+        hd.data, hd.ld, hd.nnz = data.buf.ptr, data.ld, _sparse_bound(getattr(data, 'nnz', 0), n)
+
+    def _constraint_host(self, hd, t, n, data):
+        """A dense constraint on the host.  A sparse one (lambda I, a few must-link pairs per object, dicty's ppi) is kept
+        as CSR on the device: `nnz` says so."""
+        arr = np.ascontiguousarray(data, dtype=self.np_dtype)
+        if arr.shape != (n, n):
+            raise ValueError('constraint on %s dimension mismatch' % (t,))
+        buf = self.rt.mem.from_host(arr)
+        self._keep.append(buf)
+        hd.data, hd.ld, hd.nnz = buf.ptr, arr.shape[1], _sparse_bound(int(np.count_nonzero(arr)), n)
 
     def release_relation_data(self):
         """SKF_BF16: the relations (and every engine's masks) were copied into the engine's own layout at

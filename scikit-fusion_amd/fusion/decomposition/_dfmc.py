@@ -4,7 +4,7 @@
 iteration (_dfmc.py:287-292, :319-325).  The relation matrices passed in are never modified
 (the engine completes a device-side copy)."""
 from ... import _native as nat
-from ._dfmf import run_fit, run_fit_sharded, run_fit_rows, run_fit_owned, refuse_constraint_entries
+from ._dfmf import run_fit, run_fit_sharded, run_fit_rows, run_fit_owned, refuse_constraint_entries, _fit_by_shard      # noqa: F401
 
 
 def _expand_known_entries(R, M):
@@ -24,13 +24,8 @@ def dfmc(R, M, Theta, obj_types, obj_type2rank, max_iter=10, init_type="random_v
          random_state=None, n_jobs=1, dtype='f64', G0=None, engine=None, shard=None, sparse_constraints=False):
     """Data fusion by matrix completion -- drop-in for reference ``dfmc`` (_dfmc.py:181).  Constraints given as their entries:
     as in ``_dfmf.dfmf`` (shard None / 'runs'; shard='owned' with ``sparse_constraints=True``)."""
-    if shard in ('relations', 'rows', 'owned'):
-        refuse_constraint_entries(Theta, shard, sparse_constraints)
-        if shard != 'owned':                    # (an ownership-sharded fit slices the entries by rows; the others take the mask form)
-            R, M = _expand_known_entries(R, M)
-        fit = {'relations': run_fit_sharded, 'rows': run_fit_rows, 'owned': run_fit_owned}[shard]
-        return fit(nat.SKF_DFMC, R, M, Theta, obj_types, obj_type2rank, max_iter,
-                   init_type, random_state, dtype, G0, engine, stopping, stopping_system, compute_err, callback)
-    return run_fit(nat.SKF_DFMC, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type,
-                   stopping, stopping_system, verbose, compute_err, callback, random_state,
-                   dtype, G0, engine)
+    if shard in ('relations', 'rows'):          # (an ownership-sharded fit slices the entries by rows; these take the mask form)
+        R, M = _expand_known_entries(R, M)
+    return _fit_by_shard(nat.SKF_DFMC, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, stopping,
+                         stopping_system, verbose, compute_err, callback, random_state, dtype, G0, engine, shard,
+                         sparse_constraints)

@@ -8,11 +8,13 @@ Extra keyword-only engine options (defaults keep the reference behaviour):
   G0      dict {(t,t): ndarray} overriding the initialiser (warm start / parity tests), or a `_init.DeviceInit`: the
           draws of a column-mean initialiser, which the bound plan turns into its factors on the device (whole fits only)
 """
+import collections
 import logging
 
 import numpy as np
 
 from ... import _native as nat
+from ..._distributed import world, partition_relations, gather_backbones, sum_over_ranks
 from ..._engine import DevicePlan, flatten_relations, flatten_thetas, count_objects
 from ._init import initialize, host_view, DeviceInit
 
@@ -168,6 +170,117 @@ def owned_plan(variant, rel_list, theta_list, obj_types, n_obj, obj_type2rank, d
                       part=(rank, size), owned=True)
 
 
+# What tells one way of sharing a fit out from another -- everything else is `_fit`, once.  All six take the plan first:
+#   make_plan(variant, rel_list, theta_list, obj_types, n_obj, obj_type2rank, dtype, engine) -> the plan of this process
+#   attach(plan)                   its communicator, if any
+#   load(plan, obj_types, G0)      the initial factors
+#   step(plan, n)                  n iterations
+#   sqerrs(plan, indices)          squared reconstruction errors of those relations of `rel_list`, the same on every rank
+#   collect(plan, obj_types, rel_list) -> (G, S)
+_Sharding = collections.namedtuple('_Sharding', 'make_plan attach load step sqerrs collect')
+
+
+def _fit(sharding, variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, random_state, dtype, G0, engine,
+         stopping, stopping_system, compute_err, callback):
+    """One fit, shared out as `sharding` says: the body of the reference loops (_dfmf.py:212-322, _dfmc.py:270-392) with the
+    arithmetic on the device.  A size mismatch between the relations is reported before anything is drawn from
+    `random_state`; the plain loop stays on the device, `_host_loop` runs where the host is needed every iteration."""
+    obj_types = list(obj_types)
+    n_obj = count_objects(obj_types, R)
+    if G0 is None:
+        R_first = {k: host_view(v[0]) for k, v in R.items()}
+        G0 = initialize(obj_types, n_obj, obj_type2rank, R_first, init_type, _as_rs(random_state))
+    rel_list = flatten_relations(R, M)
+    plan = sharding.make_plan(variant, rel_list, flatten_thetas(Theta), obj_types, n_obj, obj_type2rank, dtype, engine)
+    try:
+        sharding.attach(plan)
+        sharding.load(plan, obj_types, G0)
+        if not (callback or stopping or stopping_system or compute_err):
+            sharding.step(plan, max_iter)       # whole loop device-resident, no host sync
+        else:
+            _host_loop(lambda: sharding.step(plan, 1), lambda idx: sharding.sqerrs(plan, idx), rel_list, max_iter,
+                       stopping, stopping_system, compute_err,
+                       (lambda it: callback(*(sharding.collect(plan, obj_types, rel_list) + (it,)))) if callback else None)
+        return sharding.collect(plan, obj_types, rel_list)
+    finally:
+        plan.close()
+
+
+def _whole_plan(variant, rel_list, theta_list, obj_types, n_obj, obj_type2rank, dtype, engine):
+    return DevicePlan(obj_types, n_obj, obj_type2rank, rel_list, theta_list, variant, dtype=dtype, engine=engine)
+
+
+def _held_relations_plan(variant, rel_list, theta_list, obj_types, n_obj, obj_type2rank, dtype, engine):
+    """The plan of this rank in a relation-sharded fit: the relations and constraints `partition_relations` gives it.
+    `plan.held`: the index in `rel_list` of every relation the plan holds, in the plan's order."""
+    rank, _ = world()
+    rel_owner, theta_owner = partition_relations(rel_list, theta_list, n_obj, obj_type2rank)
+    held = [k for k, o in enumerate(rel_owner) if o == rank]
+    plan = _whole_plan(variant, [rel_list[k] for k in held], [t for t, o in zip(theta_list, theta_owner) if o == rank],
+                       obj_types, n_obj, obj_type2rank, dtype, engine)
+    plan.held = held
+    return plan
+
+
+def _load_at_once(plan, obj_types, G0):
+    """Every factor with one synchronisation -- or, for the draws of a column-mean initialiser, by the bound plan itself."""
+    if isinstance(G0, DeviceInit):
+        G0.apply(plan, obj_types)
+    else:
+        plan.set_factors({t: G0[t, t] for t in obj_types})
+
+
+def _load_by_type(plan, obj_types, G0):
+    for t in obj_types:
+        plan.set_factor(t, G0[t, t])
+
+
+def _attach_or_single(plan):
+    if not plan.attach_comm():
+        # a single process: every row is owned here and nothing is exchanged -- a genuine communicator of one rank (the
+        # null communicator of bench.py --emulate-rank never updates the factors: not for fits)
+        plan.attach_single_comm()
+
+
+def _sqerrs_here(plan, idx):
+    return [plan.relation_sqerr(k) for k in idx]
+
+
+def _sqerrs_of_rows(plan, idx):
+    """Every rank holds the squared error of ITS rows (row blocks, owned rows); factors and backbones are replicated."""
+    return sum_over_ranks([plan.relation_sqerr(k) for k in idx])
+
+
+def _sqerrs_of_held(plan, idx):
+    """The owner of a relation contributes its error: global relation index -> index in this rank's plan."""
+    where = {k: q for q, k in enumerate(plan.held)}
+    return sum_over_ranks([plan.relation_sqerr(where[k]) if k in where else 0.0 for k in idx])
+
+
+def _collect_held(plan, obj_types, rel_list):
+    """(G, S) of a relation-sharded fit: the replicated factors, the backbones gathered from their owners (collective)."""
+    G = {(t, t): plan.get_factor(t) for t in obj_types}
+    backbones = gather_backbones({k: plan.get_backbone(q) for q, k in enumerate(plan.held)}, len(rel_list))
+    S = {}
+    for k, (i, j, _, _) in enumerate(rel_list):
+        S.setdefault((i, j), []).append(backbones[k])
+    return G, S
+
+
+def _attach_group(plan):
+    plan.attach_comm()                 # the library issues the exchanges itself (skf_iterate_dist)
+
+
+_WHOLE = _Sharding(make_plan=_whole_plan, attach=lambda plan: None, load=_load_at_once,
+                   step=lambda plan, n: plan.iterate(n), sqerrs=_sqerrs_here, collect=_collect)
+_RELATIONS = _Sharding(make_plan=_held_relations_plan, attach=_attach_group, load=_load_by_type,
+                       step=lambda plan, n: plan.iterate_sharded(n), sqerrs=_sqerrs_of_held, collect=_collect_held)
+_ROWS = _Sharding(make_plan=lambda *graph: row_block_plan(*(graph + world())), attach=_attach_group, load=_load_by_type,
+                  step=lambda plan, n: plan.iterate_rows(n), sqerrs=_sqerrs_of_rows, collect=_collect)
+_OWNED = _Sharding(make_plan=lambda *graph: owned_plan(*(graph + world())), attach=_attach_or_single, load=_load_by_type,
+                   step=lambda plan, n: plan.iterate_dist(n), sqerrs=_sqerrs_of_rows, collect=_collect)
+
+
 def run_fit_owned(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type,
                   random_state, dtype, G0, engine, stopping=None, stopping_system=None, compute_err=False,
                   callback=None):
@@ -175,33 +288,8 @@ def run_fit_owned(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init
     the form with the least exchange): per iteration a rank sends the partial Q of every relation (reduce-scatter), its
     updated factor rows (all-gather) and c x c partial sums -- no E / D exchange (DevicePlan.iterate_dist, the library
     issues the collectives).  Every rank ends with the full (G, S)."""
-    from ..._distributed import world, sum_over_ranks
-    obj_types = list(obj_types)
-    n_obj = count_objects(obj_types, R)
-    if G0 is None:
-        R_first = {k: host_view(v[0]) for k, v in R.items()}
-        G0 = initialize(obj_types, n_obj, obj_type2rank, R_first, init_type, _as_rs(random_state))
-    rel_list = flatten_relations(R, M)
-    rank, size = world()
-    plan = owned_plan(variant, rel_list, flatten_thetas(Theta), obj_types, n_obj, obj_type2rank, dtype, engine, rank, size)
-    try:
-        if not plan.attach_comm():
-            # a single process: every row is owned here and nothing is exchanged -- a genuine communicator of one rank (the
-            # null communicator of bench.py --emulate-rank never updates the factors: not for fits)
-            plan.attach_single_comm()
-        for t in obj_types:
-            plan.set_factor(t, G0[t, t])
-        if not (callback or stopping or stopping_system or compute_err):
-            plan.iterate_dist(max_iter)
-        else:
-            def sqerrs(idx):                   # every rank holds the squared error of ITS rows
-                return sum_over_ranks([plan.relation_sqerr(k) for k in idx])
-            _host_loop(lambda: plan.iterate_dist(1), sqerrs, rel_list, max_iter, stopping, stopping_system,
-                       compute_err,
-                       (lambda it: callback(*(_collect(plan, obj_types, rel_list) + (it,)))) if callback else None)
-        return _collect(plan, obj_types, rel_list)
-    finally:
-        plan.close()
+    return _fit(_OWNED, variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, random_state, dtype, G0, engine,
+                stopping, stopping_system, compute_err, callback)
 
 
 def run_fit_rows(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type,
@@ -211,34 +299,8 @@ def run_fit_rows(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_
     (SURVEY.md 8e): every rank lists all relations with its own row block (or none), factors are
     replicated, and an iteration is four stages with all-reduces of W / Q, E / D in between
     (`DevicePlan.iterate_rows`).  Every rank ends with the full (G, S)."""
-    from ..._distributed import world
-    obj_types = list(obj_types)
-    n_obj = count_objects(obj_types, R)
-    if G0 is None:
-        R_first = {k: host_view(v[0]) for k, v in R.items()}
-        G0 = initialize(obj_types, n_obj, obj_type2rank, R_first, init_type, _as_rs(random_state))
-    rel_list = flatten_relations(R, M)
-    rank, size = world()
-    plan = row_block_plan(variant, rel_list, flatten_thetas(Theta), obj_types, n_obj, obj_type2rank, dtype,
-                          engine, rank, size)
-    try:
-        plan.attach_comm()                 # the library issues the exchanges itself (skf_iterate_dist)
-        for t in obj_types:
-            plan.set_factor(t, G0[t, t])
-        if not (callback or stopping or stopping_system or compute_err):
-            plan.iterate_rows(max_iter)
-        else:
-            from ..._distributed import sum_over_ranks
-            # every rank holds the squared error of ITS row blocks; factors and backbones are replicated
-
-            def sqerrs(idx):
-                return sum_over_ranks([plan.relation_sqerr(k) for k in idx])
-            _host_loop(lambda: plan.iterate_rows(1), sqerrs, rel_list, max_iter, stopping, stopping_system,
-                       compute_err,
-                       (lambda it: callback(*(_collect(plan, obj_types, rel_list) + (it,)))) if callback else None)
-        return _collect(plan, obj_types, rel_list)
-    finally:
-        plan.close()
+    return _fit(_ROWS, variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, random_state, dtype, G0, engine,
+                stopping, stopping_system, compute_err, callback)
 
 
 def run_fit_sharded(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type,
@@ -251,45 +313,8 @@ def run_fit_sharded(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, in
     SPMD launch of the same script): the callback path gathers the backbones collectively, and a callback on one rank
     only would leave the others out of that collective.  The current device of each rank must be set before the
     fit (torch.cuda.set_device(LOCAL_RANK)) for the RCCL reductions."""
-    from ..._distributed import partition_relations, gather_backbones, world
-    obj_types = list(obj_types)
-    n_obj = count_objects(obj_types, R)
-    if G0 is None:
-        R_first = {k: host_view(v[0]) for k, v in R.items()}
-        G0 = initialize(obj_types, n_obj, obj_type2rank, R_first, init_type, _as_rs(random_state))
-    rel_list = flatten_relations(R, M)
-    theta_list = flatten_thetas(Theta)
-    rank, _ = world()
-    rel_owner, theta_owner = partition_relations(rel_list, theta_list, n_obj, obj_type2rank)
-    mine = [k for k, o in enumerate(rel_owner) if o == rank]
-    plan = DevicePlan(obj_types, n_obj, obj_type2rank, [rel_list[k] for k in mine],
-                      [t for t, o in zip(theta_list, theta_owner) if o == rank], variant,
-                      dtype=dtype, engine=engine)
-    try:
-        plan.attach_comm()                 # the library issues the exchanges itself (skf_iterate_dist)
-        for t in obj_types:
-            plan.set_factor(t, G0[t, t])
-
-        def collect():
-            G = {(t, t): plan.get_factor(t) for t in obj_types}
-            backbones = gather_backbones({k: plan.get_backbone(q) for q, k in enumerate(mine)}, len(rel_list))
-            S = {}
-            for k, (i, j, _, _) in enumerate(rel_list):
-                S.setdefault((i, j), []).append(backbones[k])
-            return G, S
-        if not (callback or stopping or stopping_system or compute_err):
-            plan.iterate_sharded(max_iter)
-        else:
-            from ..._distributed import sum_over_ranks
-            where = {k: q for q, k in enumerate(mine)}          # global relation index -> index in this rank's plan
-
-            def sqerrs(idx):                                     # the owner of a relation contributes its error
-                return sum_over_ranks([plan.relation_sqerr(where[k]) if k in where else 0.0 for k in idx])
-            _host_loop(lambda: plan.iterate_sharded(1), sqerrs, rel_list, max_iter, stopping, stopping_system,
-                       compute_err, (lambda it: callback(*(collect() + (it,)))) if callback else None)
-        return collect()
-    finally:
-        plan.close()
+    return _fit(_RELATIONS, variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, random_state, dtype, G0,
+                engine, stopping, stopping_system, compute_err, callback)
 
 
 def run_fits_concurrent(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, dtype, G0_list, engine,
@@ -364,28 +389,25 @@ def run_fit(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type,
     """Shared driver of dfmf / dfmc: the body of the reference loops (_dfmf.py:212-322,
     _dfmc.py:270-392) with the arithmetic on the device."""
     logging.basicConfig(format="%(asctime)s %(levelname)s: %(message)s", level=50 - verbose)
-    obj_types = list(obj_types)
-    n_obj = count_objects(obj_types, R)
-    if G0 is None:
-        R_first = {k: host_view(v[0]) for k, v in R.items()}
-        G0 = initialize(obj_types, n_obj, obj_type2rank, R_first, init_type, _as_rs(random_state))
-    rel_list = flatten_relations(R, M)
-    plan = DevicePlan(obj_types, n_obj, obj_type2rank, rel_list, flatten_thetas(Theta), variant,
-                      dtype=dtype, engine=engine)
-    try:
-        if isinstance(G0, DeviceInit):          # the plan initialises itself (column means on the device), after bind
-            G0.apply(plan, obj_types)
-        else:
-            plan.set_factors({t: G0[t, t] for t in obj_types})
-        if not (callback or stopping or stopping_system or compute_err):
-            plan.iterate(max_iter)              # whole loop device-resident, no host sync
-        else:
-            _host_loop(lambda: plan.iterate(1), lambda idx: [plan.relation_sqerr(k) for k in idx], rel_list,
-                       max_iter, stopping, stopping_system, compute_err,
-                       (lambda it: callback(*(_collect(plan, obj_types, rel_list) + (it,)))) if callback else None)
-        return _collect(plan, obj_types, rel_list)
-    finally:
-        plan.close()
+    return _fit(_WHOLE, variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, random_state, dtype, G0, engine,
+                stopping, stopping_system, compute_err, callback)
+
+
+_SHARDED_FITS = {'relations': run_fit_sharded, 'rows': run_fit_rows, 'owned': run_fit_owned}
+
+
+def _fit_by_shard(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, stopping, stopping_system, verbose,
+                  compute_err, callback, random_state, dtype, G0, engine, shard, sparse_constraints):
+    """The shard dispatch of `dfmf` and `_dfmc.dfmc`: one whole fit on this process (shard None / 'runs'), or this
+    process's part of a fit shared out over the process group -- 'relations', 'rows', 'owned' -- which takes dense
+    constraints (`refuse_constraint_entries`)."""
+    if shard not in _SHARDED_FITS:
+        return run_fit(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, stopping, stopping_system,
+                       verbose, compute_err, callback, random_state, dtype, G0, engine)
+    refuse_constraint_entries(Theta, shard, sparse_constraints)
+    logging.basicConfig(format="%(asctime)s %(levelname)s: %(message)s", level=50 - verbose)
+    return _SHARDED_FITS[shard](variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, random_state, dtype,
+                                G0, engine, stopping, stopping_system, compute_err, callback)
 
 
 def refuse_constraint_entries(Theta, shard, sparse_constraints=False):
@@ -409,15 +431,9 @@ def dfmf(R, Theta, obj_types, obj_type2rank, max_iter=10, init_type="random_vcol
     of this ONE fit over the ranks.  A constraint in ``Theta`` may be an ``_engine.KnownEntries(unstored='zero')`` -- its
     entries as canonical CSR, never expanded -- with shard None / 'runs', and with shard='owned' under
     ``sparse_constraints=True`` (every rank hands over the CSR of its owned rows); any other shard: ValueError."""
-    if shard in ('relations', 'rows', 'owned'):
-        refuse_constraint_entries(Theta, shard, sparse_constraints)
-        logging.basicConfig(format="%(asctime)s %(levelname)s: %(message)s", level=50 - verbose)
-        fit = {'relations': run_fit_sharded, 'rows': run_fit_rows, 'owned': run_fit_owned}[shard]
-        return fit(nat.SKF_DFMF, R, None, Theta, obj_types, obj_type2rank, max_iter,
-                   init_type, random_state, dtype, G0, engine, stopping, stopping_system, compute_err, callback)
-    return run_fit(nat.SKF_DFMF, R, None, Theta, obj_types, obj_type2rank, max_iter, init_type,
-                   stopping, stopping_system, verbose, compute_err, callback, random_state,
-                   dtype, G0, engine)
+    return _fit_by_shard(nat.SKF_DFMF, R, None, Theta, obj_types, obj_type2rank, max_iter, init_type, stopping,
+                         stopping_system, verbose, compute_err, callback, random_state, dtype, G0, engine, shard,
+                         sparse_constraints)
 
 
 def _transform_graph(R_ij, target_obj_type, G):
@@ -436,6 +452,23 @@ def _transform_graph(R_ij, target_obj_type, G):
     for o in types[1:]:
         n_obj[o] = G[o, o].shape[0]
     return types, n_obj, sizes[0]
+
+
+def _freeze_model(plan, types, rel_list, g0, G, S, at_once):
+    """Freeze the model (G, S) of one restart into a fold-in plan: `g0` for the target `types[0]`, the fitted factors of
+    the partner types, and the l-th backbone of every pair for its l-th new relation.  `at_once`: the factors in one
+    `set_factors` without a synchronisation of its own (several plans set up together) instead of one `set_factor` each."""
+    factors = [(types[0], g0)] + [(o, G[o, o]) for o in types[1:]]
+    if at_once:
+        plan.set_factors(dict(factors), sync=False)
+    else:
+        for o, g in factors:
+            plan.set_factor(o, g)
+    seen = {}
+    for k, (i, j, _, _) in enumerate(rel_list):
+        l = seen.get((i, j), 0)
+        seen[i, j] = l + 1
+        plan.set_backbone(k, S[i, j][l])
 
 
 def transform_runs(R_ij, Theta_i, target_obj_type, obj_type2rank, models, max_iter=10, init_type="random_c",
@@ -461,12 +494,7 @@ def transform_runs(R_ij, Theta_i, target_obj_type, obj_type2rank, models, max_it
             plan = DevicePlan(types, n_obj, obj_type2rank, rel_list, theta_list, nat.SKF_TRANSFORM, dtype=dtype, target=t,
                               engine=engine)
             plans.append(plan)
-            plan.set_factors(dict([(t, g0)] + [(o, G[o, o]) for o in types[1:]]), sync=False)
-            seen = {}
-            for k, (i, j, _, _) in enumerate(rel_list):
-                l = seen.get((i, j), 0)
-                seen[i, j] = l + 1
-                plan.set_backbone(k, S[i, j][l])
+            _freeze_model(plan, types, rel_list, g0, G, S, at_once=True)
         rt.mem.synchronize()
         if not (len(plans) > 1 and plans[0].batchable() and DevicePlan.iterate_batch(plans, max_iter)):
             for plan in plans:
@@ -488,43 +516,24 @@ def transform(R_ij, Theta_i, target_obj_type, obj_type2rank, G, S, max_iter=10,
     ``_engine.KnownEntries(unstored='zero')``: its entries as canonical CSR, never expanded."""
     logging.basicConfig(format="%(asctime)s %(levelname)s: %(message)s", level=50 - verbose)
     t = target_obj_type
-    sizes = [R_ij[i, j][0].shape[0 if t == i else 1] for i, j in R_ij]
-    if len(set(sizes)) > 1:
-        from ..base import DataFusionError
-        raise DataFusionError("Target object type: %s size mismatch" % t)
-    n_t = sizes[0]
+    # object types taking part: the target + every partner type of the new relations
+    types, n_obj, n_t = _transform_graph(R_ij, t, G)
     if G0 is None:
         R_first = {k: host_view(v[0]) for k, v in R_ij.items()}        # (stored entries are read as such, never expanded)
         G0 = initialize([t], {t: n_t}, obj_type2rank, R_first, init_type,
                         _as_rs(random_state))[t, t]
-    # object types taking part: the target + every partner type of the new relations
-    types = [t]
-    for (i, j) in R_ij:
-        for o in (i, j):
-            if o not in types:
-                types.append(o)
-    n_obj = {t: n_t}
-    for o in types[1:]:
-        n_obj[o] = G[o, o].shape[0]
     rel_list = flatten_relations(R_ij)
     plan = DevicePlan(types, n_obj, obj_type2rank, rel_list, flatten_thetas(Theta_i),
                       nat.SKF_TRANSFORM, dtype=dtype, target=t, engine=engine)
     try:
-        plan.set_factor(t, G0)
-        for o in types[1:]:
-            plan.set_factor(o, G[o, o])
-        seen = {}
-        for k, (i, j, _, _) in enumerate(rel_list):
-            l = seen.get((i, j), 0)
-            seen[i, j] = l + 1
-            plan.set_backbone(k, S[i, j][l])
+        _freeze_model(plan, types, rel_list, G0, G, S, at_once=False)
         if not (callback or stopping or stopping_system or compute_err):
             plan.iterate(max_iter)
         else:
             # reference _dfmf.py:367-376, 433-450: the system error of the NEW relations per iteration and
             # `stopping_system` on its change.  (`stopping` reads an undefined name there -- a NameError at the
             # third iteration; here it is the error change of the named relation, as in dfmf().)
-            _host_loop(lambda: plan.iterate(1), lambda idx: [plan.relation_sqerr(k) for k in idx], rel_list,
+            _host_loop(lambda: plan.iterate(1), lambda idx: _sqerrs_here(plan, idx), rel_list,
                        max_iter, stopping, stopping_system, compute_err,
                        (lambda it: callback(plan.get_factor(t), it)) if callback else None)
         return plan.get_factor(t)

@@ -25,19 +25,54 @@ def _random_state(obj):
     return obj if isinstance(obj, np.random.RandomState) else np.random.RandomState(obj)
 
 
+SPARSE_RULE = 4.0       # density * max(rank_row, rank_col) at which the entry lists stop paying
+FOLD_MIN_CELLS = 1 << 20       # fold-ins, default rule: below this many cells the dense upload is free and nothing changes
+LIST_MAX_RANK, LIST_MAX_ENTRIES = 1024, 2000000000      # the limits of the library's entry lists
+
+
+def _max_rank(relation):
+    return max(int(relation.row_type.rank), int(relation.col_type.rank))
+
+
+def _cells(relation):
+    return float(relation.data.shape[0]) * float(relation.data.shape[1])
+
+
+def _listable(relation, rank, nnz, constraint=False):
+    """What every entry-list form asks of a scipy.sparse relation: no preprocessor, two different object types (a
+    constraint: one type with itself), and the limits of the library's lists for `rank` and its `nnz` entries."""
+    if relation.preprocessor or (relation.row_type == relation.col_type) != constraint:
+        return False
+    return rank <= LIST_MAX_RANK and nnz <= LIST_MAX_ENTRIES
+
+
+def _within_rule(relation, rank, nnz):
+    """density * rank <= SPARSE_RULE: where a pass over the entry lists still beats the dense one."""
+    cells = _cells(relation)
+    return cells > 0 and nnz / cells * rank <= SPARSE_RULE
+
+
+def _sparse_enough(relation, rank, nnz):
+    """The default rule of the fits (`sparse_relations` None): `_within_rule`, for relations beyond the
+    limits of the small-graph schedule only (``skf_small_graph_limits``: below them an iteration is bound by its launches,
+    the three-launch schedule is the measured path and the lists would take the graph off it)."""
+    from ..._engine import small_graph_limits
+    lim = small_graph_limits()
+    if rank <= lim['max_rank'] and max(relation.data.shape) <= lim['max_objects']:
+        return False
+    return _within_rule(relation, rank, nnz)
+
+
 def known_entries_apply(relation, known_entries):
     """Whether `relation` enters the fit as its known entries only (``Relation(..., unstored='unknown')`` on the list path
     of Dfmc: asked for by the caller, no preprocessor, fill 'mean' or a number, row type rank <= 1024 and at most 2e9
     entries -- the limits of the library's known-entry lists).  Otherwise such a relation is expanded to its MaskedArray.
     The answer depends on the whole relation only, so every rank of a shard='owned' fit gives the same one."""
-    if not (known_entries and relation.is_known_entries() and not relation.preprocessor):
+    if not (known_entries and relation.is_known_entries()):
         return False
-    if relation.row_type == relation.col_type or int(relation.row_type.rank) > 1024 or relation.data.nnz > 2000000000:
+    if not _listable(relation, int(relation.row_type.rank), relation.data.nnz):
         return False
     return isinstance(relation.fill_value, Number) or relation.fill_value == 'mean'
-
-
-SPARSE_RULE = 4.0       # density * max(rank_row, rank_col) at which the entry lists stop paying (DESIGN.md section 2)
 
 
 def stored_entries_apply(relation, sparse_relations, shard='runs'):
@@ -50,22 +85,12 @@ def stored_entries_apply(relation, sparse_relations, shard='runs'):
     objects on a side, ``skf_small_graph_limits``: below them an iteration is bound by its launches, the three-launch
     schedule is the measured path and the lists would take the graph off it); True: whenever eligible; False: never
     (``toarray()``, as before the sparse path existed)."""
-    if sparse_relations is False or shard not in ('runs', 'owned'):
+    if sparse_relations is False or shard not in ('runs', 'owned') or not relation.is_zero_unstored():
         return False
-    if not relation.is_zero_unstored() or relation.preprocessor or relation.row_type == relation.col_type:
+    rank, nnz = _max_rank(relation), int(relation.data.nnz)
+    if not _listable(relation, rank, nnz):
         return False
-    rank = max(int(relation.row_type.rank), int(relation.col_type.rank))
-    nnz = int(relation.data.nnz)
-    if rank > 1024 or nnz > 2000000000:
-        return False
-    if sparse_relations:
-        return True
-    from ..._engine import small_graph_limits
-    lim = small_graph_limits()
-    if rank <= lim['max_rank'] and max(relation.data.shape) <= lim['max_objects']:
-        return False
-    cells = float(relation.data.shape[0]) * float(relation.data.shape[1])
-    return cells > 0 and nnz / cells * rank <= SPARSE_RULE
+    return bool(sparse_relations) or _sparse_enough(relation, rank, nnz)
 
 
 def filled_entries_apply(relation, sparse_relations, shard='runs', variant='dfmf'):
@@ -77,18 +102,15 @@ def filled_entries_apply(relation, sparse_relations, shard='runs', variant='dfmf
     no mask, so the relation is an unmasked one of the DFMC plan ('mean' and numbers keep their mask and go to
     ``known_entries_apply``).  `sparse_relations` follows the rule of ``stored_entries_apply``: None: density *
     max(rank_row, rank_col) <= 4 beyond the small-graph limits; True: whenever eligible; False: never."""
-    if sparse_relations is False or shard != 'runs':
-        return False
-    if not relation.is_known_entries() or relation.preprocessor or relation.row_type == relation.col_type:
+    if sparse_relations is False or shard != 'runs' or not relation.is_known_entries():
         return False
     if isinstance(relation.fill_value, Number) or relation.fill_value == 'mean':
         if variant != 'dfmf':
             return False
     elif relation.fill_value not in ('row_mean', 'col_mean'):
         return False
-    rank = max(int(relation.row_type.rank), int(relation.col_type.rank))
-    cells = float(relation.data.shape[0]) * float(relation.data.shape[1])
-    if rank > 1024 or int(relation.data.nnz) > 2000000000 or cells <= 0:
+    rank, cells = _max_rank(relation), _cells(relation)
+    if not _listable(relation, rank, int(relation.data.nnz)) or cells <= 0:
         return False
     import scipy.sparse
     csr = scipy.sparse.csr_matrix(relation.data, copy=True)
@@ -96,13 +118,7 @@ def filled_entries_apply(relation, sparse_relations, shard='runs', variant='dfmf
     nnz = int(csr.indices.size)
     if nnz >= cells or not np.isfinite(csr.data).all():
         return False
-    if sparse_relations:
-        return True
-    from ..._engine import small_graph_limits
-    lim = small_graph_limits()
-    if rank <= lim['max_rank'] and max(relation.data.shape) <= lim['max_objects']:
-        return False
-    return nnz / cells * rank <= SPARSE_RULE
+    return bool(sparse_relations) or _sparse_enough(relation, rank, nnz)
 
 
 def constraint_entries_apply(relation, sparse_constraints, shard='runs'):
@@ -113,21 +129,18 @@ def constraint_entries_apply(relation, sparse_constraints, shard='runs'):
     `sparse_constraints` True: whenever eligible; False: never (``toarray()``); None: when nnz <= n * n / the library's own
     divisor (``small_graph_limits()``: up to there the dense-fed form is compacted to the same lists, so nothing changes but
     the hand-over) -- a denser one is expanded and takes the dense product, the measured path at that density."""
-    if sparse_constraints is False or shard not in ('runs', 'owned'):
-        return False
-    if not relation.is_zero_unstored() or relation.preprocessor or relation.row_type != relation.col_type:
+    if sparse_constraints is False or shard not in ('runs', 'owned') or not relation.is_zero_unstored():
         return False
     nnz = int(relation.data.nnz)
-    if nnz > 2000000000 or not np.isfinite(relation.data.data).all():      # (a stored NaN / inf is filled: the dense path's job)
+    if not _listable(relation, 0, nnz, constraint=True):        # (no lists by rank here: a constraint multiplies a factor)
+        return False
+    if not np.isfinite(relation.data.data).all():               # (a stored NaN / inf is filled: the dense path's job)
         return False
     if sparse_constraints:
         return True
     from ..._engine import small_graph_limits
     n = int(relation.data.shape[0])
     return nnz <= n * n // small_graph_limits()['constraint_nnz_divisor']
-
-
-FOLD_MIN_CELLS = 1 << 20       # fold-ins, default rule: below this many cells the dense upload is free and nothing changes
 
 
 def fold_entries_apply(relation, sparse_relations):
@@ -137,18 +150,14 @@ def fold_entries_apply(relation, sparse_relations):
     False: never; None: when also density * max(rank_row, rank_col) <= SPARSE_RULE (the fit's constant: a dense-fed
     preparation streams every cell once, a list-fed one gathers a c-wide row per entry, the trade of the fit's passes;
     DESIGN.md section 2 says what was measured for the fold-in) and the relation has at least 2^20 cells."""
-    if sparse_relations is False:
+    if sparse_relations is False or not relation.is_zero_unstored():
         return False
-    if not relation.is_zero_unstored() or relation.preprocessor or relation.row_type == relation.col_type:
-        return False
-    rank = max(int(relation.row_type.rank), int(relation.col_type.rank))
-    nnz = int(relation.data.nnz)
-    if rank > 1024 or nnz > 2000000000:
+    rank, nnz = _max_rank(relation), int(relation.data.nnz)
+    if not _listable(relation, rank, nnz):
         return False
     if sparse_relations:
         return True
-    cells = float(relation.data.shape[0]) * float(relation.data.shape[1])
-    return cells >= FOLD_MIN_CELLS and nnz / cells * rank <= SPARSE_RULE
+    return _cells(relation) >= FOLD_MIN_CELLS and _within_rule(relation, rank, nnz)
 
 
 def graph_matrices(fusion_graph, with_masks=False, device_dtype=None, known_entries=False, sparse_relations=False,
@@ -399,7 +408,60 @@ def store_runs(fuser, runs):
                 fuser.backbones_[relation].append(backbones[k])
 
 
-class Dfmf(FusionFit):
+class _Fuser(FusionFit):
+    """`fuse` of ``Dfmf`` and ``Dfmc``: one implementation; the class attributes say what differs."""
+
+    _variant = None             # 'dfmf' | 'dfmc': which update rules, and the variant the `*_apply` rules decide for
+    _keeps_masks = False        # what is still masked after fill + preprocess is unknown and completed by the model
+    _takes_known_entries = False    # a relation given as its known entries may enter as such (shard 'runs' / 'owned')
+    _shares_launches = False    # restarts of a small graph may share their launches, whatever n_jobs says
+
+    def _solve(self, M, **kw):
+        """One restart through the functional seam of the variant."""
+        raise NotImplementedError
+
+    def fuse(self, fusion_graph):
+        from ... import _native as nat
+        self.fusion_graph = fusion_graph
+        self.random_state = _random_state(self.random_state)
+        object_types = list(fusion_graph.object_types)
+        rank = {ot: int(ot.rank) for ot in object_types}
+        matrices = graph_matrices(fusion_graph, with_masks=self._keeps_masks, device_dtype=device_fill_dtype(self),
+                                  known_entries=self._takes_known_entries and self.shard in ('runs', 'owned'),
+                                  sparse_relations=getattr(self, 'sparse_relations', None), shard=self.shard,
+                                  sparse_constraints=getattr(self, 'sparse_constraints', None), variant=self._variant)
+        R, Theta, M = matrices if self._keeps_masks else matrices + (None,)
+        self.init_on_device_ = init_device_wanted(self) and init_device_covered(R, M)
+        G0 = initial_factors(R, object_types, rank, self.init_type, self.random_state, self.n_run, self.init_on_device_)
+        kw = dict(R=R, Theta=Theta, obj_types=object_types, obj_type2rank=rank,
+                  max_iter=self.max_iter, init_type=self.init_type, stopping=self.stopping,
+                  stopping_system=self.stopping_system, verbose=self.verbose,
+                  compute_err=self.compute_err, callback=self.callback,
+                  random_state=self.random_state, n_jobs=self.n_jobs, dtype=self.dtype)
+        code = {'dfmf': nat.SKF_DFMF, 'dfmc': nat.SKF_DFMC}[self._variant]
+        if self.shard in ('relations', 'rows', 'owned'):                   # all GPUs cooperate on every restart
+            # (an owned fit takes the constraints graph_matrices left as entries: each rank the slice of its owned rows)
+            store_runs(self, [self._solve(M, G0=G0[k], shard=self.shard, sparse_constraints=self.shard == 'owned', **kw)
+                              for k in range(self.n_run)])
+            return self
+        if self._shares_launches and shared_launches(self):
+            runs = _dfmf.run_fits_concurrent(code, R, M, Theta, object_types, rank, self.max_iter, self.dtype,
+                                             G0, None, min(self.n_run, 32), batch_only=True)
+            if runs is not None:
+                store_runs(self, runs)
+                return self
+        n_streams = concurrent_streams(self)
+        if n_streams:                                   # n_jobs restarts side by side on this GPU
+            store_runs(self, _dfmf.run_fits_concurrent(code, R, M, Theta, object_types, rank,
+                                                       self.max_iter, self.dtype, G0, None, n_streams))
+            return self
+        local = {k: self._solve(M, G0=G0[k], **kw)
+                 for k in my_runs(self.n_run)}          # one restart per GPU when distributed
+        store_runs(self, gather_runs(local, self.n_run))
+        return self
+
+
+class Dfmf(_Fuser):
     """Data fusion by matrix factorization.
 
     Parameters (identical to the reference): max_iter=100, init_type='random_c', n_run=1,
@@ -440,6 +502,7 @@ class Dfmf(FusionFit):
     """
 
     _variant = 'dfmf'
+    _shares_launches = True
 
     def __init__(self, max_iter=100, init_type='random_c', n_run=1, stopping=None,
                  stopping_system=None, verbose=0, compute_err=False, callback=None,
@@ -448,43 +511,8 @@ class Dfmf(FusionFit):
         super(Dfmf, self).__init__()
         self._set_params(vars())
 
-    def fuse(self, fusion_graph):
-        self.fusion_graph = fusion_graph
-        self.random_state = _random_state(self.random_state)
-        object_types = list(fusion_graph.object_types)
-        rank = {ot: int(ot.rank) for ot in object_types}
-        R, Theta = graph_matrices(fusion_graph, device_dtype=device_fill_dtype(self),
-                                  sparse_relations=getattr(self, 'sparse_relations', None), shard=self.shard,
-                                  sparse_constraints=getattr(self, 'sparse_constraints', None))
-        self.init_on_device_ = init_device_wanted(self) and init_device_covered(R)
-        G0 = initial_factors(R, object_types, rank, self.init_type, self.random_state, self.n_run, self.init_on_device_)
-        kw = dict(R=R, Theta=Theta, obj_types=object_types, obj_type2rank=rank,
-                  max_iter=self.max_iter, init_type=self.init_type, stopping=self.stopping,
-                  stopping_system=self.stopping_system, verbose=self.verbose,
-                  compute_err=self.compute_err, callback=self.callback,
-                  random_state=self.random_state, n_jobs=self.n_jobs, dtype=self.dtype)
-        if self.shard in ('relations', 'rows', 'owned'):                   # all GPUs cooperate on every restart
-            # (an owned fit takes the constraints graph_matrices left as entries: each rank the slice of its owned rows)
-            store_runs(self, [_dfmf.dfmf(G0=G0[k], shard=self.shard, sparse_constraints=self.shard == 'owned', **kw)
-                              for k in range(self.n_run)])
-            return self
-        if shared_launches(self):                       # restarts of a SMALL graph share their launches, whatever n_jobs says
-            from ... import _native as nat
-            runs = _dfmf.run_fits_concurrent(nat.SKF_DFMF, R, None, Theta, object_types, rank, self.max_iter, self.dtype,
-                                             G0, None, min(self.n_run, 32), batch_only=True)
-            if runs is not None:
-                store_runs(self, runs)
-                return self
-        n_streams = concurrent_streams(self)
-        if n_streams:                                   # n_jobs restarts side by side on this GPU
-            from ... import _native as nat
-            store_runs(self, _dfmf.run_fits_concurrent(nat.SKF_DFMF, R, None, Theta, object_types, rank,
-                                                       self.max_iter, self.dtype, G0, None, n_streams))
-            return self
-        local = {k: _dfmf.dfmf(G0=G0[k], **kw)
-                 for k in my_runs(self.n_run)}          # one restart per GPU when distributed
-        store_runs(self, gather_runs(local, self.n_run))
-        return self
+    def _solve(self, M, **kw):
+        return _dfmf.dfmf(**kw)
 
 
 class DfmfTransform(FusionTransform):
@@ -541,26 +569,24 @@ class DfmfTransform(FusionTransform):
                 dest = R if relation.row_type != relation.col_type else Theta
                 dest.setdefault((relation.row_type, relation.col_type), []).append(data)
 
+        def frozen_model(run):
+            """(G, S) of restart `run` (dfmf.py:109-115); only the LAST relation of a type pair survives in S there --
+            kept: one backbone per pair."""
+            G = {(ot, ot): fuser.factor(ot, run) for ot in fuser.fusion_graph.object_types}
+            S = {(rel.row_type, rel.col_type): [fuser.backbone(rel, run)]
+                 for rel in fuser.fusion_graph.relations if rel.row_type != rel.col_type}
+            return G, S
+
         self.factors_ = defaultdict(list)
         if self.n_run > 1 and not (self.callback or self.stopping or self.stopping_system or self.compute_err):
             # the fold-ins into the models of all restarts share the uploads of the new relations and every launch
             # (reference: one joblib task per restart, dfmf.py:191-199)
-            models = []
-            for run in range(self.n_run):
-                G = {(ot, ot): fuser.factor(ot, run) for ot in fuser.fusion_graph.object_types}
-                S = {(rel.row_type, rel.col_type): [fuser.backbone(rel, run)]
-                     for rel in fuser.fusion_graph.relations if rel.row_type != rel.col_type}
-                models.append((G, S))
-            self.factors_[target] = _dfmf.transform_runs(R, Theta, target, rank, models, max_iter=self.max_iter,
-                                                         init_type=init_type, random_state=self.random_state,
-                                                         dtype=self.dtype)
+            self.factors_[target] = _dfmf.transform_runs(R, Theta, target, rank, [frozen_model(run) for run in range(self.n_run)],
+                                                         max_iter=self.max_iter, init_type=init_type,
+                                                         random_state=self.random_state, dtype=self.dtype)
             return self
         for run in range(self.n_run):
-            # frozen model of this run (dfmf.py:109-115); only the LAST relation of a type pair
-            # survives in S there -- kept: one backbone per pair
-            G = {(ot, ot): fuser.factor(ot, run) for ot in fuser.fusion_graph.object_types}
-            S = {(rel.row_type, rel.col_type): [fuser.backbone(rel, run)]
-                 for rel in fuser.fusion_graph.relations if rel.row_type != rel.col_type}
+            G, S = frozen_model(run)
             G_new = _dfmf.transform(R_ij=R, Theta_i=Theta, target_obj_type=target,
                                     obj_type2rank=rank, G=G, S=S, max_iter=self.max_iter,
                                     init_type=init_type, stopping=self.stopping,

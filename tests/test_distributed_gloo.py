@@ -368,7 +368,7 @@ def test_rccl_rendezvous_is_bounded_in_time(monkeypatch):
             else:
                 time.sleep(3.0)
     monkeypatch.setenv('SKF_COMM_TIMEOUT', '0.3')
-    monkeypatch.setattr(eng, '_group_token', lambda dist: 'fake-group')
+    monkeypatch.setattr(sys.modules[eng._shared_rccl_comm.__module__], '_group_token', lambda dist: 'fake-group')
     eng._RCCL.clear()
     t0 = time.time()
     with pytest.raises(RuntimeError, match='still waits in ncclCommInitRank'):
