@@ -171,7 +171,7 @@ enum {
                                  SKF_E_INVALID at skf_plan_create: without SKF_REL_SPARSE_CSR, SKF_OPT_OWNED_ROWS plans,
                                  SKF_TRANSFORM plans; at bind: no skf_plan_set_relation_fill, a fill value that is not finite
                                  (checked with the lists, before anything gathers). */
-    SKF_REL_FOLD_CSR = 256    /* SKF_TRANSFORM plans only: the NEW relation is given as its STORED entries, every other entry ZERO,
+    SKF_REL_FOLD_CSR = 256,   /* SKF_TRANSFORM plans only: the NEW relation is given as its STORED entries, every other entry ZERO,
                                  compressed along the TARGET's side -- indptr[n_target + 1] (int64), indices (int32, into the
                                  partner type, strictly ascending within a target object) and values in the MASTER type (f64 /
                                  f32; SKF_BF16 plans: f32, never rounded to bf16).  A relation whose row type is the target: its
@@ -191,6 +191,23 @@ enum {
                                  n_t * n_p.  SKF_E_INVALID: SKF_DFMF / SKF_DFMC plans, together with SKF_REL_KNOWN_CSR /
                                  SKF_REL_SPARSE_CSR, a mask, a row block, a rank above 1024, more than 2e9 entries, a missing
                                  hand-over, a broken list.  (SKF_REL_SPARSE_CSR stays an error on SKF_TRANSFORM plans.) */
+    SKF_REL_FOLD_KNOWN = 1024 /* with SKF_REL_FOLD_CSR only (SKF_TRANSFORM plans): stored = KNOWN.  Every entry that is not stored
+                                 is UNKNOWN and takes the current model's prediction in every iteration -- the completion step
+                                 of reference _dfmc.py:319-325 followed by the target's update of _dfmf.py:385-428, with every
+                                 other factor and every backbone frozen -- without the completed relation: with T = G_p S^T (row
+                                 side; G_p S on the column side), B_r = T^T T and the known entries (i_k, v_k) of target object o
+                                     tmp1[o] = G[o] B_r + sum_k (v_k - <G[o], T[i_k]>) T[i_k]      (= R_completed[o] T)
+                                     E[o] += max(tmp1, 0) + G[o] max(-B_r, 0) ,  D[o] += max(-tmp1, 0) + G[o] max(B_r, 0)
+                                 Hand-over, validation, workspace copy and limits are those of SKF_REL_FOLD_CSR.  The
+                                 preparation forms T and B_r (unsplit, c_t x c_t f64; its split joins the B sums of the target
+                                 as for every relation) and adds nothing to the constant sums; every iteration forms X = G B_r
+                                 into ONE n_t x c_t scratch of the plan (master type, counted by skf_plan_workspace_bytes) and
+                                 makes one pass over the lists (skf_fold_known_pass; SKF_BF16 plans: on the f32 masters, T in
+                                 f32), so a plan with such a relation never takes the one-launch iteration and does not batch
+                                 (skf_plan_batchable: 0; skf_iterate_batch: SKF_E_INVALID).  skf_relation_sqerr: the KNOWN-ENTRY
+                                 objective, see there.  SKF_E_INVALID at skf_plan_create: without SKF_REL_FOLD_CSR, on SKF_DFMF /
+                                 SKF_DFMC plans; every refusal of SKF_REL_FOLD_CSR holds (skf_get_contraction and the device
+                                 initialisers among them). */
 };
 
 typedef struct {
@@ -443,7 +460,11 @@ int skf_exchange_bytes(const skf_plan* plan, int32_t world, size_t* bytes);
  * over the stored bf16 relation, bf16-rounded G_i S and G_j on the matrix cores, f32 residual.
  * A SKF_REL_SPARSE_CSR relation: tr(S^T Gram_i S Gram_j) from c x c f64 products plus one pass over the row lists,
  * sum of (r - x)^2 - x^2 with x = <(G_i S)[row], G_j[col]> in the master type (SKF_BF16: the f32 masters, not the bf16
- * rows), f64 partials per wave summed in a fixed order.  A SKF_REL_FOLD_CSR relation: the same, over its one set of lists. */
+ * rows), f64 partials per wave summed in a fixed order.  A SKF_REL_FOLD_CSR relation: the same, over its one set of lists.
+ * A SKF_REL_FOLD_CSR | SKF_REL_FOLD_KNOWN relation: the KNOWN-ENTRY objective, sum over the stored entries of (v - x)^2 with
+ * x = <G_t[o], T[i]> and the current target factor, in the master type -- one pass over the lists, f64 partials per wave
+ * summed in a fixed order.  This is NOT the reference's norm of the working copy, which carries the PREVIOUS iterate in the
+ * unknown cells (_dfmc.py:376-389): no previous iterate is kept here. */
 int skf_relation_sqerr(skf_plan* plan, int32_t rel, double* out, void* stream);
 
 /* The two contraction results the LAST iteration left in the workspace, for verification at sizes where the
@@ -551,6 +572,20 @@ int skf_to_bf16(void* dst, int64_t ldd, int32_t src_dtype, const void* src, int6
  * cross-lane sum -- the result is the host loop's, bit for bit.  Memory past column c of a row is not touched. */
 int skf_fold_lists(int32_t dtype, const int64_t* indptr, const int32_t* indices, const void* values, int64_t n_out,
                    const void* T, int64_t ldt, int32_t c, void* Ec, int64_t lde, void* Dc, int64_t ldd, void* stream);
+
+/* One iteration's pass of a fold-in on KNOWN entries (SKF_REL_FOLD_KNOWN) on the caller's buffers: for o < n_out, q < c
+ * (1 .. 1024), with the list (i_k, v_k) of output object o
+ *     tmp1[o][q] = X[o][q] + sum_k (v_k - <G[o], T[i_k]>) T[i_k][q] ,  E[o][q] += max(tmp1, 0) ,  D[o][q] += max(-tmp1, 0)
+ * X (n_out x c, the caller's G B) may be NULL: nothing is added (ldx is then ignored).  dtype SKF_F64 / SKF_F32 is the type
+ * of values, G, T, X, E and D.  Arithmetic order: `lanes` = the smallest power of two >= min(c, 64) lanes share an object, lane
+ * l owns the columns l, l + lanes, ...; the prediction is part_l = fma(G[o][q], T[i_k][q], part_l) over the lane's columns
+ * in ascending order, then the xor butterfly part += part of lane (l ^ off) for off = 1, 2, 4, ... < lanes; e = v_k - x;
+ * acc[q] = fma(e, T[i_k][q], acc[q]) in LIST ORDER; tmp1 = acc[q] + X[o][q].  Every (o, q) has one owner: no atomics, the same
+ * bits on every run.  An object with an empty list gets tmp1 = X[o].  Validation as for skf_fold_lists (the lists themselves
+ * are not validated here: skf_plan_bind_workspace does that for a plan's).  Memory past column c of a row is not touched. */
+int skf_fold_known_pass(int32_t dtype, const int64_t* indptr, const int32_t* indices, const void* values, int64_t n_out,
+                        const void* G, int64_t ldg, const void* T, int64_t ldt, int32_t c, const void* X, int64_t ldx, void* E,
+                        int64_t lde, void* D, int64_t ldd, void* stream);
 
 /* The k best columns of every row of X = H Gc^T, H = G_row[rows] S (m x c, formed by the caller with skf_gemm), Gc = G_col
  * (n_cols x c), without X: the reference materialises X on the host (fusion/base/base.py `complete`: np.dot(G1, np.dot(S,
@@ -873,7 +908,7 @@ const char* skf_version(void);
 /* Layout version of the structs and signatures above (SKF_ABI_VERSION).  A binding built against another version must not
  * call the library: descriptors grew between versions (skf_relation_desc.known_bound: 3, skf_options.flags: 4; version 5
  * adds entry points only -- skf_small_graph_limits, skf_comm_info, skf_launch_count; later: skf_fold_lists and the flag
- * SKF_REL_FOLD_CSR; skf_complete_topk_workspace_bytes, skf_complete_topk, skf_complete_entries and SKF_TOPK_MAX;
+ * SKF_REL_FOLD_CSR; skf_fold_known_pass and the flag SKF_REL_FOLD_KNOWN; skf_complete_topk_workspace_bytes, skf_complete_topk, skf_complete_entries and SKF_TOPK_MAX;
  * skf_get_constraint_lists and the flag SKF_OPT_THETA_OWNED_ROWS; skf_plan_set_relation_fill and the flag SKF_REL_FILL_RANK1;
  * skf_complete_ranks_workspace_bytes and skf_complete_ranks; skf_complete_above_workspace_bytes and skf_complete_above;
  * skf_plan_relation_norms, skf_plan_init_column_means, their workspace queries and skf_init_view, a struct of their own -- the

@@ -34,9 +34,11 @@ class KnownEntries(object):
     ``unstored='zero'``: the same container for a relation whose entries that are not stored are ZERO (what a scipy.sparse
     matrix means; SKF_REL_SPARSE_CSR, DFMF and unmasked DFMC relations): `fill` is 0, there is no mask, ``toarray`` is the
     dense relation itself.
-    ``by_col=True`` (``unstored='zero'`` only): the lists are compressed along the COLUMN type -- `indptr` has n_col + 1
+    ``by_col=True``: the lists are compressed along the COLUMN type -- `indptr` has n_col + 1
     entries and `indices` are rows, the canonical CSC -- which is what a fold-in whose target is the relation's column type
-    hands to the library (SKF_REL_FOLD_CSR: lists compressed along the target's side).  `shape` stays the relation's.
+    hands to the library (SKF_REL_FOLD_CSR: lists compressed along the target's side; with ``unstored='unknown'``
+    SKF_REL_FOLD_CSR | SKF_REL_FOLD_KNOWN, the fold-in on the known entries only).  Fits take row lists.  `shape` stays the
+    relation's.
     ``row_fill=a, col_fill=b`` (``unstored='zero'``, row lists only): a relation with MISSING values after its fill -- the
     entries not stored hold a_r * b_c, the stored ones their true values (SKF_REL_FILL_RANK1: the filled matrix is
     a b^T + D with D sparse on the stored pattern; the library forms d = v - a_r b_c itself).  One of the two vectors is
@@ -45,8 +47,6 @@ class KnownEntries(object):
     def __init__(self, indptr, indices, values, shape, fill=0.0, unstored='unknown', by_col=False, row_fill=None, col_fill=None):
         if unstored not in ('unknown', 'zero'):
             raise ValueError("unstored must be 'unknown' or 'zero', not %r" % (unstored,))
-        if by_col and unstored != 'zero':
-            raise ValueError("lists compressed along the column type need unstored='zero'")
         if (row_fill is None) != (col_fill is None):
             raise ValueError('row_fill and col_fill come together')
         if row_fill is not None and (unstored != 'zero' or by_col):
@@ -148,14 +148,15 @@ class DeviceKnownEntries(object):
         self.by_col = bool(by_col)      # lists compressed along the column type (fold-ins whose target it is)
 
 
-def upload_known_entries(ke, dtype, mem):
+def upload_known_entries(ke, dtype, mem, fold=False):
     """KnownEntries -> DeviceKnownEntries: validated on the host first (DataFusionError before any upload); values in the
     element type of the relation data (SKF_BF16: bf16 bits, rounded as dense data is: f64 -> f32 -> bf16).  Entries whose
-    unstored neighbours are zero (SKF_REL_SPARSE_CSR) go up in the master type: SKF_BF16 keeps them as f32."""
+    unstored neighbours are zero (SKF_REL_SPARSE_CSR) go up in the master type: SKF_BF16 keeps them as f32 -- and so do
+    the lists of a fold-in (`fold`: SKF_REL_FOLD_CSR, with or without SKF_REL_FOLD_KNOWN)."""
     ke.validate()
     code = nat.DTYPES[dtype] if isinstance(dtype, str) else dtype
     vals = np.ascontiguousarray(ke.values, dtype=nat.NP_DTYPE[code])
-    if code == nat.SKF_BF16 and ke.unstored != 'zero':
+    if code == nat.SKF_BF16 and ke.unstored != 'zero' and not fold:
         vals = nat.to_bf16_bits(vals)
     keep = lambda a: mem.from_host(a if a.size else np.zeros(1, dtype=a.dtype))        # (no empty allocations)
     fills = (None, None)
@@ -435,7 +436,8 @@ class DevicePlan(object):
 
     def _relation_entries(self, k, rd, i, j, data, mask, blk):
         """The known entries only (SKF_REL_KNOWN_CSR), or the stored entries of a relation that is zero elsewhere
-        (SKF_REL_SPARSE_CSR; with fill vectors SKF_REL_FILL_RANK1; in a fold-in SKF_REL_FOLD_CSR): no dense form, no mask;
+        (SKF_REL_SPARSE_CSR; with fill vectors SKF_REL_FILL_RANK1; in a fold-in SKF_REL_FOLD_CSR, and there the known entries
+        SKF_REL_FOLD_CSR | SKF_REL_FOLD_KNOWN): no dense form, no mask;
         always kept as lists.  Row ownership: the CSR of the owned rows, indptr rebased to 0, columns over the whole column
         type."""
         variant, target = self._variant, self._target
@@ -444,17 +446,18 @@ class DevicePlan(object):
         self._check_shape(k, i, j, data.shape)
         if blk is not None:
             rd.row_begin, rd.n_rows = int(blk.row_begin), self.local_rows[k]
-        dev = data if isinstance(data, DeviceKnownEntries) else upload_known_entries(data, self.dtype, self.rt.mem)
+        dev = data if isinstance(data, DeviceKnownEntries) else upload_known_entries(data, self.dtype, self.rt.mem,
+                                                                                     fold=variant == nat.SKF_TRANSFORM)
         self._keep_rel.append(dev)
         rd.known_bound = dev.known
-        if variant == nat.SKF_TRANSFORM and dev.unstored == 'zero':
-            # a fold-in: the stored entries compressed along the target's side
+        if variant == nat.SKF_TRANSFORM:
+            # a fold-in: the entries compressed along the target's side -- stored over zeros, or known over unknowns
             if dev.row_fill is not None:
                 raise ValueError('relation (%s,%s): a filled relation with missing values is for fits, not fold-ins' % (i, j))
             if dev.by_col != (j == target and i != target):
                 raise ValueError('relation (%s,%s): a fold-in takes the lists compressed along the target %s'
                                  % (i, j, target))
-            rd.flags |= nat.SKF_REL_FOLD_CSR
+            rd.flags |= nat.SKF_REL_FOLD_CSR | (0 if dev.unstored == 'zero' else nat.SKF_REL_FOLD_KNOWN)
             return dev
         if dev.by_col:
             raise ValueError('relation (%s,%s): lists compressed along the column type are for fold-ins' % (i, j))
@@ -984,9 +987,10 @@ class DevicePlan(object):
             pass
 
 
-def upload_graph(rel_list, theta_list, dtype, runtime=None):
+def upload_graph(rel_list, theta_list, dtype, runtime=None, fold=False):
     """Relations / masks / constraints to HBM ONCE, as DeviceMatrix entries that any number of plans can
-    share (concurrent restarts of one graph): same conversions as DevicePlan applies to host arrays."""
+    share (concurrent restarts of one graph): same conversions as DevicePlan applies to host arrays.  `fold`: the graph of a
+    fold-in (SKF_TRANSFORM plans), whose entry lists go up in the master type."""
     rt = runtime or nat.get_runtime()
     code = nat.DTYPES[dtype] if isinstance(dtype, str) else dtype
     npd = nat.NP_DTYPE[code]
@@ -994,7 +998,7 @@ def upload_graph(rel_list, theta_list, dtype, runtime=None):
     for rel in rel_list:
         i, j, data, mask = rel[:4]
         if isinstance(data, KnownEntries):
-            rels.append((i, j, upload_known_entries(data, code, rt.mem), mask) + tuple(rel[4:]))
+            rels.append((i, j, upload_known_entries(data, code, rt.mem, fold=fold), mask) + tuple(rel[4:]))
             continue
         if not isinstance(data, (DeviceMatrix, DeviceKnownEntries)):
             arr = np.ascontiguousarray(data, dtype=npd)

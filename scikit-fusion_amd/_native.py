@@ -20,6 +20,7 @@ SKF_REL_KNOWN_CSR = 64
 SKF_REL_SPARSE_CSR = 128
 SKF_REL_FOLD_CSR = 256
 SKF_REL_FILL_RANK1 = 512
+SKF_REL_FOLD_KNOWN = 1024
 SKF_STAGE_CONTRACT, SKF_STAGE_BACKBONE, SKF_STAGE_ACCUMULATE, SKF_STAGE_UPDATE = 0, 1, 2, 3
 SKF_X_W, SKF_X_Q, SKF_X_QM, SKF_X_ED = 0, 1, 2, 3
 SKF_COMM_SINGLE, SKF_COMM_RCCL, SKF_COMM_CALLBACK, SKF_COMM_NULL = 0, 1, 2, 3
@@ -158,6 +159,8 @@ SIGNATURES = {
                                C.c_int32, _P, C.c_size_t, _P]),
     'skf_to_bf16': (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P]),
     'skf_fold_lists': (C.c_int, [C.c_int32, _P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P]),
+    'skf_fold_known_pass': (C.c_int, [C.c_int32, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P,
+                                      C.c_int64, _P, C.c_int64, _P]),
     'skf_complete_topk_workspace_bytes': (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     'skf_complete_topk': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P,
                                     _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_size_t, _P]),

@@ -222,6 +222,10 @@ static void plan_describe_relations(skf_plan* p, int32_t n_types, int32_t n_rela
         if (fold && p->variant != SKF_TRANSFORM) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR is for SKF_TRANSFORM plans", r);
         if (fold && (csr || sp0))
             SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR excludes SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR", r);
+        const bool fold_known = (d.flags & SKF_REL_FOLD_KNOWN) != 0;      // ... stored = known, every other entry unknown
+        if (fold_known && p->variant != SKF_TRANSFORM)
+            SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_KNOWN is for SKF_TRANSFORM plans", r);
+        if (fold_known && !fold) SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_KNOWN goes with SKF_REL_FOLD_CSR", r);
         const bool fill = (d.flags & SKF_REL_FILL_RANK1) != 0;    // F = a b^T + D: a filled relation with missing values
         if (fill && (!sp0 || absent || p->owned || p->variant == SKF_TRANSFORM))
             SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FILL_RANK1 goes with SKF_REL_SPARSE_CSR on SKF_DFMF / SKF_DFMC plans of whole "
@@ -290,6 +294,7 @@ static void plan_describe_relations(skf_plan* p, int32_t n_types, int32_t n_rela
                 SKF_FAIL(SKF_E_INVALID, "relation %d: SKF_REL_FOLD_CSR beyond the list limits (a rank above 1024 or %lld > 2e9 entries)",
                          r, (long long)d.known_bound);
             s.fold = true;
+            s.fold_known = fold_known;
             s.binary = false;
             s.R_in = s.R = nullptr;
             s.kn_cap = d.known_bound;
@@ -642,6 +647,19 @@ static void plan_layout(skf_plan* p) {
             add_slot(p, r.KrIdx, cap * 4);
             add_slot(p, r.KrVal, cap * es);
             add_slot(p, r.Tm, (size_t)tp.n * tt.c * es);
+            if (r.fold_known) {
+                // stored = known: the unsplit B_r and the plan's one X = G_t B_r; the error is a pass over the lists alone
+                add_slot(p, r.Bf, (size_t)tt.c * tt.c * 8);
+                if (!p->fold_x.bytes) add_slot(p, p->fold_x, (size_t)tt.n * tt.c * es);
+                want_part(k_small, ti.c, tj.c, tj.c, true);
+                want_part(k_small, ti.c, tj.c, ti.c, true);
+                want_part(k_small, ti.c, ti.c, tj.c, true);
+                want_part(k_small, tj.c, tj.c, ti.c, true);
+                want_part(k_mixed, tp.n, tt.c, tp.c);                       // T = G_p S'
+                want_part(k_mixed, tt.n, tt.c, tt.c);                       // X = G_t B_r
+                want_partials(tt.n, 1);                                     // fold_known_err_pass: at most as many waves
+                continue;
+            }
             add_slot(p, r.H, (size_t)tt.n * tp.c * es);
             add_slot(p, r.T1, cc);
             add_slot(p, r.Xi, (size_t)ti.c * ti.c * 8);
@@ -1064,6 +1082,8 @@ int skf_iterate_batch(skf_plan* const* plans, int32_t n_plans, int32_t n_iters, 
             for (int k = 0; k < n_plans; ++k) {
                 skf_plan* p = plans[k];
                 check_bound(p);
+                for (const RelState& r : p->rels)
+                    if (r.fold_known) SKF_FAIL(SKF_E_INVALID, "plan %d holds a SKF_REL_FOLD_KNOWN relation: such fold-ins do not batch", k);
                 if (!fold_fused(p) || p->dtype != p0->dtype || p->types.size() != p0->types.size() || p->rels.size() != p0->rels.size() ||
                     p->target != p0->target)
                     SKF_FAIL(SKF_E_STATE, "plan %d does not batch with plan 0 (fold-in without constraints on the target, same graph and engine required)", k);
@@ -1391,6 +1411,12 @@ int skf_relation_sqerr(skf_plan* p, int32_t rel, double* out, void* stream) {
             GemmArgs h = gemm_args(A, 1, c, B, c, 1, C, c, c, c, (int)n, EPI_STORE, 0);
             wide_gemm(p, h, st);
         };
+        if (r.fold_known) {
+            // the known-entry objective: sum over the stored entries of (v - <G_t[o], T[i]>)^2, one pass, nothing else
+            SKF_HIP(hipMemsetAsync(acc, 0, sizeof(double), st));
+            list_total(fold_known_err_pass(p, r, st, 1));
+            return;
+        }
         if (r.fold) {
             // as for SKF_REL_SPARSE_CSR below: tr(S^T Gram_i S Gram_j) + sum over the stored entries of (r - x)^2 - x^2, the lists
             // compressed along the target: x = <H[o], G_p[idx]>, H = G_t S (row side) or G_t S^T (column side)
@@ -1482,7 +1508,7 @@ int skf_get_contraction(const skf_plan* p, int32_t rel, int32_t which, void* dst
         const RelState& r = p->rels[rel];
         const TypeState& ti = p->types[r.row];
         const TypeState& tj = p->types[r.col];
-        if (r.fold) SKF_FAIL(SKF_E_INVALID, "relation %d (SKF_REL_FOLD_CSR) forms neither P nor Q", rel);
+        if (r.fold) SKF_FAIL(SKF_E_INVALID, "relation %d (SKF_REL_FOLD_CSR%s) forms neither P nor Q", rel, r.fold_known ? " | SKF_REL_FOLD_KNOWN" : "");
         if (which == 2 && !r.kn) SKF_FAIL(SKF_E_STATE, "relation %d forms P, not P S^T (which = 2 is for known-entries relations)", rel);
         const Slot& src = which == 0 ? r.P : which == 1 ? r.Q : r.A;
         const int64_t rows = which == 1 ? tj.n : r.nr, cols = which == 0 ? tj.c : ti.c;
@@ -1656,6 +1682,24 @@ int skf_fold_lists(int32_t dtype, const int64_t* indptr, const int32_t* indices,
             launch_fold_lists<double>(indptr, (const int*)indices, values, n_out, T, ldt, c, Ec, lde, Dc, ldd, as_stream(stream));
         else
             launch_fold_lists<float>(indptr, (const int*)indices, values, n_out, T, ldt, c, Ec, lde, Dc, ldd, as_stream(stream));
+    });
+}
+
+int skf_fold_known_pass(int32_t dtype, const int64_t* indptr, const int32_t* indices, const void* values, int64_t n_out, const void* G,
+                        int64_t ldg, const void* T, int64_t ldt, int32_t c, const void* X, int64_t ldx, void* E, int64_t lde, void* D,
+                        int64_t ldd, void* stream) {
+    return guarded([&] {
+        if (dtype != SKF_F64 && dtype != SKF_F32) SKF_FAIL(SKF_E_INVALID, "skf_fold_known_pass: dtype must be SKF_F64 / SKF_F32");
+        if (!indptr || !indices || !values || !G || !T || !E || !D) SKF_FAIL(SKF_E_INVALID, "null argument");
+        if (n_out < 0 || n_out > 2000000000LL || c < 1 || c > 1024)
+            SKF_FAIL(SKF_E_INVALID, "skf_fold_known_pass: n_out %lld / width %d", (long long)n_out, c);
+        if (ldg < c || ldt < c || lde < c || ldd < c || (X && ldx < c)) SKF_FAIL(SKF_E_INVALID, "ld too small");
+        if (dtype == SKF_F64)
+            launch_fold_known<double>(indptr, (const int*)indices, values, n_out, G, ldg, T, ldt, c, X, ldx, E, lde, D, ldd, nullptr,
+                                      as_stream(stream));
+        else
+            launch_fold_known<float>(indptr, (const int*)indices, values, n_out, G, ldg, T, ldt, c, X, ldx, E, lde, D, ldd, nullptr,
+                                     as_stream(stream));
     });
 }
 

@@ -949,4 +949,123 @@ __global__ __launch_bounds__(256) void fold_lists_kernel(FoldListArgs<T> a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Fold-in on the KNOWN entries only (SKF_REL_FOLD_KNOWN, skf_fold_known_pass): every entry that is not stored is UNKNOWN
+// and takes the current model's prediction (the completion step of reference _dfmc.py:319-325), then the target's update of
+// _dfmf.py:385-428 runs on the completed relation -- which is never formed.  With T = G_p S^T (row side; G_p S on the column
+// side; n_partner x c, constant), B = T^T T (c x c, constant) and the known entries (i_k, v_k) of target object o
+//     x_k     = <G[o], T[i_k]>                          the prediction at a known entry
+//     tmp1[o] = X[o] + sum_k (v_k - x_k) T[i_k]         X = G B, formed by the caller (NULL: nothing added)
+//     E[o]   += max(tmp1, 0) ,  D[o] += max(-tmp1, 0)
+// The lists are the ones SKF_REL_FOLD_CSR hands over, but they are read once per ITERATION: this pass reads the moving factor.
+// Mapping: `lanes` adjacent lanes (a power of two, >= min(c, 64), at most 64) own one target object; lane l of the group
+// owns the columns l + lanes * j, j < CPL (CPL = 1 for c <= 64, up to 16 at c = 1024), and keeps G[o] and the accumulator of
+// those columns in registers.  Per entry the group gathers T[i_k] ONCE (adjacent lanes read adjacent columns: contiguous
+// requests) and uses the row in registers twice.  Arithmetic order, so that a host loop can repeat it:
+//     part_l = fma(G[o][q_j], T[i_k][q_j], part_l)  over the lane's columns in ascending j, from part_l = 0
+//     x_k    = the xor butterfly over the group: part += part of lane (l ^ off), off = 1, 2, 4, ... < lanes
+//     e_k    = v_k - x_k
+//     acc[q] = fma(e_k, T[i_k][q], acc[q])          in LIST ORDER, from acc = 0
+//     tmp1   = acc[q] + X[o][q]
+// Every (o, q) has one owner: no atomics, no partial buffers, no second launch; E / D take one plain read-modify-write.
+// An object with an empty list gets tmp1 = X[o].  U entries are taken per trip: their indices, values and U * CPL gathers
+// are issued before the first dependent chain (dot, butterfly, axpy) consumes one -- like fold_lists_kernel the pass is
+// bound by the latency of the gathers; U per width class is chosen so that nothing spills (resource report: no scratch).
+// The trip count is the longest list of the WAVE (lane groups with shorter lists run on with e = 0 and no loads), so the
+// cross-lane sums are reached by all 64 lanes together.  A very long list runs serially in its lanes: the accepted pattern
+// of the fold-in and initialiser passes (profiles/r10_sparse_foldin.txt); splitting one over several waves is not done.
+// ERR: no E / D; sq[wave] = sum over the wave's entries of (double)e_k * (double)e_k, one f64 partial per wave (4 per
+// workgroup, fixed order) -- the known-entry objective of skf_relation_sqerr.
+template <typename T>
+struct FoldKnownArgs {
+    const int64_t* ptr;         // [n_out + 1]
+    const int* idx;             // partner object of every entry
+    const T* val;
+    const T* G;                 // [n_out][ldg]  the moving factor
+    const T* Tm;                // [n_partner][ldt]
+    const T* X;                 // [n_out][ldx] or NULL
+    T* E;                       // [n_out][lde]
+    T* D;                       // [n_out][ldd]
+    double* sq;                 // ERR: [gridDim.x * 4]
+    int64_t n_out, ldg, ldt, ldx, lde, ldd;
+    int c, lanes;
+};
+
+template <typename T, int CPL, int U, bool ERR>
+__global__ __launch_bounds__(256) void fold_known_kernel(FoldKnownArgs<T> a) {
+    const int lanes = a.lanes;
+    const int sub = (int)threadIdx.x % lanes;
+    const int64_t o = (int64_t)blockIdx.x * (256 / lanes) + (int)threadIdx.x / lanes;
+    const bool have = o < a.n_out;
+    bool live[CPL];
+    T g[CPL], acc[CPL];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+        live[j] = have && sub + lanes * j < a.c;
+        g[j] = live[j] ? a.G[o * a.ldg + sub + lanes * j] : (T)0;
+        acc[j] = (T)0;
+    }
+    const T* Tq = a.Tm + sub;
+    const int64_t k0 = have ? a.ptr[o] : 0;
+    const int len = have ? (int)(a.ptr[o + 1] - k0) : 0;
+    int trips = len;                                    // the longest list of the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1)
+        if (off >= lanes) {                             // (uniform; the lanes of a group hold the same length)
+            const int other = __shfl_xor(trips, off, 64);
+            trips = other > trips ? other : trips;
+        }
+    double sq = 0.0;
+    for (int s = 0; s < trips; s += U) {
+        bool ok[U];
+        int64_t row[U];
+        T v[U], t[U][CPL], x[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            ok[u] = s + u < len;
+            row[u] = ok[u] ? (int64_t)a.idx[k0 + s + u] * a.ldt : 0;
+            v[u] = ok[u] ? a.val[k0 + s + u] : (T)0;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) t[u][j] = (ok[u] && live[j]) ? Tq[row[u] + lanes * j] : (T)0;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            x[u] = (T)0;
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) x[u] = fold_fma(g[j], t[u][j], x[u]);
+        }
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1)          // the butterfly of the U entries side by side
+            if (off < lanes) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) x[u] += __shfl_xor(x[u], off, 64);
+            }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const T e = ok[u] ? v[u] - x[u] : (T)0;
+            if (ERR) {
+                if (sub == 0) sq += (double)e * (double)e;
+            } else {
+#pragma unroll
+                for (int j = 0; j < CPL; ++j) acc[j] = fold_fma(e, t[u][j], acc[j]);
+            }
+        }
+    }
+    if (ERR) {
+        sq = wave_sum(sq);
+        if ((threadIdx.x & 63) == 0) a.sq[(int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)] = sq;
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) {
+        if (!live[j]) continue;
+        const int q = sub + lanes * j;
+        const T tmp = a.X ? acc[j] + a.X[o * a.ldx + q] : acc[j];
+        a.E[o * a.lde + q] += tmp > (T)0 ? tmp : (T)0;
+        a.D[o * a.ldd + q] += tmp < (T)0 ? -tmp : (T)0;
+    }
+}
+
 }  // namespace skf

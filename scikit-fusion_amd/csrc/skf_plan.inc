@@ -171,6 +171,10 @@ struct RelState {
     // KrPtr / KrIdx / KrVal at bind time (master type); Tm = G_p S^T (row side) / G_p S (column side), n_partner x c_target;
     // H = G_t S / G_t S^T (n_target x c_partner) and Xi / Xj / T1 for skf_relation_sqerr.  No P, no Q, no parts.
     bool fold = false;
+    // ... with SKF_REL_FOLD_KNOWN: stored = KNOWN, every other entry takes the model's prediction in every iteration.  The same
+    // lists and Tm; Bf = the UNSPLIT B_r = T^T T (c_t x c_t, f64) for X = G_t B_r of an iteration (skf_plan::fold_x); no H, no
+    // trace term: skf_relation_sqerr is one pass over the lists (fold_known_kernel)
+    bool fold_known = false;
     Slot FiB;                              // SKF_BF16: bf16 rows of T = G_j S^T (n_j x ldf; the rows of G_i: TypeState::Grow)
     Slot Tm;                               // T = G_j S^T in the master type (n_j x c_i)
     Slot Apart, Qpart;                     // partial outputs of the parts, [parts][n][c_i] (only with more than one part)
@@ -238,6 +242,7 @@ struct skf_plan {
     skf::Slot part_aux;
     size_t part_aux_bytes = 0;
     skf::Slot sp_part;                     // partial outputs of the parted list passes over sparse 0/1 relations
+    skf::Slot fold_x;                      // SKF_TRANSFORM with a SKF_REL_FOLD_KNOWN relation: X = G_t B_r of one relation, n_t x c_t
 
     skf::Switches sw;                      // read once in skf_plan_bind_workspace
     bool overlap = false;

@@ -326,10 +326,11 @@ static void prepare_transform(skf_plan* p, hipStream_t st) {
         TypeState& tj = p->types[r.col];
         const int ni = (int)ti.n, nj = (int)tj.n, ci = ti.c, cj = tj.c;
         if (r.fold) {                         // the stored entries, compressed along the target: T = G_p S', one pass into Ec / Dc
-            fold_prepare(p, r, st);
+            if (!r.fold_known) fold_prepare(p, r, st);
             const bool row_side = r.row == p->target;
             relation_small_terms(p, r, 0, EPI_SPLIT_ACC, row_side ? tt.Bp_tot.ptr : nullptr, row_side ? tt.Bn_tot.ptr : nullptr,
                                  row_side ? nullptr : tt.Bp_tot.ptr, row_side ? nullptr : tt.Bn_tot.ptr, row_side, !row_side, st);
+            if (r.fold_known) fold_known_prepare(p, r, st);      // (stored = known: T and the unsplit B_r, nothing into Ec / Dc)
             continue;
         }
         if (r.row == p->target) {             // _dfmf.py:392-405
@@ -356,7 +357,8 @@ static void prepare_transform(skf_plan* p, hipStream_t st) {
 // The fold-in iteration as ONE launch (foldin_step_kernel): no constraint on the target type (a constraint couples the
 // rows of an iteration through E / D, which this form never writes)
 static bool fold_fused(const skf_plan* p) {
-    return p->variant == SKF_TRANSFORM && p->engine == SKF_ENGINE_MFMA && p->thetas.empty();
+    // (a SKF_REL_FOLD_KNOWN relation reads the moving factor through its lists every iteration: the unfused path below)
+    return p->variant == SKF_TRANSFORM && p->engine == SKF_ENGINE_MFMA && p->thetas.empty() && !p->fold_x.bytes;
 }
 
 // `iters` fold-in iterations of `n_plans` plans of one graph (same object count and rank of the target), every launch
@@ -408,6 +410,8 @@ static void iterate_transform(skf_plan* p, hipStream_t st) {
     const int n = (int)tt.n, c = tt.c;
     SKF_HIP(hipMemcpyAsync(tt.E.ptr, tt.Ec.ptr, tt.E.bytes, hipMemcpyDeviceToDevice, st));
     SKF_HIP(hipMemcpyAsync(tt.D.ptr, tt.Dc.ptr, tt.D.bytes, hipMemcpyDeviceToDevice, st));
+    for (RelState& r : p->rels)              // stored = known: the split of this relation's tmp1, in relation order
+        if (r.fold_known) fold_known_step(p, r, st);
     GemmArgs g = gemm_args(tt.G.ptr, c, 1, tt.Bn_tot.ptr, c, 1, tt.E.ptr, c, n, c, c, EPI_ACC, 0);
     mixed_gemm(p, g, st);
     g = gemm_args(tt.G.ptr, c, 1, tt.Bp_tot.ptr, c, 1, tt.D.ptr, c, n, c, c, EPI_ACC, 0);

@@ -325,18 +325,23 @@ static void launch_fold_lists(const int64_t* ptr, const int* idx, const void* va
     check_launch("fold_lists");
 }
 
+// T of a fold-in relation given as lists: G_p S^T (the target is the row type, _dfmf.py:394-398) or G_p S (column type,
+// _dfmf.py:408-412), n_partner x c_target in the master type
+static void fold_form_t(skf_plan* p, RelState& r, hipStream_t st) {
+    TypeState& ti = p->types[r.row];
+    TypeState& tj = p->types[r.col];
+    const int ci = ti.c, cj = tj.c;
+    GemmArgs g = r.row == p->target ? gemm_args(tj.G.ptr, cj, 1, r.S.ptr, 1, cj, r.Tm.ptr, ci, (int)tj.n, ci, cj, EPI_STORE, 0)      // G_j S^T
+                                    : gemm_args(ti.G.ptr, ci, 1, r.S.ptr, cj, 1, r.Tm.ptr, cj, (int)ti.n, cj, ci, EPI_STORE, 0);     // G_i S
+    mixed_gemm(p, g, st);
+}
+
 // The constant sums of prepare_transform for a SKF_REL_FOLD_CSR relation: T = G_p S^T (the target is the row type,
 // _dfmf.py:394-398) or G_p S (column type, _dfmf.py:408-412) in the master type, then one pass over the lists into Ec / Dc.
 // Several relations of a plan accumulate by plain read-modify-write in relation order on the one stream.
 static void fold_prepare(skf_plan* p, RelState& r, hipStream_t st) {
-    TypeState& ti = p->types[r.row];
-    TypeState& tj = p->types[r.col];
     TypeState& tt = p->types[p->target];
-    const int ci = ti.c, cj = tj.c;
-    const bool row_side = r.row == p->target;
-    GemmArgs g = row_side ? gemm_args(tj.G.ptr, cj, 1, r.S.ptr, 1, cj, r.Tm.ptr, ci, (int)tj.n, ci, cj, EPI_STORE, 0)      // G_j S^T
-                          : gemm_args(ti.G.ptr, ci, 1, r.S.ptr, cj, 1, r.Tm.ptr, cj, (int)ti.n, cj, ci, EPI_STORE, 0);     // G_i S
-    mixed_gemm(p, g, st);
+    fold_form_t(p, r, st);
     if (p->f64)
         launch_fold_lists<double>((const int64_t*)r.KrPtr.ptr, (const int*)r.KrIdx.ptr, r.KrVal.ptr, tt.n, r.Tm.ptr, tt.c, tt.c,
                                   tt.Ec.ptr, tt.c, tt.Dc.ptr, tt.c, st);
@@ -361,6 +366,94 @@ static int fold_err_pass(skf_plan* p, const RelState& r, hipStream_t st, int sq_
     d.parts = 1; d.w = tp.c; d.mode = SRP_ERR;
     d.sq_first = sq_first;
     return srp_pass(p, d, st);
+}
+
+// ------------------------------------------------------------------------------------------
+// Fold-in on the known entries only (SKF_REL_FOLD_KNOWN, fold_known_kernel in skf_known.h)
+// ------------------------------------------------------------------------------------------
+// Workgroups of the pass over n_out objects of width c: 256 / lanes objects each; an error pass writes 4 partials per
+// workgroup -- at most srp_partials(n_out, 1), what plan_layout reserves for a fold-in relation.
+static int fold_known_lanes(int c) {
+    int lanes = 1;
+    while (lanes < 64 && lanes < c) lanes *= 2;
+    return lanes;
+}
+static int64_t fold_known_grid(int64_t n_out, int c) {
+    const int64_t per = 256 / fold_known_lanes(c);
+    return (n_out + per - 1) / per;
+}
+// sq == nullptr: E / D += the split of X + sum (v - x) T; otherwise the error partials (their number is returned)
+template <typename T>
+static int launch_fold_known(const int64_t* ptr, const int* idx, const void* val, int64_t n_out, const void* G, int64_t ldg,
+                             const void* Tm, int64_t ldt, int c, const void* X, int64_t ldx, void* E, int64_t lde, void* D,
+                             int64_t ldd, double* sq, hipStream_t st) {
+    if (n_out <= 0 || c <= 0) return 0;
+    FoldKnownArgs<T> a;
+    a.ptr = ptr; a.idx = idx; a.val = (const T*)val; a.G = (const T*)G; a.Tm = (const T*)Tm; a.X = (const T*)X;
+    a.E = (T*)E; a.D = (T*)D; a.sq = sq;
+    a.n_out = n_out; a.ldg = ldg; a.ldt = ldt; a.ldx = ldx; a.lde = lde; a.ldd = ldd; a.c = c;
+    a.lanes = fold_known_lanes(c);
+    const dim3 grid((unsigned)fold_known_grid(n_out, c));
+    // entries in flight per width class (columns per lane x entries = gathers per lane; no scratch in any instantiation)
+#define SKF_FOLD_KNOWN(CPL, U)                                                                             \
+    do {                                                                                                   \
+        if (sq) hipLaunchKernelGGL((fold_known_kernel<T, CPL, U, true>), grid, dim3(256), 0, st, a);       \
+        else hipLaunchKernelGGL((fold_known_kernel<T, CPL, U, false>), grid, dim3(256), 0, st, a);         \
+    } while (0)
+    if (c <= 64) SKF_FOLD_KNOWN(1, 8);
+    else if (c <= 128) SKF_FOLD_KNOWN(2, 4);
+    else if (c <= 256) SKF_FOLD_KNOWN(4, 4);
+    else if (c <= 512) SKF_FOLD_KNOWN(8, 2);
+    else SKF_FOLD_KNOWN(16, 2);
+#undef SKF_FOLD_KNOWN
+    check_launch("fold_known");
+    return (int)grid.x * 4;
+}
+
+// Preparation of a SKF_REL_FOLD_KNOWN relation: T, and the UNSPLIT B_r = S Gram_p S^T (row side) / S^T Gram_p S (column
+// side), c_t x c_t f64 like every c x c matrix of a plan, from the first product relation_small_terms left in r.U.  Nothing
+// goes into Ec / Dc: nothing about this relation is constant there.
+static void fold_known_prepare(skf_plan* p, RelState& r, hipStream_t st) {
+    TypeState& ti = p->types[r.row];
+    TypeState& tj = p->types[r.col];
+    const int ci = ti.c, cj = tj.c;
+    fold_form_t(p, r, st);
+    GemmArgs g = r.row == p->target ? gemm_args(r.U.ptr, cj, 1, r.S.ptr, 1, cj, r.Bf.ptr, ci, ci, ci, cj, EPI_STORE, 0)      // (S Gram_j) S^T
+                                    : gemm_args(r.S.ptr, 1, cj, r.U.ptr, cj, 1, r.Bf.ptr, cj, cj, cj, ci, EPI_STORE, 0);     // S^T (Gram_i S)
+    small_gemm(p, g, st);
+}
+
+// One iteration's share of such a relation: X = G B_r into the plan's n_t x c scratch, then E / D += the split of
+// tmp1 = X + sum over the known entries of (v - <G[o], T[i]>) T[i]   (masters in every engine: SKF_BF16 runs it in f32)
+static void fold_known_step(skf_plan* p, RelState& r, hipStream_t st) {
+    TypeState& tt = p->types[p->target];
+    const int c = tt.c;
+    GemmArgs g = gemm_args(tt.G.ptr, c, 1, r.Bf.ptr, c, 1, p->fold_x.ptr, c, (int)tt.n, c, c, EPI_STORE, 0);
+    mixed_gemm(p, g, st);
+    if (p->f64)
+        launch_fold_known<double>((const int64_t*)r.KrPtr.ptr, (const int*)r.KrIdx.ptr, r.KrVal.ptr, tt.n, tt.G.ptr, c, r.Tm.ptr, c, c,
+                                  p->fold_x.ptr, c, tt.E.ptr, c, tt.D.ptr, c, nullptr, st);
+    else
+        launch_fold_known<float>((const int64_t*)r.KrPtr.ptr, (const int*)r.KrIdx.ptr, r.KrVal.ptr, tt.n, tt.G.ptr, c, r.Tm.ptr, c, c,
+                                 p->fold_x.ptr, c, tt.E.ptr, c, tt.D.ptr, c, nullptr, st);
+}
+
+// skf_relation_sqerr of such a relation: sum over the KNOWN entries of (v - x)^2, x = <G_t[o], T[i]> with the current target
+// factor; T is formed here (the preparation may not have run, or a backbone may have changed since).  One f64 partial per
+// wave from slot `sq_first` of p->sqpart; their number is returned.
+static int fold_known_err_pass(skf_plan* p, RelState& r, hipStream_t st, int sq_first) {
+    TypeState& tt = p->types[p->target];
+    const int c = tt.c;
+    const int64_t waves = fold_known_grid(tt.n, c) * 4;
+    if ((size_t)(waves + sq_first) > p->sq_elems)
+        SKF_FAIL(SKF_E_STATE, "residual partials: %lld > %zu slots", (long long)(waves + sq_first), p->sq_elems);
+    fold_form_t(p, r, st);
+    double* sq = (double*)p->sqpart.ptr + sq_first;
+    if (p->f64)
+        return launch_fold_known<double>((const int64_t*)r.KrPtr.ptr, (const int*)r.KrIdx.ptr, r.KrVal.ptr, tt.n, tt.G.ptr, c, r.Tm.ptr,
+                                         c, c, nullptr, 0, nullptr, 0, nullptr, 0, sq, st);
+    return launch_fold_known<float>((const int64_t*)r.KrPtr.ptr, (const int*)r.KrIdx.ptr, r.KrVal.ptr, tt.n, tt.G.ptr, c, r.Tm.ptr, c,
+                                    c, nullptr, 0, nullptr, 0, nullptr, 0, sq, st);
 }
 
 // W = G_i^T R_c G_j for the backbone (_dfmc.py:311-314) with R_c = G_i,prev S_prev G_j,prev^T + E_prev:

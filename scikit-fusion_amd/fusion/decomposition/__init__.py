@@ -1,4 +1,4 @@
 from .dfmf import Dfmf, DfmfTransform
-from .dfmc import Dfmc
+from .dfmc import Dfmc, DfmcTransform
 
-__all__ = ['Dfmf', 'DfmfTransform', 'Dfmc']
+__all__ = ['Dfmf', 'DfmfTransform', 'Dfmc', 'DfmcTransform']

@@ -487,7 +487,7 @@ def transform_runs(R_ij, Theta_i, target_obj_type, obj_type2rank, models, max_it
         R_first = {k: host_view(v[0]) for k, v in R_ij.items()}        # (stored entries are read as such, never expanded)
         G0 = [initialize([t], {t: n_t}, obj_type2rank, R_first, init_type, rs)[t, t] for _ in models]
     rt = nat.get_runtime()
-    rel_list, theta_list = upload_graph(flatten_relations(R_ij), flatten_thetas(Theta_i), dtype, rt)
+    rel_list, theta_list = upload_graph(flatten_relations(R_ij), flatten_thetas(Theta_i), dtype, rt, fold=True)
     plans = []
     try:
         for (G, S), g0 in zip(models, G0):

@@ -526,7 +526,8 @@ class DfmfTransform(FusionTransform):
     expanded -- True: whenever eligible; False: never (``toarray()``); None: when density * max(rank) <= 4 and the relation
     has at least 2^20 cells (below that the dense upload is free and results stay bit for bit).  Stored non-finite values
     take `fill_value`, as in the dense path; entries that are not stored are zeros, not unknowns, and never filled.  A
-    relation given with ``unstored='unknown'`` is still expanded: the reference's fold-in fills it.
+    relation given with ``unstored='unknown'`` is still expanded: the reference's fold-in fills it (``DfmcTransform`` folds
+    new objects in on their known entries alone).
     sparse_constraints=None | True | False: a ``scipy.sparse`` constraint on the target goes to the device as its entries,
     under the rule of ``Dfmf``.
     """
@@ -537,6 +538,29 @@ class DfmfTransform(FusionTransform):
         super(DfmfTransform, self).__init__()
         self._set_params(vars())
 
+    def _enter(self, relation, target, R, Theta):
+        """One relation of the new graph into R / Theta (dfmf.py:176-189: preprocess, fill masked / non-finite entries with
+        `fill_value`), or as its stored entries where `fold_entries_apply` / `constraint_entries_apply` say so."""
+        key = (relation.row_type, relation.col_type)
+        if fold_entries_apply(relation, getattr(self, 'sparse_relations', None)):
+            # the stored entries, compressed along the target's side; `data[~isfinite] = fill_value` of the dense
+            # path on the stored values (what is not stored is zero, not unknown: nothing else to fill)
+            data = relation.stored_entries(by_col=relation.row_type != target)
+            data.values[~np.isfinite(data.values)] = self.fill_value
+            R.setdefault(key, []).append(data)
+            return
+        if relation.row_type == target and constraint_entries_apply(relation, getattr(self, 'sparse_constraints', None)):
+            Theta.setdefault(key, []).append(relation.constraint_entries())
+            return
+        data = relation.preprocessor(relation.dense_data()) if relation.preprocessor \
+            else relation.dense_data()
+        if np.ma.is_masked(data):
+            data.fill_value = self.fill_value
+            data = data.filled()
+        data[~np.isfinite(data)] = self.fill_value
+        dest = R if relation.row_type != relation.col_type else Theta
+        dest.setdefault(key, []).append(data)
+
     def transform(self, target, fusion_graph, fuser):
         self.target = target
         self.fusion_graph = fusion_graph
@@ -546,28 +570,10 @@ class DfmfTransform(FusionTransform):
         self.random_state = _random_state(self.random_state)
         rank = {ot: int(ot.rank) for ot in fusion_graph.object_types}
 
-        # dfmf.py:176-189: preprocess, fill masked / non-finite entries with `fill_value`
         R, Theta = {}, {}
         for row_type, col_type in product(fusion_graph.object_types, repeat=2):
             for relation in fusion_graph.get_relations(row_type, col_type):
-                if fold_entries_apply(relation, getattr(self, 'sparse_relations', None)):
-                    # the stored entries, compressed along the target's side; `data[~isfinite] = fill_value` of the dense
-                    # path on the stored values (what is not stored is zero, not unknown: nothing else to fill)
-                    data = relation.stored_entries(by_col=relation.row_type != target)
-                    data.values[~np.isfinite(data.values)] = self.fill_value
-                    R.setdefault((relation.row_type, relation.col_type), []).append(data)
-                    continue
-                if relation.row_type == target and constraint_entries_apply(relation, getattr(self, 'sparse_constraints', None)):
-                    Theta.setdefault((relation.row_type, relation.col_type), []).append(relation.constraint_entries())
-                    continue
-                data = relation.preprocessor(relation.dense_data()) if relation.preprocessor \
-                    else relation.dense_data()
-                if np.ma.is_masked(data):
-                    data.fill_value = self.fill_value
-                    data = data.filled()
-                data[~np.isfinite(data)] = self.fill_value
-                dest = R if relation.row_type != relation.col_type else Theta
-                dest.setdefault((relation.row_type, relation.col_type), []).append(data)
+                self._enter(relation, target, R, Theta)
 
         def frozen_model(run):
             """(G, S) of restart `run` (dfmf.py:109-115); only the LAST relation of a type pair survives in S there --
