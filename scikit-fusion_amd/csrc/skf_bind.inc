@@ -269,19 +269,20 @@ static void build_tile_lists(skf_plan* p, RelState& r, hipStream_t st) {
 // Step 1: every relation's mask in the engine's layout and its lists, whichever way the entries came in.
 static void bind_relation_lists(skf_plan* p, hipStream_t st) {
     for (RelState& r : p->rels) {
-        if (r.fold) {
+        const RelForm form = form_of(r);
+        if (form == REL_FOLD || form == REL_FOLD_KNOWN) {
             copy_fold_lists(p, r, st);
             continue;
         }
-        if ((r.kn_csr || r.sp0) && r.absent) continue;      // (row ownership, no row of the relation here: no lists, only the flag)
-        if (r.kn_csr || r.sp0) {               // the caller's CSR, validated, then the same lists the mask form builds
+        if (form == REL_STORED || r.kn_csr) {  // the caller's CSR, validated, then the same lists the mask form builds
+            if (r.absent) continue;            // (row ownership, no row of the relation here: no lists, only the flag)
             if (!r.csr_ptr) SKF_FAIL(SKF_E_INVALID, "a SKF_REL_KNOWN_CSR / SKF_REL_SPARSE_CSR relation without skf_plan_set_known_entries");
             build_known_lists_csr(p, r, st);
             continue;
         }
         if (!r.mask) continue;
         pack_mask(p, r, st);
-        if (r.kn) {                            // the known entries as lists; no working copy of the relation
+        if (form == REL_KNOWN) {               // the known entries as lists; no working copy of the relation
             build_known_lists(p, r, st);
             continue;
         }
@@ -368,7 +369,7 @@ static void bind_bf16_copies(skf_plan* p, hipStream_t st) {
         if (t.Grow.bytes) SKF_HIP(hipMemsetAsync(t.Grow.ptr, 0, t.Grow.bytes, st));
     }
     for (RelState& r : p->rels) {
-        if (r.absent || r.kn || r.sp0 || r.fold) continue;
+        if (r.absent || form_of(r) != REL_DENSE) continue;      // (the list forms keep no copy of a matrix)
         const int64_t rows = r.nr, cols = p->types[r.col].n;
         if (r.binary) {
             int* bad = (int*)p->sqpart.ptr;                  // (scratch word)

@@ -27,15 +27,18 @@ static InitForm init_form(const skf_plan* p, int32_t rel, const char* op, bool f
     if (p->variant == SKF_TRANSFORM) SKF_FAIL(SKF_E_INVALID, "%s: not for SKF_TRANSFORM plans", op);
     if (p->owned || p->sliced || r.absent || r.nr != p->types[r.row].n)
         SKF_FAIL(SKF_E_INVALID, "%s: relation %d is not held whole here (SKF_OPT_OWNED_ROWS plans and row blocks initialise on the host)", op, rel);
-    const bool known_lists = filled && r.kn && !r.sp0;
-    if (!known_lists && (r.masked || r.kn || r.kn_csr || r.mask))
+    const RelForm form = form_of(r);
+    const bool known_lists = filled && form == REL_KNOWN;
+    if (!known_lists && (r.masked || form == REL_KNOWN || r.kn_csr || r.mask))
         SKF_FAIL(SKF_E_INVALID, filled ? "%s: relation %d is masked and kept dense" : "%s: relation %d is masked / given as its known entries", op, rel);
     if (r.fill && !filled) SKF_FAIL(SKF_E_INVALID, "%s: relation %d carries a rank-one fill (SKF_REL_FILL_RANK1)", op, rel);
-    if (r.fold) SKF_FAIL(SKF_E_INVALID, "%s: relation %d is a fold-in list", op, rel);
-    if (known_lists) return INIT_KNOWN;
-    if (r.sp0) return r.fill ? INIT_RANK1 : INIT_LISTS;
-    if (p->bf16 && r.binary) return INIT_BITS;
-    return INIT_DENSE;
+    switch (form) {
+    case REL_FOLD: case REL_FOLD_KNOWN: SKF_FAIL(SKF_E_INVALID, "%s: relation %d is a fold-in list", op, rel);
+    case REL_KNOWN: return INIT_KNOWN;
+    case REL_STORED: return r.fill ? INIT_RANK1 : INIT_LISTS;
+    case REL_DENSE: break;
+    }
+    return p->bf16 && r.binary ? INIT_BITS : INIT_DENSE;
 }
 
 // ---- line norms ----------------------------------------------------------------------------------------------------------------

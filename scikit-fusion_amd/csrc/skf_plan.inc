@@ -1,5 +1,8 @@
 // skf_plan.inc -- part of the one translation unit skf_api.hip (textually included there, inside its namespaces; not a
-// header of its own): the plan: switches, per-type / per-relation state, workspace slots, and the launch helpers of one iteration (Gram, constraints, side updates, contractions; the pseudo-inverse: skf_pinv.inc).
+// header of its own): the plan -- its switches, the state of a type / a relation / a constraint, the form a relation comes
+// in (RelForm), the workspace slots -- and the launch primitives the steps are put together from: the product kinds and
+// their split-K scratch, the relation contractions, Gram, the constraint terms, the c x c terms, the fused side update.
+// Plan creation: skf_create.inc; the steps of an iteration: skf_steps.inc; the pseudo-inverse: skf_pinv.inc.
 // ------------------------------------------------------------------------------------------
 // plan
 // ------------------------------------------------------------------------------------------
@@ -184,6 +187,26 @@ struct RelState {
     Slot SmQ;                              // ... and Q as shares over row ranges of the relation, [sm_qparts][n_j][c_i]
     int sm_qparts = 0;
 };
+
+// The form a relation comes in -- what the plan stores of it and which passes read it.  Every relation has exactly ONE; the
+// flags above that decide it exclude each other (plan_describe_relation refuses every other combination, plan_decide_lists
+// sets `kn` only where neither `sp0` nor `fold` is set):
+//   REL_FOLD_KNOWN  fold && fold_known    SKF_TRANSFORM: the known entries along the target, everything else unknown
+//   REL_FOLD        fold && !fold_known   SKF_TRANSFORM: the stored entries along the target, everything else zero
+//   REL_STORED      sp0                   the stored entries as row and column lists, everything else zero (fill: + a b^T)
+//   REL_KNOWN       kn                    SKF_DFMC: the known entries as row and column lists (kn_csr: from the caller's
+//                                         CSR, else from a mask whose known share is small enough)
+//   REL_DENSE       none of these         a matrix: f64 / f32, the padded bf16 copy or the bitmap (binary; sparse /
+//                                         sp_gather: lists of its ones beside it), with or without a mask (masked)
+// `absent` (no local rows) and `masked` go with REL_DENSE, REL_KNOWN and REL_STORED alike and change nothing about the form.
+// `fold`, `fold_known` and `sp0` are final once the relation is described; `kn` is decided by plan_decide_lists, which reads
+// REL_DENSE until then as "a matrix, or known entries that may yet become lists".  Everything after plan creation sees the final form.
+enum RelForm { REL_DENSE, REL_KNOWN, REL_STORED, REL_FOLD, REL_FOLD_KNOWN };
+static inline RelForm form_of(const RelState& r) {
+    if (r.fold) return r.fold_known ? REL_FOLD_KNOWN : REL_FOLD;
+    if (r.sp0) return REL_STORED;
+    return r.kn ? REL_KNOWN : REL_DENSE;
+}
 
 struct ThetaState {
     int type = 0;

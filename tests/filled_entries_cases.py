@@ -15,7 +15,7 @@ import skfusion_amd._native as nat
 from skfusion_amd._engine import DevicePlan, KnownEntries
 from skfusion_amd.fusion import FusionGraph, Relation, ObjectType, Dfmf, Dfmc
 from skfusion_amd.fusion.decomposition import dfmf as dfmf_mod
-from helpers import relerr, within
+from helpers import plan_create_status, relerr, within
 import known_cases as K
 import sparse_dfmf_cases as SC
 
@@ -283,19 +283,8 @@ def pass_case(n_a, n_b, c_a, c_b, dtype, parts, pattern, what, monkeypatch, seed
 
 # ---- refusals ---------------------------------------------------------------------------------------------------------------
 def _raw_create(variant, flags, opt_flags=0, part_count=0):
-    rt = nat.get_runtime()
-    tdesc = (nat.TypeDesc * 2)()
-    tdesc[0].n_obj, tdesc[0].rank, tdesc[1].n_obj, tdesc[1].rank = 40, 8, 30, 6
-    rdesc = (nat.RelationDesc * 1)()
-    rdesc[0].row_type, rdesc[0].col_type = 0, 1
-    rdesc[0].flags, rdesc[0].known_bound = flags, 10
-    opt = nat.Options(nat.SKF_F64, variant, 0 if variant == nat.SKF_TRANSFORM else -1, nat.SKF_ENGINE_MFMA, 0, part_count, opt_flags)
-    handle = nat._P()
-    try:
-        return rt.lib.skf_plan_create(2, tdesc, 1, rdesc, 0, (nat.ThetaDesc * 1)(), C.byref(opt), C.byref(handle))
-    finally:
-        if handle.value:
-            rt.lib.skf_plan_destroy(handle)
+    return plan_create_status(nat.get_runtime().lib, [(40, 8), (30, 6)], [dict(row_type=0, col_type=1, flags=flags, known_bound=10)],
+                              variant=variant, target=0 if variant == nat.SKF_TRANSFORM else -1, part=(0, part_count), opt_flags=opt_flags)[0]
 
 
 def refused_flag_cases():

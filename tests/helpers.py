@@ -313,6 +313,36 @@ def fit_owned(variant, R, M, Theta, types, rank, G0, max_iter, size, dtype='f64'
             p.close()
 
 
+# ---- skf_plan_create on raw descriptors -------------------------------------------------------------------
+def plan_create_status(lib, types, relations=(), thetas=(), dtype=0, variant=0, target=-1, engine=0, part=(0, 0), opt_flags=0):
+    """skf_plan_create on raw descriptors -> (status, text of skf_last_error()).  types: (n_obj, rank) pairs; relations /
+    thetas: dicts of the fields of skf_relation_desc / skf_theta_desc that differ from zero (pointers as integers); the rest
+    are the fields of skf_options (defaults: SKF_F64, SKF_DFMF, no target, SKF_ENGINE_MFMA, one part).  The validation
+    answers before any HIP call is made; a plan that was created is destroyed again.  The text belongs to a refusal only --
+    an accepted call leaves the last one in place."""
+    import ctypes as C
+    import skfusion_amd._native as nat
+    tdesc = (nat.TypeDesc * max(len(types), 1))()
+    for k, (n_obj, rank) in enumerate(types):
+        tdesc[k].n_obj, tdesc[k].rank = n_obj, rank
+    rdesc = (nat.RelationDesc * max(len(relations), 1))()
+    for k, fields in enumerate(relations):
+        for name, value in fields.items():
+            setattr(rdesc[k], name, value)
+    hdesc = (nat.ThetaDesc * max(len(thetas), 1))()
+    for k, fields in enumerate(thetas):
+        for name, value in fields.items():
+            setattr(hdesc[k], name, value)
+    opt = nat.Options(dtype, variant, target, engine, part[0], part[1], opt_flags)
+    handle = nat._P()
+    try:
+        status = lib.skf_plan_create(len(types), tdesc, len(relations), rdesc, len(thetas), hdesc, C.byref(opt), C.byref(handle))
+        return status, lib.skf_last_error().decode()
+    finally:
+        if handle.value:
+            lib.skf_plan_destroy(handle)
+
+
 # ---- measured deviations -------------------------------------------------------------------------------
 # `within(value, bound, what)` asserts value < bound and records (what, value, bound); conftest writes the
 # records of a session to gpurun_out/test_deviations.txt, so the bounds in the GPU tests can be kept at a

@@ -21,7 +21,7 @@ import pytest
 
 import skfusion_amd._native as nat
 from skfusion_amd._engine import DevicePlan, KnownEntries
-from helpers import relerr, within
+from helpers import plan_create_status, relerr, within
 import known_cases as K
 
 
@@ -247,27 +247,15 @@ def invalid_lists_case(kind, dtype='f64', variant=None):
 
 def invalid_flag_cases():
     """SKF_E_INVALID at plan creation: a fold-in plan, both CSR flags at once, a mask, a row block."""
-    import ctypes as C
     rt = nat.get_runtime()
+    keep = rt.mem.empty(4096)
 
     def create(variant, flags, mask=False, n_rows=0, part_count=0, opt_flags=0):
-        tdesc = (nat.TypeDesc * 2)()
-        tdesc[0].n_obj, tdesc[0].rank, tdesc[1].n_obj, tdesc[1].rank = 40, 8, 30, 6
-        rdesc = (nat.RelationDesc * 1)()
-        rdesc[0].row_type, rdesc[0].col_type = 0, 1
-        rdesc[0].flags, rdesc[0].known_bound = flags, 10
-        rdesc[0].n_rows = n_rows
-        keep = rt.mem.empty(4096)
+        rel = dict(row_type=0, col_type=1, flags=flags, known_bound=10, n_rows=n_rows)
         if mask:
-            rdesc[0].mask, rdesc[0].mask_ld = keep.ptr, 30
-        opt = nat.Options(nat.SKF_F64, variant, 0 if variant == nat.SKF_TRANSFORM else -1, nat.SKF_ENGINE_MFMA, 0, part_count,
-                          opt_flags)
-        handle = nat._P()
-        try:
-            return rt.lib.skf_plan_create(2, tdesc, 1, rdesc, 0, (nat.ThetaDesc * 1)(), C.byref(opt), C.byref(handle))
-        finally:
-            if handle.value:
-                rt.lib.skf_plan_destroy(handle)
+            rel.update(mask=keep.ptr, mask_ld=30)
+        return plan_create_status(rt.lib, [(40, 8), (30, 6)], [rel], variant=variant, target=0 if variant == nat.SKF_TRANSFORM else -1,
+                                  part=(0, part_count), opt_flags=opt_flags)[0]
     bad = -1                                            # SKF_E_INVALID
     assert nat.SKF_E_INVALID == bad
     assert create(nat.SKF_DFMF, nat.SKF_REL_SPARSE_CSR) == 0

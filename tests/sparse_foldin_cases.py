@@ -20,7 +20,7 @@ import pytest
 
 import skfusion_amd._native as nat
 from skfusion_amd._engine import DevicePlan, KnownEntries
-from helpers import relerr, within
+from helpers import plan_create_status, relerr, within
 import known_cases as K
 from dense_cases import constraint
 
@@ -265,21 +265,11 @@ def zero_relation_case(dtype, ranks, what, n=None, seed=3):
 # ---- 4. flags and lists ------------------------------------------------------------------------------------------------
 def create_status(lib, variant, flags, mask_ptr=None, n_rows=0, ranks=(8, 6), known=10, target=0):
     """Status of skf_plan_create for one 40 x 30 relation (no HIP call is made before the validation answers)."""
-    tdesc = (nat.TypeDesc * 2)()
-    tdesc[0].n_obj, tdesc[0].rank, tdesc[1].n_obj, tdesc[1].rank = 40, ranks[0], 30, ranks[1]
-    rdesc = (nat.RelationDesc * 1)()
-    rdesc[0].row_type, rdesc[0].col_type = 0, 1
-    rdesc[0].flags, rdesc[0].known_bound = flags, known
-    rdesc[0].n_rows = n_rows
+    rel = dict(row_type=0, col_type=1, flags=flags, known_bound=known, n_rows=n_rows)
     if mask_ptr is not None:
-        rdesc[0].mask, rdesc[0].mask_ld = mask_ptr, 30
-    opt = nat.Options(nat.SKF_F64, variant, target if variant == nat.SKF_TRANSFORM else -1, nat.SKF_ENGINE_MFMA, 0, 0, 0)
-    handle = nat._P()
-    try:
-        return lib.skf_plan_create(2, tdesc, 1, rdesc, 0, (nat.ThetaDesc * 1)(), C.byref(opt), C.byref(handle))
-    finally:
-        if handle.value:
-            lib.skf_plan_destroy(handle)
+        rel.update(mask=mask_ptr, mask_ld=30)
+    return plan_create_status(lib, [(40, ranks[0]), (30, ranks[1])], [rel], variant=variant,
+                              target=target if variant == nat.SKF_TRANSFORM else -1)[0]
 
 
 def creation_flag_cases(lib, mask_ptr):

@@ -18,7 +18,7 @@ import skfusion_amd._native as nat
 from skfusion_amd._engine import DevicePlan, DeviceKnownEntries, KnownEntries, owned_rows
 from skfusion_amd._engine import flatten_relations, flatten_thetas, count_objects
 from skfusion_amd.fusion.decomposition._dfmf import owned_plan, _host_loop
-from helpers import relerr, within, fit_owned, ThreadGroup
+from helpers import plan_create_status, relerr, within, fit_owned, ThreadGroup
 
 import known_cases as K
 import known_csr_cases as KC
@@ -61,19 +61,10 @@ def creation_cases():
     n_a, n_b = 40, 30
 
     def create(variant, flags, dtype=nat.SKF_F64, row_begin=0, n_rows=0, part=(0, 2), owned=True):
-        tdesc = (nat.TypeDesc * 2)()
-        tdesc[0].n_obj, tdesc[0].rank, tdesc[1].n_obj, tdesc[1].rank = n_a, 8, n_b, 6
-        rdesc = (nat.RelationDesc * 1)()
-        rdesc[0].row_type, rdesc[0].col_type = 0, 1
-        rdesc[0].flags, rdesc[0].known_bound = flags, 0 if flags & nat.SKF_REL_ABSENT else 10
-        rdesc[0].row_begin, rdesc[0].n_rows = row_begin, n_rows
-        opt = nat.Options(dtype, variant, -1, nat.SKF_ENGINE_MFMA, part[0], part[1], nat.SKF_OPT_OWNED_ROWS if owned else 0)
-        handle = nat._P()
-        try:
-            return rt.lib.skf_plan_create(2, tdesc, 1, rdesc, 0, (nat.ThetaDesc * 1)(), C.byref(opt), C.byref(handle))
-        finally:
-            if handle.value:
-                rt.lib.skf_plan_destroy(handle)
+        rel = dict(row_type=0, col_type=1, flags=flags, known_bound=0 if flags & nat.SKF_REL_ABSENT else 10, row_begin=row_begin,
+                   n_rows=n_rows)
+        return plan_create_status(rt.lib, [(n_a, 8), (n_b, 6)], [rel], dtype=dtype, variant=variant, part=part,
+                                  opt_flags=nat.SKF_OPT_OWNED_ROWS if owned else 0)[0]
     ok, bad = 0, nat.SKF_E_INVALID
     sp0, kn, absent = nat.SKF_REL_SPARSE_CSR, nat.SKF_REL_KNOWN_CSR, nat.SKF_REL_ABSENT
     assert owned_rows('f64', n_a, 0, 2)[:2] == (0, 20) and owned_rows('f64', n_a, 1, 2)[:2] == (20, 20)

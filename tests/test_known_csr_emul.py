@@ -8,6 +8,7 @@ import skfusion_amd._native as nat
 from emul.runtime import emulated_runtime, use_runtime
 
 import known_csr_cases as KC
+from helpers import plan_create_status
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -79,16 +80,10 @@ def test_known_csr_flag_is_refused_where_it_does_not_apply():
     t[0].n_obj, t[0].rank, t[1].n_obj, t[1].rank = 4, 2, 6, 2
     r = (nat.RelationDesc * 1)()
     r[0].row_type, r[0].col_type, r[0].flags, r[0].known_bound = 0, 1, nat.SKF_REL_KNOWN_CSR, 3
+    sizes, known_csr = [(4, 2), (6, 2)], dict(row_type=0, col_type=1, flags=nat.SKF_REL_KNOWN_CSR, known_bound=3)
     for variant in (nat.SKF_DFMF, nat.SKF_TRANSFORM):
-        h = nat._P()
-        code = rt.lib.skf_plan_create(2, t, 1, r, 0, None, C.byref(nat.Options(nat.SKF_F64, variant, 0, 0, 0, 0, 0)),
-                                      C.byref(h))
-        assert code == nat.SKF_E_INVALID
-    r[0].n_rows = 2                                     # a row block
-    h = nat._P()
-    assert rt.lib.skf_plan_create(2, t, 1, r, 0, None, C.byref(nat.Options(nat.SKF_F64, nat.SKF_DFMC, -1, 0, 0, 0, 0)),
-                                  C.byref(h)) == nat.SKF_E_INVALID
-    r[0].n_rows = 0
+        assert plan_create_status(rt.lib, sizes, [known_csr], variant=variant, target=0)[0] == nat.SKF_E_INVALID
+    assert plan_create_status(rt.lib, sizes, [dict(known_csr, n_rows=2)], variant=nat.SKF_DFMC)[0] == nat.SKF_E_INVALID      # a row block
     h = nat._P()
     rt.call('skf_plan_create', 2, t, 1, r, 0, None, C.byref(nat.Options(nat.SKF_F64, nat.SKF_DFMC, -1, 0, 0, 0, 0)),
             C.byref(h))
