@@ -903,6 +903,61 @@ int skf_launch_count(int64_t* launches);
  * run on the caller's scratch and are not counted. */
 int skf_split_clamps(int64_t* clamps);
 
+/* Held-out pairs scored inside the fit: early stopping on data the model never trained on, and the best iterate kept.  The
+ * reference's `stopping` / `stopping_system` (_dfmf.py:212-221, 301-322) read the training objective, which keeps falling
+ * while the model overfits.  A MONITORED plan scores lists of held-out (row, column, value) triples after every iteration
+ * of skf_iterate, on the same stream, judges the result on the device and keeps a device copy of the best (G, S); the host
+ * reads the verdict when it likes (skf_plan_get_monitor) and is never needed to decide.
+ *   A list: COO of one relation, rows (int32, NON-DECREASING), cols (int32, any order), values (the plan's master type:
+ *     double for SKF_F64, float for SKF_F32 / SKF_BF16), n >= 1 entries; duplicate pairs are allowed.  Device pointers, owned
+ *     by the caller, valid while attached.  At most one list per relation.
+ *   Squared error of list l under (G, S): sum over its entries of ((double)v - (double)x)^2, x = <(G_i S)[row], G_j[col]> with
+ *     exactly the bits skf_complete_entries returns on the same H = G_i S and G_j (16 lanes per entry, fixed fold).  A slab
+ *     of 1024 entries is one workgroup and one f64 partial, added in a fixed order; a list's total is its partials first to
+ *     last.  No atomics: two runs give the same bits, and the grid depends on n alone.  H is formed in the master type (the
+ *     SKF_BF16 engine scores on its f32 masters) by the product the plan's own H = G_i S goes through, on scratch of the
+ *     monitor's workspace.
+ *   Judge (one workgroup, after every iteration): history[it * n_lists + l] = the error of list l while it < capacity_iters;
+ *     total = the errors added in list order (the POOLED criterion).  The first total that is not NaN is an improvement;
+ *     afterwards total < best - min_delta is; a NaN total never improves.  An improvement records best, best_iter (1-based:
+ *     the number of iterations of the best model) and lets the snapshot -- every factor master and every backbone -- be
+ *     taken; anything else counts one more iteration without improvement, and with patience > 0, patience such iterations
+ *     in a row stop the monitor: best, best_iter and the snapshot are frozen from then on (stop_iter: the iteration that
+ *     stopped it).  Iterations issued after that still run and are still scored into the history; the plan's own state is
+ *     never rewritten.
+ *   skf_plan_heldout_workspace_bytes: bytes of the monitor's workspace -- 256 B of state words, the slab partials, per list H
+ *     (n_i x c_j) and its split-K scratch, the history (capacity_iters * n_lists * 8 B) and one snapshot of all factors and
+ *     backbones; nothing of size n_i x n_j.
+ *   skf_plan_set_heldout: on a bound SKF_DFMF / SKF_DFMC plan without row blocks, owned rows or a communicator; the rank of
+ *     a list's column type at most 1024; the workspace 256-byte aligned and at least that large.  The lists are validated on
+ *     the device before anything gathers through them (indices in range, rows non-decreasing, values finite).  Every
+ *     refusal is SKF_E_INVALID (SKF_E_STATE: not bound) and leaves the plan UNMONITORED; n_lists = 0 detaches.  Binding a
+ *     workspace again detaches too.  A monitored plan never replays a hipGraph and does not batch (skf_plan_batchable: 0).
+ *   skf_plan_heldout_sqerr: out_dev[l] (device, n_lists f64) = the squared error of list l under the current (G, S) -- what
+ *     skf_get_factor / skf_get_backbone return now, the convention of skf_relation_sqerr.  Judges nothing.
+ *   skf_plan_get_heldout_product: H of list `list` as the last evaluation left it (verification accessor), master type.
+ *   skf_plan_get_monitor: synchronises; any output pointer may be NULL.  history_host (HOST memory, `capacity` rows of n_lists
+ *     f64) receives min(seen, capacity_iters, capacity) rows.
+ *   skf_get_best_factor / skf_get_best_backbone: as skf_get_factor / skf_get_backbone, out of the snapshot; SKF_E_STATE
+ *     while no judged iteration has improved. */
+typedef struct skf_heldout_desc {
+    int32_t rel;
+    int64_t n;
+    const int32_t* rows;
+    const int32_t* cols;
+    const void* values;
+} skf_heldout_desc;
+int skf_plan_heldout_workspace_bytes(const skf_plan* plan, int32_t n_lists, const skf_heldout_desc* descs, int64_t capacity_iters,
+                                     size_t* bytes);
+int skf_plan_set_heldout(skf_plan* plan, int32_t n_lists, const skf_heldout_desc* descs, int32_t patience, double min_delta,
+                         int64_t capacity_iters, void* workspace, size_t workspace_bytes, void* stream);
+int skf_plan_heldout_sqerr(skf_plan* plan, double* out_dev, void* stream);
+int skf_plan_get_heldout_product(const skf_plan* plan, int32_t list, void* H, int64_t ld, void* stream);
+int skf_plan_get_monitor(const skf_plan* plan, int64_t* seen, int64_t* best_iter, int64_t* stop_iter, int32_t* stopped, double* best,
+                         double* history_host, int64_t capacity, void* stream);
+int skf_get_best_factor(const skf_plan* plan, int32_t type, void* G, int64_t ld, void* stream);
+int skf_get_best_backbone(const skf_plan* plan, int32_t rel, void* S, int64_t ld, void* stream);
+
 const char* skf_last_error(void);
 const char* skf_version(void);
 /* Layout version of the structs and signatures above (SKF_ABI_VERSION).  A binding built against another version must not
@@ -915,7 +970,8 @@ const char* skf_version(void);
  * structs before it are those of version 4; skf_complete_digits_workspace_bytes and skf_complete_digits;
  * skf_complete_row_kth_workspace_bytes and skf_complete_row_kth; skf_plan_relation_norms_filled,
  * skf_plan_init_column_means_filled and their workspace queries; skf_complete_hist_workspace_bytes, skf_complete_hist and
- * SKF_HIST_MAX_EDGES). */
+ * SKF_HIST_MAX_EDGES; skf_heldout_desc, a struct of its own, skf_plan_heldout_workspace_bytes, skf_plan_set_heldout,
+ * skf_plan_heldout_sqerr, skf_plan_get_heldout_product, skf_plan_get_monitor, skf_get_best_factor and skf_get_best_backbone). */
 #define SKF_ABI_VERSION 5
 int skf_abi_version(void);
 

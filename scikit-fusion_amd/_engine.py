@@ -959,6 +959,96 @@ class DevicePlan(object):
         self.rt.mem.synchronize()
         return float(self.rt.mem.to_host(self._scalar, (1,), np.float64)[0])
 
+    # -- held-out pairs scored inside the fit (csrc/skf_heldout.h; include/skfusion_hip.h, skf_plan_set_heldout) ----------
+    def set_heldout(self, lists, patience=0, min_delta=0.0, capacity=0):
+        """Attach held-out lists: `lists` = [(relation index, rows, cols, values)] -- COO of held-out pairs with their true
+        values, at most one list per relation, any order (sorted by row here, stably).  From now on every iteration of
+        `iterate` scores them, judges the pooled squared error on the device (an improvement is total < best - min_delta;
+        `patience` > 0: that many iterations in a row without one stop the monitor) and keeps a device copy of the best
+        (G, S); `capacity`: iterations of history kept.  An empty `lists` detaches.  The lists are validated on the device:
+        SkfNativeError (SKF_E_INVALID) for an index out of range or a value that is not finite, plan left unmonitored."""
+        mem = self.rt.mem
+        self._heldout = None
+        if not lists:
+            self.rt.call('skf_plan_set_heldout', self.handle, 0, None, 0, 0.0, 0, None, 0, self.stream)
+            return
+        desc = (nat.HeldoutDesc * len(lists))()
+        keep = []
+        for l, (rel, rows, cols, vals) in enumerate(lists):
+            rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+            cols = np.ascontiguousarray(cols, dtype=np.int64).reshape(-1)
+            vals = np.ascontiguousarray(vals, dtype=self.np_dtype).reshape(-1)
+            if not (rows.size == cols.size == vals.size):
+                raise ValueError('held-out list of relation %d: rows, cols and values differ in length' % rel)
+            for a in (rows, cols):          # (what does not fit an int32 is out of range anyway: the device refuses -1)
+                a[(a < 0) | (a > 0x7fffffff)] = -1
+            order = np.argsort(rows, kind='stable')
+            bufs = [mem.from_host(a if a.size else np.zeros(1, dtype=a.dtype), sync=False)
+                    for a in (rows[order].astype(np.int32), cols[order].astype(np.int32), vals[order])]
+            keep.append(bufs)
+            desc[l].rel, desc[l].n = int(rel), int(rows.size)
+            desc[l].rows, desc[l].cols, desc[l].values = bufs[0].ptr, bufs[1].ptr, bufs[2].ptr
+        mem.synchronize()                               # the uploads (torch's stream) before the engine's check
+        need = C.c_size_t()
+        self.rt.call('skf_plan_heldout_workspace_bytes', self.handle, len(lists), desc, int(capacity), C.byref(need))
+        ws = mem.empty(need.value)
+        self.rt.call('skf_plan_set_heldout', self.handle, len(lists), desc, int(patience), float(min_delta), int(capacity),
+                     ws.ptr, need.value, self.stream)
+        self._heldout = dict(keep=keep, ws=ws, n_lists=len(lists), rels=[int(x[0]) for x in lists], capacity=int(capacity), out=mem.empty(8 * len(lists)))
+
+    def _monitored(self):
+        h = getattr(self, '_heldout', None)
+        if h is None:
+            raise ValueError('no held-out lists attached (set_heldout)')
+        return h
+
+    def heldout_sqerr(self):
+        """float64 array, one per attached list: sum (v - x)^2 over the list under the current (G, S) (skf_plan_heldout_sqerr)."""
+        h = self._monitored()
+        self.rt.call('skf_plan_heldout_sqerr', self.handle, h['out'].ptr, self.stream)
+        self.rt.mem.synchronize()
+        return self.rt.mem.to_host(h['out'], (h['n_lists'],), np.float64)
+
+    def heldout_product(self, l):
+        """H = G_i S of list `l` as the last evaluation left it (verification accessor), in the master type."""
+        h = self._monitored()
+        i, j = self.relations[h['rels'][l]][:2]
+        shape = (self.n_obj[self.index[i]], self.rank[self.index[j]])
+        buf = self.rt.mem.empty(shape[0] * shape[1] * np.dtype(self.np_dtype).itemsize)
+        self.rt.call('skf_plan_get_heldout_product', self.handle, int(l), buf.ptr, shape[1], self.stream)
+        self.rt.mem.synchronize()
+        return self.rt.mem.to_host(buf, shape, self.np_dtype)
+
+    def monitor(self, history=True):
+        """The monitor's words (one synchronisation): dict(seen, best_iter -- 1-based, 0: none yet --, stop_iter, stopped, best,
+        history -- the judged iterations x lists kept so far, or None when not asked for)."""
+        h = self._monitored()
+        seen, best_iter, stop_iter = C.c_int64(), C.c_int64(), C.c_int64()
+        stopped, best = C.c_int32(), C.c_double()
+        cap = h['capacity'] if history else 0
+        host = np.zeros((max(cap, 1), h['n_lists']), dtype=np.float64)
+        self.rt.call('skf_plan_get_monitor', self.handle, C.byref(seen), C.byref(best_iter), C.byref(stop_iter), C.byref(stopped),
+                     C.byref(best), host.ctypes.data if cap else None, cap, self.stream)
+        return dict(seen=seen.value, best_iter=best_iter.value, stop_iter=stop_iter.value, stopped=bool(stopped.value),
+                    best=best.value, history=host[:min(seen.value, cap)].copy() if history else None)
+
+    def best_factor(self, t):
+        """The factor of type `t` of the best iterate (skf_get_best_factor); SkfNativeError (SKF_E_STATE) before there is one."""
+        k = self.index[t]
+        shape = (self.n_obj[k], self.rank[k])
+        buf = self.rt.mem.empty(shape[0] * shape[1] * np.dtype(self.np_dtype).itemsize)
+        self.rt.call('skf_get_best_factor', self.handle, k, buf.ptr, shape[1], self.stream)
+        self.rt.mem.synchronize()
+        return self.rt.mem.to_host(buf, shape, self.np_dtype).astype(np.float64)
+
+    def best_backbone(self, rel):
+        """The backbone of relation `rel` of the best iterate (skf_get_best_backbone)."""
+        shape = self._backbone_shape(rel)
+        buf = self.rt.mem.empty(shape[0] * shape[1] * np.dtype(self.np_dtype).itemsize)
+        self.rt.call('skf_get_best_backbone', self.handle, rel, buf.ptr, shape[1], self.stream)
+        self.rt.mem.synchronize()
+        return self.rt.mem.to_host(buf, shape, self.np_dtype).astype(np.float64)
+
     def set_profiling(self, enable=True):
         self.rt.call('skf_plan_set_profiling', self.handle, 1 if enable else 0)
 
@@ -979,6 +1069,7 @@ class DevicePlan(object):
             self._comm = None
         self._keep, self._keep_rel = [], []
         self.ws = None
+        self._heldout = None
 
     def __del__(self):
         try:

@@ -82,6 +82,11 @@ class InitView(C.Structure):
     _fields_ = [('rel', C.c_int32), ('take', C.c_int32), ('sel', C.c_void_p)]
 
 
+class HeldoutDesc(C.Structure):
+    """skf_heldout_desc: one held-out list of skf_plan_set_heldout (device pointers)."""
+    _fields_ = [('rel', C.c_int32), ('n', C.c_int64), ('rows', C.c_void_p), ('cols', C.c_void_p), ('values', C.c_void_p)]
+
+
 SKF_OPT_OWNED_ROWS = 1
 SKF_OPT_THETA_OWNED_ROWS = 2   # constraints given as their entries: the CSR of the owned rows (needs SKF_OPT_OWNED_ROWS)
 SKF_TOPK_MAX = 64            # include/skfusion_hip.h: longest list skf_complete_topk keeps per row
@@ -190,6 +195,14 @@ SIGNATURES = {
     'skf_plan_init_column_means_filled_workspace_bytes': (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(InitView), C.POINTER(C.c_size_t)]),
     'skf_plan_init_column_means_filled': (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(InitView), C.POINTER(C.c_double), _P, C.c_int64, _P,
                                                     C.c_size_t, _P]),
+    'skf_plan_heldout_workspace_bytes': (C.c_int, [_P, C.c_int32, C.POINTER(HeldoutDesc), C.c_int64, C.POINTER(C.c_size_t)]),
+    'skf_plan_set_heldout': (C.c_int, [_P, C.c_int32, C.POINTER(HeldoutDesc), C.c_int32, C.c_double, C.c_int64, _P, C.c_size_t, _P]),
+    'skf_plan_heldout_sqerr': (C.c_int, [_P, _P, _P]),
+    'skf_plan_get_heldout_product': (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
+    'skf_plan_get_monitor': (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_double), _P, C.c_int64, _P]),
+    'skf_get_best_factor': (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
+    'skf_get_best_backbone': (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
     'skf_pinv_sym_workspace_bytes': (C.c_int, [C.c_int32, C.POINTER(C.c_size_t)]),
     'skf_pinv_sym': (C.c_int, [C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_size_t, _P]),
     'skf_fill_uniform': (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, C.c_int64, C.c_uint64,

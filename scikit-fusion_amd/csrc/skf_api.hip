@@ -23,6 +23,7 @@
 #include "skf_small.h"
 #include "skf_complete.h"
 #include "skf_init.h"
+#include "skf_heldout.h"
 // the product build compiles the GEMM-class kernel templates in units of their own, side by side with this file
 // (tools/gen_inst_units.py, __graft_entry__.build); a build of this file alone (emulator, probes) instantiates them here
 #ifdef SKF_SPLIT_BUILD
@@ -141,6 +142,8 @@ static inline int wave_grid(int64_t rows) {
 
 #include "skf_init.inc"
 
+#include "skf_heldout.inc"
+
 }  // namespace skf
 
 using namespace skf;
@@ -255,6 +258,7 @@ int skf_plan_bind_workspace(skf_plan* p, void* ws, size_t bytes, void* stream) {
             p->graph_exec = nullptr;
         }
         p->graph_failed = false;
+        p->mon = HeldoutMonitor();           // (a monitor lives in a workspace of its own and belongs to the binding it was attached to)
         p->bound = true;
         p->prepared = false;
         p->first_iter = true;
@@ -343,6 +347,13 @@ int skf_iterate(skf_plan* p, int32_t n_iters, void* stream) {
             for (int it = 0; it < n_iters; ++it) iterate_transform(p, st);
         } else {
             int it = 0;
+            // a monitored plan (skf_plan_set_heldout): the held-out lists are scored and judged after every iteration, on
+            // the same stream; never the hipGraph path
+            if (monitored(p))
+                for (; it < n_iters; ++it) {
+                    iterate_fit(p, st);
+                    heldout_step(p, st);
+                }
             // The iteration is ~50-80 launches; for small graphs (launch-latency regime) the
             // remaining iterations replay ONE captured hipGraph.  Capture needs a real stream
             // (not the legacy default stream) and is skipped while profiling events are recorded.
@@ -398,6 +409,7 @@ int skf_iterate_batch(skf_plan* const* plans, int32_t n_plans, int32_t n_iters, 
         for (int k = 0; k < n_plans; ++k) {
             skf_plan* p = plans[k];
             check_bound(p);
+            if (monitored(p)) SKF_FAIL(SKF_E_STATE, "plan %d scores held-out lists (skf_plan_set_heldout): it does not batch", k);
             for (size_t i = 0; i < p->types.size(); ++i)
                 if (!p->types[i].set) SKF_FAIL(SKF_E_STATE, "plan %d: factor of object type %zu not set", k, i);
             // one launch serves every plan (plan 0's grid, LDS and job tables): the small-graph schedule, the same engine and
@@ -441,7 +453,7 @@ int skf_plan_batchable(const skf_plan* p, int32_t* yes) {
     return guarded([&] {
         check_bound(p);
         if (!yes) SKF_FAIL(SKF_E_INVALID, "null pointer");
-        *yes = (p->small_fused || fold_fused(p)) ? 1 : 0;
+        *yes = ((p->small_fused || fold_fused(p)) && !monitored(p)) ? 1 : 0;
     });
 }
 

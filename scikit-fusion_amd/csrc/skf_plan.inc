@@ -237,6 +237,37 @@ struct ThetaState {
     const void* csr_val = nullptr;
 };
 
+// Held-out pairs scored inside the fit (skf_plan_set_heldout; kernels skf_heldout.h, host side skf_heldout.inc): the lists
+// the caller attached and where the monitor's own workspace keeps what belongs to them.  Empty `lists`: the plan is unmonitored.
+struct HeldoutList {
+    int rel = 0;
+    int64_t n = 0;
+    const int* rows = nullptr;
+    const int* cols = nullptr;
+    const void* vals = nullptr;
+    int64_t blocks = 0;                    // slabs of the pass = f64 partials of the list
+    void* H = nullptr;                     // G_i S (n_i x c_j, master type)
+    void* part = nullptr;                  // split-K scratch of that product
+    size_t part_bytes = 0;
+};
+struct HeldoutMonitor {
+    std::vector<HeldoutList> lists;
+    int patience = 0;
+    double min_delta = 0.0;
+    int64_t capacity = 0;
+    HeldoutState* state = nullptr;         // device: the monitor's words
+    int64_t* offs = nullptr;               // device: first partial of every list, n_lists + 1
+    double* cur = nullptr;                 // device: the totals of the last evaluation, one per list
+    double* partials = nullptr;
+    double* history = nullptr;             // device: [capacity][n_lists]
+    HeldoutSeg* segs = nullptr;            // device: the ranges the snapshot copies
+    int n_segs = 0;
+    int64_t max_words = 0;                 // longest range (the snapshot's grid)
+    std::vector<void*> snap_g, snap_s;     // device: the best factor of every type / backbone of every relation
+    std::vector<int64_t> host_offs;        // what `offs` / `segs` were uploaded from
+    std::vector<HeldoutSeg> host_segs;
+};
+
 }  // namespace skf
 
 struct skf_plan {
@@ -306,6 +337,7 @@ struct skf_plan {
     skf::Slot sm_tables, sm_jobs1, sm_jobs3, sm_wpart, sm_gpart, sm_tickets, sm_batch;
     std::vector<const void*> sm_batch_host;        // device addresses of the tables of the plans of the last batch (this plan first)
     std::vector<skf::SmJob> sm_j1, sm_j3;
+    skf::HeldoutMonitor mon;               // skf_plan_set_heldout: held-out lists scored after every iteration of skf_iterate
     ~skf_plan() {
         for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev_rel) (void)hipEventDestroy(e);

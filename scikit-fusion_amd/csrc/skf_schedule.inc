@@ -272,7 +272,7 @@ static void iterate_fit(skf_plan* p, hipStream_t st) {
 }
 
 static bool use_graph(skf_plan* p, hipStream_t st, int n_iters) {
-    if (st == nullptr || p->profiling || p->graph_failed || n_iters < 4) return false;
+    if (st == nullptr || p->profiling || p->graph_failed || n_iters < 4 || !p->mon.lists.empty()) return false;
     // opt-in (SKF_GRAPH=1): measured on dicty (50 launches / 0.5 ms iteration) the replay is not
     // faster than the asynchronous eager launches -- the iteration is bound by kernel time
     return p->graph_on || p->sw.graph;

@@ -21,11 +21,11 @@ def _expand_known_entries(R, M):
 
 def dfmc(R, M, Theta, obj_types, obj_type2rank, max_iter=10, init_type="random_vcol",
          stopping=None, stopping_system=None, verbose=0, compute_err=False, callback=None,
-         random_state=None, n_jobs=1, dtype='f64', G0=None, engine=None, shard=None, sparse_constraints=False):
+         random_state=None, n_jobs=1, dtype='f64', G0=None, engine=None, shard=None, sparse_constraints=False, validation=None):
     """Data fusion by matrix completion -- drop-in for reference ``dfmc`` (_dfmc.py:181).  Constraints given as their entries:
-    as in ``_dfmf.dfmf`` (shard None / 'runs'; shard='owned' with ``sparse_constraints=True``)."""
+    as in ``_dfmf.dfmf`` (shard None / 'runs'; shard='owned' with ``sparse_constraints=True``); ``validation``: as there."""
     if shard in ('relations', 'rows'):          # (an ownership-sharded fit slices the entries by rows; these take the mask form)
         R, M = _expand_known_entries(R, M)
     return _fit_by_shard(nat.SKF_DFMC, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, stopping,
                          stopping_system, verbose, compute_err, callback, random_state, dtype, G0, engine, shard,
-                         sparse_constraints)
+                         sparse_constraints, validation)

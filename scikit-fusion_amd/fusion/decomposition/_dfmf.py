@@ -52,11 +52,61 @@ def _rel_index(rel_list, target):
     return hits[l]
 
 
-def _host_loop(step, sqerrs, rel_list, max_iter, stopping, stopping_system, compute_err, on_iter):
+class Validation(object):
+    """Held-out pairs scored inside one fit (csrc/skf_heldout.h; `DevicePlan.set_heldout`): what the fit is given, and what
+    it leaves behind.
+    lists: [(target, rows, cols, values)], target = (row_type, col_type) or ((row_type, col_type), l) as for `stopping`;
+    the held-out pairs of that relation with their true values, at most one list per relation.  After every iteration the
+    device adds up (v - x)^2 over every list and judges the POOLED sum over all lists: an improvement is
+    total < best - min_delta (the first total always is); `patience` > 0: that many iterations in a row without one end
+    the fit.  The loop stays on the device: `check_every` iterations are issued at a time and only the monitor's state
+    words are read in between, so a fit that stops at iteration t runs on to the next multiple of `check_every` -- the
+    judge froze at t, and history, best iterate and returned model do not depend on `check_every`.
+    restore_best: the fit returns the (G, S) of the best iterate (a device copy taken when it was judged); False: the last.
+    Left behind: sqerr (iterations x lists, up to the stop), best_iter (1-based; 0: every total was NaN), n_iter (iterations
+    run), stopped."""
+
+    def __init__(self, lists, patience=None, min_delta=0.0, check_every=8, restore_best=True):
+        if int(check_every) < 1:
+            raise ValueError('check_every must be at least 1')
+        if patience is not None and int(patience) < 1:
+            raise ValueError('patience must be at least 1 (None: never stop early)')
+        if not (float(min_delta) >= 0.0):
+            raise ValueError('min_delta must be >= 0')
+        self.lists, self.patience, self.min_delta = list(lists), patience, float(min_delta)
+        self.check_every, self.restore_best = int(check_every), bool(restore_best)
+        self.sqerr = self.best_iter = self.n_iter = self.stopped = None
+
+
+def _monitored_loop(plan, sharding, validation, max_iter, host_loop):
+    """The loop of a fit with held-out lists: chunks of `check_every` iterations, the monitor's words read in between --
+    or, where the host is needed every iteration anyway (`host_loop`: callback, stopping, error logging), that loop with a
+    chunk of one and the monitor's verdict as one more reason to stop.  Returns the iterations run."""
+    done = [0]
+
+    def stopped():
+        return plan.monitor(history=False)['stopped']
+    if host_loop is not None:
+        def step():
+            sharding.step(plan, 1)
+            done[0] += 1
+        host_loop(step, stopped)
+        return done[0]
+    while done[0] < max_iter:
+        n = min(validation.check_every, max_iter - done[0])
+        sharding.step(plan, n)
+        done[0] += n
+        if stopped():
+            break
+    return done[0]
+
+
+def _host_loop(step, sqerrs, rel_list, max_iter, stopping, stopping_system, compute_err, on_iter, stop=None):
     """The body of the reference loops with their early-stopping / error logging (_dfmf.py:212-221, 301-322;
     _dfmc.py:270-279, 370-392; fold-in _dfmf.py:367-376, 433-450), one device iteration per pass.
     step(): one iteration; sqerrs(indices): squared reconstruction errors of those relations (summed over the
-    ranks of a sharded fit, so that every rank takes the same decision); on_iter(it): the callback hook."""
+    ranks of a sharded fit, so that every rank takes the same decision); on_iter(it): the callback hook; stop(): one more
+    reason to end the loop, asked before every iteration after the first (a fit with held-out lists: the monitor's verdict)."""
     if stopping_system:
         compute_err = True
     err_t = (None, None)
@@ -68,6 +118,9 @@ def _host_loop(step, sqerrs, rel_list, max_iter, stopping, stopping_system, comp
             break
         if it > 1 and stopping_system and err_s[1] - err_s[0] < stopping_system:
             log.info("Early stopping: matrix system change < %5.4f", stopping_system)
+            break
+        if it > 0 and stop is not None and stop():
+            log.info("Early stopping: held-out error without improvement")
             break
         step()
         if compute_err:
@@ -181,7 +234,7 @@ _Sharding = collections.namedtuple('_Sharding', 'make_plan attach load step sqer
 
 
 def _fit(sharding, variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, random_state, dtype, G0, engine,
-         stopping, stopping_system, compute_err, callback):
+         stopping, stopping_system, compute_err, callback, validation=None):
     """One fit, shared out as `sharding` says: the body of the reference loops (_dfmf.py:212-322, _dfmc.py:270-392) with the
     arithmetic on the device.  A size mismatch between the relations is reported before anything is drawn from
     `random_state`; the plain loop stays on the device, `_host_loop` runs where the host is needed every iteration."""
@@ -195,15 +248,35 @@ def _fit(sharding, variant, R, M, Theta, obj_types, obj_type2rank, max_iter, ini
     try:
         sharding.attach(plan)
         sharding.load(plan, obj_types, G0)
-        if not (callback or stopping or stopping_system or compute_err):
+        on_iter = (lambda it: callback(*(sharding.collect(plan, obj_types, rel_list) + (it,)))) if callback else None
+        host_loop = None
+        if callback or stopping or stopping_system or compute_err:
+            host_loop = lambda step, stop=None: _host_loop(step, lambda idx: sharding.sqerrs(plan, idx), rel_list, max_iter,
+                                                           stopping, stopping_system, compute_err, on_iter, stop)
+        if validation is not None:
+            return _fit_validated(plan, sharding, validation, obj_types, rel_list, max_iter, host_loop)
+        if host_loop is None:
             sharding.step(plan, max_iter)       # whole loop device-resident, no host sync
         else:
-            _host_loop(lambda: sharding.step(plan, 1), lambda idx: sharding.sqerrs(plan, idx), rel_list, max_iter,
-                       stopping, stopping_system, compute_err,
-                       (lambda it: callback(*(sharding.collect(plan, obj_types, rel_list) + (it,)))) if callback else None)
+            host_loop(lambda: sharding.step(plan, 1))
         return sharding.collect(plan, obj_types, rel_list)
     finally:
         plan.close()
+
+
+def _fit_validated(plan, sharding, validation, obj_types, rel_list, max_iter, host_loop):
+    """The loop and the read-back of a fit with held-out lists (`Validation`), on a loaded whole plan."""
+    lists = [(_rel_index(rel_list, target), rows, cols, vals) for target, rows, cols, vals in validation.lists]
+    plan.set_heldout(lists, validation.patience or 0, validation.min_delta, capacity=max_iter)
+    validation.n_iter = _monitored_loop(plan, sharding, validation, max_iter, host_loop)
+    m = plan.monitor()
+    validation.stopped = m['stopped']
+    validation.best_iter = m['best_iter']
+    validation.sqerr = m['history'][:m['stop_iter']] if m['stopped'] else m['history']
+    if not (validation.restore_best and m['best_iter'] > 0):
+        return sharding.collect(plan, obj_types, rel_list)
+    values = [plan.best_factor(t) for t in obj_types] + [plan.best_backbone(k) for k in range(len(rel_list))]
+    return _unpack(values, obj_types, rel_list)
 
 
 def _whole_plan(variant, rel_list, theta_list, obj_types, n_obj, obj_type2rank, dtype, engine):
@@ -385,25 +458,27 @@ def run_fits_concurrent(variant, R, M, Theta, obj_types, obj_type2rank, max_iter
 
 
 def run_fit(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, stopping,
-            stopping_system, verbose, compute_err, callback, random_state, dtype, G0, engine):
+            stopping_system, verbose, compute_err, callback, random_state, dtype, G0, engine, validation=None):
     """Shared driver of dfmf / dfmc: the body of the reference loops (_dfmf.py:212-322,
     _dfmc.py:270-392) with the arithmetic on the device."""
     logging.basicConfig(format="%(asctime)s %(levelname)s: %(message)s", level=50 - verbose)
     return _fit(_WHOLE, variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, random_state, dtype, G0, engine,
-                stopping, stopping_system, compute_err, callback)
+                stopping, stopping_system, compute_err, callback, validation)
 
 
 _SHARDED_FITS = {'relations': run_fit_sharded, 'rows': run_fit_rows, 'owned': run_fit_owned}
 
 
 def _fit_by_shard(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, stopping, stopping_system, verbose,
-                  compute_err, callback, random_state, dtype, G0, engine, shard, sparse_constraints):
+                  compute_err, callback, random_state, dtype, G0, engine, shard, sparse_constraints, validation=None):
     """The shard dispatch of `dfmf` and `_dfmc.dfmc`: one whole fit on this process (shard None / 'runs'), or this
     process's part of a fit shared out over the process group -- 'relations', 'rows', 'owned' -- which takes dense
     constraints (`refuse_constraint_entries`)."""
     if shard not in _SHARDED_FITS:
         return run_fit(variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, stopping, stopping_system,
-                       verbose, compute_err, callback, random_state, dtype, G0, engine)
+                       verbose, compute_err, callback, random_state, dtype, G0, engine, validation)
+    if validation is not None:
+        raise ValueError("held-out validation lists need a whole fit on this process (shard='runs'), not shard=%r" % (shard,))
     refuse_constraint_entries(Theta, shard, sparse_constraints)
     logging.basicConfig(format="%(asctime)s %(levelname)s: %(message)s", level=50 - verbose)
     return _SHARDED_FITS[shard](variant, R, M, Theta, obj_types, obj_type2rank, max_iter, init_type, random_state, dtype,
@@ -425,15 +500,17 @@ def refuse_constraint_entries(Theta, shard, sparse_constraints=False):
 
 def dfmf(R, Theta, obj_types, obj_type2rank, max_iter=10, init_type="random_vcol",
          stopping=None, stopping_system=None, verbose=0, compute_err=False, callback=None,
-         random_state=None, n_jobs=1, dtype='f64', G0=None, engine=None, shard=None, sparse_constraints=False):
+         random_state=None, n_jobs=1, dtype='f64', G0=None, engine=None, shard=None, sparse_constraints=False, validation=None):
     """Data fusion by matrix factorization -- drop-in for reference ``dfmf`` (_dfmf.py:127).
     ``shard='relations'`` (with an initialised torch.distributed group) partitions the relations
     of this ONE fit over the ranks.  A constraint in ``Theta`` may be an ``_engine.KnownEntries(unstored='zero')`` -- its
     entries as canonical CSR, never expanded -- with shard None / 'runs', and with shard='owned' under
-    ``sparse_constraints=True`` (every rank hands over the CSR of its owned rows); any other shard: ValueError."""
+    ``sparse_constraints=True`` (every rank hands over the CSR of its owned rows); any other shard: ValueError.
+    ``validation``: a `Validation` -- held-out pairs scored on the device after every iteration, early stopping on their
+    pooled squared error and the best iterate returned (shard None / 'runs')."""
     return _fit_by_shard(nat.SKF_DFMF, R, None, Theta, obj_types, obj_type2rank, max_iter, init_type, stopping,
                          stopping_system, verbose, compute_err, callback, random_state, dtype, G0, engine, shard,
-                         sparse_constraints)
+                         sparse_constraints, validation)
 
 
 def _transform_graph(R_ij, target_obj_type, G):

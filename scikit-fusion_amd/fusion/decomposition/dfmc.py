@@ -19,7 +19,10 @@ class Dfmc(_Fuser):
     whole matrix stays on every process's host for the initialisers; 'rows' / 'relations' expand it); such a relation with
     fill_value 'row_mean' / 'col_mean' (no mask is left) as entries plus rank one with shard='runs' (``sparse_relations``,
     ``filled_entries_apply``); one whose unstored entries are zero on its stored entries (``sparse_relations``, see ``Dfmf``); a
-    ``scipy.sparse`` constraint as its entries (``sparse_constraints``, see ``Dfmf``)."""
+    ``scipy.sparse`` constraint as its entries (``sparse_constraints``, see ``Dfmf``).
+    validation, patience, min_delta, check_every, restore_best: held-out pairs scored inside the fit, early stopping on their
+    pooled squared error and the best iterate returned, as in ``Dfmf`` -- the held-out pairs of a relation with missing
+    values must be among its UNKNOWN cells (``heldout_lists`` refuses a pair the training relation knows)."""
 
     _variant = 'dfmc'
     _keeps_masks = True
@@ -29,7 +32,8 @@ class Dfmc(_Fuser):
     def __init__(self, max_iter=100, init_type='random_c', n_run=1, stopping=None,
                  stopping_system=None, verbose=0, compute_err=False, callback=None,
                  random_state=None, n_jobs=1, dtype='f64', shard='runs', device_fill=False, sparse_relations=None,
-                 sparse_constraints=None, init_device=None):
+                 sparse_constraints=None, init_device=None, validation=None, patience=None, min_delta=0.0, check_every=8,
+                 restore_best=True):
         super(Dfmc, self).__init__()
         self._set_params(vars())
 

@@ -408,6 +408,95 @@ def store_runs(fuser, runs):
                 fuser.backbones_[relation].append(backbones[k])
 
 
+def _relation_name(relation):
+    return 'R_(%s,%s)' % (relation.row_type.name, relation.col_type.name)
+
+
+def heldout_lists(fuser):
+    """`validation` = [(relation, heldout)] of a fuser -> the lists of `_dfmf.Validation`: [(((row_type, col_type), l), rows,
+    cols, values)], l the relation's position among the graph's relations of its pair.  `heldout`: a scipy.sparse matrix
+    of the relation's shape whose STORED entries are the held-out pairs with their true values, or (rows, cols, values).
+    Refused, naming the relation (DataFusionError: not in the graph; ValueError: the rest): a constraint, a preprocessor
+    on the relation, a shard other than 'runs', two lists for one relation, no pair at all, an index out of range, a value
+    that is not finite, and a held-out pair the training relation KNOWS -- a stored entry of a scipy.sparse relation with
+    ``unstored='unknown'``, an unmasked cell of a MaskedArray: validation data leaking into training.  Plain arrays and
+    ``unstored='zero'`` relations have no notion of an unknown cell and are accepted as they are."""
+    from ..base import DataFusionError
+    import scipy.sparse
+    graph = fuser.fusion_graph
+    if fuser.shard != 'runs':
+        raise ValueError("validation needs shard='runs' (a whole fit on this process), not shard=%r" % (fuser.shard,))
+    out, seen = [], []
+    for item in fuser.validation:
+        relation, held = item
+        if not any(relation is r for r in graph.relations):
+            raise DataFusionError('validation: relation %s is not in the fusion graph' % _relation_name(relation))
+        name = _relation_name(relation)
+        if relation.row_type == relation.col_type:
+            raise ValueError('validation: %s is a constraint, not a relation between two object types' % name)
+        if relation.preprocessor:
+            raise ValueError('validation: %s has a preprocessor: held-out values would be compared with preprocessed data' % name)
+        if any(relation is r for r in seen):
+            raise ValueError('validation: two held-out lists for %s' % name)
+        seen.append(relation)
+        if scipy.sparse.issparse(held):
+            if tuple(held.shape) != tuple(relation.data.shape):
+                raise ValueError('validation: held-out matrix of %s has shape %r, the relation %r'
+                                 % (name, tuple(held.shape), tuple(relation.data.shape)))
+            coo = scipy.sparse.coo_matrix(held)
+            rows, cols, vals = coo.row, coo.col, coo.data
+        else:
+            rows, cols, vals = held
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        cols = np.asarray(cols, dtype=np.int64).reshape(-1)
+        vals = np.asarray(vals, dtype=np.float64).reshape(-1)
+        if not (rows.size == cols.size == vals.size) or rows.size == 0:
+            raise ValueError('validation: %s needs rows, cols and values of one length, at least one pair' % name)
+        n_r, n_c = relation.data.shape
+        if rows.min() < 0 or rows.max() >= n_r or cols.min() < 0 or cols.max() >= n_c:
+            raise ValueError('validation: a held-out pair of %s lies outside its %d x %d entries' % (name, n_r, n_c))
+        if not np.isfinite(vals).all():
+            raise ValueError('validation: a held-out value of %s is not finite' % name)
+        known = None
+        if relation.is_known_entries():
+            csr = scipy.sparse.csr_matrix(relation.data)
+            pattern = scipy.sparse.csr_matrix((np.ones(csr.indices.size, dtype=np.int8), csr.indices, csr.indptr), shape=csr.shape)
+            known = np.asarray(pattern[rows, cols]).reshape(-1) != 0
+        elif np.ma.isMaskedArray(relation.data):
+            known = ~np.ma.getmaskarray(relation.data)[rows, cols]
+        if known is not None and known.any():
+            raise ValueError('validation: %d held-out pairs of %s are known to the training relation (validation data leaks '
+                             'into training)' % (int(np.count_nonzero(known)), name))
+        order = np.lexsort((cols, rows))                # by row, then column: one list whatever order the pairs came in
+        rows, cols, vals = rows[order], cols[order], vals[order]
+        pair = (relation.row_type, relation.col_type)
+        l = [k for k, r in enumerate(graph.get_relations(*pair)) if r is relation][0]
+        out.append(((pair, l), rows, cols, vals))
+    if not out:
+        raise ValueError('validation: no held-out list given')
+    return out
+
+
+def _new_validation(fuser, lists):
+    return _dfmf.Validation(lists, patience=fuser.patience, min_delta=fuser.min_delta, check_every=fuser.check_every,
+                            restore_best=fuser.restore_best)
+
+
+def store_validation(fuser, per_run):
+    """What the monitors of the restarts left behind -> per-run attributes, as factors_ / backbones_ are kept:
+    validation_sqerr_[run] (iterations x lists), validation_rmse_[run] (pooled over the lists, per iteration),
+    best_iter_[run], n_iter_[run], stopped_early_[run]; all None for a fit without `validation`."""
+    if per_run is None:
+        fuser.validation_sqerr_ = fuser.validation_rmse_ = fuser.best_iter_ = fuser.n_iter_ = fuser.stopped_early_ = None
+        return
+    pairs = float(sum(v[1].size for v in per_run[0].lists))
+    fuser.validation_sqerr_ = [v.sqerr for v in per_run]
+    fuser.validation_rmse_ = [np.sqrt(v.sqerr.sum(axis=1) / pairs) for v in per_run]
+    fuser.best_iter_ = [int(v.best_iter) for v in per_run]
+    fuser.n_iter_ = [int(v.n_iter) for v in per_run]
+    fuser.stopped_early_ = [bool(v.stopped) for v in per_run]
+
+
 class _Fuser(FusionFit):
     """`fuse` of ``Dfmf`` and ``Dfmc``: one implementation; the class attributes say what differs."""
 
@@ -423,6 +512,13 @@ class _Fuser(FusionFit):
     def fuse(self, fusion_graph):
         from ... import _native as nat
         self.fusion_graph = fusion_graph
+        validation = getattr(self, 'validation', None)
+        if validation is None and getattr(self, 'patience', None) is not None:
+            raise ValueError('patience without validation: early stopping on held-out pairs needs the pairs')
+        lists = heldout_lists(self) if validation is not None else None
+        if lists is not None:
+            _new_validation(self, lists)                # (the parameter checks, before anything is uploaded)
+        store_validation(self, None)
         self.random_state = _random_state(self.random_state)
         object_types = list(fusion_graph.object_types)
         rank = {ot: int(ot.rank) for ot in object_types}
@@ -439,6 +535,14 @@ class _Fuser(FusionFit):
                   compute_err=self.compute_err, callback=self.callback,
                   random_state=self.random_state, n_jobs=self.n_jobs, dtype=self.dtype)
         code = {'dfmf': nat.SKF_DFMF, 'dfmc': nat.SKF_DFMC}[self._variant]
+        if lists is not None:
+            # every restart is monitored on its own, one after the other: the shared-launch and concurrent paths are for
+            # the plain loop (as with a callback)
+            monitors = {k: _new_validation(self, lists) for k in my_runs(self.n_run)}
+            local = {k: self._solve(M, G0=G0[k], validation=monitors[k], **kw) for k in monitors}
+            store_runs(self, gather_runs(local, self.n_run))
+            store_validation(self, [monitors[k] for k in range(self.n_run)] if len(monitors) == self.n_run else None)
+            return self
         if self.shard in ('relations', 'rows', 'owned'):                   # all GPUs cooperate on every restart
             # (an owned fit takes the constraints graph_matrices left as entries: each rank the slice of its owned rows)
             store_runs(self, [self._solve(M, G0=G0[k], shard=self.shard, sparse_constraints=self.shard == 'owned', **kw)
@@ -499,6 +603,18 @@ class Dfmf(_Fuser):
     entries of relations with missing values; False: never.  An
     ineligible fit initialises on the host whatever this says.  ``init_on_device_`` (after ``fuse``) says what ran.
     ``device_fill=True`` goes with these initialisers when they run on the device.
+    validation=None | [(relation, heldout)]: held-out pairs scored INSIDE the fit (shard='runs').  `heldout` is a
+    ``scipy.sparse`` matrix of the relation's shape whose stored entries are the held-out pairs with their true values, or
+    a tuple (rows, cols, values).  After every iteration the device adds up (value - prediction)^2 over every list; the
+    criterion is the POOLED sum of squared errors over all lists (one number per iteration, whatever the lists' sizes).
+    patience=None | n: n iterations in a row without an improvement (pooled sum < best - min_delta) end the fit;
+    check_every=8: iterations issued between two looks at the verdict -- the loop stays on the device, so a fit that stops at
+    iteration t runs on to the next multiple, but history, best iterate and model do not depend on it.
+    restore_best=True: ``factor()`` / ``backbone()`` are the best iterate (a device copy taken when it was judged); False:
+    the last.  After ``fuse``, per run: ``validation_sqerr_`` (iterations x lists, up to the stop), ``validation_rmse_``
+    (pooled), ``best_iter_`` (1-based), ``n_iter_``, ``stopped_early_``; all None without `validation`.  Restarts are
+    monitored one after the other.  See ``heldout_lists`` for what is refused (a held-out pair the training relation knows
+    among them).
     """
 
     _variant = 'dfmf'
@@ -507,7 +623,8 @@ class Dfmf(_Fuser):
     def __init__(self, max_iter=100, init_type='random_c', n_run=1, stopping=None,
                  stopping_system=None, verbose=0, compute_err=False, callback=None,
                  random_state=None, n_jobs=1, dtype='f64', shard='runs', device_fill=False, sparse_relations=None,
-                 sparse_constraints=None, init_device=None):
+                 sparse_constraints=None, init_device=None, validation=None, patience=None, min_delta=0.0, check_every=8,
+                 restore_best=True):
         super(Dfmf, self).__init__()
         self._set_params(vars())
 
